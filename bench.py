@@ -118,7 +118,15 @@ def parse_args():
                     help='a functional run (the GPU tests of the full-size sharded configs): no separate set-up step -- the '
                          'first timed step plans and allocates -- so `value` is not a performance figure')
     ap.add_argument('--no-parity', action='store_true', help='skip the pin check after the timed steps')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step returned to DIR/<name>.npy (`dump_outputs`): <Z0> per sample in '
+                         'full and a fixed, seeded sample of the state\'s amplitudes')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.rehearse_rank is not None:
+        ap.error('--dump-outputs: a rehearsal leaves the exchanges out, its amplitudes are not outputs')
+    return args
 
 
 def random_circuit_spec(nqubit, depth, seed=1234):
@@ -426,6 +434,35 @@ def qaoa_ring(dq, n, device, distributed):
     return cir.to(device), pairs
 
 
+DUMP_STATE_SAMPLES = 1 << 20     # amplitudes of the state written by --dump-outputs (all of them if the state is smaller)
+
+
+def dump_outputs(out_dir, state, expectation, seed, suffix=''):
+    """``--dump-outputs``: what the last timed step handed its caller, as float32 / float64 arrays (the state's real
+    precision) -- ``expectation`` (<Z0> per sample, all of it), ``state_sample`` ((K, 2): real and imaginary parts of K
+    amplitudes of the flattened state, at most ``DUMP_STATE_SAMPLES``) and ``state_sample_index`` (their flat indices,
+    sorted; drawn from ``seed`` alone, so that two builds given the same arguments write the same positions).  A sharded
+    state is this rank's shard in the reference's order; ``suffix`` tells the ranks' files apart.  Returns the names."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = state.reshape(-1)
+    real = np.float64 if flat.dtype == torch.complex128 else np.float32
+    total = flat.numel()
+    if total <= DUMP_STATE_SAMPLES:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(seed).choice(total, DUMP_STATE_SAMPLES, replace=False)).astype(np.int64)
+    amp = flat[torch.from_numpy(idx).to(flat.device)].cpu()
+    arrays = {'state_sample': torch.view_as_real(amp).numpy().astype(real),
+              'state_sample_index': idx.astype(np.float64)}      # (exact: the state has fewer than 2^53 amplitudes)
+    if expectation is not None:
+        arrays['expectation'] = expectation.detach().reshape(-1).cpu().numpy().astype(real)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + '.npy'), arr)
+    return sorted(name + suffix for name in arrays)
+
+
 def self_launch(args) -> int:
     """``--gpus N`` (N > 1) outside a torchrun environment: start the N ranks here -- one process per GPU, the same
     command line -- instead of silently measuring one rank.  RCCL needs one GPU per rank (exit 2 if the box has
@@ -714,6 +751,10 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     prof['enabled'] = False
+    dumped = None
+    if args.dump_outputs and not rehearse:      # (before anything below runs the circuit again)
+        st_ = cir.state.amps if distributed else cir.state      # a shard: the reference's order (drop-in layout)
+        dumped = dump_outputs(args.dump_outputs, st_, out, args.seed, f'_rank{rank}' if multi else '')
     remap_rows, comm_stats = None, None
     if distributed:
         dq.distributed.TIMING['enabled'] = False
@@ -1049,6 +1090,8 @@ def main():
             }
         if qaoa is not None:
             line['config']['qaoa_ring'] = qaoa
+        if dumped is not None:
+            line['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if not args.no_cpu_baseline and not multi:
             line['cpu_baseline'] = cpu_baseline(min(n, 28), dtype, args.cpu_seconds)
         print(json.dumps(line))

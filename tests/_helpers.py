@@ -1088,6 +1088,22 @@ def check_transforms_random(dq, device=None, n=10, seed=0, ngates=40, dtype=torc
         assert (tf.jacfwd(fvec)(x) - jac).abs().max().item() < 20 * tol, ('jacfwd', seed)
 
 
+#: ranks of a sharded GPU test that may share one device over gloo (with the test's own process: five on the device)
+MAX_RANKS_SHARING_A_GPU = 4
+
+
+def skip_unless_ranks_fit(world, device_count=None):
+    """Skip a sharded GPU test, before it starts anything, whose ``world`` ranks neither get a device each (RCCL) nor
+    are few enough to share device 0 (gloo, ``MAX_RANKS_SHARING_A_GPU``)."""
+    import pytest
+
+    if device_count is None:
+        device_count = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    backend, _devices = pick_transport(world, device_count)
+    if backend == 'gloo' and world > MAX_RANKS_SHARING_A_GPU:
+        pytest.skip(f'needs {world} GPUs (one per rank), found {device_count}')
+
+
 def pick_transport(world, device_count=None):
     """Transport of a sharded GPU test with ``world`` ranks: ``('nccl', one device per rank)`` -- RCCL over xGMI, the
     reference's own transport (communication.py:9-35, README.md:223-255) -- as soon as the box shows at least ``world``

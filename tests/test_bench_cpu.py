@@ -137,3 +137,68 @@ def test_transport_selector_of_the_sharded_gpu_tests():
     finally:
         del os.environ['DQ_TEST_TRANSPORT']
     assert pick_transport(2)[0] in ('gloo', 'nccl')        # (whatever this box shows)
+
+
+def test_sharded_gpu_tests_skip_when_their_ranks_do_not_fit():
+    """``_helpers.skip_unless_ranks_fit``: up to four ranks share one device; more need a device each."""
+    from _helpers import skip_unless_ranks_fit
+
+    for world, count in ((1, 1), (2, 1), (4, 1), (8, 8), (4, 0)):
+        skip_unless_ranks_fit(world, device_count=count)
+    for world, count in ((8, 1), (8, 4), (8, 0)):
+        with pytest.raises(pytest.skip.Exception, match=f'needs {world} GPUs'):
+            skip_unless_ranks_fit(world, device_count=count)
+
+
+@pytest.mark.parametrize('dtype', ['c64', 'c128'])
+def test_dump_outputs_writes_what_the_timed_step_returned(tmp_path, dtype):
+    """``--dump-outputs DIR``: <Z0> per sample and the amplitudes of the last timed step, in the state's real precision;
+    two runs with the same arguments write the same arrays, sample 0 (the generator's own angles) is the oracle's state,
+    and ``--steps`` is the number of timed steps."""
+    from oracle import statevec_oracle as oracle
+
+    n, depth, batch = 10, 6, 3
+    real = np.float32 if dtype == 'c64' else np.float64
+    runs = []
+    for k, steps in enumerate((3, 2)):
+        out = tmp_path / f'run{k}'
+        pr, lines = run_bench('--nqubit', n, '--batch', batch, '--depth', depth, '--dtype', dtype, '--steps', steps,
+                              '--warmup', 0, '--no-cpu-baseline', '--no-parity', '--dump-outputs', out)
+        assert pr.returncode == 0, pr.stderr[-2000:]
+        line = lines[0]
+        assert line['steps'] == steps and line['ms_per_step'] > 0
+        assert line['dumped_outputs']['arrays'] == ['expectation', 'state_sample', 'state_sample_index']
+        runs.append({f[:-4]: np.load(out / f) for f in os.listdir(out)})
+    got = runs[0]
+    assert set(got) == {'expectation', 'state_sample', 'state_sample_index'}
+    for name in got:
+        assert got[name].dtype == (np.float64 if name == 'state_sample_index' else real), name
+        assert np.array_equal(got[name], runs[1][name]), name
+    assert got['expectation'].shape == (batch,) and got['state_sample'].shape == (batch << n, 2)
+    assert np.array_equal(got['state_sample_index'], np.arange(batch << n))        # (small state: all of it)
+    cdt = torch.complex64 if dtype == 'c64' else torch.complex128
+    spec = oracle.random_circuit_spec(n, depth, 1234)
+    angles = torch.tensor([[op[2] for op in spec if op[0] == 'rx']], dtype=torch.float64)      # (encoded: full precision)
+    with torch.no_grad():
+        ref = oracle.run_spec(n, spec, dtype=cdt, data=angles)[0].numpy()
+    amp0 = got['state_sample'][:1 << n, 0] + 1j * got['state_sample'][:1 << n, 1]
+    tol = 1e-4 if dtype == 'c64' else 1e-10
+    assert np.abs(amp0 - ref).max() < tol
+    assert abs(got['expectation'][0] - (np.abs(ref[:1 << (n - 1)]) ** 2).sum() + (np.abs(ref[1 << (n - 1):]) ** 2).sum()) < tol
+
+
+def test_dump_outputs_samples_a_large_state_at_seeded_positions(tmp_path, monkeypatch):
+    import bench
+
+    monkeypatch.setattr(bench, 'DUMP_STATE_SAMPLES', 100)
+    state = torch.randn(4, 64, dtype=torch.complex128)
+    names = bench.dump_outputs(str(tmp_path), state, None, 7)
+    assert names == ['state_sample', 'state_sample_index']
+    idx = np.load(tmp_path / 'state_sample_index.npy')
+    amp = np.load(tmp_path / 'state_sample.npy')
+    assert idx.dtype == np.float64 and amp.dtype == np.float64 and amp.shape == (100, 2)
+    assert len(np.unique(idx)) == 100 and np.all(np.diff(idx) > 0) and idx.max() < 256
+    flat = state.reshape(-1).numpy()[idx.astype(np.int64)]
+    assert np.array_equal(amp[:, 0], flat.real) and np.array_equal(amp[:, 1], flat.imag)
+    bench.dump_outputs(str(tmp_path / 'again'), state, None, 7)
+    assert np.array_equal(np.load(tmp_path / 'again' / 'state_sample_index.npy'), idx)

@@ -52,8 +52,9 @@ def _run(case, world, backend=None):
     """``backend`` None: RCCL with one device per rank when the box shows >= ``world`` devices, else gloo with every rank
     on device 0 (``_helpers.pick_transport``; the selector has a CPU test)."""
     sys.path.insert(0, HERE)
-    from _helpers import pick_transport
+    from _helpers import pick_transport, skip_unless_ranks_fit
 
+    skip_unless_ranks_fit(world)
     devices = [0] * world
     if backend is None:
         backend, devices = pick_transport(world)

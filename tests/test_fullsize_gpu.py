@@ -22,6 +22,11 @@ pytestmark = pytest.mark.gpu
 def _bench(*args, need_gib, timeout=900):
     import gc
 
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from _helpers import pick_transport, skip_unless_ranks_fit
+
+    world = int(args[args.index('--gpus') + 1])
+    skip_unless_ranks_fit(world)
     gc.collect()
     torch.cuda.empty_cache()        # (what this pytest process still caches from earlier tests is not free for the ranks)
     torch.cuda.synchronize()
@@ -31,10 +36,6 @@ def _bench(*args, need_gib, timeout=900):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    sys.path.insert(0, os.path.join(ROOT, 'tests'))
-    from _helpers import pick_transport
-
-    world = int(args[args.index('--gpus') + 1])
     transport, _devices = pick_transport(world)       # RCCL, one device per rank, when the box shows enough devices
     pr = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--backend', transport, '--steps', '1', '--warmup', '0',
                          '--functional', '--no-cpu-baseline'] + [str(a) for a in args],
@@ -66,10 +67,11 @@ def test_config4_n32_on_four_ranks(vbits):
 
 
 def test_config5_n33_on_eight_ranks_and_the_qaoa_gradient():
-    """Config 5 at the largest size eight ranks sharing one 288-GB GPU can hold: the forward at n = 33 (8 x 16 GiB), the
+    """Config 5 at the largest size eight ranks sharing one 288-GB GPU's memory can hold: the forward at n = 33 (8 x 16 GiB), the
     QAOA ring (hlayer, cnot . rz . cnot per ring edge, rx layer, one <Z_i Z_j> per edge; examples/qaoa.py:21-64) with
     its gradient through the fused sharded reverse sweep at n = 31 (the adjoint holds eight shard-sized buffers per
-    rank) against the closed form n sin(4 beta) sin(4 gamma) / 2."""
+    rank) against the closed form n sin(4 beta) sin(4 gamma) / 2.  Eight ranks do not share one GPU: with fewer than eight
+    devices the test skips (``_helpers.skip_unless_ranks_fit``)."""
     line = _bench('--gpus', 8, '--config', 5, '--nqubit', 30, '--qaoa-nqubit', 31, need_gib=170, timeout=1500)
     _check(line, 33, 8)
     q = line['config']['qaoa_ring']
