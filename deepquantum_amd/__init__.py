@@ -34,7 +34,7 @@ from .layer import (
     U3Layer, XLayer, YLayer, ZLayer,
 )
 from .operation import Channel, Gate, Layer, Operation
-from .qmath import amplitude_encoding, expectation, measure, multi_kron
+from .qmath import amplitude_encoding, expectation, measure, meyer_wallach_measure, multi_kron, partial_trace
 from .state import DistributedQubitState, QubitState
 from .utils import CapturedGraph, dtype_map
 from . import qasm3  # noqa: E402  (after the circuit classes it builds on)

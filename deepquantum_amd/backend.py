@@ -640,3 +640,48 @@ def deinterleave(pair: torch.Tensor, which: int) -> torch.Tensor:
     fn = getattr(lib, f'dq_deinterleave_{_suffix(pair)}')
     _lib.check(fn(_ptr(pair), _ptr(out), out.numel(), int(which), _stream(pair)), 'dq_deinterleave')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+def rdm1_cross(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    """T[b, k, a, c] = sum over the other wires of conj(bra[b, a on wire k, ..]) ket[b, c on wire k, ..] for every wire
+    k at once: complex128 (B, n, 2, 2).  ``bra is ket`` reads the state once per pass (``dq_rdm1_cross_*``)."""
+    n = _nqubit(ket)
+    if bra.shape != ket.shape or bra.dtype != ket.dtype:
+        raise ValueError('bra/ket must be (batch, 2**n) tensors of one shape and dtype')
+    if not (bra.is_contiguous() and ket.is_contiguous()):
+        raise ValueError('bra/ket must be contiguous')
+    if not _use_hip(ket):
+        return _test_backend.rdm1_cross(bra, ket)
+    same = bra.data_ptr() == ket.data_ptr()
+    lib = _lib.load()
+    fn = getattr(lib, f'dq_rdm1_cross_{_suffix(ket)}')
+    out = torch.empty(ket.shape[0], n, 2, 2, 2, dtype=torch.float64, device=ket.device)
+    for lo in range(0, ket.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, ket.shape[0])
+        nbytes = lib.dq_rdm1_ws_bytes(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
+        rc = fn(_ptr(bra[lo:hi]), _ptr(ket[lo:hi]), n, hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
+        _lib.check(rc, 'dq_rdm1_cross')
+    return torch.view_as_complex(out)
+
+
+def apply_wire_sum(state: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
+    """sum_k (mats[b, k] on wire k) state[b]: the state's dtype, (B, 2**n); ``mats`` complex (B, n, 2, 2)
+    (``dq_apply_wire_sum_*``)."""
+    n = _nqubit(state)
+    if not state.is_contiguous():
+        raise ValueError('state must be contiguous')
+    if mats.shape != (state.shape[0], n, 2, 2):
+        raise ValueError(f'mats must have shape ({state.shape[0]}, {n}, 2, 2), got {tuple(mats.shape)}')
+    if not _use_hip(state):
+        return _test_backend.apply_wire_sum(state, mats)
+    m = torch.view_as_real(mats.to(device=state.device, dtype=torch.complex128).resolve_conj().resolve_neg().contiguous())
+    out = torch.empty_like(state)
+    lib = _lib.load()
+    fn = getattr(lib, f'dq_apply_wire_sum_{_suffix(state)}')
+    for lo in range(0, state.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, state.shape[0])
+        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(m[lo:hi]), n, hi - lo, _stream(state))
+        _lib.check(rc, 'dq_apply_wire_sum')
+    return out

@@ -492,3 +492,142 @@ def expect_z_multi(state: torch.Tensor, zmasks: Sequence[int]) -> torch.Tensor:
     if not state.is_contiguous():
         state = state.contiguous()
     return _ExpectZMulti.apply(state, tuple(int(z) for z in zmasks))
+
+
+def _fold(x: torch.Tensor, d: int | None, v: int) -> torch.Tensor:
+    """The vmapped dimension of ``x`` (at ``d``; None: not mapped) folded into its batch dimension."""
+    x = x.movedim(d, 0) if d is not None else x.unsqueeze(0).expand(v, *x.shape)
+    return x.reshape(v * x.shape[1], *x.shape[2:]).contiguous()
+
+
+class _Rdm1Cross(torch.autograd.Function):
+    """T[b, k, a, c] = sum_rest conj(bra[a on wire k, rest]) ket[c on wire k, rest]: complex128 (B, n, 2, 2), every wire
+    at once (``dq_rdm1_cross_*``; bra and ket the same tensor: one read of the state per pass).  T is anti-linear in
+    bra and linear in ket, so its cotangents are sums of one-wire operators: bra gets W(ket; conj(G)), ket gets
+    W(bra; G^T) (per-wire transpose) -- ``_WireSum`` nodes, whose own backward is again this node: derivatives of any
+    order."""
+
+    @staticmethod
+    def forward(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+        pk = _plain(ket)
+        return backend.rdm1_cross(pk if bra is ket else _plain(bra), pk)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        bra, ket = inputs
+        ctx.same = bra is ket
+        ctx.save_for_backward(bra, ket)
+        ctx.save_for_forward(bra, ket)
+
+    @staticmethod
+    def jvp(ctx, bra_t, ket_t):
+        _single_forward_level()
+        bra, ket = ctx.saved_tensors
+        out = None
+        if bra_t is not None:
+            out = rdm1_cross(bra_t, ket)
+        if ket_t is not None:
+            term = rdm1_cross(bra, ket_t)
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):
+        bra, ket = ctx.saved_tensors
+        g = g.to(torch.complex128)
+        if ctx.same:                           # one sum of one-wire operators for both slots of the one tensor
+            return wire_sum(ket, g.conj() + g.transpose(-1, -2)), None
+        gbra = wire_sum(ket, g.conj()) if ctx.needs_input_grad[0] else None
+        gket = wire_sum(bra, g.transpose(-1, -2)) if ctx.needs_input_grad[1] else None
+        return gbra, gket
+
+    @staticmethod
+    def vmap(info, in_dims, bra, ket):
+        v = info.batch_size
+        same = bra is ket and in_dims[0] == in_dims[1]
+        kf = _fold(ket, in_dims[1], v)
+        bf = kf if same else _fold(bra, in_dims[0], v)
+        out = _Rdm1Cross.apply(bf, kf)
+        return out.reshape(v, -1, *out.shape[1:]), 0
+
+
+class _WireSum(torch.autograd.Function):
+    """W(psi; M) = sum_k (M_k on wire k) psi for M complex (B, n, 2, 2): the state's dtype (``dq_apply_wire_sum_*``).
+    Linear in psi (cotangent: W(g; M^H), per-wire conjugate transpose) and in M (cotangent: T(psi, g)^T, the cross
+    reduction)."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
+        return backend.apply_wire_sum(_plain(state), _plain(mats))
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, mats = inputs
+        ctx.save_for_backward(state, mats)
+        ctx.save_for_forward(state, mats)
+
+    @staticmethod
+    def jvp(ctx, state_t, mats_t):
+        _single_forward_level()
+        state, mats = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = wire_sum(state_t, mats)
+        if mats_t is not None:
+            term = wire_sum(state, mats_t)
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):
+        state, mats = ctx.saved_tensors
+        gstate = gmats = None
+        if ctx.needs_input_grad[0]:
+            gstate = wire_sum(g, mats.mH)
+        if ctx.needs_input_grad[1]:
+            gmats = rdm1_cross(state, g).transpose(-1, -2).to(mats.dtype)
+        return gstate, gmats
+
+    @staticmethod
+    def vmap(info, in_dims, state, mats):
+        v = info.batch_size
+        sf = _fold(state, in_dims[0], v)
+        out = _WireSum.apply(sf, _fold(mats, in_dims[1], v))
+        return out.reshape(v, -1, out.shape[-1]), 0
+
+
+def _no_legacy(*ts: torch.Tensor) -> None:
+    legacy = _functorch.is_legacy_batched
+    if any(legacy(t) for t in ts):
+        raise RuntimeError('deepquantum_amd: the entanglement reductions do not run under the legacy vmap of '
+                           'torch.autograd.functional.jacobian / hessian(vectorize=True); use vectorize=False or '
+                           'torch.func.jacrev / hessian')
+
+
+def rdm1_cross(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    """Differentiable one-body cross reduction of two (B, 2**n) states, complex128 (B, n, 2, 2), indexed by wire:
+    ``rdm1_cross(psi, psi)[b, k].T`` is the reduced density matrix of wire k (pass the same tensor twice: one read)."""
+    _no_legacy(bra, ket)
+    if bra.dtype != ket.dtype:
+        raise ValueError('bra and ket must have one dtype')
+    same = bra is ket
+    if not _is_batched(ket) and not ket.is_contiguous():
+        ket = ket.contiguous()
+    if same:
+        bra = ket
+    elif not _is_batched(bra) and not bra.is_contiguous():
+        bra = bra.contiguous()
+    return _Rdm1Cross.apply(bra, ket)
+
+
+def wire_sum(state: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
+    """Differentiable sum of one-wire operators, ``sum_k (mats[:, k] on wire k) state`` for a (B, 2**n) state and
+    complex (B, n, 2, 2) matrices indexed by wire."""
+    _no_legacy(state, mats)
+    if not mats.is_complex():
+        mats = mats.to(torch.complex128)
+    if not _is_batched(state) and not state.is_contiguous():
+        state = state.contiguous()
+    if not _is_batched(mats):
+        mats = mats.resolve_conj().resolve_neg().contiguous()
+    return _WireSum.apply(state, mats)

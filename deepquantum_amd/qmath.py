@@ -249,3 +249,72 @@ def sample2expval(sample: dict) -> torch.Tensor:
     total = sum(sample.values())
     acc = sum(cnt * (-1) ** (bits.count('1') % 2) for bits, cnt in sample.items())
     return torch.tensor([acc / total])
+
+
+def _entangle_input(state_tsr: torch.Tensor, what: str) -> tuple[torch.Tensor, int]:
+    """(batch, 2, ..., 2) -> the flat (batch, 2**n) state and n = ndim - 1."""
+    from .state import DistributedQubitState
+
+    if isinstance(state_tsr, DistributedQubitState):
+        raise NotImplementedError(f'{what}: sharded states are not supported (the coherences of the global wires need a '
+                                  'pairwise exchange)')
+    if not isinstance(state_tsr, torch.Tensor) or state_tsr.ndim < 2:
+        raise ValueError(f'{what}: input must have the shape (batch, 2, ..., 2), got '
+                         f'{tuple(getattr(state_tsr, "shape", ()))}')
+    if any(d != 2 for d in state_tsr.shape[1:]):
+        raise ValueError(f'{what}: every non-batch dimension must be 2, got shape {tuple(state_tsr.shape)}')
+    if not state_tsr.is_complex():
+        state_tsr = state_tsr.to(torch.complex64 if state_tsr.dtype != torch.float64 else torch.complex128)
+    n = state_tsr.ndim - 1
+    return state_tsr.reshape(state_tsr.shape[0], 1 << n), n
+
+
+def _rdm1(state_tsr: torch.Tensor, what: str) -> tuple[torch.Tensor, int, torch.dtype]:
+    flat, n = _entangle_input(state_tsr, what)
+    return ops.rdm1_cross(flat, flat), n, flat.real.dtype
+
+
+def single_qubit_rdms(state_tsr: torch.Tensor) -> torch.Tensor:
+    """Reduced density matrix of every wire, ``rho_k = Tr_{others} |psi><psi|``: (batch, n, 2, 2) in the state's dtype
+    for an input of shape (batch, 2, ..., 2) -- what ``partial_trace(psi psi^dagger, n, all but k)`` returns for each
+    k, from a fixed number of reads of the state instead of a 4^n matrix.  Not normalised."""
+    t, _n, _rd = _rdm1(state_tsr, 'single_qubit_rdms')
+    return t.transpose(-1, -2).to(state_tsr.dtype if state_tsr.is_complex() else t.dtype)
+
+
+def meyer_wallach_measure(state_tsr: torch.Tensor) -> torch.Tensor:
+    """Meyer-Wallach entanglement measure (reference: qmath.py:874-890), ``(4 / n) sum_k (p0 p1 - |c|^2)`` with
+    ``p0, p1, c`` the entries of the reduced density matrix of wire k: (batch,) real.  No normalisation is applied,
+    as in the reference.  Differentiable to any order."""
+    t, n, rdt = _rdm1(state_tsr, 'meyer_wallach_measure')
+    p0, p1, c = t[..., 0, 0].real, t[..., 1, 1].real, t[..., 0, 1]
+    val = (p0 * p1 - (c.real * c.real + c.imag * c.imag)).sum(-1) * (4.0 / n)
+    return val.to(rdt)
+
+
+def meyer_wallach_measure_brennen(state_tsr: torch.Tensor) -> torch.Tensor:
+    """Brennen's form of the Meyer-Wallach measure (reference: qmath.py:941-965), ``2 (1 - (1/n) sum_k Tr rho_k^2)``:
+    (batch,) real.  The reference builds the 4^n density matrix; here it is the same one-body reduction as
+    :func:`meyer_wallach_measure`."""
+    t, n, rdt = _rdm1(state_tsr, 'meyer_wallach_measure_brennen')
+    p0, p1, c = t[..., 0, 0].real, t[..., 1, 1].real, t[..., 0, 1]
+    purity = p0 * p0 + p1 * p1 + 2.0 * (c.real * c.real + c.imag * c.imag)
+    return (2.0 * (1.0 - purity.sum(-1) / n)).to(rdt)
+
+
+def linear_map_mw(state_tsr: torch.Tensor, j: int, b: int) -> torch.Tensor:
+    """Project wire ``j`` of a (batch, 2, ..., 2) state onto |b> (reference: qmath.py:893-918): a view of shape
+    (batch, 2, ..., 2) with that wire removed, not normalised."""
+    if b not in (0, 1):
+        raise ValueError('b must be 0 or 1')
+    if not 0 <= j < state_tsr.ndim - 1:
+        raise ValueError(f'wire {j} out of range for {state_tsr.ndim - 1} qubits')
+    return state_tsr.select(j + 1, b)
+
+
+def generalized_distance(state1: torch.Tensor, state2: torch.Tensor) -> torch.Tensor:
+    """``<s1|s1> <s2|s2> - |<s1|s2>|^2`` of (batch, 2^n, 1) inputs, shape (batch, 1, 1) real (reference:
+    qmath.py:921-938)."""
+    overlap = state1.mH @ state2
+    norms = (state1.mH @ state1).real * (state2.mH @ state2).real
+    return norms - (overlap.real * overlap.real + overlap.imag * overlap.imag)

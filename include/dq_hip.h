@@ -45,7 +45,7 @@ typedef enum {
     DQ_ERR_UNSUPPORTED = -3  /* valid request outside what this build implements */
 } DqStatus;
 
-#define DQ_ABI_VERSION 25
+#define DQ_ABI_VERSION 26
 
 int dq_abi_version(void);
 /* Thread-local, never NULL. */
@@ -459,6 +459,29 @@ int dq_interleave_c64(const void* a, const void* b, void* out, int64_t count, dq
 int dq_interleave_c128(const void* a, const void* b, void* out, int64_t count, dq_stream_t stream);
 int dq_deinterleave_c64(const void* in, void* out, int64_t count, int which, dq_stream_t stream);
 int dq_deinterleave_c128(const void* in, void* out, int64_t count, int which, dq_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 5. One-body reductions for entanglement measures (ABI 26; csrc/dq_entangle.hip).  Replace the permute-copies and
+ *    inner products of qmath.meyer_wallach_measure / linear_map_mw / generalized_distance (qmath.py:874-938) and the
+ *    4^n density matrix of meyer_wallach_measure_brennen (qmath.py:941-965).  Wire k is index bit n - 1 - k.
+ *    1 <= n <= 40, 1 <= batch <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of device workspace dq_rdm1_cross_* needs (cross != 0: bra != ket); -1 on a bad argument. */
+int64_t dq_rdm1_ws_bytes(int n, int64_t batch, int is_c128, int cross);
+/* out[b, k, a, c] = sum over the other wires of conj(bra[b, a on wire k, rest]) * ket[b, c on wire k, rest]:
+ * DEVICE complex128 [batch, n, 2, 2], fully overwritten.  bra == ket reads the state once per pass.  Passes: 1 +
+ * ceil((n - 12) / 8) (complex64), 1 + ceil((n - 12) / 9) (complex128; its cross reduction 1 + ceil((n - 11) / 8)).
+ * Workgroups write fixed-order partial sums into `ws` (at least dq_rdm1_ws_bytes bytes) and a second kernel adds
+ * them: no atomics, results are bitwise reproducible. */
+int dq_rdm1_cross_c64(const void* bra, const void* ket, int n, int64_t batch, double* out, void* ws, int64_t ws_bytes,
+                      dq_stream_t stream);
+int dq_rdm1_cross_c128(const void* bra, const void* ket, int n, int64_t batch, double* out, void* ws, int64_t ws_bytes,
+                       dq_stream_t stream);
+/* out[b] = sum_k (mats[b, k] acting on wire k) psi[b]; mats: DEVICE complex128 [batch, n, 2, 2].  The reverse mode of
+ * dq_rdm1_cross_*.  Same passes as dq_rdm1_cross_* with bra == ket: the first writes out, later ones read psi and add
+ * into out.  out must not alias psi. */
+int dq_apply_wire_sum_c64(const void* psi, void* out, const double* mats, int n, int64_t batch, dq_stream_t stream);
+int dq_apply_wire_sum_c128(const void* psi, void* out, const double* mats, int n, int64_t batch, dq_stream_t stream);
 
 #ifdef __cplusplus
 }
