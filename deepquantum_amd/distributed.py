@@ -41,7 +41,7 @@ from typing import Sequence
 import torch
 import torch.distributed as dist
 
-from . import backend, executor
+from . import backend, executor, schedule
 from .bitmath import get_bit
 from .communication import comm_exchange_arrays, exchange_chunks, exchange_pieces
 from .executor import Prim
@@ -108,7 +108,9 @@ _SWEEP: dict = {'grads': None}
 LAST_RUN = {'remaps': 0, 'pairwise_exchanges': 0, 'local_flushes': 0, 'folded_permutes': 0, 'permute_passes': 0,
             'wire_bytes': 0, 'groups': 1, 'virtual_bits': 0, 'virtual_remaps': 0, 'zero_shard_stretches': 0,
             'known_zero_stretches': 0, 'local_first_exchanges': 0, 'zero_fills': 0, 'sliced_remaps': 0,
-            'slice_launches_last': 0, 'slice_launches_first': 0, 'deferred_tails': 0, 'deferred_gates': 0}
+            'slice_launches_last': 0, 'slice_launches_first': 0, 'deferred_tails': 0, 'deferred_gates': 0,
+            # the eviction rule the schedule used (`schedule.evict`; CONFIG['evict_foldable'] resolved)
+            'evict_foldable': True}
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -670,38 +672,34 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
     vb = _vbits(state)
     L, W = state.log_num_amps_per_node - vb, state.world_size       # (with virtual rank bits: L = bits of a ROW)
     ph = _phys(state)
-    pairs = sorted(pairs, key=lambda pr: ph[pr[0]])          # ascending rank bit -> ascending peer rank
     k = len(pairs)
-    rbits = [ph[lq] - L for lq, _ in pairs]                 # bits of the (virtual) world's rank: the low vb are rows
-    assert all(0 <= r < state.log_num_nodes + vb for r in rbits) and all(ph[eq] < L for _, eq in pairs)
+    assert all(ph[lq] >= L for lq, _ in pairs) and all(ph[eq] < L for _, eq in pairs)
     # a sliced exchange in flight (`_remap_sliced`): the first pass of THIS stretch takes it slice by slice
     arr = state.__dict__.pop('_arrivals', None)
-    # 1. the entering qubits go to the top k local bits (chunk index = their joint value): destination bit d takes
-    #    source bit src_of_dst[d]
-    ent_bits = [ph[eq] for _, eq in pairs]
+    if vb:
+        # (the planner re-fills ONE class of far positions per remap, `schedule.evict`)
+        real = [ph[lq] - L >= vb for lq, _ in pairs]
+        assert all(real) or not any(real), 'a remap trades real OR virtual rank bits'
+        if not real[0]:                 # virtual bits trade places: a re-labelling of the shard, no exchange
+            _remap_virtual(state, pairs, pending)
+            return
+        pending[:] = [q for q in (_localize(state, p) for p in pending) if q is not None]      # row by row
+    # 1. the entering qubits go to the top k local bits (chunk index = their joint value) -- with slices, the slice qubits
+    #    right below them (protocol bit i on local bit L - k - B + i) -- in the passes in front of the exchange
+    #    (`schedule.relabel`: ``ph`` already is the placement behind the exchange)
+    ent_bits = {ph[eq] for _, eq in pairs}
     sq = [q for q in slice_qubits if ph[q] < L and ph[q] not in ent_bits]
     sliced = (len(sq) > 0 and vb == 0 and _view(state).shape[0] == 1 and _live(state) and L - k - len(sq) >= 12
               and _SWEEP['grads'] is None and CONFIG['fold_permute'] and not state.__dict__.get('_as_rank0')
               and not state.__dict__.get('_behind_reset'))
     if not sliced:
         sq = []
-    sbits = [ph[q] for q in sq]
-    #    (with slices: the slice qubits right below them -- protocol bit i on local bit L - k - B + i)
-    src_of_dst = [b for b in range(L) if b not in ent_bits and b not in sbits] + sbits + ent_bits
-    out_perm = [0] * L
-    for d, sp in enumerate(src_of_dst):
-        out_perm[sp] = d
+    pairs, rbits, out_perm = schedule.relabel(ph, pairs, L, [ph[q] for q in sq])   # rbits: the low vb are rows
+    assert all(0 <= r < state.log_num_nodes + vb for r in rbits)
     identity = out_perm == list(range(L))
     # 2. chunk c goes to the peer whose rank bits `rbits` spell c; what comes back from that peer lands in
     #    the same chunk slot.  Peers outside the 2^k group get empty messages.
     chunk = (1 << (L - k))
-    if vb:
-        # (the planner re-fills ONE class of far positions per remap, `_plan_remap`)
-        assert all(r < vb for r in rbits) or all(r >= vb for r in rbits), 'a remap trades real OR virtual rank bits'
-        if rbits[0] < vb:               # virtual bits trade places: a re-labelling of the shard, no exchange
-            _remap_virtual(state, pairs, pending)
-            return
-        pending[:] = [q for q in (_localize(state, p) for p in pending) if q is not None]      # row by row
     peers = []
     for c in range(1 << k):
         peer = state.rank
@@ -713,7 +711,7 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
     streams = _group_streams(state, len(groups))
     if sliced or arr is not None:
         if _remap_sliced(state, pairs, rbits, pending, out_perm, identity, k, chunk, peers, len(sq), arr):
-            _remap_bookkeeping(ph, pairs, rbits, out_perm, L)
+            LAST_RUN['remaps'] += 1
             return
         a, b = _view(state), _bview(state)        # (the stretch may have run and changed the buffers' roles)
     # the first stretch behind reset(): rank 0 holds |0..0> -- its first passes skip what is still known to be zero --
@@ -728,7 +726,7 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
     first_exchange = state.__dict__.pop('_behind_reset', False)
     if as0 and fresh and first_exchange and vb == 0 and _live(state):
         _first_exchange_local(state, pairs, rbits, pending, out_perm, identity, k, chunk)
-        _remap_bookkeeping(ph, pairs, rbits, out_perm, L)
+        LAST_RUN['remaps'] += 1
         state.__dict__['_known_zero_local'] = ((1 << k) - 1) << (L - k)
         return
     if zeros:
@@ -805,7 +803,7 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
     if not identity:
         LAST_RUN['folded_permutes' if executor.LAST_RUN.get('permute_folded') else 'permute_passes'] += 1
     LAST_RUN['groups'] = len(groups)
-    _remap_bookkeeping(ph, pairs, rbits, out_perm, L)
+    LAST_RUN['remaps'] += 1
     if first_exchange and _live(state):
         # The first exchange behind reset(): only rank 0 had anything to send, so on every rank (and in every row) what
         # arrived lies in chunk 0 and the other chunks hold the zeros the other ranks sent -- the qubits that came from
@@ -1012,19 +1010,6 @@ def _first_exchange_local(state: DistributedQubitState, pairs, rbits, pending: l
     LAST_RUN['groups'] = 1
 
 
-def _remap_bookkeeping(ph: list[int], pairs, rbits, out_perm, L: int) -> None:
-    """Local qubits moved with the permutation; entering qubit i now is rank bit rbits[i]; leaving qubit i is local bit
-    L - k + i."""
-    k = len(pairs)
-    for q, p_ in enumerate(ph):
-        if p_ < L:
-            ph[q] = out_perm[p_]
-    for i, (lq, eq) in enumerate(pairs):
-        ph[eq] = L + rbits[i]
-        ph[lq] = L - k + i
-    LAST_RUN['remaps'] += 1
-
-
 def _remap_virtual(state: DistributedQubitState, pairs, pending: list[Prim]) -> None:
     """A remap that trades VIRTUAL rank bits only (CONFIG['virtual_bits']): nothing leaves the GPU -- the qubits on the
     virtual bits and the entering row-local qubits swap index positions of the ONE shard, and that re-labelling rides on
@@ -1066,280 +1051,8 @@ def _remap_virtual(state: DistributedQubitState, pairs, pending: list[Prim]) -> 
         state.__dict__['_vbits'] = vb
 
 
-#: the eviction policy in force (set per call by `_dist_apply_prims` from CONFIG['evict_foldable']; None there = whichever
-#: the dry-run model prefers for the circuit at hand, `choose_eviction`)
-_EVICT = [True]
-
-
-#: index bits below this are the contiguous low bits of a complex64 tile (fusion.default_geometry: min_low = 4; 3 for
-#: complex128 -- the stricter bound serves both): `fusion._place_writes` folds a final permutation only if it fixes them
-_UNFOLDABLE_BELOW = 4
-
-
-def _next_use(prims: Sequence[Prim], start: int, n: int) -> list[int]:
-    """Index of the next gate (>= start) acting NON-diagonally on each logical qubit (inf if none soon)."""
-    inf = 1 << 60
-    nxt = [inf] * n
-    left = n
-    stop = min(len(prims), start + CONFIG['horizon'])
-    for j in range(start, stop):
-        p = prims[j]
-        if p.kind == 'diag':
-            continue
-        for t in p.targets:
-            if nxt[t] == inf:
-                nxt[t] = j
-                left -= 1
-        if left == 0:
-            break
-    return nxt
-
-
-def _plan_remap(ph: list[int], prims: Sequence[Prim], i: int, n: int, L: int, v: int = 0) -> list[tuple[int, int]]:
-    """Which qubits trade places so that gate ``i`` becomes local: evict to the rank bits the qubits whose
-    next non-diagonal use is farthest away (Belady).  Pure function of the gate list: every rank computes
-    the same plan.
-
-    ``v`` virtual rank bits (positions L .. L + v - 1; L = bits of a row): the two classes of far positions are
-    re-filled SEPARATELY -- a remap either trades real rank bits only (its wire time hides behind the other rows'
-    passes) or virtual bits only (chunks move between rows of the shard: no wire at all) -- virtual bits first when
-    gate ``i`` waits for one of them; the loop comes back for the other class if the gate still is not local."""
-    nxt = _next_use(prims, i, n)
-    needed = {t for t in prims[i].targets} if prims[i].kind != 'diag' else set()
-    if v:
-        on_virtual = any(L <= ph[t] < L + v for t in needed)
-        mine = (lambda p_: L <= p_ < L + v) if on_virtual else (lambda p_: p_ >= L + v)
-    else:
-        mine = lambda p_: p_ >= L                 # noqa: E731
-    g = sum(1 for q in range(n) if mine(ph[q]))   # far positions of the class that is re-filled
-    is_glob = [mine(ph[q]) for q in range(n)]
-    frozen = [ph[q] >= L and not mine(ph[q]) for q in range(n)]       # the other class: stays where it is
-    # farthest next use first; ties: keep what already is global (less traffic), then qubits above the contiguous run
-    # of a tile (moving a lower bit cannot ride on a fused pass's permuted store), then canonical order
-    # (a local qubit on the contiguous low bits of a tile cannot be moved by a fused pass's permuted store -- its remap
-    # would cost a re-labelling pass of its own: with CONFIG['evict_foldable'] such a qubit is evicted only when nothing else is left)
-    low = _UNFOLDABLE_BELOW if (_EVICT[0] and L >= 12) else 0      # (shards of at least a tile)
-    order = sorted((q for q in range(n) if not frozen[q]),
-                   key=lambda q: (1 if (not is_glob[q] and ph[q] < low) else 0, -nxt[q], 0 if is_glob[q] else 1, 0 if ph[q] >= 4 else 1, -q))
-    new_global = set(order[:g])
-    assert not ({t for t in needed if not frozen[t]} & new_global), 'gate needs more local qubits than a shard has'
-    leaving = [q for q in range(n) if is_glob[q] and q not in new_global]
-    entering = [q for q in new_global if not is_glob[q]]
-    assert len(leaving) == len(entering) and leaving, 'remap requested although the gate is local'
-    # a canonical global qubit (logical bit L + j) prefers its own rank bit j: cheaper to canonicalise later
-    pairs, free_enter = [], list(entering)
-    for lq in leaving:
-        own = ph[lq]                                   # physical rank bit being vacated
-        pick = next((eq for eq in free_enter if eq == own), free_enter[0])
-        free_enter.remove(pick)
-        pairs.append((lq, pick))
-    return pairs
-
-
-_ORDERS: dict = {}
-
-
-def _structure(prims: Sequence[Prim]) -> tuple:
-    """What the exchange schedule of a gate list depends on (no matrices): the key of the schedule caches."""
-    return tuple((p.kind, tuple(p.targets), tuple(p.controls), p.mode, tuple(p.order)) for p in prims)
-
-
-def _order_for_remaps(prims: Sequence[Prim], ph0: Sequence[int], n: int, L: int, v: int = 0,
-                      structure: tuple | None = None) -> list[Prim]:
-    """`_order_indices` applied; the order is cached by the gate list's structure and the starting placement (round 6: it
-    is 10 ms of host time for the 1360 gates of the n = 34 benchmark circuit, in front of the step's first launch)."""
-    key = (structure if structure is not None else _structure(prims), tuple(ph0), n, L, v, _EVICT[0])
-    order = _ORDERS.get(key)
-    if order is None:
-        order = _order_indices(prims, ph0, n, L, v)
-        if len(_ORDERS) >= 16:
-            _ORDERS.pop(next(iter(_ORDERS)))
-        _ORDERS[key] = order
-    return [prims[i] for i in order]
-
-
-def _order_indices(prims: Sequence[Prim], ph0: Sequence[int], n: int, L: int, v: int = 0) -> list[int]:
-    """The gate list in an order that needs far fewer exchanges: list scheduling over the commutation DAG of the
-    circuit (`fusion._Dag`: two gates commute when on every shared qubit both act diagonally, or both as functions of
-    X) -- every gate that is ready and local under the current placement runs; only when ALL ready gates wait for a
-    qubit on the rank bits does a remap happen (simulated here with the same farthest-next-use rule as `_plan_remap`).
-    In program order a gate on a global qubit stops everything behind it, although most of what follows neither
-    depends on it nor touches that qubit: on the benchmark circuit (depth 40) the exchange steps go 15 -> 4 (2 ranks),
-    20 -> 5 (4), 22 -> 5 (8 ranks) and the bytes on the wire down by 73-78 %.  The re-ordering is exact (commuting
-    operators), a pure function of the gate list and the starting placement: every rank computes the same order."""
-    from . import fusion
-
-    g = n - L
-    ops = [fusion.PrimOp(p.kind, tuple(p.targets), tuple(p.controls), 0, p.mode) for p in prims]
-    dag = fusion._Dag(ops, n)
-    ph = list(ph0)
-    retired = [False] * len(prims)
-    order: list[int] = []
-    inf = 1 << 60
-    while dag.done < dag.n_ops:
-        progressed = True
-        while progressed:
-            progressed = False
-            for i in list(dag.ready):
-                p = prims[i]
-                if p.kind == 'diag' or all(ph[t] < L for t in p.targets):
-                    order.append(i)
-                    dag.retire(i)
-                    retired[i] = True
-                    progressed = True
-        if dag.done >= dag.n_ops:
-            break
-        # every ready gate has a target on the rank bits: new global qubits = the ones not needed for longest
-        nxt = [inf] * n
-        left = n
-        for j in range(dag.ready[0], len(prims)):
-            if retired[j] or prims[j].kind == 'diag':
-                continue
-            for t in prims[j].targets:
-                if nxt[t] == inf:
-                    nxt[t] = j
-                    left -= 1
-            if left == 0:
-                break
-        if v:      # (virtual rank bits: one class of far positions is re-filled at a time, as in `_plan_remap`)
-            waits = {t for i in dag.ready if prims[i].kind != 'diag' for t in prims[i].targets}
-            on_virtual = any(L <= ph[t] < L + v for t in waits)
-            mine = (lambda p_: L <= p_ < L + v) if on_virtual else (lambda p_: p_ >= L + v)
-        else:
-            mine = lambda p_: p_ >= L             # noqa: E731
-        is_glob = [mine(ph[q]) for q in range(n)]
-        frozen = [ph[q] >= L and not mine(ph[q]) for q in range(n)]
-        low = _UNFOLDABLE_BELOW if (_EVICT[0] and L >= 12) else 0
-        cand = sorted((q for q in range(n) if not frozen[q]),
-                      key=lambda q: (1 if (not is_glob[q] and ph[q] < low) else 0, -nxt[q], 0 if is_glob[q] else 1, 0 if ph[q] >= 4 else 1, -q))
-        new_global = set(cand[:sum(is_glob)])
-        leaving = [q for q in range(n) if is_glob[q] and q not in new_global]
-        entering = [q for q in new_global if not is_glob[q]]
-        if not leaving:          # (cannot happen: some ready gate has a global target, and its next use is now)
-            i = dag.ready[0]
-            order.append(i)
-            dag.retire(i)
-            retired[i] = True
-            continue
-        for lq, eq in zip(leaving, entering):
-            ph[lq], ph[eq] = ph[eq], ph[lq]
-    return order
-
-
-_PLACEMENTS: dict = {}
-
-
-def _dry_canonicalize(ph: list[int], n: int, L: int) -> tuple[int, float]:
-    """(exchanges, volume in shards) that `_canonicalize` would need from placement ``ph`` (no data; ``ph`` is updated):
-    the same rounds -- every misplaced rank bit trades with its owner, or with a filler while the owner itself sits on
-    another rank bit."""
-    steps, vol = 0, 0.0
-    for _ in range(4):
-        misplaced = [q for q in range(n) if ph[q] >= L and ph[q] != q]
-        if not misplaced:
-            break
-        used: set = set()
-        pairs = []
-        for lq in misplaced:
-            owner = ph[lq]
-            pick = owner if (ph[owner] < L and owner not in used) else next(q for q in range(L) if ph[q] < L and q not in used)
-            used.add(pick)
-            pairs.append((lq, pick))
-        for lq, pick in pairs:
-            ph[lq], ph[pick] = ph[pick], ph[lq]
-        steps += 1
-        vol += 1 - 0.5 ** len(pairs)
-    return steps, vol
-
-
-def _dry_remaps(prims: Sequence[Prim], ph0: Sequence[int], n: int, lr: int, v: int, restore: bool = False,
-                trace: list | None = None) -> tuple[int, float]:
-    """(exchanges of real rank bits, their volume in shards) of the remap schedule started from placement ``ph0`` -- the
-    loop of `count_exchange_steps` without the statistics.  ``restore``: plus what the canonicalisation at the end of a
-    drop-in forward (``keep_layout=False``) costs from where the schedule leaves the qubits.  ``trace``: a list that
-    receives one (k, trades real rank bits) per remap of the gate schedule, in order."""
-    L = lr + v
-    ph = list(ph0)
-    order = _order_for_remaps(prims, ph, n, lr, v)
-    steps, vol, i = 0, 0.0, 0
-    while i < len(order):
-        p = order[i]
-        if p.kind != 'diag' and any(ph[t] >= lr for t in p.targets):
-            pairs = sorted(_plan_remap(ph, order, i, n, lr, v), key=lambda pr: ph[pr[0]])
-            k = len(pairs)
-            rb = [ph[lq] for lq, _ in pairs]
-            ent = [ph[eq] for _, eq in pairs]
-            new_local = {sp: d for d, sp in enumerate([b for b in range(lr) if b not in ent] + ent)}
-            for q in range(n):
-                if ph[q] < lr:
-                    ph[q] = new_local[ph[q]]
-            for j, (lq, eq) in enumerate(pairs):
-                ph[eq], ph[lq] = rb[j], lr - k + j
-            if trace is not None:
-                # (k, trades real rank bits, the re-labelling in front of it can ride on a pass: no entering qubit on the
-                # contiguous low bits of a tile)
-                trace.append((k, rb[0] >= L, all(e >= _UNFOLDABLE_BELOW for e in ent) or lr < 12))
-            if rb[0] >= L:
-                steps += 1
-                vol += 1 - 0.5**k
-            continue
-        i += 1
-    if restore:
-        cs, cv = _dry_canonicalize(ph, n, L)
-        steps, vol = steps + cs, vol + cv
-    return steps, vol
-
-
-def initial_placement(prims: Sequence[Prim], n: int, L: int, v: int = 0, restore: bool = False,
-                      structure: tuple | None = None) -> list[int]:
-    """Where the qubits of a circuit that starts from |0..0> should sit at the start: |0..0> is the same vector under
-    every permutation of the qubits (rank 0 holds the one non-zero amplitude at local index 0 in any of them), so the
-    FIRST placement costs nothing -- no exchange, not even a re-labelling pass.  Candidates: the reference layout
-    (wires 0 .. g-1 on the rank bits -- a layered circuit needs them within its first layer) and the placements that put
-    g of the g + 3 qubits whose first non-diagonal gate comes last (farthest next use, asked at gate 0) on the rank bits
-    and the next v on the virtual ones (CONFIG['virtual_bits']); each is dry-run through the whole remap schedule
-    (`_dry_remaps`, ~10 ms) and the one with the fewest exchanges wins -- the reference layout unless another one saves a
-    whole exchange.  Never worse than the reference start, typically one exchange and one stretch boundary less (n = 34 on 8 ranks:
-    5 -> 4 exchanges, 35 -> 33 passes).  A pure function of the gate list, cached by its structure: every rank computes
-    the same placement.  ``canonicalize`` restores the reference's order whenever somebody asks for it; ``restore`` (a
-    drop-in forward, ``keep_layout=False``) charges every candidate the exchanges of that canonicalisation too, so that
-    "never worse than the reference start" holds for the step as it runs."""
-    from itertools import combinations
-
-    g = n - L
-    canonical = list(range(n))
-    if g <= 0 or not prims:
-        return canonical
-    # (the tuple itself: a hash of strings is randomised per process, and a collision on one rank only would give the
-    # ranks different placements)
-    key = (n, L, v, bool(restore), CONFIG['horizon'], CONFIG['reorder'], _EVICT[0],
-           structure if structure is not None else _structure(prims))
-    hit = _PLACEMENTS.get(key)
-    if hit is not None:
-        return list(hit)
-    nxt = _next_use(prims, 0, n)
-    order = sorted(range(n), key=lambda q: (-nxt[q], 0 if q >= L else 1, -q))
-    lr = L - v
-    best = (_dry_remaps(prims, canonical, n, lr, v, restore), 0, canonical)
-    for ci, pick in enumerate(combinations(order[:g + 3], g)):
-        ph = list(canonical)
-        rest = [q for q in order if q not in pick]
-        for positions, want in ((range(L, n), list(pick)), (range(lr, L), rest[:v])):
-            have = [q for q in range(n) if ph[q] in positions]
-            leaving = [q for q in have if q not in want]
-            entering = [q for q in want if q not in have]
-            for lq, eq in zip(leaving, entering):
-                ph[lq], ph[eq] = ph[eq], ph[lq]
-        cand = (_dry_remaps(prims, ph, n, lr, v, restore), ci + 1, ph)
-        # (fewer EXCHANGES, not merely less volume: a placement that only trims the volume was measured to cost more in
-        # passes and un-folded re-labellings than it saves on the wire -- rehearsal of n = 34 / 8 ranks with virtual bits)
-        if cand[0][0] < best[0][0] or (cand[0][0] == best[0][0] and best[1] > 0 and cand[0] < best[0]):
-            best = cand
-    if len(_PLACEMENTS) >= 32:
-        _PLACEMENTS.pop(next(iter(_PLACEMENTS)))
-    _PLACEMENTS[key] = list(best[2])
-    return list(best[2])
-
+# ---------------------------------------------------------------------------------------------------
+# the exchange schedule (`schedule`: pure functions of the gate list's structure and of `_knobs`)
 
 #: The dry-run cost model behind `choose_virtual_bits`, in units of ONE PASS over the shard (read + write at the rate the
 #: pass kernel reaches on a shard, 5.5 TB/s: profiles/r05/strong_rehearsal.txt).  A stretch boundary -- every remap, real
@@ -1348,95 +1061,53 @@ def initial_placement(prims: Sequence[Prim], n: int, L: int, v: int = 0, restore
 #: `link_GBs`, of which only the first row's share 2^-v is exposed with v virtual bits (all of it with v = 0).
 MODEL = {'pass_GBs': 5500.0, 'link_GBs': 153.0, 'boundary_passes': 1.7}
 
-_VBITS: dict = {}
+
+def _knobs(evict: bool | None = None) -> schedule.Knobs:
+    """The planner's settings as CONFIG and MODEL stand now.  The eviction rule: ``evict``, or (None) the one the last
+    `dist_apply_prims` call used (LAST_RUN['evict_foldable'])."""
+    return schedule.Knobs(CONFIG['horizon'], bool(CONFIG['reorder']), bool(CONFIG['initial_placement']),
+                          bool(CONFIG['first_exchange_local']), LAST_RUN['evict_foldable'] if evict is None else bool(evict),
+                          tuple(sorted(MODEL.items())))
 
 
-def modelled_cost(trace: Sequence[tuple[int, bool]], v: int, first_is_local: bool) -> float:
-    """Cost of a remap schedule (`_dry_remaps(trace=...)`) in passes over the shard: see `MODEL`."""
-    wire_pass = MODEL['pass_GBs'] / (2.0 * MODEL['link_GBs'])       # one shard over ONE link, in passes
-    cost, first = 0.0, first_is_local and v == 0
-    for k, real, *rest in trace:
-        cost += MODEL['boundary_passes']
-        if rest and not rest[0]:
-            cost += 1.0             # a re-labelling pass of its own in front of the exchange
-        if real:
-            if first:               # the first exchange behind reset() without the wire: a copy of 2^-k and a memset
-                cost += 0.5
-            else:
-                cost += wire_pass / (1 << k) * (0.5 ** v)
-            first = False
-    return cost
+def _order_for_remaps(prims: Sequence[Prim], ph0: Sequence[int], n: int, L: int, v: int = 0,
+                      structure: tuple | None = None) -> list[Prim]:
+    """The gate list in commutation-DAG order (`schedule.order_indices`) from placement ``ph0``."""
+    st = structure if structure is not None else schedule.structure(prims)
+    return [prims[i] for i in schedule.order_indices(st, tuple(ph0), n, L, v, _knobs())]
 
 
-_EVICTIONS: dict = {}
+def initial_placement(prims: Sequence[Prim], n: int, L: int, v: int = 0, restore: bool = False,
+                      structure: tuple | None = None) -> list[int]:
+    """The free first placement of a circuit that starts from |0..0> (`schedule.initial_placement`)."""
+    st = structure if structure is not None else schedule.structure(prims)
+    return list(schedule.initial_placement(st, n, L, v, bool(restore), _knobs()))
 
 
 def choose_eviction(prims: Sequence[Prim], n: int, L: int, v: int = 0, fresh: bool = False, restore: bool = False,
                     structure: tuple | None = None) -> bool:
-    """CONFIG['evict_foldable'] = None: both eviction rules dry-run through the whole schedule, the cheaper one by
-    `modelled_cost` wins (ties: the foldable rule).  A pure function of the gate list: every rank chooses alike."""
-    key = (n, L, v, fresh, restore, CONFIG['first_exchange_local'], CONFIG['initial_placement'], tuple(sorted(MODEL.items())),
-           structure if structure is not None else _structure(prims))
-    hit = _EVICTIONS.get(key)
-    if hit is not None:
-        return hit
-    keep = _EVICT[0]
-    costs = {}
-    try:
-        for rule in (True, False):
-            _EVICT[0] = rule
-            ph = (initial_placement(prims, n, L, v, restore=restore, structure=structure)
-                  if (fresh and CONFIG['initial_placement']) else list(range(n)))
-            trace: list = []
-            _dry_remaps(prims, ph, n, L - v, v, trace=trace)
-            costs[rule] = modelled_cost(trace, v, fresh and CONFIG['first_exchange_local'])
-    finally:
-        _EVICT[0] = keep
-    if len(_EVICTIONS) >= 16:
-        _EVICTIONS.pop(next(iter(_EVICTIONS)))
-    _EVICTIONS[key] = costs[True] <= costs[False] + 1e-9
-    return _EVICTIONS[key]
+    """CONFIG['evict_foldable'] = None: the eviction rule the dry-run model prices lower (`schedule.choose_eviction`)."""
+    st = structure if structure is not None else schedule.structure(prims)
+    return schedule.choose_eviction(st, n, L, v, bool(fresh), bool(restore), _knobs())
 
 
 def choose_virtual_bits(prims: Sequence[Prim], n: int, L: int, candidates: Sequence[int] = (0, 1, 2), fresh: bool = False,
                         restore: bool = False, structure: tuple | None = None) -> int:
-    """CONFIG['virtual_bits'] = None: v from the dry-run model (`modelled_cost`), never one the model puts behind v = 0
-    (round 5 defaulted to 2 under RCCL; its own rehearsal of n = 34 on 8 ranks had v = 2 SLOWER than v = 0 for the slowest
-    rank: the hidden wire was paid for with three times the launches and 60-70 ms of compute).  Every candidate's schedule
-    is dry-run from the placement it would start from; ties go to the smaller v.  A pure function of the gate list and
-    CONFIG: every rank chooses alike."""
-    return _choose_virtual_bits(prims, n, L, candidates, fresh, restore, structure)[0]
+    """CONFIG['virtual_bits'] = None: v from the dry-run model (`schedule.choose_virtual_bits`), never one the model puts
+    behind v = 0 (round 5 defaulted to 2 under RCCL; its own rehearsal of n = 34 on 8 ranks had v = 2 SLOWER than v = 0
+    for the slowest rank: the hidden wire was paid for with three times the launches and 60-70 ms of compute).  Every
+    candidate's schedule is dry-run from the placement it would start from; ties go to the smaller v."""
+    st = structure if structure is not None else schedule.structure(prims)
+    return schedule.choose_virtual_bits(st, n, L, tuple(candidates), bool(fresh), bool(restore), _knobs())[0]
 
 
-def _choose_virtual_bits(prims, n, L, candidates=(0, 1, 2), fresh=False, restore=False, structure=None) -> tuple[int, dict]:
-    key = (n, L, tuple(candidates), fresh, restore, CONFIG['first_exchange_local'], CONFIG['initial_placement'], _EVICT[0],
-           tuple(sorted(MODEL.items())), structure if structure is not None else _structure(prims))
-    hit = _VBITS.get(key)
-    if hit is not None:
-        return hit
-    best, table = None, {}
-    for v in candidates:
-        if L - v < 1:
-            continue
-        ph = (initial_placement(prims, n, L, v, restore=restore, structure=structure)
-              if (fresh and CONFIG['initial_placement']) else list(range(n)))
-        trace: list = []
-        _dry_remaps(prims, ph, n, L - v, v, trace=trace)
-        cost = modelled_cost(trace, v, fresh and CONFIG['first_exchange_local'])
-        table[v] = {'cost_in_passes': cost, 'remaps_real': sum(1 for t_ in trace if t_[1]),
-                    'remaps_virtual': sum(1 for t_ in trace if not t_[1]),
-                    'relabelling_passes': sum(1 for t_ in trace if not t_[2])}
-        if best is None or cost < best[1] - 1e-9:
-            best = (v, cost)
-    if len(_VBITS) >= 16:
-        _VBITS.pop(next(iter(_VBITS)))
-    _VBITS[key] = (best[0] if best else 0, table)
-    return _VBITS[key]
-
-
-def virtual_bits_table(prims: Sequence[Prim], n: int, L: int, **kw) -> dict:
+def virtual_bits_table(prims: Sequence[Prim], n: int, L: int, candidates: Sequence[int] = (0, 1, 2), fresh: bool = False,
+                       restore: bool = False, structure: tuple | None = None) -> dict:
     """The model's table behind `choose_virtual_bits` (bench.py prints it): {v: cost in passes, remaps}, and the choice."""
-    v, table = _choose_virtual_bits(prims, n, L, **kw)
+    st = structure if structure is not None else schedule.structure(prims)
+    v, rows = schedule.choose_virtual_bits(st, n, L, tuple(candidates), bool(fresh), bool(restore), _knobs())
+    table = {row[0]: dict(zip(('cost_in_passes', 'remaps_real', 'remaps_virtual', 'relabelling_passes'), row[1:]))
+             for row in rows}
     return {'chosen': v, 'candidates': table, 'model': dict(MODEL)}
 
 
@@ -1447,19 +1118,6 @@ def slice_bits_wanted(state: DistributedQubitState) -> int:
         overlaps = state.amps.is_cuda and (CONFIG['elide_exchange'] or (dist.is_initialized() and dist.get_backend() == 'nccl'))
         nb = 3 if overlaps else 0           # (three bits against two, rehearsal of n = 34 / 8 ranks: −4 .. −7 ms per step)
     return int(nb) if (state.batch is None and _vbits(state) == 0) else 0
-
-
-def _slice_qubits(ph: list[int], prims: Sequence[Prim], i: int, n: int, L: int, pairs, nbits: int) -> list[int]:
-    """The qubits the passes around the exchange ``pairs`` are sliced by: local, staying local, movable by a permuted store,
-    and -- after the evicted ones -- needed LAST (farthest next non-diagonal use from gate ``i`` on): neither the gates
-    left for the last pass in front of the exchange nor the first ones behind it have any business with them.  A pure
-    function of the gate list and the placement: every rank picks the same."""
-    if nbits <= 0:
-        return []
-    nxt = _next_use(prims, i, n)
-    leaving_local = {eq for _, eq in pairs}
-    cand = sorted((q for q in range(n) if _UNFOLDABLE_BELOW <= ph[q] < L and q not in leaving_local), key=lambda q: (-nxt[q], -q))
-    return cand[:nbits]
 
 
 class _Pending(list):
@@ -1537,19 +1195,21 @@ def _defer_tail(state: DistributedQubitState, pending: list[Prim], pairs) -> lis
     return carry
 
 
-def _remap_for(state: DistributedQubitState, prims: Sequence[Prim], i: int, pending: list[Prim]) -> list[Prim]:
-    """The remap that makes gate ``i`` local, behind the local gates ``pending``.  Returns the logical primitives of a
-    deferred tail (`_defer_tail`): the caller localizes them under the new layout before anything else."""
-    L = state.log_num_amps_per_node - _vbits(state)
-    pairs = _plan_remap(_phys(state), prims, i, state.nqubit, L, _vbits(state))
+def _remap_for(state: DistributedQubitState, st: tuple, i: int, pending: list[Prim], knobs: schedule.Knobs) -> list[Prim]:
+    """The remap that makes gate ``i`` of the (ordered) structure ``st`` local, behind the local gates ``pending``.  Returns
+    the logical primitives of a deferred tail (`_defer_tail`): the caller localizes them under the new layout before
+    anything else."""
+    vb = _vbits(state)
+    L = state.log_num_amps_per_node - vb
+    pairs = schedule.plan_remap(_phys(state), st, i, state.nqubit, L, vb, knobs)
     carry = _defer_tail(state, pending, pairs)
     nb = slice_bits_wanted(state)
-    _remap(state, pairs, pending, _slice_qubits(_phys(state), prims, i, state.nqubit, L, pairs, nb) if nb else ())
+    _remap(state, pairs, pending, schedule.slice_qubits(_phys(state), st, i, state.nqubit, L, pairs, nb, knobs.horizon))
     return carry
 
 
 def count_exchange_steps(prims: Sequence[Prim], n: int, g: int, virtual_bits: int = 0, reorder: bool = False,
-                         placement: bool = False) -> dict:
+                         placement: bool = False, evict: bool | None = None) -> dict:
     """Dry run of both modes on a gate list (no data): number of exchange steps and the volume each rank
     sends, in units of one shard.  Used by tests and to size the design.
 
@@ -1560,7 +1220,8 @@ def count_exchange_steps(prims: Sequence[Prim], n: int, g: int, virtual_bits: in
     but the first row's share, 1 - 2^-v of it -- and ``exposed_wire_volume``.  v = 0: everything is exposed (an
     un-batched shard has nothing to overlap with).
     ``reorder``: the gate list in commutation-DAG order first, as `dist_run` runs it.  ``placement``: the free first
-    placement of a circuit that starts from |0..0> (`initial_placement`)."""
+    placement of a circuit that starts from |0..0> (`initial_placement`).  ``evict``: the eviction rule (None: the one
+    the last `dist_apply_prims` call used)."""
     L = n - g
     pw_steps, pw_vol = 0, 0.0
     for p in prims:
@@ -1574,41 +1235,19 @@ def count_exchange_steps(prims: Sequence[Prim], n: int, g: int, virtual_bits: in
                 pw_steps += 2 * nglob
                 pw_vol += 2 * nglob * 0.5
     v = int(virtual_bits)
-    lr = L - v                                   # bits of a row
-    ph = initial_placement(prims, n, L, v) if placement else list(range(n))
-    if reorder:
-        prims = _order_for_remaps(prims, ph, n, lr, v)
-    rm_steps, rm_vol, i = 0, 0.0, 0
-    v_steps, hidden, exposed = 0, 0.0, 0.0
-    while i < len(prims):
-        p = prims[i]
-        if p.kind != 'diag' and any(ph[t] >= lr for t in p.targets):
-            pairs = _plan_remap(ph, prims, i, n, lr, v)
-            pairs = sorted(pairs, key=lambda pr: ph[pr[0]])
-            k = len(pairs)
-            rb = [ph[lq] for lq, _ in pairs]
-            ent = [ph[eq] for _, eq in pairs]
-            rest = [b for b in range(lr) if b not in ent]
-            new_local = {sp: d for d, sp in enumerate(rest + ent)}
-            for q in range(n):
-                if ph[q] < lr:
-                    ph[q] = new_local[ph[q]]
-            for j, (lq, eq) in enumerate(pairs):
-                ph[eq], ph[lq] = rb[j], lr - k + j
-            k_real = sum(1 for r in rb if r >= L)          # real rank bits among the leaving positions
-            assert k_real in (0, k), 'a remap trades real OR virtual rank bits'
-            rm_steps += 1
-            if k_real == 0:                                  # a local re-labelling (rides on a pass): nothing on the wire
-                v_steps += 1
-                continue
-            wire = 1 - 0.5**k_real                           # of every row, i.e. of the shard
-            rm_vol += wire
+    knobs = _knobs(evict)
+    st = schedule.structure(prims)
+    ph = schedule.initial_placement(st, n, L, v, False, knobs) if placement else tuple(range(n))
+    _, rm_vol, trace = schedule.dry_remaps(st, ph, n, L - v, v, knobs, reorder=reorder)
+    hidden, exposed = 0.0, 0.0
+    for k, real, _ in trace:
+        if real:
+            wire = 1 - 0.5**k                            # of every row, i.e. of the shard
             hidden += wire * (1 - 0.5**v)
             exposed += wire * 0.5**v
-            continue
-        i += 1
-    return {'pairwise_steps': pw_steps, 'pairwise_volume': pw_vol, 'remap_steps': rm_steps, 'remap_volume': rm_vol,
-            'virtual_bits': v, 'virtual_steps': v_steps, 'hidden_wire_volume': hidden, 'exposed_wire_volume': exposed}
+    return {'pairwise_steps': pw_steps, 'pairwise_volume': pw_vol, 'remap_steps': len(trace), 'remap_volume': rm_vol,
+            'virtual_bits': v, 'virtual_steps': sum(1 for t in trace if not t[1]), 'hidden_wire_volume': hidden,
+            'exposed_wire_volume': exposed}
 
 
 def canonicalize(state: DistributedQubitState) -> DistributedQubitState:
@@ -1623,19 +1262,9 @@ def _canonicalize(state: DistributedQubitState) -> DistributedQubitState:
     n, L = state.nqubit, state.log_num_amps_per_node
     ph = _phys(state)
     for _ in range(4):
-        glob = [q for q in range(n) if ph[q] >= L]
-        misplaced = [q for q in glob if ph[q] != q]
-        if not misplaced:
+        pairs = schedule.canonical_round(ph, n, L)
+        if not pairs:
             break
-        pairs, used = [], set()
-        for lq in misplaced:
-            owner = ph[lq]                              # logical qubit that belongs on this rank bit
-            if ph[owner] < L and owner not in used:
-                pick = owner
-            else:                                       # owner itself is on the move: park a filler there
-                pick = next(q for q in range(L) if ph[q] < L and q not in used)
-            used.add(pick)
-            pairs.append((lq, pick))
         _exchange_qubits(state, pairs)
     assert all(ph[q] == q for q in range(L, n)), 'rank bits not canonical after 4 exchange rounds'
     src_of_dst = [0] * L
@@ -1680,8 +1309,11 @@ def _dist_apply_prims(state: DistributedQubitState, prims: Sequence[Prim], mode:
         mode = 'pairwise'
     if mode == 'pairwise' and not _is_canonical(state):
         canonicalize(state)
+    # the planner's input and settings, once per call (None = whichever rule the dry-run model prefers: below)
+    structure = schedule.structure(prims) if mode == 'remap' else None
+    knobs = _knobs(True if CONFIG['evict_foldable'] is None else CONFIG['evict_foldable'])
+    fresh = bool(state.__dict__.get('_fresh_zero'))
     # virtual rank bits: an un-batched shard of a forward circuit, rows of at least one tile
-    _EVICT[0] = True if CONFIG['evict_foldable'] is None else bool(CONFIG['evict_foldable'])
     vb = CONFIG['virtual_bits']
     tile = executor._geometry(state.amps.dtype == torch.complex128).m
     eligible = mode == 'remap' and state.batch is None and _SWEEP['grads'] is None and state.amps.ndim == 1
@@ -1692,14 +1324,15 @@ def _dist_apply_prims(state: DistributedQubitState, prims: Sequence[Prim], mode:
         vb = 0
         if overlaps and eligible:
             cands = [v for v in (0, 1, 2) if state.log_num_amps_per_node - v >= tile]
-            vb = choose_virtual_bits(prims, state.nqubit, state.log_num_amps_per_node, cands,
-                                     fresh=bool(state.__dict__.get('_fresh_zero')), restore=not keep_layout)
+            vb = schedule.choose_virtual_bits(structure, state.nqubit, state.log_num_amps_per_node, tuple(cands), fresh,
+                                              not keep_layout, knobs)[0]
     vb = int(vb or 0)
     if vb and not (eligible and state.log_num_amps_per_node - vb >= tile):
         vb = 0
     if CONFIG['evict_foldable'] is None and mode == 'remap' and state.world_size > 1 and state.log_num_amps_per_node - vb >= 12:
-        _EVICT[0] = choose_eviction(prims, state.nqubit, state.log_num_amps_per_node, vb,
-                                    fresh=bool(state.__dict__.get('_fresh_zero')), restore=not keep_layout)
+        knobs = knobs._replace(evict_foldable=schedule.choose_eviction(structure, state.nqubit, state.log_num_amps_per_node,
+                                                                       vb, fresh, not keep_layout, knobs))
+    LAST_RUN['evict_foldable'] = knobs.evict_foldable
     LAST_RUN['virtual_bits'] = vb
     if mode != 'remap':
         state.__dict__.pop('_fresh_zero', None)       # (gate-by-gate exchanges: not for them)
@@ -1715,7 +1348,7 @@ def _dist_apply_prims(state: DistributedQubitState, prims: Sequence[Prim], mode:
         # virtual rank bits, gate-by-gate exchanges
         _materialize_zeros(state)
     try:
-        return _dist_apply_loop(state, prims, mode, keep_layout, expect_z)
+        return _dist_apply_loop(state, prims, mode, keep_layout, expect_z, structure, knobs)
     finally:
         state.__dict__.pop('_as_rank0', None)
         if vb:
@@ -1724,16 +1357,16 @@ def _dist_apply_prims(state: DistributedQubitState, prims: Sequence[Prim], mode:
 
 
 def _dist_apply_loop(state: DistributedQubitState, prims: Sequence[Prim], mode: str, keep_layout: bool,
-                     expect_z: Sequence[int] | None) -> DistributedQubitState:
+                     expect_z: Sequence[int] | None, st: tuple | None, knobs: schedule.Knobs) -> DistributedQubitState:
+    """``st``: the structure of ``prims`` ('remap' mode), ``knobs``: the planner's settings (`_knobs`)."""
     vb = _vbits(state)
-    structure = _structure(prims) if mode == 'remap' else None
-    if (mode == 'remap' and CONFIG['initial_placement'] and state.__dict__.get('_fresh_zero') and _is_canonical(state)
-            and state.world_size > 1):
-        # behind reset(): the first placement is free (see `initial_placement`)
-        state.__dict__['_phys'] = initial_placement(prims, state.nqubit, state.log_num_amps_per_node, vb,
-                                                    restore=not keep_layout, structure=structure)
-    if mode == 'remap' and CONFIG['reorder']:
-        prims = _order_for_remaps(prims, _phys(state), state.nqubit, state.log_num_amps_per_node - vb, vb, structure)
+    n, L = state.nqubit, state.log_num_amps_per_node
+    if mode == 'remap' and knobs.initial_placement and state.__dict__.get('_fresh_zero') and _is_canonical(state) and state.world_size > 1:
+        # behind reset(): the first placement is free (see `schedule.initial_placement`)
+        state.__dict__['_phys'] = list(schedule.initial_placement(st, n, L, vb, not keep_layout, knobs))
+    if mode == 'remap' and knobs.reorder:
+        order = schedule.order_indices(st, tuple(_phys(state)), n, L - vb, vb, knobs)
+        prims, st = [prims[j] for j in order], tuple(st[j] for j in order)
     pending = _Pending()
     i, nprims = 0, len(prims)
     while i < nprims:
@@ -1742,7 +1375,7 @@ def _dist_apply_loop(state: DistributedQubitState, prims: Sequence[Prim], mode: 
             # virtual rank bits: what a gate is on THIS rank depends on how its stretch ends -- row by row in front of
             # an exchange of real rank bits, on the whole shard otherwise -- so it is localized when the stretch runs
             if p.kind != 'diag' and any(t >= state.log_num_amps_per_node - vb for t in p.targets):
-                _remap_for(state, prims, i, pending)
+                _remap_for(state, st, i, pending, knobs)
             else:
                 pending.add(p, prims[i])
                 i += 1
@@ -1761,7 +1394,7 @@ def _dist_apply_loop(state: DistributedQubitState, prims: Sequence[Prim], mode: 
             _exchange_prim(state, p)
             i += 1
         else:
-            carry = _remap_for(state, prims, i, pending)     # local gates so far + exchange; then gate i under the new layout
+            carry = _remap_for(state, st, i, pending, knobs)     # local gates so far + exchange; then gate i under the new layout
             for q in carry:                                  # (a deferred tail: first in line behind the exchange)
                 loc = _localize(state, _translate(q, _phys(state)))
                 assert loc != 'exchange', 'a deferred gate targets a qubit that left for the rank bits'

@@ -1,11 +1,11 @@
 """Dry run (no data, no GPU) of one rank's schedule of a sharded circuit: the commutation-DAG order, the remaps, and the
 fused passes of every local stretch with their gate counts -- what `bench.py --rehearse-rank` runs, for sizing the
-exchange schedule offline.  usage: python tools/dist_schedule_dry.py [n] [g = log2 ranks] [rank] [--place] [--defer]"""
+exchange schedule offline.  usage: python tools/dist_schedule_dry.py [n] [g = log2 ranks] [rank] [--place]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench
-from deepquantum_amd import distributed as D, executor, fusion
+from deepquantum_amd import distributed as D, executor, fusion, schedule
 
 
 def gate_prims(n, depth=40, seed=1234):
@@ -29,34 +29,24 @@ def merged(prims):
 
 
 def stretches(n, g, rank, prims, place=False):
-    """[(localized prims of the stretch, pairs of the remap behind it or None)] for rank ``rank``."""
+    """[(localized prims of the stretch, out_perm of the remap behind it or None)] for rank ``rank``."""
     L = n - g
-    ph = list(range(n))
-    if place:
-        ph = D.initial_placement(prims, n, L, 0)
-    order = D._order_for_remaps(prims, ph, n, L, 0)
+    knobs = D._knobs(True)
+    st = schedule.structure(prims)
+    ph = list(schedule.initial_placement(st, n, L, 0, False, knobs)) if place else list(range(n))
+    order = schedule.order_indices(st, tuple(ph), n, L, 0, knobs)
+    prims, st = [prims[j] for j in order], tuple(st[j] for j in order)
     out, pending, i = [], [], 0
-    while i < len(order):
-        p = D._translate(order[i], ph)
-        loc = D._localize_at(L, rank, p)
-        if loc is None:
-            i += 1
+    while i < len(prims):
+        loc = D._localize_at(L, rank, D._translate(prims[i], ph))
+        if loc == 'exchange':
+            _, _, out_perm = schedule.relabel(ph, schedule.plan_remap(ph, st, i, n, L, 0, knobs), L)
+            out.append((pending, out_perm))
+            pending = []
             continue
-        if loc != 'exchange':
+        if loc is not None:
             pending.append(loc)
-            i += 1
-            continue
-        pairs = D._plan_remap(ph, order, i, n, L, 0)
-        pairs = sorted(pairs, key=lambda pr: ph[pr[0]])
-        rbits = [ph[lq] - L for lq, _ in pairs]
-        ent = [ph[eq] for _, eq in pairs]
-        src_of_dst = [b for b in range(L) if b not in ent] + ent
-        out_perm = [0] * L
-        for d, sp in enumerate(src_of_dst):
-            out_perm[sp] = d
-        out.append((pending, out_perm))
-        D._remap_bookkeeping(ph, pairs, rbits, out_perm, L)
-        pending = []
+        i += 1
     out.append((pending, None))
     return out
 
