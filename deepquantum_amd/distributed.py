@@ -35,8 +35,8 @@ Two execution modes (``CONFIG['mode']``):
 from __future__ import annotations
 
 from collections import Counter
-from dataclasses import replace
-from typing import Sequence
+from dataclasses import dataclass, field, replace
+from typing import NamedTuple, Sequence
 
 import torch
 import torch.distributed as dist
@@ -91,8 +91,10 @@ CONFIG = {'mode': 'remap', 'remap_min_prims': 8, 'horizon': 1 << 14, 'overlap_gr
           # stretch starts on slice j as soon as it has arrived.  The B qubits are the local ones needed last after the
           # evicted ones -- outside the tiles of both passes on (nearly) every rank; where one is not, that rank launches
           # fewer, bigger slices and the protocol stays the same.  Costs a third shard-sized buffer (the first pass behind
-          # the exchange must not write where slices are still being sent from).  None = 3 where an exchange can overlap
-          # with compute at all (RCCL on device shards, or the rehearsal of such a job), 0 elsewhere; an int forces it
+          # the exchange must not write where slices are still being sent from), a fourth while two sliced remaps follow
+          # each other (the first one's source is the spare again only behind the stretch in front of the second).  None = 3
+          # where an exchange can overlap with compute at all (RCCL on device shards, or the rehearsal of such a job), 0
+          # elsewhere; an int forces it
           'slice_exchange': None,
           # an under-filled LAST pass of a stretch (at most this many kernel gates) is not run at all: its gates move behind
           # the exchange, where the next stretch's first passes take them in (legal when none of them targets a qubit that
@@ -115,6 +117,43 @@ LAST_RUN = {'remaps': 0, 'pairwise_exchanges': 0, 'local_flushes': 0, 'folded_pe
 
 # ---------------------------------------------------------------------------------------------------
 # helpers on one shard
+@dataclass(slots=True)
+class ShardRecord:
+    """What this module keeps about one `DistributedQubitState` (``state.record``): the placement (phys[logical bit] =
+    physical bit, None = canonical; virtual rank bits; `_raw` nesting), the zero knowledge of the run under way
+    (`_take_zeros`, `_materialize_zeros`), the work in flight and <Z..Z> of the last circuit's final pass."""
+
+    phys: list | None = None
+    vbits: int = 0
+    raw: int = 0
+    fresh_zero: bool = False            # the run started behind reset(): rank 0 holds |0..0>, everybody else zeros
+    behind_reset: bool = False          # ... until its first exchange of real rank bits
+    as_rank0: bool = False              # the first stretch is localized as rank 0 sees it (CONFIG['first_exchange_local'])
+    zero_shard: bool = False            # this rank's shard is all zeros (virtual remaps behind reset())
+    known_zero_local: int = 0           # local bits known to be |0> (behind the first exchange)
+    lazy_zero: bool = False             # logical zeros of a lazy reset()
+    zeros_owed: tuple | None = None     # ('top', k): logical zeros of the first exchange without the wire
+    inflight: list = field(default_factory=list)      # (group stream, exchanges) in flight
+    inflight_keep: list | None = None   # the matrices those streams read
+    arrivals: dict | None = None        # a sliced exchange in flight (`_remap_sliced`)
+    spare: torch.Tensor | None = None   # the buffer the sliced route rotates through
+    expz: dict | None = None
+
+    def end_run(self) -> None:
+        """The end of `dist_apply_prims`: what is known about zeros holds for that run only."""
+        self.fresh_zero = self.behind_reset = self.zero_shard = False
+        self.known_zero_local = 0
+
+    def reset(self) -> None:
+        """`DistributedQubitState.reset`: canonical order, no cached values, real zeros."""
+        self.phys = self.expz = self.zeros_owed = None
+        self.lazy_zero = False
+
+    def copy(self) -> 'ShardRecord':
+        """What a deep copy of the state inherits: the placement (the copy has been settled and materialised first)."""
+        return ShardRecord(phys=None if self.phys is None else list(self.phys), vbits=self.vbits)
+
+
 class _raw:
     """While one of these is open on a state its ``amps`` is the raw shard in whatever qubit order the last remap left
     (DistributedQubitState.__getattr__ restores the canonical order for everybody else).  Re-entrant."""
@@ -124,26 +163,21 @@ class _raw:
 
     def __enter__(self):
         for st in self.states:
-            st.__dict__['_raw'] = st.__dict__.get('_raw', 0) + 1
+            st.record.raw += 1
 
     def __exit__(self, *exc):
         for st in self.states:
-            st.__dict__['_raw'] -= 1
+            st.record.raw -= 1
         return False
-
-
-def _vbits(state: DistributedQubitState) -> int:
-    """Virtual rank bits the state currently runs with (CONFIG['virtual_bits']; only inside `_dist_apply_prims`)."""
-    return state.__dict__.get('_vbits', 0)
 
 
 def _view(state: DistributedQubitState) -> torch.Tensor:
     """(batch, 2^L) view of the shard(s) -- with virtual rank bits: (2^v rows, 2^(L - v)) of the one shard."""
-    return state.amps.view(-1, state.num_amps_per_node >> _vbits(state))
+    return state.amps.view(-1, state.num_amps_per_node >> state.record.vbits)
 
 
 def _bview(state: DistributedQubitState) -> torch.Tensor:
-    return state.buffer.view(-1, state.num_amps_per_node >> _vbits(state))
+    return state.buffer.view(-1, state.num_amps_per_node >> state.record.vbits)
 
 
 def _live(state: DistributedQubitState) -> bool:
@@ -162,9 +196,9 @@ def _materialize_zeros(state: DistributedQubitState) -> None:
     everything behind the first LAZY_HEAD amplitudes of every row; ``_zeros_owed = ('top', k)`` behind the first
     exchange without the wire: chunk slots 1 .. 2^k - 1).  Called by whoever is about to read the shard without the
     known-zero masks that make the garbage unreachable."""
-    d = state.__dict__
-    fresh = d.pop('_lazy_zero', False)
-    owed = d.pop('_zeros_owed', None)
+    rec = state.record
+    fresh, owed = rec.lazy_zero, rec.zeros_owed
+    rec.lazy_zero, rec.zeros_owed = False, None
     if not fresh and owed is None:
         return
     rows = state._buffers['amps'].view(-1, state.num_amps_per_node)
@@ -187,10 +221,10 @@ def _localize(state: DistributedQubitState, p: Prim) -> Prim | None | str:
     target is a global qubit: data has to move).  With virtual rank bits every row of the shard is a rank of the
     virtual world: a primitive whose predicates or phases depend on a virtual bit comes back with one matrix per row
     (the identity on the rows it does not act on)."""
-    vb = _vbits(state)
+    vb = state.record.vbits
     if vb == 0:
         # (the first stretch behind reset() with CONFIG['first_exchange_local']: every rank computes what RANK 0 holds)
-        return _localize_at(state.log_num_amps_per_node, 0 if state.__dict__.get('_as_rank0') else state.rank, p)
+        return _localize_at(state.log_num_amps_per_node, 0 if state.record.as_rank0 else state.rank, p)
     L = state.log_num_amps_per_node
     lr = L - vb
     if p.kind != 'diag' and any(t >= lr for t in p.targets):
@@ -338,9 +372,12 @@ def remap_timings() -> list[dict]:
 def _settle(state: DistributedQubitState) -> None:
     """Join the group streams: everything in flight for this state (exchanges included) is ordered before whatever the
     current stream does next."""
-    _arrivals_done(state, state.__dict__.pop('_arrivals', None))
-    keep = state.__dict__.pop('_inflight_keep', None)
-    for stream, works in state.__dict__.pop('_inflight', []):
+    rec = state.record
+    arr, rec.arrivals = rec.arrivals, None
+    _arrivals_done(state, arr)
+    keep, inflight = rec.inflight_keep, rec.inflight
+    rec.inflight_keep, rec.inflight = None, []
+    for stream, works in inflight:
         if stream is not None:
             with torch.cuda.stream(stream):
                 for w in works:
@@ -364,33 +401,25 @@ class _EventWait:
         torch.cuda.current_stream().wait_event(self.event)
 
 
-def _arrivals_done(state: DistributedQubitState, arr: dict | None) -> None:
+def _arrivals_done(state: DistributedQubitState, arr: dict | None, consumed: bool = False, slice_: int | None = None) -> None:
     """Join a sliced exchange (`_remap_sliced`): every slice is ordered before what the current stream does next, and the
-    buffer the slices were sent from becomes the state's spare third buffer again."""
+    buffer the slices were sent from becomes the state's spare buffer again.  ``consumed``: the stretch behind the exchange
+    has run (`_run_stretch`) and its first pass has already waited for every slice (`executor.run(slicing=...)` calls
+    every ``before(j)``).  (The spare comes back only here: see `_remap_sliced` for the buffer count.)  ``slice_``: wait
+    for that slice only (the first pass's ``before(j)``)."""
     if arr is None:
         return
+    if consumed:
+        assert all(w is None for w in arr['works']), 'a slice of the exchange was never waited for'
     for j, w in enumerate(arr['works']):
-        if w is not None:
+        if w is not None and slice_ in (None, j):
             w.wait()
             arr['works'][j] = None
+    if slice_ is not None:
+        return
     if TIMING['enabled'] and arr.get('timing') is not None and 'done' not in arr['timing']:
         arr['timing']['done'] = _mark(None)
-    state.__dict__['_spare'] = arr.pop('src', None)
-
-
-def _first_slicing(state: DistributedQubitState, arr: dict | None) -> dict | None:
-    """``executor.run(slicing=...)`` for the first pass behind a sliced exchange: slice j is waited for right before the
-    first launch that reads it."""
-    if arr is None:
-        return None
-
-    def before(j: int) -> None:
-        w = arr['works'][j]
-        if w is not None:
-            w.wait()
-            arr['works'][j] = None
-
-    return {'first': (arr['bits'], before)}
+    state.record.spare = arr.pop('src', None)
 
 
 def _rows_of(pending: Sequence[Prim], rows: slice, total: int) -> list[Prim]:
@@ -407,40 +436,28 @@ def _rows_of(pending: Sequence[Prim], rows: slice, total: int) -> list[Prim]:
 
 
 def _run_rows(a: torch.Tensor, b: torch.Tensor, pending: Sequence[Prim], rows: slice,
-              out_perm: Sequence[int] | None = None, expect_z: dict | None = None, zero: bool = False,
+              out_perm: Sequence[int] | None = None, expect_z: dict | None = None, zero: bool | int = False,
               need_zeros=None, slicing: dict | None = None) -> bool:
     """Fused local passes on rows ``rows`` of the shard ``a`` with the receive buffer ``b`` as the second buffer of the
     permuted stores; afterwards local bit q sits at position out_perm[q].  Returns True if the result lives in ``b``.
-    ``zero``: the rows are |0..0> (rank 0's shard right after ``reset()``): the first passes skip what is still known to be
-    zero (executor.CONFIG['zero_state'])."""
+    ``zero``, ``need_zeros``: executor.run's ``zero_state`` (|0..0>, or a mask of known-zero bits) and ``need_zeros``."""
     total = a.shape[0]
     x, y = a[rows], b[rows]
-    if need_zeros is not None and (_SWEEP['grads'] is not None or not (CONFIG['fold_permute'] or out_perm is None)):
-        need_zeros()                              # (routes below that take no masks)
-        need_zeros = None
-    if slicing is not None and (_SWEEP['grads'] is not None or not (CONFIG['fold_permute'] or out_perm is None)):
-        executor._slicing_all(slicing, 'first')   # (routes below that take no slices: everything has to be there first)
-        slicing = {k_: v_ for k_, v_ in slicing.items() if k_ != 'first'}
-        post = slicing
-        slicing = None
-    else:
-        post = None
+    folds = CONFIG['fold_permute'] or out_perm is None
+    # (a sliced exchange -- `_remap_sliced` -- needs CONFIG['fold_permute'] and no reverse sweep: slices reach no other route)
+    assert slicing is None or (_SWEEP['grads'] is None and folds), 'a sliced exchange on a route that takes no slices'
     if _SWEEP['grads'] is not None:               # a stretch of a fused reverse sweep: reductions inside the passes
         out = executor.run(x, _rows_of(pending, rows, total), inplace=True, scratch=y, out_perm=out_perm, amps=a.numel(),
-                           grads=_SWEEP['grads'][rows])
-    elif CONFIG['fold_permute'] or out_perm is None:
-        # (``need_zeros``: the shard holds garbage where it is logically zero; the executor calls it before anything reads
-        # there -- i.e. unless the known-zero masks of ``zero`` apply to this schedule from its first pass to its last)
+                           grads=_SWEEP['grads'][rows], need_zeros=need_zeros)
+    elif folds:
         out = executor.run(x, _rows_of(pending, rows, total), inplace=True, scratch=y, out_perm=out_perm, amps=a.numel(),
                            expect_z=expect_z, zero_state=zero, need_zeros=need_zeros, slicing=slicing)
     else:                                         # A/B: the re-labelling as a pass of its own
-        out = executor.run(x, _rows_of(pending, rows, total), inplace=True, scratch=y)
+        out = executor.run(x, _rows_of(pending, rows, total), inplace=True, scratch=y, need_zeros=need_zeros)
         if out.data_ptr() not in (x.data_ptr(), y.data_ptr()):
             x.copy_(out)
             out = x
         out = executor.run(out, [], inplace=True, scratch=y if out.data_ptr() == x.data_ptr() else x, out_perm=out_perm)
-    if post is not None:
-        executor._slicing_all(post, 'last', out)
     if out.data_ptr() == y.data_ptr():
         return True
     if out.data_ptr() != x.data_ptr():        # (states smaller than a tile come back in a fresh tensor)
@@ -448,38 +465,112 @@ def _run_rows(a: torch.Tensor, b: torch.Tensor, pending: Sequence[Prim], rows: s
     return False
 
 
+# ---------------------------------------------------------------------------------------------------
+# local stretches: every route that runs the gates between two exchanges takes the zero facts once (`_take_zeros`), lets
+# ONE rule decide whether logical zeros may stay (`_zeros_may_stay`) and starts / ends the same way
+class _Zeros(NamedTuple):
+    """What is known about zeros at the start of a stretch (`_take_zeros`; the fields of `ShardRecord`): ``zeros``: this
+    rank's shard is all zeros; ``first_exchange``: the stretch ends in the first exchange behind reset(); ``lazy``: the
+    logical zeros left -- 'reset' (behind LAZY_HEAD), 'owed' (chunk slots) or None."""
+
+    fresh: bool
+    kz: int
+    zeros: bool
+    as_rank0: bool
+    first_exchange: bool
+    lazy: str | None
+
+    @property
+    def zero(self) -> bool | int:
+        """``executor.run(zero_state=...)`` for a shard that is not all zeros: |0..0> (rank 0 behind reset()) or the mask."""
+        return True if self.fresh and not self.zeros else self.kz
+
+
+def _take_zeros(state: DistributedQubitState) -> _Zeros:
+    """The zero facts of the stretch about to run, taken off the state (the logical zeros stay until the stretch is done)."""
+    rec = state.record
+    z = _Zeros(rec.fresh_zero, rec.known_zero_local, state.rank != 0 and (rec.fresh_zero or rec.zero_shard), rec.as_rank0,
+               rec.behind_reset, 'reset' if rec.lazy_zero else 'owed' if rec.zeros_owed is not None else None)
+    rec.fresh_zero = rec.zero_shard = rec.as_rank0 = rec.behind_reset = False
+    rec.known_zero_local = 0
+    return z
+
+
+def _zeros_may_stay(z: _Zeros, ngroups: int, runs: bool, rank0_input: bool = False) -> bool:
+    """Whether logical zeros may stay into a stretch of ``ngroups`` groups of rows (``runs``: gates or a re-labelling):
+    only ONE group's masked passes (the executor clears them where the masks fail, ``need_zeros``), with masks that cover
+    them -- rank 0's |0..0> for a lazy reset, that or the known-zero bits for owed slots.  ``rank0_input``: every rank runs
+    rank 0's |0..0> (`_first_exchange_local` writes its 1), so its masks hold on ranks that otherwise hold zeros."""
+    if z.lazy is None or ngroups != 1 or not runs:
+        return False
+    if rank0_input:
+        return True
+    return not z.zeros and (z.fresh if z.lazy == 'reset' else bool(z.fresh or z.kz))
+
+
+def _stretch_start(state: DistributedQubitState, z: _Zeros, pending: Sequence[Prim], runs: bool, ngroups: int = 1,
+                   skip_zeros: bool = False, rank0_input: bool = False):
+    """Count the stretch, and make the logical zeros real unless they may stay (`_zeros_may_stay`).  Returns the
+    executor's ``need_zeros`` (None: nothing logical left).  ``skip_zeros``: the route runs no pass on a shard of zeros
+    (zeros stay zeros under any gates, in any layout); `_flush` runs them like anybody."""
+    LAST_RUN['local_flushes'] += bool(pending)
+    if skip_zeros and z.zeros:
+        LAST_RUN['zero_shard_stretches'] += 1
+    elif pending:
+        LAST_RUN['known_zero_stretches'] += bool(z.kz)
+    if _zeros_may_stay(z, ngroups, runs, rank0_input):
+        return lambda: _materialize_zeros(state)
+    _materialize_zeros(state)
+    return None
+
+
+def _stretch_end(state: DistributedQubitState, pending: list[Prim], out_perm: Sequence[int] | None) -> bool:
+    """The stretch has run: masked passes that ran through have written everything, so no logical zeros are left.  Returns
+    whether there were any (they went through the masked passes unmaterialised)."""
+    rec = state.record
+    kept = rec.lazy_zero or rec.zeros_owed is not None
+    rec.lazy_zero, rec.zeros_owed = False, None
+    pending.clear()
+    if out_perm is not None:
+        LAST_RUN['folded_permutes' if executor.LAST_RUN.get('permute_folded') else 'permute_passes'] += 1
+    return kept
+
+
+def _run_stretch(state: DistributedQubitState, pending: list[Prim], z: _Zeros, out_perm: Sequence[int] | None = None,
+                 arr: dict | None = None, slicing: dict | None = None, expect_z: dict | None = None,
+                 gates: Sequence[Prim] | None = None, skip_zeros: bool = False, rank0_input: bool = False) -> bool:
+    """The stretch ``pending`` on the whole shard as one group of rows, the re-labelling ``out_perm`` (None: none) written by
+    its last pass; the result ends in ``state.amps``.  ``arr``: a sliced exchange in flight, taken slice by slice by the
+    first pass; ``slicing``: the last pass's slices (`_remap_sliced`); ``gates``: what runs, if not ``pending`` as it is
+    (`_remap_virtual` localizes it row by row).  Returns what `_stretch_end` does."""
+    runs = bool(pending) or out_perm is not None
+    need_zeros = _stretch_start(state, z, pending, runs, 1, skip_zeros, rank0_input)
+    if arr is not None:        # the first pass waits for slice j right before the first launch that reads it
+        slicing = {} if slicing is None else slicing        # (the executor reports into the caller's dict: ``done``)
+        slicing['first'] = (arr['bits'], lambda j: _arrivals_done(state, arr, slice_=j))
+    if (runs or slicing is not None) and not (skip_zeros and z.zeros):
+        a, b = _view(state), _bview(state)
+        if _run_rows(a, b, pending if gates is None else gates, slice(0, a.shape[0]), out_perm, expect_z,
+                     True if rank0_input else z.zero, need_zeros, slicing):
+            state.amps, state.buffer = state.buffer, state.amps
+    if arr is not None:
+        first = slicing.get('done', {}).get('first', 0)
+        LAST_RUN['slice_launches_first'] += first
+        if TIMING['enabled'] and arr.get('timing') is not None:
+            arr['timing']['slices_first'] = first
+        _arrivals_done(state, arr, consumed=True)
+    return _stretch_end(state, pending, out_perm)
+
+
 def _flush(state: DistributedQubitState, pending: list[Prim], expect_z: dict | None = None) -> None:
-    arr = state.__dict__.pop('_arrivals', None)      # (a sliced exchange in flight: the first pass below takes it slice by slice)
-    if arr is not None and not pending:
+    rec = state.record
+    arr, rec.arrivals = rec.arrivals, None       # (a sliced exchange in flight: the first pass below takes it slice by slice)
+    if not pending:
         _arrivals_done(state, arr)
         arr = None
     _settle(state)
-    fresh = state.__dict__.pop('_fresh_zero', False)
-    state.__dict__.pop('_zero_shard', None)      # (a shard of zeros runs its passes here like anybody: zeros in, zeros out)
-    state.__dict__.pop('_as_rank0', None)        # (no exchange came: ranks != 0 ran rank 0's gates on zeros -- zeros out)
-    kz = state.__dict__.pop('_known_zero_local', 0)
-    zero = (fresh and state.rank == 0) or kz
-    lazy = bool(state.__dict__.get('_lazy_zero') or state.__dict__.get('_zeros_owed'))
-    if lazy and not (pending and zero):
-        _materialize_zeros(state)                # (nothing runs, or it runs unmasked: the logical zeros become real ones)
-        lazy = False
-    if not pending:
-        return
-    LAST_RUN['local_flushes'] += 1
-    LAST_RUN['known_zero_stretches'] += bool(kz)
-    a, b = _view(state), _bview(state)
-    slicing = _first_slicing(state, arr)
-    if _run_rows(a, b, pending, slice(0, a.shape[0]), expect_z=expect_z, zero=zero,
-                 need_zeros=(lambda: _materialize_zeros(state)) if lazy else None, slicing=slicing):
-        state.amps, state.buffer = state.buffer, state.amps
-    if arr is not None:
-        LAST_RUN['slice_launches_first'] += slicing.get('done', {}).get('first', 0)
-        if TIMING['enabled'] and arr.get('timing') is not None:
-            arr['timing']['slices_first'] = slicing.get('done', {}).get('first', 0)
-        _arrivals_done(state, arr)
-    state.__dict__.pop('_lazy_zero', None)       # (masked passes that ran through have written everything)
-    state.__dict__.pop('_zeros_owed', None)
-    pending.clear()
+    # (a shard of zeros runs its passes here like anybody -- also a rank != 0 that ran rank 0's gates and no exchange came)
+    _run_stretch(state, pending, _take_zeros(state), arr=arr, expect_z=expect_z)
 
 
 def _expect_z_local(state: DistributedQubitState, zmasks: Sequence[int]) -> tuple[dict, list[float]]:
@@ -507,12 +598,12 @@ def _expect_z_finish(state: DistributedQubitState, zmasks: Sequence[int], holder
     if state.world_size > 1 and dist.is_initialized():
         _all_reduce(buf)
     # (whether every rank contributed is a number on the device: `expectation()` looks at it -- no host sync in the forward)
-    state.__dict__['_expz'] = {'masks': [int(z) for z in zmasks], 'values': buf[:, :k], 'ranks': buf[0, k]}
+    state.record.expz = {'masks': [int(z) for z in zmasks], 'values': buf[:, :k], 'ranks': buf[0, k]}
 
 
 def cached_expect_z(state: DistributedQubitState) -> dict | None:
     """The Z-string values the last circuit's final pass left on the state, if every rank took part."""
-    ez = state.__dict__.get('_expz')
+    ez = state.record.expz
     if ez is None:
         return None
     if 'ok' not in ez:
@@ -609,29 +700,26 @@ def _many_target_global(state: DistributedQubitState, p: Prim) -> None:
 
 
 def _exchange_prim(state: DistributedQubitState, p: Prim) -> None:
-    L = state.log_num_amps_per_node
     LAST_RUN['pairwise_exchanges'] += 1
     if len(p.targets) == 1:
         _one_target_global(state, p)
     else:
         # free local slots must not collide with local controls: handled inside
         _many_target_global(state, p)
-    del L
 
 
 # ---------------------------------------------------------------------------------------------------
 # qubit remap: logical -> physical permutation + k-qubit all-to-all
 def _phys(state: DistributedQubitState) -> list[int]:
     """phys[logical bit] = physical bit (physical bit p >= L is rank bit p - L)."""
-    ph = state.__dict__.get('_phys')
-    if ph is None:
-        ph = list(range(state.nqubit))
-        state.__dict__['_phys'] = ph
-    return ph
+    rec = state.record
+    if rec.phys is None:
+        rec.phys = list(range(state.nqubit))
+    return rec.phys
 
 
 def _is_canonical(state: DistributedQubitState) -> bool:
-    ph = state.__dict__.get('_phys')
+    ph = state.record.phys
     return ph is None or all(p == q for q, p in enumerate(ph))
 
 
@@ -669,13 +757,12 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
     chunk c of the shard goes to the peer whose rank bits spell c -- issued asynchronously, so that the next group's
     passes run while this group's amplitudes are on the links.  Nothing waits here: ``_settle`` (or the next remap of
     the same group) does."""
-    vb = _vbits(state)
-    L, W = state.log_num_amps_per_node - vb, state.world_size       # (with virtual rank bits: L = bits of a ROW)
+    rec = state.record
+    vb = rec.vbits
+    L = state.log_num_amps_per_node - vb       # (with virtual rank bits: L = bits of a ROW)
     ph = _phys(state)
     k = len(pairs)
     assert all(ph[lq] >= L for lq, _ in pairs) and all(ph[eq] < L for _, eq in pairs)
-    # a sliced exchange in flight (`_remap_sliced`): the first pass of THIS stretch takes it slice by slice
-    arr = state.__dict__.pop('_arrivals', None)
     if vb:
         # (the planner re-fills ONE class of far positions per remap, `schedule.evict`)
         real = [ph[lq] - L >= vb for lq, _ in pairs]
@@ -690,8 +777,7 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
     ent_bits = {ph[eq] for _, eq in pairs}
     sq = [q for q in slice_qubits if ph[q] < L and ph[q] not in ent_bits]
     sliced = (len(sq) > 0 and vb == 0 and _view(state).shape[0] == 1 and _live(state) and L - k - len(sq) >= 12
-              and _SWEEP['grads'] is None and CONFIG['fold_permute'] and not state.__dict__.get('_as_rank0')
-              and not state.__dict__.get('_behind_reset'))
+              and _SWEEP['grads'] is None and CONFIG['fold_permute'] and not rec.as_rank0 and not rec.behind_reset)
     if not sliced:
         sq = []
     pairs, rbits, out_perm = schedule.relabel(ph, pairs, L, [ph[q] for q in sq])   # rbits: the low vb are rows
@@ -706,57 +792,40 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
         for i, r in enumerate(rbits):
             peer = (peer & ~(1 << (r - vb))) | (((c >> i) & 1) << (r - vb))
         peers.append(peer)
-    a, b = _view(state), _bview(state)
+    if sliced:
+        _remap_sliced(state, pairs, rbits, pending, out_perm, identity, k, chunk, peers, len(sq))
+        LAST_RUN['remaps'] += 1
+        return
+    if rec.arrivals is not None:
+        # an ordinary exchange behind a sliced one: the stretch runs first, its first pass taking the slices as they
+        # arrive; the re-labelling is then a pass of its own below
+        _flush(state, pending)
     groups = _row_groups(state)
     streams = _group_streams(state, len(groups))
-    if sliced or arr is not None:
-        if _remap_sliced(state, pairs, rbits, pending, out_perm, identity, k, chunk, peers, len(sq), arr):
-            LAST_RUN['remaps'] += 1
-            return
-        a, b = _view(state), _bview(state)        # (the stretch may have run and changed the buffers' roles)
     # the first stretch behind reset(): rank 0 holds |0..0> -- its first passes skip what is still known to be zero --
     # and every other rank holds nothing but zeros, which stay zeros under any gates and in any layout: no pass at all
     # (with virtual rank bits the rows of rank 0's shard are |0..0> and zeros: the masks hold for both; the other ranks
     # have skipped every stretch since reset() -- `_remap_virtual` -- and receive their first amplitudes now)
-    fresh = state.__dict__.pop('_fresh_zero', False)
-    as0 = state.__dict__.pop('_as_rank0', False)
-    zeros = state.rank != 0 and (fresh or state.__dict__.pop('_zero_shard', False))
-    state.__dict__.pop('_zero_shard', None)
-    kz = state.__dict__.pop('_known_zero_local', 0)
-    first_exchange = state.__dict__.pop('_behind_reset', False)
-    if as0 and fresh and first_exchange and vb == 0 and _live(state):
-        _first_exchange_local(state, pairs, rbits, pending, out_perm, identity, k, chunk)
+    z = _take_zeros(state)
+    if z.as_rank0 and z.fresh and z.first_exchange and vb == 0 and _live(state):
+        _first_exchange_local(state, z, rbits, pending, out_perm, identity, k, chunk)
         LAST_RUN['remaps'] += 1
-        state.__dict__['_known_zero_local'] = ((1 << k) - 1) << (L - k)
+        rec.known_zero_local = ((1 << k) - 1) << (L - k)
         return
-    if zeros:
-        LAST_RUN['zero_shard_stretches'] += 1
-    elif pending:
-        LAST_RUN['known_zero_stretches'] += bool(kz)
-    # logical zeros (a lazy reset, the first exchange without the wire): the masked passes of ONE group of rows may run on
-    # them -- the executor clears them itself if the masks do not apply; every other case gets real zeros first
-    lazy = bool(state.__dict__.get('_lazy_zero') or state.__dict__.get('_zeros_owed'))
-    if lazy and not (len(groups) == 1 and not zeros and (pending or not identity) and (fresh and state.rank == 0 or kz)
-                     and not (state.__dict__.get('_lazy_zero') and not fresh)):
-        _materialize_zeros(state)
-        lazy = False
-    need_zeros = (lambda: _materialize_zeros(state)) if lazy else None
-    inflight_prev = {id(st): (st, works) for st, works in state.__dict__.pop('_inflight', [])}
+    runs = bool(pending) or not identity
+    need_zeros = _stretch_start(state, z, pending, runs, len(groups), skip_zeros=True)
+    a, b = _view(state), _bview(state)
+    inflight_prev = {id(st): (st, works) for st, works in rec.inflight}
+    rec.inflight = []
     inflight, landed_in_a = [], []
-    if pending:
-        LAST_RUN['local_flushes'] += 1
     for rows, stream in zip(groups, streams):
         with _on(stream):
             for w in inflight_prev.pop(id(stream), (None, []))[1]:    # this group's previous exchange
                 _wait(w, stream)
             t_start = _mark(stream)
-            if zeros:
-                in_b = False
-            else:
-                in_b = (_run_rows(a, b, pending, rows, None if identity else out_perm, zero=fresh or kz, need_zeros=need_zeros)
-                        if (pending or not identity) else False)
-                state.__dict__.pop('_lazy_zero', None)      # (ran through masked -- or were cleared: all is written)
-                state.__dict__.pop('_zeros_owed', None)
+            in_b = False
+            if runs and not z.zeros:
+                in_b = _run_rows(a, b, pending, rows, None if identity else out_perm, zero=z.zero, need_zeros=need_zeros)
             src, dst = (b, a) if in_b else (a, b)
             works = []
             if _live(state):
@@ -785,13 +854,13 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
             inflight.append((stream, works))
     for st, works in inflight_prev.values():                          # (streams of another grouping: join them)
         inflight.append((st, works))
-    state.__dict__['_inflight'] = inflight
+    rec.inflight = inflight
     # The passes queued on the group streams read the matrices of `pending` -- some of them temporaries that
     # `_localize` made on the main stream (rank-selected phases of diagonal gates on global qubits).  Dropping the last
     # reference here would hand their memory back to the caching allocator while that work is still queued, and the
     # next main-stream allocation could overwrite it: they stay referenced until `_settle` has joined the streams.
     if any(st is not None for st, _ in inflight):
-        state.__dict__.setdefault('_inflight_keep', []).append(list(pending))
+        rec.inflight_keep = (rec.inflight_keep or []) + [list(pending)]
     if not all(landed_in_a):
         if any(landed_in_a):         # groups disagree on the buffer they ended in (never with equal group sizes)
             _settle(state)
@@ -799,76 +868,49 @@ def _remap(state: DistributedQubitState, pairs: list[tuple[int, int]], pending: 
                 if in_a:
                     b[rows].copy_(a[rows])
         state.amps, state.buffer = state.buffer, state.amps
-    pending.clear()
-    if not identity:
-        LAST_RUN['folded_permutes' if executor.LAST_RUN.get('permute_folded') else 'permute_passes'] += 1
+    _stretch_end(state, pending, None if identity else out_perm)
     LAST_RUN['groups'] = len(groups)
     LAST_RUN['remaps'] += 1
-    if first_exchange and _live(state):
+    if z.first_exchange and _live(state):
         # The first exchange behind reset(): only rank 0 had anything to send, so on every rank (and in every row) what
         # arrived lies in chunk 0 and the other chunks hold the zeros the other ranks sent -- the qubits that came from
         # the rank bits, now on the top k local bits, are still |0>, and the next stretch starts with their mask
         # (executor.run(zero_state=mask): its first passes move 2^-k of the shard)
-        state.__dict__['_known_zero_local'] = ((1 << k) - 1) << (L - k)
+        rec.known_zero_local = ((1 << k) - 1) << (L - k)
 
 
 def _remap_sliced(state: DistributedQubitState, pairs, rbits, pending: list[Prim], out_perm, identity: bool, k: int,
-                  chunk: int, peers: list[int], nb: int, arr: dict | None) -> bool:
-    """A remap of an un-batched shard with its exchange in 2^nb slices (CONFIG['slice_exchange']; ``nb`` = 0: an ordinary
-    exchange, but the first pass of this stretch takes the PREVIOUS sliced exchange ``arr`` slice by slice).
+                  chunk: int, peers: list[int], nb: int) -> None:
+    """A remap of an un-batched shard with its exchange in 2^nb slices (CONFIG['slice_exchange']).
 
     The last pass of ``pending`` -- which also writes the re-labelling ``out_perm``: entering qubits on the top k local
     bits, the nb slice qubits right below them -- is launched slice by slice (`executor.run(slicing=...)`); behind every
     protocol slice j (the value of the nb bits) its part of every chunk -- contiguous: chunk c, slice j -- leaves for peer c
     on the exchange stream while the next launch computes.  Nothing waits here: the next stretch's first pass waits for
-    slice j right before it reads it (`_first_slicing`), `_settle` for everything.  The pass behind the exchange must not
-    write where slices are still being sent from, so the state's buffers rotate through a THIRD one: received -> ``amps``,
-    spare -> ``buffer``, and the buffer the slices leave from becomes the spare when the last slice has gone.
-    Returns False when there is nothing sliced to do (the caller's ordinary route runs)."""
-    if nb == 0 and (arr is None or not pending):
-        _arrivals_done(state, arr)
-        return False
-    for key in ('_fresh_zero', '_zero_shard', '_behind_reset'):
-        state.__dict__.pop(key, None)
-    kz = state.__dict__.pop('_known_zero_local', 0)
-    lazy = bool(state.__dict__.get('_lazy_zero') or state.__dict__.get('_zeros_owed'))
-    if lazy and not (kz and (pending or not identity)):
-        _materialize_zeros(state)
-        lazy = False
-    if nb == 0:
-        # an ordinary exchange behind a sliced one: run the stretch here (its first pass in slices), then fall back
-        a, b = _view(state), _bview(state)
-        slicing = _first_slicing(state, arr)
-        LAST_RUN['local_flushes'] += 1
-        LAST_RUN['known_zero_stretches'] += bool(kz)
-        if _run_rows(a, b, pending, slice(0, 1), zero=kz, need_zeros=(lambda: _materialize_zeros(state)) if lazy else None,
-                     slicing=slicing):
-            state.amps, state.buffer = state.buffer, state.amps
-        state.__dict__.pop('_lazy_zero', None)
-        state.__dict__.pop('_zeros_owed', None)
-        LAST_RUN['slice_launches_first'] += slicing.get('done', {}).get('first', 0)
-        if TIMING['enabled'] and arr.get('timing') is not None:
-            arr['timing']['slices_first'] = slicing.get('done', {}).get('first', 0)
-        _arrivals_done(state, arr)
-        pending.clear()
-        return False
+    slice j right before it reads it (`_run_stretch`), `_settle` for everything.
+
+    The pass behind the exchange must not write where slices are still being sent from, so the buffers rotate: received
+    -> ``amps`` (the spare is the receive buffer), the buffer that was not the source -> ``buffer``, and the source is out
+    of reach as ``arrivals['src']`` until `_arrivals_done` makes it the spare again -- behind the NEXT stretch.  Three
+    shard-sized buffers; four while a second sliced remap follows right behind this one (its spare is not back yet)."""
+    rec = state.record
+    arr, rec.arrivals = rec.arrivals, None      # (a sliced exchange in flight: this stretch's first pass takes it)
+    z = _take_zeros(state)
     _settle(state)
-    L = state.log_num_amps_per_node
     nsl = 1 << nb
     sub = chunk >> nb
-    a, b = _view(state), _bview(state)
-    spare = state.__dict__.pop('_spare', None)
+    elt = state.amps.element_size()
+    spare, rec.spare = rec.spare, None
     if spare is None or spare.shape != state.amps.shape or spare.dtype != state.amps.dtype or spare.device != state.amps.device:
-        spare = torch.empty_like(state.amps)
-    on_gpu = a.is_cuda
-    xs = _group_streams(state, 2)[1] if on_gpu else None          # the exchange stream
+        spare = torch.empty_like(state.amps)            # (the previous sliced exchange still holds the old spare: a fourth)
+    xs = _group_streams(state, 2)[1] if state.amps.is_cuda else None          # the exchange stream
     works: list = [None] * nsl
-    bufs: dict = {}
-    rec = None
+    bufs: dict = {'src': None, 'dst': spare.view(_view(state).shape)}
+    timing = None
     if TIMING['enabled']:
-        rec = {'remap': LAST_RUN['remaps'] + 1, 'rows': (0, 1), 'k': k, 'bytes': ((1 << k) - 1) * chunk * a.element_size(),
-               'start': _mark(None), 'issued': None, 'exchange': None, 'stream': None, 'slices': nsl}
-        TIMING['remaps'].append(rec)
+        timing = {'remap': LAST_RUN['remaps'] + 1, 'rows': (0, 1), 'k': k, 'bytes': ((1 << k) - 1) * chunk * elt,
+                  'start': _mark(None), 'issued': None, 'exchange': None, 'stream': None, 'slices': nsl}
+        TIMING['remaps'].append(timing)
 
     def pieces(t: torch.Tensor, j: int) -> list[torch.Tensor]:
         v = torch.view_as_real(t[0]).reshape(1 << k, nsl, sub * 2)
@@ -889,10 +931,10 @@ def _remap_sliced(state: DistributedQubitState, pairs, rbits, pending: list[Prim
 
     def issue(j: int, where: torch.Tensor) -> None:
         src, dst = where, bufs['dst']
-        nbytes = ((1 << k) - 1) * sub * a.element_size()
+        nbytes = ((1 << k) - 1) * sub * elt
         LAST_RUN['wire_bytes'] += nbytes
-        if rec is not None and rec['issued'] is None:
-            rec['issued'] = _mark(None)
+        if timing is not None and timing['issued'] is None:
+            timing['issued'] = _mark(None)
         if CONFIG['elide_exchange']:
             if CONFIG['elide_exchange'] == 'loopback' and xs is not None:
                 ev = torch.cuda.Event()
@@ -925,46 +967,29 @@ def _remap_sliced(state: DistributedQubitState, pairs, rbits, pending: list[Prim
         else:
             works[j] = exchange_pieces(pieces(dst, j), pieces(src, j), peers, what, async_op=False)
 
-    slicing = {'last': ([L - k - nb + i for i in range(nb)], after)}
-    if arr is not None:
-        slicing.update(_first_slicing(state, arr))
-    bufs['src'], bufs['dst'] = None, spare.view(a.shape)
-    LAST_RUN['known_zero_stretches'] += bool(kz)
-    if pending:
-        LAST_RUN['local_flushes'] += 1
-    in_b = _run_rows(a, b, pending, slice(0, 1), None if identity else out_perm, zero=kz,
-                     need_zeros=(lambda: _materialize_zeros(state)) if lazy else None, slicing=slicing)
-    assert bufs['src'] is not None and (bufs['src'].data_ptr() == b.data_ptr()) == in_b, 'slices left from the wrong buffer'
-    state.__dict__.pop('_lazy_zero', None)
-    state.__dict__.pop('_zeros_owed', None)
-    done = slicing.get('done', {})
+    bits = [state.log_num_amps_per_node - k - nb + i for i in range(nb)]
+    slicing = {'last': (bits, after)}
+    _run_stretch(state, pending, z, None if identity else out_perm, arr=arr, slicing=slicing)
+    assert bufs['src'] is not None and bufs['src'].data_ptr() == state.amps.data_ptr(), 'slices left from the wrong buffer'
+    last = slicing.get('done', {}).get('last', 0)
     LAST_RUN['sliced_remaps'] += 1
-    LAST_RUN['slice_launches_last'] += done.get('last', 0)
-    LAST_RUN['slice_launches_first'] += done.get('first', 0)
-    if arr is not None:
-        if TIMING['enabled'] and arr.get('timing') is not None:
-            arr['timing']['slices_first'] = done.get('first', 0)
-        _arrivals_done(state, arr)
-    if rec is not None:
-        rec['slices_last'] = done.get('last', 0)
+    LAST_RUN['slice_launches_last'] += last
+    if timing is not None:
+        timing['slices_last'] = last
     # received -> amps, the old spare's place is taken by the buffer that was NOT the source, the source stays out of
     # reach until its slices have gone
-    src_t, other_t = (state.buffer, state.amps) if in_b else (state.amps, state.buffer)
-    state.amps, state.buffer = spare, other_t
-    state.__dict__['_arrivals'] = {'bits': [L - k - nb + i for i in range(nb)], 'works': works, 'src': src_t, 'timing': rec}
-    pending.clear()
-    if not identity:
-        LAST_RUN['folded_permutes' if executor.LAST_RUN.get('permute_folded') else 'permute_passes'] += 1
+    src_t = state.amps
+    state.amps, state.buffer = spare, state.buffer
+    rec.arrivals = {'bits': bits, 'works': works, 'src': src_t, 'timing': timing}
     LAST_RUN['groups'] = 1
-    return True
 
 
-def _first_exchange_local(state: DistributedQubitState, pairs, rbits, pending: list[Prim], out_perm, identity: bool,
+def _first_exchange_local(state: DistributedQubitState, z: _Zeros, rbits, pending: list[Prim], out_perm, identity: bool,
                           k: int, chunk: int) -> None:
     """The first exchange behind reset() without the wire (CONFIG['first_exchange_local']).  Before it only rank 0 holds
     anything: the all-to-all would bring rank r chunk c(r) of RANK 0's shard (c(r) = r's bits on the exchanged rank bits),
     landing in chunk slot 0 (the sender's code), and zeros from everybody else.  ``pending`` was localized as rank 0 sees
-    the gates (`_localize`, ``_as_rank0``), so every rank of rank 0's group computes that shard itself -- |0..0> in, the
+    the gates (`_localize`, ``as_rank0``), so every rank of rank 0's group computes that shard itself -- |0..0> in, the
     known-zero masks on: a fraction of a pass -- keeps its chunk and zeroes the other slots.  Ranks of a group without
     rank 0 (k < log2 W) would receive zeros only: they keep their zeros and run nothing."""
     _settle(state)
@@ -979,35 +1004,20 @@ def _first_exchange_local(state: DistributedQubitState, pairs, rbits, pending: l
         _materialize_zeros(state)         # (a shard of zeros from here on: real ones)
         pending.clear()
         return
-    a, b = _view(state), _bview(state)
-    rows = slice(0, a.shape[0])
+    LAST_RUN['groups'] = 1
     if state.rank != 0:
-        a[:, 0] = 1                       # rank 0's input: |0..0> (the rest of the shard is zero -- really, or logically)
-    if pending:
-        LAST_RUN['local_flushes'] += 1
-    lazy = bool(state.__dict__.get('_lazy_zero'))
-    if pending or not identity:
-        in_b = _run_rows(a, b, pending, rows, None if identity else out_perm, zero=True,
-                         need_zeros=(lambda: _materialize_zeros(state)) if lazy else None)
-    else:
-        _materialize_zeros(state)
-        in_b = False
-    was_lazy = lazy and state.__dict__.pop('_lazy_zero', False)     # (still set: the masked passes ran through, all is written)
-    src, dst = (b, a) if in_b else (a, b)
-    dst[:, :chunk].copy_(src[:, code * chunk:(code + 1) * chunk])
-    if not in_b:                          # the new shard lies in the receive buffer
-        state.amps, state.buffer = state.buffer, state.amps
-    if was_lazy:
+        _view(state)[:, 0] = 1            # rank 0's input: |0..0> (the rest of the shard is zero -- really, or logically)
+    kept = _run_stretch(state, pending, z, None if identity else out_perm, rank0_input=True)
+    a, b = _view(state), _bview(state)
+    b[:, :chunk].copy_(a[:, code * chunk:(code + 1) * chunk])
+    state.amps, state.buffer = state.buffer, state.amps     # (the new shard lies in the receive buffer)
+    if kept:
         # the other chunk slots -- the zeros the other ranks would have sent -- stay un-cleared: the next stretch starts
         # with the known-zero mask of the k qubits that came from the rank bits and reads nothing there; whoever cannot
         # vouch for that clears them first (`_materialize_zeros`)
-        state.__dict__['_zeros_owed'] = ('top', k)
+        state.record.zeros_owed = ('top', k)
     else:
-        dst[:, chunk:].zero_()
-    pending.clear()
-    if not identity:
-        LAST_RUN['folded_permutes' if executor.LAST_RUN.get('permute_folded') else 'permute_passes'] += 1
-    LAST_RUN['groups'] = 1
+        b[:, chunk:].zero_()
 
 
 def _remap_virtual(state: DistributedQubitState, pairs, pending: list[Prim]) -> None:
@@ -1015,10 +1025,10 @@ def _remap_virtual(state: DistributedQubitState, pairs, pending: list[Prim]) -> 
     virtual bits and the entering row-local qubits swap index positions of the ONE shard, and that re-labelling rides on
     the last pass of the stretch in front of it, which therefore runs on the whole shard (gates controlled by a virtual
     bit are ordinary local controls there) instead of row by row."""
-    vb = state.__dict__.pop('_vbits')
+    rec = state.record
+    vb, rec.vbits = rec.vbits, 0
     try:
         _settle(state)
-        _materialize_zeros(state)
         L = state.log_num_amps_per_node
         ph = _phys(state)
         out_perm = list(range(L))
@@ -1026,29 +1036,18 @@ def _remap_virtual(state: DistributedQubitState, pairs, pending: list[Prim]) -> 
             assert L - vb <= ph[lq] < L and ph[eq] < L - vb
             out_perm[ph[lq]], out_perm[ph[eq]] = ph[eq], ph[lq]
         # behind reset(): rank 0's shard is |0..0> (the first stretch runs with the known-zero masks), everybody else's is
-        # all zeros and stays so -- under any gates, in any order of the index bits -- until the first REAL exchange
-        fresh = state.__dict__.pop('_fresh_zero', False)
-        kz = state.__dict__.pop('_known_zero_local', 0)      # (positions of a row: the same bits of the whole shard)
-        zeros = state.rank != 0 and (fresh or state.__dict__.get('_zero_shard', False))
-        if pending:
-            LAST_RUN['local_flushes'] += 1
-        if zeros:
-            state.__dict__['_zero_shard'] = True
-            LAST_RUN['zero_shard_stretches'] += 1
-        else:
-            LAST_RUN['known_zero_stretches'] += bool(kz)
-            local = [q for q in (_localize(state, p) for p in pending) if q is not None]
-            a, b = _view(state), _bview(state)
-            if _run_rows(a, b, local, slice(0, a.shape[0]), out_perm, zero=fresh or kz):
-                state.amps, state.buffer = state.buffer, state.amps
-        pending.clear()
-        LAST_RUN['folded_permutes' if executor.LAST_RUN.get('permute_folded') else 'permute_passes'] += 1
+        # all zeros and stays so -- under any gates, in any order of the index bits -- until the first REAL exchange: a
+        # re-labelling is none, so the state stays behind reset() and a shard of zeros stays one
+        z = _take_zeros(state)
+        rec.behind_reset, rec.zero_shard = z.first_exchange, z.zeros
+        gates = [] if z.zeros else [q for q in (_localize(state, p) for p in pending) if q is not None]
+        _run_stretch(state, pending, z, out_perm, gates=gates, skip_zeros=True)
         for lq, eq in pairs:
             ph[lq], ph[eq] = ph[eq], ph[lq]
         LAST_RUN['remaps'] += 1
         LAST_RUN['virtual_remaps'] += 1
     finally:
-        state.__dict__['_vbits'] = vb
+        rec.vbits = vb
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1117,7 +1116,7 @@ def slice_bits_wanted(state: DistributedQubitState) -> int:
     if nb is None:
         overlaps = state.amps.is_cuda and (CONFIG['elide_exchange'] or (dist.is_initialized() and dist.get_backend() == 'nccl'))
         nb = 3 if overlaps else 0           # (three bits against two, rehearsal of n = 34 / 8 ranks: −4 .. −7 ms per step)
-    return int(nb) if (state.batch is None and _vbits(state) == 0) else 0
+    return int(nb) if (state.batch is None and state.record.vbits == 0) else 0
 
 
 class _Pending(list):
@@ -1162,7 +1161,7 @@ def _defer_tail(state: DistributedQubitState, pending: list[Prim], pairs) -> lis
     every rank whether or not the gates form ITS last pass."""
     cap = int(CONFIG['defer_tail'] or 0)
     if (not cap or not isinstance(pending, _Pending) or pending.src is None or len(pending.every) < 32
-            or _vbits(state) or _SWEEP['grads'] is not None
+            or state.record.vbits or _SWEEP['grads'] is not None
             or _view(state).shape[0] != 1      # (batched shards: measured neutral -- weak series n = 31: 350 / 365 ms with, 350 / 357 without)
             or LAST_RUN['remaps'] < 2):         # (the first two stretches run behind |0..0> / with known-zero masks: cheap anyway)
         return []
@@ -1199,7 +1198,7 @@ def _remap_for(state: DistributedQubitState, st: tuple, i: int, pending: list[Pr
     """The remap that makes gate ``i`` of the (ordered) structure ``st`` local, behind the local gates ``pending``.  Returns
     the logical primitives of a deferred tail (`_defer_tail`): the caller localizes them under the new layout before
     anything else."""
-    vb = _vbits(state)
+    vb = state.record.vbits
     L = state.log_num_amps_per_node - vb
     pairs = schedule.plan_remap(_phys(state), st, i, state.nqubit, L, vb, knobs)
     carry = _defer_tail(state, pending, pairs)
@@ -1285,23 +1284,23 @@ def dist_apply_prims(state: DistributedQubitState, prims: Sequence[Prim], mode: 
     for short gate lists (which otherwise go gate by gate, pairwise exchanges).  ``fresh_zero``: the caller has just
     ``reset()`` the state -- it is |0..0>: rank 0 holds one 1, everybody else zeros -- and the first local stretch makes
     use of it (`_remap`, `_flush`)."""
+    rec = state.record
     with _raw(state):
         if fresh_zero and executor.CONFIG['zero_state'] and _SWEEP['grads'] is None and _is_canonical(state):
-            state.__dict__['_fresh_zero'] = True
-            state.__dict__['_behind_reset'] = True      # (until the first exchange of real rank bits)
-        elif state.__dict__.get('_lazy_zero'):
+            rec.fresh_zero = rec.behind_reset = True    # (behind_reset: until the first exchange of real rank bits)
+        elif rec.lazy_zero:
             _materialize_zeros(state)                   # (a lazy reset() nobody takes up: real zeros)
         try:
             return _dist_apply_prims(state, prims, mode, keep_layout, force_mode, expect_z)
         finally:
             _materialize_zeros(state)                   # (a no-op unless logical zeros are left: nobody outside sees them)
-            for key in ('_fresh_zero', '_zero_shard', '_behind_reset', '_known_zero_local'):
-                state.__dict__.pop(key, None)
+            rec.end_run()
 
 
 def _dist_apply_prims(state: DistributedQubitState, prims: Sequence[Prim], mode: str | None, keep_layout: bool,
                       force_mode: bool = False, expect_z: Sequence[int] | None = None) -> DistributedQubitState:
-    state.__dict__.pop('_expz', None)        # (cached expectation values belong to the state as it was)
+    rec = state.record
+    rec.expz = None                          # (cached expectation values belong to the state as it was)
     for k in LAST_RUN:
         LAST_RUN[k] = 0
     mode = mode or CONFIG['mode']
@@ -1312,7 +1311,7 @@ def _dist_apply_prims(state: DistributedQubitState, prims: Sequence[Prim], mode:
     # the planner's input and settings, once per call (None = whichever rule the dry-run model prefers: below)
     structure = schedule.structure(prims) if mode == 'remap' else None
     knobs = _knobs(True if CONFIG['evict_foldable'] is None else CONFIG['evict_foldable'])
-    fresh = bool(state.__dict__.get('_fresh_zero'))
+    fresh = rec.fresh_zero
     # virtual rank bits: an un-batched shard of a forward circuit, rows of at least one tile
     vb = CONFIG['virtual_bits']
     tile = executor._geometry(state.amps.dtype == torch.complex128).m
@@ -1335,35 +1334,34 @@ def _dist_apply_prims(state: DistributedQubitState, prims: Sequence[Prim], mode:
     LAST_RUN['evict_foldable'] = knobs.evict_foldable
     LAST_RUN['virtual_bits'] = vb
     if mode != 'remap':
-        state.__dict__.pop('_fresh_zero', None)       # (gate-by-gate exchanges: not for them)
-        state.__dict__.pop('_behind_reset', None)
+        rec.fresh_zero = rec.behind_reset = False      # (gate-by-gate exchanges: not for them)
     if vb:
         _settle(state)
-        state.__dict__['_vbits'] = vb
-    if (mode == 'remap' and vb == 0 and CONFIG['first_exchange_local'] and state.__dict__.get('_fresh_zero')
+        rec.vbits = vb
+    if (mode == 'remap' and vb == 0 and CONFIG['first_exchange_local'] and rec.fresh_zero
             and state.world_size > 1):
-        state.__dict__['_as_rank0'] = True       # (until the first exchange: `_remap` / `_flush` take it off)
-    elif state.__dict__.get('_lazy_zero') and not (state.rank == 0 and state.__dict__.get('_fresh_zero') and mode == 'remap' and vb == 0):
+        rec.as_rank0 = True                      # (until the first exchange: `_remap` / `_flush` take it off)
+    elif rec.lazy_zero and not (state.rank == 0 and rec.fresh_zero and mode == 'remap' and vb == 0):
         # a lazily reset shard somebody will read unmasked: the ranks that hold zeros and send them over the wire, rows of
         # virtual rank bits, gate-by-gate exchanges
         _materialize_zeros(state)
     try:
         return _dist_apply_loop(state, prims, mode, keep_layout, expect_z, structure, knobs)
     finally:
-        state.__dict__.pop('_as_rank0', None)
+        rec.as_rank0 = False
         if vb:
             _settle(state)
-            state.__dict__.pop('_vbits', None)
+            rec.vbits = 0
 
 
 def _dist_apply_loop(state: DistributedQubitState, prims: Sequence[Prim], mode: str, keep_layout: bool,
                      expect_z: Sequence[int] | None, st: tuple | None, knobs: schedule.Knobs) -> DistributedQubitState:
     """``st``: the structure of ``prims`` ('remap' mode), ``knobs``: the planner's settings (`_knobs`)."""
-    vb = _vbits(state)
+    vb = state.record.vbits
     n, L = state.nqubit, state.log_num_amps_per_node
-    if mode == 'remap' and knobs.initial_placement and state.__dict__.get('_fresh_zero') and _is_canonical(state) and state.world_size > 1:
+    if mode == 'remap' and knobs.initial_placement and state.record.fresh_zero and _is_canonical(state) and state.world_size > 1:
         # behind reset(): the first placement is free (see `schedule.initial_placement`)
-        state.__dict__['_phys'] = list(schedule.initial_placement(st, n, L, vb, not keep_layout, knobs))
+        state.record.phys = list(schedule.initial_placement(st, n, L, vb, not keep_layout, knobs))
     if mode == 'remap' and knobs.reorder:
         order = schedule.order_indices(st, tuple(_phys(state)), n, L - vb, vb, knobs)
         prims, st = [prims[j] for j in order], tuple(st[j] for j in order)
@@ -1401,7 +1399,7 @@ def _dist_apply_loop(state: DistributedQubitState, prims: Sequence[Prim], mode: 
                 pending.add(loc if isinstance(loc, Prim) else None, q)
     if vb:                        # back to ONE shard of 2^L amplitudes (the rows are its top local index bits): the last
         _settle(state)            # stretch runs on the whole shard
-        state.__dict__.pop('_vbits', None)
+        state.record.vbits = 0
         pending[:] = [q for q in (_localize(state, p) for p in pending) if q is not None]
     if expect_z:
         # the Z-type observables of the circuit: reduced from the registers of the last local pass (DQ_FG_EXPZ)

@@ -740,8 +740,8 @@ def _run_nograd(state: torch.Tensor, prims: Sequence[Prim], inplace: bool = Fals
         last_si = len(plan.steps) - 1
         fold_ok = out_perm is None or (permute and plan.steps.applied_final_perm)
         sliced = {'first': 0, 'last': 0}
-        if slicing is not None and plan.steps and not isinstance(plan.steps[0], fusion.FusedStep):
-            _slicing_all(slicing, 'first')
+        if slicing is not None and not (plan.steps and isinstance(plan.steps[0], fusion.FusedStep)):
+            _slicing_all(slicing, 'first')   # (the first step is no fused pass, or there is none: everything before it)
         for si, st in enumerate(plan.steps):
             if isinstance(st, fusion.FusedStep):
                 src, shared_in = (shared_in, None) if shared_in is not None else (x, None)

@@ -275,6 +275,10 @@ class DistributedQubitState(_ComplexBuffers):
 
     def __init__(self, nqubit: int, batch: int | None = None, device: Any = None, dtype: torch.dtype = torch.cfloat) -> None:
         super().__init__()
+        from .distributed import ShardRecord
+
+        #: the sharded routines' bookkeeping: placement, zero knowledge, work in flight (`distributed.ShardRecord`)
+        self.record = ShardRecord()
         if self.REHEARSE is not None:
             self.world_size, self.rank = self.REHEARSE
         else:
@@ -312,13 +316,13 @@ class DistributedQubitState(_ComplexBuffers):
                 finally:
                     d['_building'] = False
         if name == 'amps':
-            d = self.__dict__
-            if (d.get('_lazy_zero') or d.get('_zeros_owed')) and not d.get('_raw', 0):
+            rec = self.record
+            if (rec.lazy_zero or rec.zeros_owed is not None) and not rec.raw:
                 from .distributed import _materialize_zeros      # (somebody outside the sharded routines looks: real zeros)
 
                 _materialize_zeros(self)
-            ph = d.get('_phys')
-            if ph is not None and not d.get('_raw', 0) and any(p != q for q, p in enumerate(ph)):
+            ph = rec.phys
+            if ph is not None and not rec.raw and any(p != q for q, p in enumerate(ph)):
                 from .distributed import canonicalize
 
                 canonicalize(self)
@@ -326,8 +330,8 @@ class DistributedQubitState(_ComplexBuffers):
 
     def __deepcopy__(self, memo):
         # a copy is a state of its own: exchanges in flight on the group streams are joined first (the copy kernels run
-        # on the current stream), and the bookkeeping of whoever holds the original open (`_raw` nesting, cached
-        # expectation values, stream hand-offs) is not inherited
+        # on the current stream), and of the sharded routines' bookkeeping it inherits the placement only
+        # (`ShardRecord.copy`: not the `_raw` nesting, cached expectation values, stream hand-offs or the spare buffer)
         from copy import deepcopy
 
         from .distributed import _materialize_zeros, _settle
@@ -337,10 +341,10 @@ class DistributedQubitState(_ComplexBuffers):
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for key, value in self.__dict__.items():
-            if key in ('_raw', '_inflight', '_inflight_keep', '_expz', '_building', '_spare', '_arrivals'):      # (the third buffer of a
-                #  sliced exchange is scratch: a copy gets its own when it needs one)
-                continue
-            new.__dict__[key] = deepcopy(value, memo)
+            if key == 'record':
+                new.__dict__[key] = value.copy()
+            elif key != '_building':
+                new.__dict__[key] = deepcopy(value, memo)
         return new
 
     def state_dict(self, *args, **kwargs):
@@ -358,13 +362,10 @@ class DistributedQubitState(_ComplexBuffers):
 
         ``lazy`` (round 6; only ``DistributedQubitCircuit.forward``, which hands the state to ``dist_run(fresh_zero=True)``
         right away): the shard is NOT cleared -- a 16-GiB memset per step -- beyond its first `LAZY_HEAD` amplitudes; the
-        flag ``_lazy_zero`` tells `distributed.dist_apply_prims` that the rest is logically zero but holds whatever the
+        flag ``record.lazy_zero`` tells `distributed.dist_apply_prims` that the rest is logically zero but holds whatever the
         last step left.  The passes behind |0..0> neither read nor keep it (known-zero masks); whoever cannot vouch for
         that clears it first (`distributed._materialize_zeros`)."""
-        self.__dict__.pop('_phys', None)   # canonical qubit order (first: ``amps`` below must not trigger an exchange)
-        self.__dict__.pop('_expz', None)   # (expectation values cached by a circuit's last pass)
-        self.__dict__.pop('_lazy_zero', None)
-        self.__dict__.pop('_zeros_owed', None)
+        self.record.reset()               # canonical qubit order (first: ``amps`` below must not trigger an exchange)
         cur = self._buffers['amps']       # (read past the lazy-build hook of __getattr__: it calls us)
         if tuple(cur.shape) != tuple(self._shape):
             self.amps = torch.zeros(self._shape, dtype=cur.dtype, device=cur.device)
@@ -374,7 +375,7 @@ class DistributedQubitState(_ComplexBuffers):
             if self.POISON_LAZY:
                 rows[:, self.LAZY_HEAD:] = float('nan')
             rows[:, :self.LAZY_HEAD] = 0
-            self.__dict__['_lazy_zero'] = True
+            self.record.lazy_zero = True
         else:
             cur.zero_()             # (the receive buffer is scratch: every use writes all of what it then reads)
         if self.rank == 0:

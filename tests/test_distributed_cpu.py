@@ -486,6 +486,104 @@ def _case_sliced_exchange_w4(dq, rank, world):
     _sliced_exchange_check(dq, rank, world, 18, double=False)
 
 
+#: '{world}-{batched}{lazy_layout}{slice_exchange}{virtual_bits}{first_exchange_local}{fold_permute}{defer_tail}': sha1 (first
+#: 16 hex digits) of the canonical JSON of every rank's LAST_RUN and fused-pass launch count over two forwards.  Taken
+#: before the local-stretch routes of distributed.py were merged into one runner: the merge changed none of them.
+STRETCH_PINS = {
+    '2-0000000': 'a45d3747f1a8161b', '2-00000112': 'a0f132d76211e9ca', '2-00001012': '29369fd15409b000', '2-0000110': '73d2422c6949e4d8',
+    '2-00200012': '6ded46de587ba77f', '2-0020010': 'd9d7c620385f7707', '2-0020100': '4ecbf25f97bbe790', '2-00201112': '970d139852fae8c0',
+    '2-01000012': '49bd77a0533578ed', '2-0100010': '613b4bc056e43cf4', '2-0100100': 'e0c2fed2f930f433', '2-01001112': 'eba71d855f8f1c94',
+    '2-0120000': '49bd77a0533578ed', '2-01200112': '10815491ce66e21d', '2-01201012': 'e0c2fed2f930f433', '2-0120110': '655392f97e781d54',
+    '2-00011012': '74c8a3b2fe04973f', '2-00011112': '6be8ec37d356645c', '2-01011012': '86e53e3cb718c6b8', '2-01011112': '725f1e80d2fa8977',
+    '2-10000012': '8f31ae97f327bad8', '2-10001112': 'ac42469dd329cc7e', '2-11000112': '5d4d677e5dc61131', '2-11001012': '2ce684f9aedcc58a',
+    '4-0000000': '14c8c0fe9fb29288', '4-00000112': 'ea0c7a86617386b3', '4-00001012': '9316273c8c11a3b6', '4-0000110': 'f00cc80a6300a4d0',
+    '4-00200012': '597b1d8d713ed0ce', '4-0020010': '9b0ed7829d9486ac', '4-0020100': '0bb2d5013d2b48ec', '4-00201112': '0d198365de8d9ca2',
+    '4-01000012': 'f20df52797a73a06', '4-0100010': 'bb440ffbca8f63e8', '4-0100100': 'c143b6299051d75a', '4-01001112': '06c413423812a1c0',
+    '4-0120000': 'b035bb3e8277e385', '4-01200112': '6836e11c15e79d94', '4-01201012': '5e305e58e08d5af0', '4-0120110': '725f605992776127',
+    '4-00011012': '24082d91535298df', '4-00011112': 'd80ac4007c3f0f2f', '4-01011012': 'f2c5bb4d4428c3f7', '4-01011112': '67d2a95d3ae4b8ac',
+    '4-10000012': '5b3b52437ffc05fc', '4-10001112': '936fb3ef326077aa', '4-11000112': '21c26f81f52ed801', '4-11001012': '4ae41facc7a849b5',
+}
+
+
+def _stretch_pins_check(dq, rank, world, n):
+    """Every route that runs a local stretch of the sharded state -- plain flushes, grouped and sliced remaps, the first
+    exchange without the wire, virtual re-labellings, deferred tails -- over a grid of the settings that pick between them,
+    with lazy resets that leave NaN where they do not clear (`_worker`): the statistics of every forward and the fused-pass
+    launches of the CPU test double are pinned per setting, the shards checked against the dense circuit."""
+    import hashlib
+    import itertools
+    import json
+    from collections import Counter
+
+    import bench
+    import torch.distributed as dist
+    from deepquantum_amd import distributed as D
+    from deepquantum_amd import executor
+
+    dtype = torch.complex64
+    spec = bench.random_circuit_spec(n, 32, seed=77)
+    per = (1 << n) // world
+    be = dq.backend.get_test_backend()
+    old_ex, old_d = dict(executor.CONFIG), dict(D.CONFIG)
+    executor.CONFIG['permute_min_bits'] = 11
+    # (batched, lazy_layout, slice_exchange, virtual_bits, first_exchange_local, fold_permute, defer_tail): un-batched with
+    # v = 0 -- where every other setting picks a route -- the half of the 2^5 grid whose number of settings that are on is
+    # even (every four of the five meet in all their 16 combinations); v = 1 (no slices, no first exchange without the
+    # wire, no deferral) and batched shards (neither slices nor virtual bits nor deferral): the other settings' half grids
+    ft = (False, True)
+    grid = [(0, lz, nb, 0, fel, fold, df) for lz, nb, fel, fold, df in itertools.product(ft, (0, 2), ft, ft, (0, 12))
+            if (lz + bool(nb) + fel + fold + bool(df)) % 2 == 0]
+    grid += [(0, lz, 0, 1, True, fold, 12) for lz, fold in itertools.product(ft, ft)]
+    grid += [(4, lz, 0, 0, fel, fold, 12) for lz, fel, fold in itertools.product(ft, ft, ft) if (lz + fel + fold) % 2 == 0]
+    seen, dense = Counter(), {}
+    try:
+        for batch, lazy, nb, vb, fel, fold, defer in grid:
+            if batch not in dense:
+                cir, data = bench.build_circuit(dq, n, spec, batch or None, dtype, 'cpu')
+                with torch.no_grad():
+                    dense[batch] = (data, cir(data).reshape(-1, 1 << n), cir.expectation())
+            data, ref, ref_ev = dense[batch]
+            D.CONFIG.update(slice_exchange=nb, virtual_bits=vb, first_exchange_local=fel, fold_permute=fold, defer_tail=defer)
+            key = f'{world}-{int(bool(batch))}{int(lazy)}{nb}{vb}{int(fel)}{int(fold)}{defer}'
+            cir, _ = bench.build_circuit(dq, n, spec, batch or None, dtype, 'cpu', distributed=True)
+            cir.lazy_layout = lazy
+            runs = []
+            with torch.no_grad():
+                for _rep in range(2):           # (the second forward starts from what the first left in every buffer)
+                    calls = be.fused_calls
+                    st = cir(data)
+                    runs.append([dict(D.LAST_RUN), be.fused_calls - calls])
+                    ev = cir.expectation()
+                    err = (st.amps.reshape(-1, per) - ref[:, rank * per:(rank + 1) * per]).abs().max().item()
+                    assert err < 2e-5, f'rank {rank} setting {key}: shard error {err}; {runs[-1]}'
+                    assert (ev.reshape(-1) - ref_ev.reshape(-1)).abs().max().item() < 2e-4, (key, ev, ref_ev)
+            every = [None] * world
+            dist.all_gather_object(every, runs)
+            pin = hashlib.sha1(json.dumps(every, sort_keys=True).encode()).hexdigest()[:16]
+            if os.environ.get('DQ_PIN_RECORD'):
+                if rank == 0:
+                    print(f'{key!r}: {pin!r},', flush=True)
+            else:
+                assert pin == STRETCH_PINS.get(key), f'setting {key}: {every}'
+            for stats, _ in runs:
+                seen.update({k_: bool(v_) for k_, v_ in stats.items()})
+        # (the grid reaches every route)
+        for k_ in ('sliced_remaps', 'slice_launches_first', 'virtual_remaps', 'local_first_exchanges', 'zero_fills',
+                   'known_zero_stretches', 'deferred_tails', 'folded_permutes', 'permute_passes'):
+            assert seen[k_], (k_, seen)
+    finally:
+        executor.CONFIG.update(old_ex)
+        D.CONFIG.update(old_d)
+
+
+def _case_stretch_pins_w2(dq, rank, world):
+    _stretch_pins_check(dq, rank, world, 16)
+
+
+def _case_stretch_pins_w4(dq, rank, world):
+    _stretch_pins_check(dq, rank, world, 18)
+
+
 def _case_virtual_bits_w2(dq, rank, world):
     _virtual_bits_check(dq, rank, world, 14, double=True)       # complex128: rows of 2^11 amplitudes = one tile
 
@@ -828,7 +926,8 @@ def _case_sampled_expectation_w4(dq, rank, world):
                                         ('expectation_grad_w4', 4), ('measure_w2', 2), ('batched_w4', 4), ('folded_permute_w2', 2),
                                         ('golden_w2', 2), ('golden_w4', 4), ('golden_w8', 8),
                                         ('fused_sweep_w2', 2), ('fused_sweep_w4', 4), ('grouped_exchange_w4', 4), ('virtual_bits_w2', 2), ('virtual_bits_w4', 4), ('initial_placement_w4', 4),
-                                        ('zero_state_w2', 2), ('zero_state_w4', 4), ('sliced_exchange_w2', 2), ('sliced_exchange_w4', 4), ('deferred_tail_w2', 2), ('deferred_tail_w4', 4)])
+                                        ('zero_state_w2', 2), ('zero_state_w4', 4), ('sliced_exchange_w2', 2), ('sliced_exchange_w4', 4), ('deferred_tail_w2', 2), ('deferred_tail_w4', 4),
+                                        ('stretch_pins_w2', 2), ('stretch_pins_w4', 4)])
 def test_sharded_circuit(case, world):
     _run(case, world)
 
