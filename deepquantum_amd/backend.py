@@ -464,9 +464,10 @@ def gate_grad(
     if not _use_hip(x):
         return _test_backend.gate_grad(x, gy, targets, controls)
     d = 1 << k
-    if k > 2:
-        # Dense blocks on > 2 wires with trainable entries (LatentGate on many wires) are rare; the
-        # contraction is a plain GEMM (gy_mat @ x_mat^H) and is left to rocBLAS through torch.
+    if RDMK_MIN <= k <= RDMK_MAX:
+        return rdmk_cross(x, gy, targets, controls)
+    if k > RDMK_MAX:
+        # beyond the matrix-core reduction: a plain GEMM (gy_mat @ x_mat^H) left to rocBLAS through torch
         return _gate_grad_gemm(x, gy, n, targets, controls)
     out = torch.zeros(x.shape[0], d, d, 2, dtype=torch.float64, device=x.device)
     lib = _lib.load()
@@ -516,6 +517,44 @@ def gate_grad_multi(x: torch.Tensor, gy: torch.Tensor, gates: Sequence[tuple[int
         start = stop
     out = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
     return torch.view_as_complex(out.contiguous())
+
+
+RDMK_MIN, RDMK_MAX = 3, 10     # the k-wire cross reduction of dq_rdmk_cross_*
+
+
+def rdmk_cross(
+    x: torch.Tensor, gy: torch.Tensor, targets: Sequence[int], controls: Sequence[int] = ()
+) -> torch.Tensor:
+    """out[b, a, c] = sum over the controlled amplitude groups of gy[b, a] conj(x[b, c]) for 3 <= k <= 10 targets
+    (matrix MSB = targets[0]): complex128 (B, 2^k, 2^k), on the matrix cores without copying the state
+    (``dq_rdmk_cross_*``).  ``x is gy`` (the same buffer) is the reduced density matrix of the target wires: half the
+    tiles, and the result is exactly Hermitian.  The workspace comes from PyTorch's allocator (legal under capture)."""
+    n = _nqubit(x)
+    targets, controls = [int(t) for t in targets], [int(c) for c in controls]
+    k = len(targets)
+    if x.shape != gy.shape or x.dtype != gy.dtype:
+        raise ValueError('x/gy must be (batch, 2**n) tensors of one shape and dtype')
+    if not (x.is_contiguous() and gy.is_contiguous()):
+        raise ValueError('x/gy must be contiguous')
+    if not RDMK_MIN <= k <= RDMK_MAX:
+        raise ValueError(f'rdmk_cross: {k} targets, supported {RDMK_MIN}..{RDMK_MAX}')
+    if not _use_hip(x):
+        return _test_backend.gate_grad(x, gy, targets, controls)
+    same = x.data_ptr() == gy.data_ptr()
+    d = 1 << k
+    lib = _lib.load()
+    fn = getattr(lib, f'dq_rdmk_cross_{_suffix(x)}')
+    out = torch.empty(x.shape[0], d, d, 2, dtype=torch.float64, device=x.device)
+    for lo in range(0, x.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, x.shape[0])
+        nbytes = lib.dq_rdmk_ws_bytes(n, k, len(controls), hi - lo, int(x.dtype == torch.complex128), int(same))
+        if nbytes < 0:
+            raise ValueError(f'rdmk_cross: bad shape (n={n}, k={k}, controls={len(controls)})')
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+        rc = fn(_ptr(x[lo:hi]), _ptr(gy[lo:hi]), n, _lib.int_array(targets), k, _lib.int_array(controls), len(controls),
+                hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(x))
+        _lib.check(rc, 'dq_rdmk_cross')
+    return torch.view_as_complex(out)
 
 
 def _gate_grad_gemm(x, gy, n, targets, controls):

@@ -340,6 +340,35 @@ class QubitCircuit(Operation):
         return qmath.measure(self.state, shots=shots, with_prob=with_prob, wires=self.wires_measure,
                              den_mat=self.den_mat, block_size=block_size)
 
+    def reduced_density_matrix(self, wires: int | list[int]) -> torch.Tensor:
+        """Reduced density matrix of ``wires`` (in that matrix order, ``wires[0]`` the most significant bit) of the final
+        state of the last forward: (2**k, 2**k), or (B, 2**k, 2**k) for a batch.  A state vector goes through
+        :func:`qmath.reduced_density_matrix` (1 to 10 wires, not normalised); a density matrix (``den_mat=True``)
+        through :func:`qmath.partial_trace`."""
+        if self.state is None:
+            raise RuntimeError('reduced_density_matrix: run the circuit first')
+        if self.den_mat:
+            return qmath.density_matrix_rdm(self.state, self.nqubit, wires)
+        return qmath.reduced_density_matrix(self.state, self.nqubit, wires)
+
+    def entanglement_entropy(self, wires: int | list[int], alpha: float = 1.0, base: float | None = None) -> torch.Tensor:
+        """Entropy of the normalised reduced density matrix of ``wires`` of the final state: (B,) real, or a 0-d tensor
+        for a single state.  See :func:`qmath.entanglement_entropy` for ``alpha``, ``base`` and the eigenvalue cut-off.
+        A density matrix is mixed, so there the entropy is that of ``wires`` themselves (no complement)."""
+        if self.state is None:
+            raise RuntimeError('entanglement_entropy: run the circuit first')
+        if not self.den_mat:
+            return qmath.entanglement_entropy(self.state, self.nqubit, wires, alpha=alpha, base=base)
+        alpha = float(alpha)
+        if not alpha > 0:
+            raise ValueError(f'entanglement_entropy: alpha must be > 0, got {alpha}')
+        rho = qmath.density_matrix_rdm(self.state, self.nqubit, wires)
+        single = rho.ndim == 2
+        rho = rho.unsqueeze(0) if single else rho
+        tau = 1e-12 if rho.dtype == torch.complex128 else 1e-6
+        val = qmath._entropy_of(rho, alpha, base, tau).to(rho.real.dtype)
+        return val.squeeze(0) if single else val
+
     def expectation(self, shots: int | None = None) -> torch.Tensor:
         """Expectation value of every registered observable, stacked on the last dimension
         (reference: circuit.py:381-428)."""
@@ -822,6 +851,12 @@ class DistributedQubitCircuit(QubitCircuit):
             return None
         return measure_dist(self.state, shots=shots, with_prob=with_prob, wires=self.wires_measure,
                             block_size=block_size)
+
+    def reduced_density_matrix(self, wires: int | list[int]) -> torch.Tensor:
+        raise NotImplementedError('reduced_density_matrix: sharded states are not supported')
+
+    def entanglement_entropy(self, wires: int | list[int], alpha: float = 1.0, base: float | None = None) -> torch.Tensor:
+        raise NotImplementedError('entanglement_entropy: sharded states are not supported')
 
     def expectation(self, shots: int | None = None) -> torch.Tensor:
         from . import executor

@@ -4,6 +4,7 @@ functions the QubitCircuit hot path uses.  All heavy lifting is delegated to the
 
 from __future__ import annotations
 
+import math
 from collections import Counter
 from typing import TYPE_CHECKING, Any
 
@@ -318,3 +319,142 @@ def generalized_distance(state1: torch.Tensor, state2: torch.Tensor) -> torch.Te
     overlap = state1.mH @ state2
     norms = (state1.mH @ state1).real * (state2.mH @ state2).real
     return norms - (overlap.real * overlap.real + overlap.imag * overlap.imag)
+
+
+RDM_MAX_WIRES = 10      # the k-wire reduction of dq_rdmk_cross_* (k <= 2: dq_gate_grad_*)
+
+
+def _state_batch(state: torch.Tensor, nqubit: int, what: str) -> tuple[torch.Tensor, bool]:
+    """A state vector in any accepted form -> the flat complex (B, 2**n) tensor and whether it was a single state
+    (``ndim == 1`` or ``(ndim == 2 and shape[-1] == 1)``, the rule of :func:`measure`)."""
+    from .state import DistributedQubitState
+
+    if isinstance(state, DistributedQubitState):
+        raise NotImplementedError(f'{what}: sharded states are not supported (kept wires that are global in the '
+                                  'placement need a remap)')
+    if not isinstance(state, torch.Tensor):
+        raise ValueError(f'{what}: state must be a tensor, got {type(state).__name__}')
+    n = int(nqubit)
+    if n < 1 or n > 40:
+        raise ValueError(f'{what}: nqubit={nqubit} out of range')
+    dim = 1 << n
+    single = state.ndim == 1 or (state.ndim == 2 and state.shape[-1] == 1)
+    if single:
+        ok = state.numel() == dim
+    else:
+        ok = state.ndim >= 2 and tuple(state.shape[1:]) in ((dim,), (dim, 1), (2,) * n)
+    if not ok:
+        raise ValueError(f'{what}: a state of {n} qubits must have the shape (2**n,), (2**n, 1), (B, 2**n), '
+                         f'(B, 2**n, 1) or (B, 2, ..., 2); got {tuple(state.shape)}')
+    if not state.is_complex():
+        state = state.to(torch.complex128 if state.dtype == torch.float64 else torch.complex64)
+    return state.reshape(1 if single else state.shape[0], dim), single
+
+
+def _wire_list(wires: Any, nqubit: int, what: str) -> list[int]:
+    if isinstance(wires, int):
+        wires = [wires]
+    try:
+        wires = [int(w) for w in wires]
+    except TypeError:
+        raise ValueError(f'{what}: wires must be an int or a list of ints, got {wires!r}') from None
+    if not wires or len(set(wires)) != len(wires) or any(w < 0 or w >= nqubit for w in wires):
+        raise ValueError(f'{what}: wires must be distinct and in [0, {nqubit}), got {wires}')
+    return wires
+
+
+def _rdm_flat(flat: torch.Tensor, nqubit: int, wires: list[int]) -> torch.Tensor:
+    """(B, 2**n) -> complex128 (B, 2**k, 2**k): rho[b] = Tr_{other wires} |psi_b><psi_b|, ``wires[0]`` = matrix MSB.
+    The same tensor on both sides of ``ops.gate_grad``: the Hermitian route of the kernel, differentiable to any
+    order through the node's rules."""
+    return ops.gate_grad(flat, flat, [nqubit - 1 - w for w in wires])
+
+
+def reduced_density_matrix(state: torch.Tensor, nqubit: int, wires: int | list[int]) -> torch.Tensor:
+    """Reduced density matrix ``rho_A = Tr_B |psi><psi|`` of the wires ``A = wires`` (1 to 10 of them; all n gives
+    psi psi^dagger): (2**k, 2**k) for a single state, (B, 2**k, 2**k) for a batch, in the state's complex dtype.
+
+    ``state`` is (2**n,), (2**n, 1), (B, 2**n), (B, 2**n, 1) or (B, 2, ..., 2).  The order of ``wires`` is the matrix
+    index order (``wires[0]`` is the most significant bit); for sorted wires the result equals
+    ``partial_trace(psi psi^dagger, n, complement)``.  Not normalised: ``Tr rho_A = <psi|psi>``.  The state is read
+    without the 4**n matrix (a Gram reduction on the matrix cores, ``dq_rdmk_cross_*``); differentiable to any order,
+    and usable under ``torch.vmap`` / ``torch.func`` and graph capture."""
+    flat, single = _state_batch(state, nqubit, 'reduced_density_matrix')
+    wires = _wire_list(wires, int(nqubit), 'reduced_density_matrix')
+    if len(wires) > RDM_MAX_WIRES:
+        raise ValueError(f'reduced_density_matrix: {len(wires)} wires, at most {RDM_MAX_WIRES}')
+    rho = _rdm_flat(flat, int(nqubit), wires).to(flat.dtype)
+    return rho.squeeze(0) if single else rho
+
+
+def _entropy_of(rho: torch.Tensor, alpha: float, base: float | None, tau: float) -> torch.Tensor:
+    """Entropy of (B, D, D) Hermitian matrices, normalised by their trace first: (B,) float64."""
+    rho = rho.to(torch.complex128)
+    tr = rho.diagonal(dim1=-2, dim2=-1).sum(-1).real
+    rho = rho / tr[:, None, None]
+    if alpha == 2:
+        # -log Tr rho^2 = -log ||rho||_F^2 (Hermitian): no eigensolver
+        val = -torch.log((rho.real * rho.real + rho.imag * rho.imag).sum((-2, -1)))
+    else:
+        lam = torch.linalg.eigvalsh(rho)
+        keep = lam > tau
+        lam = torch.where(keep, lam, torch.ones_like(lam))       # (dropped terms: no value, no gradient)
+        if alpha == 1:
+            val = -(torch.where(keep, lam * torch.log(lam), torch.zeros_like(lam))).sum(-1)
+        else:
+            val = torch.log(torch.where(keep, lam**alpha, torch.zeros_like(lam)).sum(-1)) / (1.0 - alpha)
+    if base is not None:
+        val = val / math.log(base)
+    return val
+
+
+def entanglement_entropy(state: torch.Tensor, nqubit: int, wires: int | list[int], alpha: float = 1.0,
+                         base: float | None = None) -> torch.Tensor:
+    """Entanglement entropy across the cut ``wires | rest`` of a pure state: the entropy of ``rho_A / Tr rho_A``.
+    (B,) real, or a 0-d tensor for a single state (input forms as :func:`reduced_density_matrix`).
+
+    ``alpha == 1``: von Neumann, ``-sum lambda log lambda`` (eigenvalues from ``torch.linalg.eigvalsh`` in complex128);
+    ``alpha == 2``: ``-log Tr rho^2``, from the Frobenius norm without an eigensolver; any other ``alpha > 0``: Renyi,
+    ``log sum lambda**alpha / (1 - alpha)``.  Eigenvalues at or below tau contribute nothing and carry no gradient:
+    tau = 1e-12 for complex128 states, 1e-6 for complex64.  ``base=None``: natural log.  A pure state has
+    ``S(A) = S(B)``, so the smaller side of the cut is reduced: either side may hold up to 10 wires; a cut with more
+    than 10 on both sides raises ``ValueError``."""
+    flat, single = _state_batch(state, nqubit, 'entanglement_entropy')
+    n = int(nqubit)
+    wires = _wire_list(wires, n, 'entanglement_entropy')
+    alpha = float(alpha)
+    if not alpha > 0:
+        raise ValueError(f'entanglement_entropy: alpha must be > 0, got {alpha}')
+    if base is not None and (base <= 0 or base == 1):
+        raise ValueError(f'entanglement_entropy: base must be > 0 and != 1, got {base}')
+    rest = [w for w in range(n) if w not in wires]
+    side = sorted(wires) if len(wires) <= len(rest) else rest
+    if len(side) > RDM_MAX_WIRES:
+        raise ValueError(f'entanglement_entropy: both sides of the cut exceed {RDM_MAX_WIRES} wires '
+                         f'({len(wires)} | {len(rest)})')
+    rdt = flat.real.dtype
+    if not side:                      # the whole state: pure, no entropy
+        val = torch.zeros(flat.shape[0], dtype=rdt, device=flat.device)
+    else:
+        tau = 1e-12 if flat.dtype == torch.complex128 else 1e-6
+        val = _entropy_of(_rdm_flat(flat, n, side), alpha, base, tau).to(rdt)
+    return val.squeeze(0) if single else val
+
+
+def density_matrix_rdm(rho: torch.Tensor, nqubit: int, wires: list[int]) -> torch.Tensor:
+    """Reduced density matrix of the wires ``wires`` (in that matrix order) of (B, 2**n, 2**n) or (2**n, 2**n) density
+    matrices: ``partial_trace`` over the rest, permuted to the order of ``wires``."""
+    n = int(nqubit)
+    wires = _wire_list(wires, n, 'reduced_density_matrix')
+    single = rho.ndim == 2
+    rest = [w for w in range(n) if w not in wires]
+    red = partial_trace(rho if rho.ndim == 3 else rho.unsqueeze(0), n, rest)
+    k = len(wires)
+    red = red.reshape(-1, 1 << k, 1 << k)
+    order = sorted(wires)
+    if order != wires:
+        perm = [order.index(w) for w in wires]
+        b = red.shape[0]
+        red = red.reshape([b] + [2] * (2 * k)).permute([0] + [1 + p for p in perm] + [1 + k + p for p in perm])
+        red = red.reshape(b, 1 << k, 1 << k)
+    return red.squeeze(0) if single else red

@@ -45,7 +45,7 @@ typedef enum {
     DQ_ERR_UNSUPPORTED = -3  /* valid request outside what this build implements */
 } DqStatus;
 
-#define DQ_ABI_VERSION 26
+#define DQ_ABI_VERSION 27
 
 int dq_abi_version(void);
 /* Thread-local, never NULL. */
@@ -482,6 +482,25 @@ int dq_rdm1_cross_c128(const void* bra, const void* ket, int n, int64_t batch, d
  * into out.  out must not alias psi. */
 int dq_apply_wire_sum_c64(const void* psi, void* out, const double* mats, int n, int64_t batch, dq_stream_t stream);
 int dq_apply_wire_sum_c128(const void* psi, void* out, const double* mats, int n, int64_t batch, dq_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 6. k-wire cross reduction on the matrix cores (ABI 27; csrc/dq_rdm.hip).  The reduced density matrix of k wires
+ *    (x == gy) and the matrix cotangent of a dense gate on 3..10 wires, without copying the state:
+ *        out[b, a, c] = sum_r gy[b, dep_T(a) | dep_R(r) | cmask] * conj(x[b, dep_T(c) | dep_R(r) | cmask])
+ *    T = the k target bits (matrix MSB = targets[0]), controls fixed at 1, R = the other n - k - nc bits.
+ *    3 <= k <= 10 (any other k: DQ_ERR_UNSUPPORTED), any n >= k + nc up to 40, 1 <= batch <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of device workspace dq_rdmk_cross_* needs (hermitian != 0: x == gy); -1 on a bad argument.  At most twice the
+ * output plus 1 % of the state. */
+int64_t dq_rdmk_ws_bytes(int n, int k, int nc, int64_t batch, int is_c128, int hermitian);
+/* out: DEVICE complex128 [batch, 2^k, 2^k], fully overwritten (the caller does not zero it).  x == gy computes the
+ * tiles on or above the diagonal and writes the rest as their exact conjugate: the result is exactly Hermitian.
+ * Workgroups write fixed-order partial sums into `ws` (at least dq_rdmk_ws_bytes bytes) and a second kernel adds them:
+ * no atomics, results are bitwise reproducible. */
+int dq_rdmk_cross_c64(const void* x, const void* gy, int n, const int* targets, int k, const int* controls, int nc,
+                      int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+int dq_rdmk_cross_c128(const void* x, const void* gy, int n, const int* targets, int k, const int* controls, int nc,
+                       int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
 
 #ifdef __cplusplus
 }
