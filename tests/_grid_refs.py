@@ -1,0 +1,189 @@
+"""Plain complex128 / float64 references of the kernels, built from torch tensor operations only (index arithmetic,
+gathers, reshape / permute + matmul) on whatever device the inputs live on: the large-grid tests run them on the GPU,
+test_grid_paths_cpu.py checks them against the CPU oracle at small n.  None of them calls a project kernel.
+
+The reductions return the value and S, the same sum taken over the absolute values of its terms: the scale a rounding
+error of the summation is measured against."""
+
+from __future__ import annotations
+
+import torch
+
+C128 = torch.complex128
+
+
+def parity(v: torch.Tensor) -> torch.Tensor:
+    """popcount(v) & 1 of a non-negative int64 tensor."""
+    for s in (32, 16, 8, 4, 2, 1):
+        v = v ^ (v >> s)
+    return v & 1
+
+
+def z_sign(i: torch.Tensor, zmask: int) -> torch.Tensor:
+    """(-1)^popcount(i & zmask) as float64."""
+    return (1 - 2 * parity(i & zmask)).to(torch.float64)
+
+
+def _nbits(t: torch.Tensor) -> int:
+    return t.shape[-1].bit_length() - 1
+
+
+def bit_view(t: torch.Tensor, special) -> tuple[torch.Tensor, dict]:
+    """View (B, 2^n) as (B, d_1, .., d_m), most significant index bits first, where every bit of ``special`` has an axis of
+    its own (size 2) and the runs of other bits between them share one axis.  Returns the view and {bit: axis}."""
+    n = _nbits(t)
+    sizes, axis_of, run = [], {}, 0
+    for p in range(n - 1, -1, -1):
+        if p in special:
+            if run:
+                sizes.append(1 << run)
+                run = 0
+            axis_of[p] = len(sizes) + 1
+            sizes.append(2)
+        else:
+            run += 1
+    if run:
+        sizes.append(1 << run)
+    return t.reshape(t.shape[0], *sizes), axis_of
+
+
+def gate_matrix_view(t: torch.Tensor, targets, controls=()) -> torch.Tensor:
+    """The controlled slice of ``t`` (controls = 1) as a (B, 2^k, rest) VIEW-permuted tensor: axis 1 the targets
+    (targets[0] = matrix-index MSB), then the other bits, most significant first -- so the flattened column index is the
+    uncontrolled non-target bits in ascending order, the kernels' column numbering (insert_zeros)."""
+    v, axis_of = bit_view(t, set(targets) | set(controls))
+    idx = [slice(None)] * v.ndim
+    for c in controls:
+        idx[axis_of[c]] = 1
+    sl = v[tuple(idx)]
+    gone = sorted(axis_of[c] for c in controls)
+    pos = {a: a - sum(g < a for g in gone) for a in range(v.ndim) if a not in gone}
+    tax = [pos[axis_of[q]] for q in targets]
+    rest = [a for a in range(1, sl.ndim) if a not in tax]
+    return sl.permute([0] + tax + rest)
+
+
+def apply_gate(x: torch.Tensor, mats: torch.Tensor, targets, controls=()):
+    """(U on ``targets`` where all ``controls`` are 1) x in complex128: gather the controlled slice to (B, 2^k, rest), one
+    matmul, scatter back.  ``mats``: (D, D), (1, D, D) or (B, D, D).  Returns (out, xm, ym): xm / ym the (B, D, rest)
+    matrices before and after (for the negative controls)."""
+    k = len(targets)
+    out = x.to(C128, copy=True)
+    view = gate_matrix_view(out, targets, controls)
+    xm = view.clone(memory_format=torch.contiguous_format).reshape(x.shape[0], 1 << k, -1)     # (a copy, never a view of out)
+    u = mats.to(device=x.device, dtype=C128)
+    ym = (u if u.ndim == 3 else u.unsqueeze(0)) @ xm
+    view.copy_(ym.reshape(view.shape))
+    return out, xm, ym
+
+
+def expect_pauli(psi: torch.Tensor, xmask: int, zmask: int):
+    """Re <psi|P|psi> for P = i^ny X^x Z^z (Y = i X Z on its bit): (B,) float64 and S = sum_i |psi_i| |psi_{i^x}|."""
+    i = torch.arange(psi.shape[-1], device=psi.device)
+    j = i ^ xmask
+    y = psi.to(C128)
+    terms = y.conj() * y[:, j] * z_sign(j, zmask)
+    ny = bin(xmask & zmask).count('1')
+    val = (terms.sum(-1) * (1j ** ny)).real
+    return val, (y.abs() * y.abs()[:, j]).sum(-1)
+
+
+def inner(bra: torch.Tensor, ket: torch.Tensor):
+    a, b = bra.to(C128), ket.to(C128)
+    return (a.conj() * b).sum(-1), (a.abs() * b.abs()).sum(-1)
+
+
+def probabilities(psi: torch.Tensor) -> torch.Tensor:
+    y = torch.view_as_real(psi).to(torch.float64)
+    return y[..., 0] ** 2 + y[..., 1] ** 2
+
+
+def expect_z_multi(psi: torch.Tensor, zmasks):
+    """<psi| Z-string_k |psi>: (B, K) float64, and S = sum_i |psi_i|^2 (B, 1)."""
+    p = probabilities(psi)
+    i = torch.arange(psi.shape[-1], device=psi.device)
+    return torch.stack([(p * z_sign(i, z)).sum(-1) for z in zmasks], dim=1), p.sum(-1, keepdim=True)
+
+
+def scale_z_signs(x: torch.Tensor, zmasks, coef: torch.Tensor) -> torch.Tensor:
+    """(sum_k coef[b, k] Z-string_k) x_b in complex128."""
+    i = torch.arange(x.shape[-1], device=x.device)
+    w = torch.zeros(x.shape, dtype=torch.float64, device=x.device)
+    for k, z in enumerate(zmasks):
+        w += coef[:, k : k + 1].to(device=x.device, dtype=torch.float64) * z_sign(i, z)
+    return x.to(C128) * w
+
+
+def outcome_index(n: int, bits, device) -> torch.Tensor:
+    """Outcome of every index for a marginal over ``bits`` (bits[0] = the outcome's MSB)."""
+    i = torch.arange(1 << n, device=device)
+    o = torch.zeros_like(i)
+    for q, b in enumerate(bits):
+        o |= ((i >> b) & 1) << (len(bits) - 1 - q)
+    return o
+
+
+def marginal(psi: torch.Tensor, bits) -> torch.Tensor:
+    """(B, 2^len(bits)) float64.  Its terms are non-negative: S is the value itself."""
+    o = outcome_index(_nbits(psi), bits, psi.device)
+    out = torch.zeros(psi.shape[0], 1 << len(bits), dtype=torch.float64, device=psi.device)
+    return out.index_add_(1, o, probabilities(psi))
+
+
+def rdm1_cross(bra: torch.Tensor, ket: torch.Tensor):
+    """T[b, k, a, c] = sum over the other wires of conj(bra[.. a on wire k ..]) ket[.. c on wire k ..] (wire k = index bit
+    n - 1 - k): (B, n, 2, 2) complex128, and S, the same sums over |bra| |ket|.  Elementwise products and torch's own
+    (cascaded) sums rather than an einsum: a GEMM whose inner dimension is the whole state adds in an order of its own,
+    and its rounding at 2^22 terms is of the order this reference is used to judge."""
+    b, n = ket.shape[0], _nbits(ket)
+    x, y = bra.to(C128), ket.to(C128)
+    t = torch.empty(b, n, 2, 2, dtype=C128, device=ket.device)
+    s = torch.empty(b, n, 2, 2, dtype=torch.float64, device=ket.device)
+    for k in range(n):
+        xv, yv = x.reshape(b, 1 << k, 2, -1), y.reshape(b, 1 << k, 2, -1)
+        for a in (0, 1):
+            for c in (0, 1):
+                t[:, k, a, c] = (xv[:, :, a].conj() * yv[:, :, c]).sum((1, 2))
+                s[:, k, a, c] = (xv[:, :, a].abs() * yv[:, :, c].abs()).sum((1, 2))
+    return t, s
+
+
+def src_index(nl: int, src_of_dst, device) -> torch.Tensor:
+    """sigma(i) = sum_p bit_p(i) << src_of_dst[p]: permute_bits reads out[i] = in[sigma(i)]."""
+    i = torch.arange(1 << nl, device=device)
+    s = torch.zeros_like(i)
+    for p, sp in enumerate(src_of_dst):
+        s |= ((i >> p) & 1) << sp
+    return s
+
+
+def expand_index(nl: int, mask: int, value: int, device) -> torch.Tensor:
+    """Packed position c -> amplitude index with ``value`` re-inserted at the ``mask`` bits."""
+    c = torch.arange(1 << (nl - bin(mask).count('1')), device=device)
+    out = torch.zeros_like(c)
+    src = 0
+    for p in range(nl):
+        if not (mask >> p) & 1:
+            out |= ((c >> src) & 1) << p
+            src += 1
+    return out | value
+
+
+def tile_cross(x: torch.Tensor, gy: torch.Tensor, tile_bits, tile: int, target: int, controls=()) -> torch.Tensor:
+    """The share of gate_grad(x, gy, [target], controls) that one tile of gate_grad_multi holds: the pairs whose index bits
+    outside ``tile_bits`` spell ``tile`` (ascending).  (B, 2, 2) complex128; zero when a control outside the tile is 0."""
+    n = _nbits(x)
+    outside = [p for p in range(n) if p not in tile_bits]
+    base = 0
+    for q, p in enumerate(outside):
+        base |= ((tile >> q) & 1) << p
+    e = torch.full((1 << len(tile_bits),), base, dtype=torch.long, device=x.device)
+    a = torch.arange(1 << len(tile_bits), device=x.device)
+    for q, p in enumerate(tile_bits):
+        e |= ((a >> q) & 1) << p
+    cm = sum(1 << c for c in controls)
+    e0 = e[(((e >> target) & 1) == 0) & ((e & cm) == cm)]
+    e1 = e0 | (1 << target)
+    xs = torch.stack([x[:, e0], x[:, e1]], dim=1).to(C128)
+    ys = torch.stack([gy[:, e0], gy[:, e1]], dim=1).to(C128)
+    return ys @ xs.mH

@@ -1,0 +1,216 @@
+"""Mirrors of the launchers' grid arithmetic, for the large-grid tests (test_grid_paths_gpu.py).
+
+Each function copies what one launcher in ``deepquantum_amd/csrc`` (or ``backend.py``) computes from a shape: how many
+workgroups it launches and so how many times a workgroup goes round its loop, whether the streaming (non-temporal)
+instantiation is picked, how many passes a plan has.  A GPU case asserts from these that its shape reaches the path it
+claims; test_grid_paths_cpu.py checks the mirrors against the thresholds they stand for and, where the library reports
+the arithmetic itself (``dq_rdm1_ws_bytes``), against the library.  If a constant in a launcher changes, the mirror here
+must change with it, or the cases stop claiming what they cover -- loudly."""
+
+from __future__ import annotations
+
+GIB = 1 << 30
+
+
+def _cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def _csize(c128: bool) -> int:
+    return 16 if c128 else 8
+
+
+# ---- dq_dense.hip, apply_dense_mfma (k = 5..10 on the matrix cores) -----------------------------------------------------
+def dense(n: int, k: int, nc: int, batch: int, c128: bool, shared: bool, bit0_used: bool) -> dict:
+    """dq_dense.hip:380-435.  ``bit0_used``: index bit 0 is a target or a control.  Returns the route ('dense56', 'staged1'
+    = apply_dense_mfma_kernel<T, 1>, 'staged2' = <T, 2>), whether the non-temporal instantiation runs, and for dense56 the
+    column groups, the groups one pass of the grid covers and the loop iterations of a workgroup."""
+    d = 1 << k
+    colbits = n - k - nc
+    ncols = (batch if shared else 1) << colbits
+    nt = (batch << n) * _csize(c128) >= GIB                                   # dq_dense.hip:394
+    cpl = 1 if c128 else 2
+    cg = 16 * cpl
+    if (d == 32 or (d == 64 and not c128)) and ncols % cg == 0 and (c128 or not bit0_used):     # dq_dense.hip:398
+        ngroups = ncols // cg
+        resident = 256 * (3 if (not c128 and d == 32) else 2)               # dq_dense.hip:402
+        per_wg = 4 if d == 32 else 2
+        blocks = min(_cdiv(ngroups, per_wg), resident)
+        per_pass = blocks * per_wg
+        return dict(route='dense56', nt=nt, ngroups=ngroups, col_group=cg, per_pass=per_pass,
+                    iterations=_cdiv(ngroups, per_pass))
+    return dict(route='staged1' if d == 32 else 'staged2', nt=nt, iterations=1)
+
+
+# ---- dq_gate.hip, copy_uncontrolled_kernel (controlled gates out of place) ----------------------------------------------
+def copy_uncontrolled(n: int, batch: int) -> dict:
+    """dq_gate.hip:190 / :237: one grid over all batch * 2^n amplitudes, at most 65536 workgroups of 256."""
+    total = batch << n
+    blocks = min(_cdiv(total, 256), 65536)
+    return dict(blocks=blocks, iterations=_cdiv(total, blocks * 256))
+
+
+# ---- dq_reduce.hip ------------------------------------------------------------------------------------------------------
+RED_BLOCKS, RED_THREADS = 1024, 256                                          # dq_reduce.hip:15-16
+
+
+def red_blocks(work: int) -> int:
+    """dq_reduce.hip:311."""
+    return max(1, min(_cdiv(work, RED_THREADS), RED_BLOCKS))
+
+
+def expect_pauli(n: int, xmask: int) -> dict:
+    """dq_reduce.hip:327-331: pairs of amplitudes for strings with an X or Y factor, single amplitudes otherwise."""
+    work = 1 << (n - 1) if xmask else 1 << n
+    nb = red_blocks(work)
+    return dict(blocks=nb, items=work, iterations=_cdiv(work, nb * RED_THREADS))
+
+
+def inner(count: int) -> dict:
+    """dq_reduce.hip:594."""
+    nb = red_blocks(count)
+    return dict(blocks=nb, iterations=_cdiv(count, nb * RED_THREADS))
+
+
+def scale_zsigns(n: int) -> dict:
+    """dq_reduce.hip:575-577 (the matrix-core kernel, n >= 8): 1024 amplitudes per workgroup and iteration."""
+    assert n >= 8
+    nb = max(1, min((1 << n) >> 10, 2048))
+    return dict(blocks=nb, chunk=1024, iterations=_cdiv(1 << n, nb * 1024))
+
+
+def expect_zmulti(n: int, c128: bool) -> dict:
+    """backend.py:361 picks the workgroups; dq_reduce.hip (expect_zmulti_mfma_kernel) reads U slices of 256 amplitudes
+    per workgroup and iteration, U = 8 (complex64) / 4 (complex128)."""
+    nb = max(1, min(2048, (1 << n) // 1024))
+    u = 4 if c128 else 8
+    return dict(blocks=nb, window=u * RED_THREADS, iterations=_cdiv(1 << n, u * nb * RED_THREADS))
+
+
+def probs(count: int) -> dict:
+    """dq_reduce.hip:610-611: one grid over all batch * 2^n amplitudes."""
+    nb = min(_cdiv(count, 256), 65536)
+    return dict(blocks=nb, iterations=_cdiv(count, nb * 256))
+
+
+def marginal(n: int, bits: list[int], batch: int, c128: bool) -> dict:
+    """dq_reduce.hip:634-691: the chunk's bits, and ``run``: how many bits of the chunk number a workgroup loops over
+    (2^run chunks each).  ``chunk_bits``: the index bits inside a chunk; ``cpos``: the chunk number's bits, low first."""
+    vec = 1 if c128 else 2
+    c = min(n, 12)
+    low = min(n, 8 - vec)
+    nw = len(bits)
+    measured = sum(1 << b for b in bits)
+    out_of = {b: nw - 1 - i for i, b in enumerate(bits)}
+    cand = [b for b in range(low, n) if not (measured >> b) & 1]
+    cand += [b for o in range(nw) for b in range(low, n) if (measured >> b) & 1 and out_of[b] == o]
+    in_chunk = set(range(low)) | set(cand[:c - low])
+    cpos, run = [], 0
+    for pas in (0, 1):
+        for b in range(n):
+            if b not in in_chunk and ((measured >> b) & 1) == pas:
+                cpos.append(b)
+                run += pas == 0
+    while run > 0 and (1 << (n - c - run)) * batch < 2048:
+        run -= 1
+    return dict(run=run, chunk_bits=sorted(in_chunk), cpos=cpos, blocks=1 << (n - c - run))
+
+
+def gate_grad(n: int, k: int, nc: int) -> dict:
+    """dq_reduce.hip:920-922: amplitude groups (2^(n-k-nc)) over at most 512 workgroups of 256."""
+    groups = 1 << (n - k - nc)
+    nb = min(_cdiv(groups, RED_THREADS), 512)
+    return dict(blocks=nb, groups=groups, iterations=_cdiv(groups, nb * RED_THREADS))
+
+
+def gate_grad_multi(n: int, c128: bool, gates) -> list[dict]:
+    """backend.py:489-517 (how the gates are packed into launches and the workgroups) and dq_reduce.hip:818-859 (the
+    tile's bits: the low L, the launch's targets at or above L, then the lowest free bits above L).  One dict per
+    launch: its gate indices, the tile bits (ascending), the tiles and how many a workgroup visits at most."""
+    tile, per_call, low = (10, 4, 3) if c128 else (11, 8, 4)
+    assert n >= tile
+    nblocks = min(1 << (n - tile), 1536)
+    out, start = [], 0
+    while start < len(gates):
+        stop, high = start, set()
+        while stop < len(gates) and stop - start < per_call:
+            t = int(gates[stop][0])
+            if t >= low and t not in high and len(high) == tile - low:
+                break
+            if t >= low:
+                high.add(t)
+            stop += 1
+        hb, p = set(high), low
+        while len(hb) < tile - low:
+            if p not in hb:
+                hb.add(p)
+            p += 1
+        ntiles = 1 << (n - tile)
+        out.append(dict(gates=list(range(start, stop)), tile_bits=sorted(set(range(low)) | hb), blocks=nblocks,
+                        ntiles=ntiles, iterations=_cdiv(ntiles, nblocks), pairs_per_thread=(1 << (tile - 1)) // RED_THREADS))
+        start = stop
+    return out
+
+
+# ---- dq_entangle.hip: rdm1_cross / apply_wire_sum ------------------------------------------------------------------------
+ENT_ROW = 12 * 8                                                             # dq_entangle.hip:27
+
+
+def ent_plan(n: int, c128: bool, cross: bool) -> list[dict]:
+    """dq_entangle.hip:376-395 (ent_plan, ent_nwg) for ONE batch: the passes, their tiles and workgroups."""
+    m = 11 if (c128 and cross) else 12
+    m0 = min(n, m)
+    gmax = m - (3 if c128 else 4)
+    passes = [dict(ntiles=1 << (n - m0))]
+    lo = m0
+    while lo < n:
+        passes.append(dict(ntiles=1 << (n - m)))
+        lo += gmax
+    return passes
+
+
+def ent_nwg(ntiles: int, batch: int) -> int:
+    return min(ntiles, max(1, _cdiv(2048, batch)))
+
+
+def entangle(n: int, batch: int, c128: bool, cross: bool) -> dict:
+    ps = ent_plan(n, c128, cross)
+    nwg = [ent_nwg(p['ntiles'], batch) for p in ps]
+    return dict(passes=len(ps), ntiles=[p['ntiles'] for p in ps], nwg=nwg,
+                iterations=[_cdiv(p['ntiles'], w) for p, w in zip(ps, nwg)])
+
+
+def rdm1_ws_bytes(n: int, batch: int, c128: bool, cross: bool) -> int:
+    """dq_entangle.hip:397-405 (ent_ws_doubles): one row of ENT_ROW doubles per workgroup and pass, plus the tile sums of
+    pass 0 when it has more than one tile."""
+    ps = ent_plan(n, c128, cross)
+    total = sum(batch * ent_nwg(p['ntiles'], batch) * ENT_ROW for p in ps)
+    if ps[0]['ntiles'] > 1:
+        total += batch * ps[0]['ntiles'] * 2
+    return 8 * total
+
+
+# ---- dq_dist.hip: permute_bits, pack, unpack_axpby -------------------------------------------------------------------------
+def permute(nl: int, src_of_dst, batch: int, c128: bool) -> dict:
+    """dq_dist.hip:198-259: the variant ('lds', 'tiled_pair', 'tiled', 'elementwise'), its workgroups, their loop
+    iterations and (tiled kernels) the streaming flag."""
+    low_in_place = all(src_of_dst[p] < 5 for p in range(min(5, nl)))
+    if nl >= 12 and not low_in_place:
+        ntile = 1 << (nl - 10)
+        nblk = min(ntile, 256 * 16)
+        return dict(variant='lds', blocks=nblk, iterations=_cdiv(ntile, nblk), nt=False)
+    if nl >= 12:
+        pair = not c128 and src_of_dst[0] == 0
+        ntile = 1 << (nl - (1 if pair else 0) - 10)
+        nblk = min(ntile, 256 * 16)
+        return dict(variant='tiled_pair' if pair else 'tiled', blocks=nblk, iterations=_cdiv(ntile, nblk),
+                    nt=(batch << nl) * _csize(c128) >= GIB)
+    nb = min(_cdiv(1 << nl, 256), 65536)
+    return dict(variant='elementwise', blocks=nb, iterations=_cdiv(1 << nl, nb * 256), nt=False)
+
+
+def pack(nl: int, mask: int) -> dict:
+    """dq_dist.hip:290-292 (pack) and :308-310 (unpack_axpby): one thread per packed amplitude, at most 65536 workgroups."""
+    count = 1 << (nl - bin(mask).count('1'))
+    nb = min(_cdiv(count, 256), 65536)
+    return dict(blocks=nb, iterations=_cdiv(count, nb * 256))

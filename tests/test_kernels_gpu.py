@@ -8,6 +8,7 @@ import random
 import pytest
 import torch
 
+import _grid_refs
 from deepquantum_amd import _lib, backend, fusion
 from oracle import statevec_oracle as oracle
 from test_fusion_cpu import random_ops, run_reference
@@ -463,8 +464,9 @@ def test_permute_bits_against_index_arithmetic(dtype, n, batch):
 def test_reductions_and_relayout_at_full_size():
     """Size-independent properties at the headline's size (n = 28, complex64, one sample = 2 GiB), where no CPU reference
     finishes in seconds: marginals are consistent with each other and with the norm whatever bits are measured, the
-    matrix-core sums over Z strings equal the one-string kernel, scale_z_signs is its own inverse for a single string,
-    and permute_bits followed by the inverse permutation is the identity bit for bit (both kernel variants)."""
+    matrix-core sums over Z strings equal the one-string kernel, scale_z_signs is its own inverse for a single string and
+    applies the sign of the index bits, and permute_bits followed by the inverse permutation is the identity bit for bit
+    (both kernel variants), its first result the index gather."""
     import random
 
     n = 28
@@ -487,9 +489,16 @@ def test_reductions_and_relayout_at_full_size():
     for k, z in enumerate(masks):
         assert abs(many[0, k].item() - backend.expect_pauli(x, 0, z)[0].item()) < 1e-10, hex(z)
     one = torch.ones(1, 1, dtype=torch.float64, device=dev())
-    y = backend.scale_z_signs(backend.scale_z_signs(x, [masks[0]], one), [masks[0]], one)
+    y1 = backend.scale_z_signs(x, [masks[0]], one)
+    y = backend.scale_z_signs(y1, [masks[0]], one)
     assert torch.equal(y, x)
-    for perm in (rng.sample(range(n), n), [1, 0] + list(range(2, n)), list(range(1, n)) + [0]):
+    # ... and the sign itself, from the index bits (an involution that applied no sign at all would pass the above)
+    step = 1 << 26
+    for lo in range(0, 1 << n, step):
+        sign = _grid_refs.z_sign(torch.arange(lo, lo + step, device=dev()), masks[0]).to(torch.float32)
+        assert torch.equal(y1[:, lo : lo + step], x[:, lo : lo + step] * sign), lo
+    del y1, y
+    for i, perm in enumerate((rng.sample(range(n), n), [1, 0] + list(range(2, n)), list(range(1, n)) + [0])):
         inv = [0] * n
         for p, sp in enumerate(perm):
             inv[sp] = p
@@ -498,6 +507,13 @@ def test_reductions_and_relayout_at_full_size():
         backend.permute_bits(x, perm, out=a)
         backend.permute_bits(a, inv, out=b)
         assert torch.equal(b, x), perm
+        if i == 0:      # ... and the first result against the index gather (a copy-only kernel passes the round trip)
+            for lo in range(0, 1 << n, step):
+                i_dst = torch.arange(lo, lo + step, device=dev())
+                src = torch.zeros_like(i_dst)
+                for p, sp in enumerate(perm):
+                    src |= ((i_dst >> p) & 1) << sp
+                assert torch.equal(a[:, lo : lo + step], x[:, src]), (perm, lo)
 
 
 @pytest.mark.parametrize('batch', [1, 5])
