@@ -1,12 +1,14 @@
 """Plain complex128 / float64 references of the kernels, built from torch tensor operations only (index arithmetic,
 gathers, reshape / permute + matmul) on whatever device the inputs live on: the large-grid tests run them on the GPU,
-test_grid_paths_cpu.py checks them against the CPU oracle at small n.  None of them calls a project kernel.
+test_grid_paths_cpu.py checks them against the CPU oracle at small n.  None of them calls a project kernel.  (f32_chain,
+the emulation of a k-ordered float32 accumulation, adds on the host with numpy: torch has no sequential float32 scan.)
 
 The reductions return the value and S, the same sum taken over the absolute values of its terms: the scale a rounding
 error of the summation is measured against."""
 
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 C128 = torch.complex128
@@ -187,3 +189,105 @@ def tile_cross(x: torch.Tensor, gy: torch.Tensor, tile_bits, tile: int, target: 
     xs = torch.stack([x[:, e0], x[:, e1]], dim=1).to(C128)
     ys = torch.stack([gy[:, e0], gy[:, e1]], dim=1).to(C128)
     return ys @ xs.mH
+
+
+# ---- the k-wire cross reduction (dq_rdm.hip) -------------------------------------------------------------------------------
+def cross_index(n: int, targets, controls, device):
+    """The amplitude index of matrix row a (MSB = targets[0]; the controls at 1 folded in) and of contraction column r:
+    bit q of r is the q-th lowest rest bit, the kernel's own order (a chunk is a run of columns, a split a run of chunks)."""
+    k = len(targets)
+    rest = [p for p in range(n) if p not in targets and p not in controls]
+    va = torch.arange(1 << k, device=device)
+    a = torch.full_like(va, sum(1 << c for c in controls))
+    for i, p in enumerate(targets):
+        a |= ((va >> (k - 1 - i)) & 1) << p
+    vr = torch.arange(1 << len(rest), device=device)
+    r = torch.zeros_like(vr)
+    for q, p in enumerate(rest):
+        r |= ((vr >> q) & 1) << p
+    return a, r
+
+
+def _cross_sample(xs, ys, idx):
+    """One sample: ``idx`` (W, D, kw) amplitude indices.  W small matmuls and one sum over W in float64, so that no GEMM adds
+    more than 2^14 terms in an order of its own."""
+    ym = ys.to(C128)[idx]
+    xm = ym if xs is ys else xs.to(C128)[idx]
+    return (ym @ xm.mH).sum(0), (ym.abs() @ xm.abs().mT).sum(0)
+
+
+def cross(x: torch.Tensor, gy: torch.Tensor, targets, controls=()):
+    """out[b, a, c] = sum over the contraction columns of gy[b, a, r] conj(x[b, c, r]) (the controls at 1) in complex128,
+    and S, the same sum over |gy| |x|: (B, D, D) each.  One sample at a time: the gather of one sample's 2^(n - nc)
+    amplitudes is the largest temporary."""
+    n = _nbits(x)
+    a, r = cross_index(n, targets, controls, x.device)
+    kw = min(r.numel(), 1 << 14)
+    idx = r.reshape(-1, 1, kw) | a.reshape(1, -1, 1)
+    same = x.data_ptr() == gy.data_ptr()
+    vals, ss = zip(*(_cross_sample(gy[b] if same else x[b], gy[b], idx) for b in range(x.shape[0])))
+    return torch.stack(vals), torch.stack(ss)
+
+
+def chunk_columns(geo: dict, split: int, chunk: int) -> tuple[int, int]:
+    """(first column, count) of chunk ``chunk`` of contraction split ``split`` under the plan ``geo``
+    (_launch_geometry.rdmk): chunks are runs of kc columns (the lowest rest bits), the split is the top of the chunk number."""
+    assert 0 <= split < geo['nsplit'] and 0 <= chunk < geo['nch']
+    return (split * geo['nch'] + chunk) * geo['kc'], min(geo['kc'], geo['terms'])
+
+
+def cross_columns(x, gy, targets, controls, sample: int, first: int, count: int):
+    """What the contraction columns [first, first + count) of one sample add to cross(): (D, D) complex128 and its S.
+    The reference less this is the negative control of a dropped chunk."""
+    a, r = cross_index(_nbits(x), targets, controls, x.device)
+    idx = (r[first : first + count].reshape(1, 1, -1) | a.reshape(1, -1, 1))
+    return _cross_sample(x[sample], gy[sample], idx)
+
+
+def internal_order(targets) -> list[int]:
+    """p[i] = the caller's matrix index of the kernel's internal row i, whose bit q is the q-th lowest target position
+    (tiles are runs of dt internal rows)."""
+    k = len(targets)
+    rank = {t: q for q, t in enumerate(sorted(targets))}
+    p = [0] * (1 << k)
+    for a in range(1 << k):
+        p[sum(((a >> (k - 1 - i)) & 1) << rank[t] for i, t in enumerate(targets))] = a
+    return p
+
+
+def to_internal(m: torch.Tensor, targets) -> torch.Tensor:
+    p = torch.tensor(internal_order(targets), device=m.device)
+    return m[..., p, :][..., :, p]
+
+
+def swap_tiles(m: torch.Tensor, dt: int, t1, t2) -> torch.Tensor:
+    """(internal order) the dt x dt blocks at tile coordinates t1 and t2 exchanged."""
+    out = m.clone()
+    (i1, j1), (i2, j2) = t1, t2
+    out[..., i1 * dt : (i1 + 1) * dt, j1 * dt : (j1 + 1) * dt] = m[..., i2 * dt : (i2 + 1) * dt, j2 * dt : (j2 + 1) * dt]
+    out[..., i2 * dt : (i2 + 1) * dt, j2 * dt : (j2 + 1) * dt] = m[..., i1 * dt : (i1 + 1) * dt, j1 * dt : (j1 + 1) * dt]
+    return out
+
+
+def conj_tile(m: torch.Tensor, dt: int, t) -> torch.Tensor:
+    """(internal order) the block at tile coordinates t conjugated: a mirrored tile that lost its sign."""
+    out = m.clone()
+    i, j = t
+    out[..., i * dt : (i + 1) * dt, j * dt : (j + 1) * dt] = m[..., i * dt : (i + 1) * dt, j * dt : (j + 1) * dt].conj()
+    return out
+
+
+def f32_chain(ye: torch.Tensor, xe: torch.Tensor, window: int | None) -> torch.Tensor:
+    """sum_r ye[e, r] conj(xe[e, r]) for complex64 rows (E, K) as a k-ordered float32 chain, the accumulation DESIGN 4.6
+    documents for the complex64 kernel: float32 products (re: yr xr, yi xi; im: yi xr, -yr xi, index by index), added one
+    after the other in float32 over ``window`` contraction indices, the windows added in float64.  ``window`` None: one
+    float32 chain over all K (a flush that never happens).  (E,) complex128."""
+    assert ye.dtype == xe.dtype == torch.complex64 and ye.shape == xe.shape
+    yr, yi, xr, xi = ye.real, ye.imag, xe.real, xe.imag
+    terms = torch.stack([torch.stack([yr * xr, yi * xi], -1), torch.stack([yi * xr, -(yr * xi)], -1)])    # (2, E, K, 2) f32
+    e, k = ye.shape
+    w = 2 * (window or k)
+    t = terms.reshape(2, e, (2 * k) // w, w).cpu().numpy()
+    acc = np.add.accumulate(t, axis=-1, dtype=np.float32)[..., -1]          # (sequential; np.sum would add in pairs)
+    tot = torch.from_numpy(acc.astype(np.float64).sum(-1))
+    return torch.complex(tot[0], tot[1]).to(ye.device)

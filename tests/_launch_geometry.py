@@ -190,6 +190,37 @@ def rdm1_ws_bytes(n: int, batch: int, c128: bool, cross: bool) -> int:
     return 8 * total
 
 
+# ---- dq_rdm.hip: rdmk_cross (k = 3..10 on the matrix cores) ----------------------------------------------------------------
+RDM_SUB, RDM_FLUSH, RDM_TARGET_WG, RDM_MIN_CHUNKS = 10, 256, 2048, 4         # dq_rdm.hip:36-40
+
+
+def rdmk(n: int, k: int, nc: int, batch: int, c128: bool, herm: bool) -> dict:
+    """dq_rdm.hip, rdm_tile / rdm_plan / rdmk_cross_impl for ONE launch (batch <= 65535).  ``tile``: TT, ``dt`` its valid
+    rows, ``nt`` tiles per side, ``ntl`` tile slots; ``kc`` contraction indices per chunk (the lowest ``chunk_bits`` rest
+    bits), ``chunks`` in all, ``nsplit`` x ``nch`` of them per workgroup (splits = the top bits of the chunk number).
+    ``flushes``: f32 -> double flushes inside the chunk loop (complex64 only; one more follows the loop), ``flush_then_more``:
+    one of them is followed by further chunks.  ``pad_rows``: 2^k < TT; ``pad_chunk``: fewer rest bits than chunk bits."""
+    tt = 64 if k >= 6 else (32 if k == 5 else 16)
+    tbits = tt.bit_length() - 1
+    cbits = RDM_SUB - tbits
+    d = 1 << k
+    dt = min(d, tt)
+    nt = d // dt
+    ntl = nt * (nt + 1) // 2 if herm else nt * nt
+    r = n - k - nc
+    total = 1 << (r - cbits) if r > cbits else 1
+    per_split = batch * ntl * dt * dt * 2
+    budget = (batch * d * d * 16 + (batch << n) * _csize(c128) // 100) // 8
+    ns = 1
+    while ns * 2 * RDM_MIN_CHUNKS <= total and per_split * ns * 2 <= budget and batch * ntl * ns < RDM_TARGET_WG:
+        ns *= 2
+    nch = total // ns
+    return dict(tile=tt, dt=dt, nt=nt, ntl=ntl, kc=1 << cbits, chunk_bits=cbits, chunks=total, nsplit=ns, nch=nch,
+                terms=1 << r, workgroups=batch * ntl * ns,
+                flushes=0 if c128 else nch // RDM_FLUSH, flush_then_more=not c128 and nch > RDM_FLUSH,
+                pad_rows=d < tt, pad_chunk=r < cbits, ws_bytes=8 * per_split * ns)
+
+
 # ---- dq_dist.hip: permute_bits, pack, unpack_axpby -------------------------------------------------------------------------
 def permute(nl: int, src_of_dst, batch: int, c128: bool) -> dict:
     """dq_dist.hip:198-259: the variant ('lds', 'tiled_pair', 'tiled', 'elementwise'), its workgroups, their loop

@@ -1,7 +1,8 @@
 """k-wire reduced density matrices and entanglement entropy on the MI355X (``dq_rdmk_cross_*``): the kernel against an
-explicit complex128 einsum over wire sets, controls and both routes, exact Hermiticity and reproducibility, the
-reference's fixtures, known answers at 26 qubits, derivatives, the routing of ``backend.gate_grad``, memory and graph
-capture."""
+explicit complex128 einsum over wire sets, controls and both routes (also element by element against tau * S, the
+criterion of test_rdmk_paths_gpu.py, which takes the kernel path by path), exact Hermiticity and reproducibility, the
+reference's fixtures, known answers at 26 qubits, derivatives, the routing of ``backend.gate_grad`` and its GEMM
+fallback above ten wires, memory and graph capture."""
 
 import math
 import os
@@ -12,7 +13,9 @@ import numpy as np
 import pytest
 import torch
 
+import _grid_refs as R
 import deepquantum_amd as dq
+from _rdmk_cases import TAU_C64, TAU_SUM
 from deepquantum_amd import backend, ops, qmath
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -87,6 +90,16 @@ def _check(got, ref, dtype, x, gy, what):
     assert err <= TOL[dtype] * max(scale, 1e-30), f'{what}: error {err:.3e} (scale {scale:.3e})'
 
 
+def _check_elementwise(got, x, gy, tg, ctl, dtype, what):
+    """|got - ref| <= tau * S element by element, S the same sum over |gy| |x| (the criterion of test_rdmk_paths_gpu.py,
+    whose _rdmk_cases.py derives the complex64 figure)."""
+    ref, s = R.cross(x, gy, tg, ctl)
+    tau = TAU_C64 if dtype == torch.complex64 else TAU_SUM
+    err = (got - ref).abs()
+    assert (err <= tau * s).all(), f'{what}: max |got - ref| / S = {float((err / s).max()):.3e} (tau {tau:.0e})'
+    return float((err / s).max())
+
+
 @pytest.mark.parametrize('dtype', [torch.complex64, torch.complex128])
 def test_kernel_against_explicit_einsum(dtype):
     for i, (n, tg, ctl, b, same) in enumerate(_cases()):
@@ -94,7 +107,9 @@ def test_kernel_against_explicit_einsum(dtype):
         gy = x if same else rand_state(b, n, dtype, seed=1000 + i)
         got = backend.rdmk_cross(x, gy, tg, ctl)
         assert got.dtype == torch.complex128 and got.shape == (b, 1 << len(tg), 1 << len(tg))
-        _check(got, explicit_cross(x, gy, tg, ctl), dtype, x, gy, f'n={n} targets={tg} controls={ctl} b={b} same={same}')
+        what = f'n={n} targets={tg} controls={ctl} b={b} same={same}'
+        _check(got, explicit_cross(x, gy, tg, ctl), dtype, x, gy, what)
+        _check_elementwise(got, x, gy, tg, ctl, dtype, what)
 
 
 def test_hermitian_exact_and_reproducible():
@@ -229,6 +244,22 @@ def test_routing_never_needs_the_gemm_fallback(monkeypatch):
         wires = [n - 1 - t for t in tg]
         rho = qmath.reduced_density_matrix(x, n, wires)
         _check(rho.to(torch.complex128), explicit_cross(x, x, tg), torch.complex64, x, x, f'rdm k={k}')
+
+
+@pytest.mark.parametrize('dtype', [torch.complex64, torch.complex128])
+def test_gemm_fallback_above_ten_wires(dtype, monkeypatch):
+    """k = 11 with a control at n = 14: ``backend.gate_grad`` hands it to ``_gate_grad_gemm`` (asserted), which is held to
+    the reference and the criteria of the matrix-core route.  K = 4: a complex64 GEMM of four terms rounds at a few 2^-24
+    of S, inside TAU_C64."""
+    n, tg, ctl = 14, [13, 2, 7, 0, 11, 4, 9, 1, 12, 6, 3], [8]
+    x, gy = rand_state(2, n, dtype, seed=31), rand_state(2, n, dtype, seed=32)
+    calls, gemm = [], backend._gate_grad_gemm
+    monkeypatch.setattr(backend, '_gate_grad_gemm', lambda *a: calls.append(1) or gemm(*a))
+    got = backend.gate_grad(x, gy, tg, ctl)
+    assert calls == [1] and got.dtype == torch.complex128 and got.shape == (2, 2048, 2048)
+    _check(got, explicit_cross(x, gy, tg, ctl), dtype, x, gy, f'gemm fallback {dtype}')
+    worst = _check_elementwise(got, x, gy, tg, ctl, dtype, f'gemm fallback {dtype}')
+    print(f'gemm fallback, k = 11, {dtype}: worst |got - ref| / S = {worst:.3e}')
 
 
 def test_workspace_budget_at_26_qubits():
