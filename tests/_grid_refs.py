@@ -291,3 +291,62 @@ def f32_chain(ye: torch.Tensor, xe: torch.Tensor, window: int | None) -> torch.T
     acc = np.add.accumulate(t, axis=-1, dtype=np.float32)[..., -1]          # (sequential; np.sum would add in pairs)
     tot = torch.from_numpy(acc.astype(np.float64).sum(-1))
     return torch.complex(tot[0], tot[1]).to(ye.device)
+
+
+# ---- the reductions of a wave-tile pass (include/dq_hip.h, DQ_FG_GRAD / DQ_FG_EXPZ) ----------------------------------------
+def grad_sums(x: torch.Tensor, t: int, s: int, controls=()):
+    """G[b, a, c] = sum lambda[t = a] conj(psi[t = c]) over the amplitudes whose ``controls`` are all 1 (index bit s: 0 = psi,
+    1 = lambda): (B, 2, 2) complex128, and S, the same sums over |lambda| |psi| (float64)."""
+    v = gate_matrix_view(x.to(C128), [t, s], controls)                     # (B, 2 [t], 2 [s], rest ..)
+    lam, psi = v[:, :, 1].flatten(2), v[:, :, 0].flatten(2)
+    g = torch.empty(x.shape[0], 2, 2, dtype=C128, device=x.device)
+    sa = torch.empty(x.shape[0], 2, 2, dtype=torch.float64, device=x.device)
+    for a in (0, 1):
+        for c in (0, 1):
+            g[:, a, c] = (lam[:, a] * psi[:, c].conj()).sum(-1)
+            sa[:, a, c] = (lam[:, a].abs() * psi[:, c].abs()).sum(-1)
+    return g, sa
+
+
+def grad_components(g: torch.Tensor, sa: torch.Tensor, variant: int):
+    """The eight components a DQ_FG_GRAD record of this ``loc`` variant adds (include/dq_hip.h:110-121) and the sums over
+    absolute values each was formed from: (B, 8) float64 each, NaN where the variant leaves the component untouched."""
+    full = torch.view_as_real(g.reshape(-1, 4)).reshape(-1, 8)
+    fabs = sa.reshape(-1, 4).repeat_interleave(2, dim=1)
+    out, oabs = torch.full_like(full, float('nan')), torch.full_like(fabs, float('nan'))
+    if variant == 0:
+        out, oabs = full.clone(), fabs.clone()
+    elif variant == 1:
+        out[:, 0::2], oabs[:, 0::2] = full[:, 0::2], fabs[:, 0::2]
+    elif variant == 2:
+        out[:, 0], oabs[:, 0] = full[:, 0] + full[:, 6], fabs[:, 0] + fabs[:, 6]
+        out[:, 3], oabs[:, 3] = full[:, 3] + full[:, 5], fabs[:, 3] + fabs[:, 5]
+    elif variant == 3:
+        out[:, [0, 1, 6, 7]], oabs[:, [0, 1, 6, 7]] = full[:, [0, 1, 6, 7]], fabs[:, [0, 1, 6, 7]]
+    else:
+        out[:, 3], oabs[:, 3] = full[:, 3] + full[:, 5], fabs[:, 3] + fabs[:, 5]
+    return out, oabs
+
+
+def tile_indices(n: int, blk_pos, tile: int, device, held_zero=()) -> tuple[torch.Tensor, list[int]]:
+    """The amplitude indices of tile number ``tile`` of a wave-tile pass -- bit j of the number at index bit blk_pos[j], the
+    bits ``held_zero`` at 0, every other index bit free -- in ascending order, and the free bits (ascending: local bit q of
+    the gathered tile is free[q])."""
+    fixed = set(blk_pos) | set(held_zero)
+    free = [p for p in range(n) if p not in fixed]
+    a = torch.arange(1 << len(free), device=device)
+    idx = torch.full_like(a, sum(((tile >> j) & 1) << p for j, p in enumerate(blk_pos)))
+    for q, p in enumerate(free):
+        idx |= ((a >> q) & 1) << p
+    return idx, free
+
+
+def tile_grad_sums(x, idx, free, t, s, controls=()):
+    """What the amplitudes ``idx`` (tile_indices) add to grad_sums(x, t, s, controls): t and s are free bits of the tile; a
+    control outside the tile is the same for all of them."""
+    inside = [c for c in controls if c in free]
+    for c in controls:
+        if c not in free and not (int(idx[0]) >> c) & 1:
+            z = torch.zeros(x.shape[0], 2, 2, dtype=C128, device=x.device)
+            return z, z.real.clone()
+    return grad_sums(x[:, idx], free.index(t), free.index(s), [free.index(c) for c in inside])

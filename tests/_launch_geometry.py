@@ -245,3 +245,82 @@ def pack(nl: int, mask: int) -> dict:
     count = 1 << (nl - bin(mask).count('1'))
     nb = min(_cdiv(count, 256), 65536)
     return dict(blocks=nb, iterations=_cdiv(count, nb * 256))
+
+
+# ---- dq_wave.hip: wave_launch and the prologue of wave_pass_kernel ---------------------------------------------------------
+WAVE_TPW_FLOOR = 2048                                                        # dq_wave.hip:649 / :652
+
+
+def wave_pass(n: int, batch: int, c128: bool, *, grad: bool = False, only_expz: bool = False, ext: bool = False,
+              shared_input: bool = False, zero_bits_outside: int = 0, slice_bits: int = 0, env: dict | None = None) -> dict:
+    """dq_wave.hip, wave_launch (:619-687) and the kernel's prologue (:137-175), for the default environment (no DQ_WAVE_*
+    variable set) or, with ``env``, under the measurement knobs it names (DQ_WAVE_NT, _XCD, _TPW, _GRAD_TPW, _EXPZ_TPW,
+    _XCD_TPW as strings, parsed like atoi; DQ_WAVE_TILE_ORDER changes which index bit a tile-number bit stands for, not the
+    launch).  ``grad``: a reducing launch (``grads`` given: the GRAD instantiation); ``only_expz``: it holds no
+    DQ_FG_GRAD record; ``ext``: its records lie in device memory; ``shared_input``: ONE input state for the batch
+    (in_bstride = 0); ``zero_bits_outside`` / ``slice_bits``: known-zero / held index bits outside the tile.
+
+    tiles, tpw (tiles a wave walks), grid_x, xcd (the value of bits 18..22 of the flag word: 31 or 0), regroup (the
+    shared-input renumbering of :141-146 runs), nt_loads / nt_stores (what the body is told, :205), idle_waves (waves of the
+    last workgroup of a sample that find no first tile, :173) and second_stride (what :174 adds to a wave's tile number
+    for its second and every later walk; None at tpw = 1: the sum is formed but the walk it leads to is past the tile
+    count).  xcd under DQ_WAVE_XCD = C > 1: log2(C) + 1 where grid.x % (8 C) == 0."""
+    env = env or {}
+    knob = lambda name, default: int(env.get('DQ_WAVE_' + name, default))                              # noqa: E731
+    m = 11 if c128 else 12                                                    # :46 / :61 (W::M)
+    tiles = 1 << (n - m - zero_bits_outside - slice_bits)                     # :382-397 (nb), :637
+    tpw = 1
+    if grad:                                                                  # :639
+        cap = knob('EXPZ_TPW', 2) if only_expz else knob('GRAD_TPW', 2)       # :642 / :644 / :648 (gcap, zcap: 2 by default)
+        assert not (ext and only_expz)                                        # :645 (records in device memory: never only_expz)
+        while tpw < cap and (tiles * batch) // (8 * tpw) >= WAVE_TPW_FLOOR:   # :649
+            tpw *= 2
+    else:
+        while tpw < knob('TPW', 1) and (tiles * batch) // (8 * tpw) >= WAVE_TPW_FLOOR:      # :651-652 (idle by default)
+            tpw *= 2
+    grid_x = _cdiv(tiles, 4 * tpw)                                            # :654
+    nt_bits = knob('NT', 3 if (batch << n) * _csize(c128) >= GIB else 0) & 3   # :665-667 (bit 0 loads, bit 1 stores)
+    xcd_env, xcd = knob('XCD', 1), 0                                          # :668, :672
+    if xcd_env and not shared_input and (tpw == 1 or knob('XCD_TPW', 1)):     # :677
+        if xcd_env == 1 and grid_x % 8 == 0:                                  # :678
+            xcd = 31
+        elif xcd_env > 1 and xcd_env & (xcd_env - 1) == 0 and grid_x % (8 * xcd_env) == 0:     # :679-680
+            xcd = xcd_env.bit_length()
+    regroup = shared_input and grid_x % 8 == 0                                # :141
+    per_wg = 4 * tpw
+    walked = grid_x * 4                                                       # first-walk tile numbers 0 .. walked - 1 (:159)
+    return dict(tiles=tiles, tpw=tpw, grid_x=grid_x, xcd=xcd, regroup=regroup,
+                nt_loads=bool(nt_bits & 1) and not shared_input, nt_stores=bool(nt_bits & 2),      # :205 (a shared input: no streaming loads)
+                idle_waves=max(0, walked - tiles),                            # :173 at the first tile
+                second_stride=_cdiv(tiles, per_wg) * 4 if tpw >= 2 else None)  # :174
+
+
+def wave_grid_visits(geo: dict, batch: int) -> list[tuple[int, int]]:
+    """The kernel's index arithmetic (:138-175) re-done for every workgroup and wave of the grid ``geo`` describes: the
+    (sample, tile) pairs it visits, in any order, duplicates kept."""
+    gx, tiles, tpw = geo['grid_x'], geo['tiles'], geo['tpw']
+    lper = 2 + (tpw.bit_length() - 1)                                         # :172
+    stride = ((tiles + (1 << lper) - 1) >> lper) * 4                          # :174
+    step = geo['second_stride'] if geo['second_stride'] is not None else stride     # (the mirror's own line is what is walked)
+    assert step > 0
+    out = []
+    for by in range(batch):
+        for bx in range(gx):
+            grp, sample = bx, by                                              # :138
+            if geo['regroup']:                                                # :141-146
+                lin = by * gx + bx
+                group, r = divmod(lin, 8 * batch)
+                sample, grp = r >> 3, group * 8 + (r & 7)
+            xv = geo['xcd']
+            if xv:                                                            # :151-157
+                q, j = bx >> 3, bx & 7
+                if xv == 31:
+                    grp = j * (gx >> 3) + q
+                else:
+                    grp = ((q >> (xv - 1)) << (xv + 2)) + (j << (xv - 1)) + (q & ((1 << (xv - 1)) - 1))
+            for wave in range(4):
+                t = grp * 4 + wave                                            # :159
+                while t < tiles:                                              # :173
+                    out.append((sample, t))
+                    t += step                                                 # :174
+    return out

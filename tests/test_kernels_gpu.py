@@ -155,10 +155,12 @@ def test_fused_batched_matrices_and_out_of_place(is128):
     assert torch.equal(xd.cpu(), x)  # input untouched
 
 
-@pytest.mark.parametrize('is128,n,b', [(False, 15, 3), (False, 16, 16), (True, 14, 5), (False, 13, 4), (True, 11, 2)])
+@pytest.mark.parametrize('is128,n,b', [(False, 15, 3), (False, 16, 16), (True, 14, 5), (False, 13, 4), (True, 11, 2),
+                                       (False, 17, 3), (True, 16, 5)])
 def test_fused_pass_with_one_shared_input_state(is128, n, b):
     """dq_apply_fused_bcast_*: every sample reads the same input state (the first pass of a batched circuit),
-    with its own matrices; workgroups of one tile are remapped to neighbours on one XCD."""
+    with its own matrices; workgroups of one tile are remapped to neighbours on one XCD (from eight workgroups per sample
+    on: the last two shapes; test_pass_paths_cpu.py pins which shapes get there)."""
     dtype = torch.complex128 if is128 else torch.complex64
     ops, mats0 = random_ops(n, 30, 21, kinds=('gen', 'x', 'diag', 'gen2'))
     per_sample = []
