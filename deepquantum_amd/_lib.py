@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DQHIP_LIBRARY') or os.path.join(_HERE, 'libdqhip.so')
 
 DQ_OK = 0
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 # enum DqFusedKind / DqBitLoc (include/dq_hip.h)
 FG_GEN1, FG_X1, FG_DIAG1, FG_GEN2, FG_DIAG2, FG_RESERVED5, FG_GRAD, FG_EXPZ = range(8)
@@ -131,6 +131,8 @@ _SIGNATURES = {
     'dq_apply_wire_sum_{s}': (_i, [_vp, _vp, _vp, _i, _i64, _vp]),
     'dq_rdmk_ws_bytes': (_i64, [_i, _i, _i, _i64, _i, _i]),
     'dq_rdmk_cross_{s}': (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),
+    'dq_sample_ws_bytes': (_i64, [_i, _i64, _i]),
+    'dq_sample_{s}': (_i, [_vp, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

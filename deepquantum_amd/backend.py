@@ -724,3 +724,85 @@ def apply_wire_sum(state: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
         rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(m[lo:hi]), n, hi - lo, _stream(state))
         _lib.check(rc, 'dq_apply_wire_sum')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+_sample_ws_cache: dict[tuple, torch.Tensor] = {}
+
+
+def _sample_workspace(state: torch.Tensor, batch: int, n: int, nbytes: int) -> torch.Tensor:
+    # A tree is cached per (device, batch, n, stream), like `_workspace`: two streams must not share it.  Unlike that
+    # scratch a tree is 1.6 % of a complex64 state (34 MiB at n = 28, 545 MiB at batch 16), so a device and stream keep
+    # ONE: a call with another (batch, n) drops the tree before it.  The allocator hands the block back to the stream
+    # it was allocated on, and a captured graph holds the tree it used through `pin_if_capturing`.
+    dev_stream = (state.device, torch.cuda.current_stream(state.device).cuda_stream)
+    key = (dev_stream[0], batch, n, dev_stream[1])
+    ws = _sample_ws_cache.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():      # (from the graph's pool: it lives with the graph, uncached)
+            return torch.empty(nbytes // 8, dtype=torch.float64, device=state.device)
+        for k in [k for k in _sample_ws_cache if (k[0], k[3]) == dev_stream]:
+            del _sample_ws_cache[k]
+        ws = own(torch.empty(nbytes // 8, dtype=torch.float64, device=state.device))
+        _sample_ws_cache[key] = ws
+    return ws
+
+
+def clear_sample_workspace() -> None:
+    """Drop the cached trees of ``sample_indices`` (one per device and stream, 2^n / 63 doubles per sample): the next
+    call builds its own.  For a state that only just fits in memory next to what else is to be allocated."""
+    _sample_ws_cache.clear()
+
+
+def sample_indices(state: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """Inverse-CDF samples of |psi|^2 for explicit uniforms: ``out[b, s]`` = the smallest i with
+    ``C_b(i) > u[b, s] * T_b``, C_b the running sum of ``|state[b]|^2`` in double and T_b its total (the state need not
+    be normalised).  ``state``: (B, 2**n) contiguous complex; ``u``: float64 (B, shots) in [0, 1) on the same device.
+    Returns int64 (B, shots) flat indices; an index of probability zero is never returned.  No 2**n-element temporary
+    (a tree of partial sums, 1.6 % of a complex64 state), no host synchronisation (``dq_sample_*``).
+
+    The kernel reads the state with 16-byte loads: a state whose first amplitude is not 16-byte aligned (a complex64
+    view at an odd storage offset) is refused with the kernel's argument error, not copied -- ``clone()`` it first.
+    The tree stays cached for the next call with the same device, batch, n and stream, one per device and stream;
+    ``clear_sample_workspace()`` drops it."""
+    n = _nqubit(state)
+    if not state.is_contiguous():
+        raise ValueError('state must be contiguous')
+    if u.ndim != 2 or u.shape[0] != state.shape[0] or u.shape[1] < 1 or u.dtype != torch.float64 or u.device != state.device:
+        raise ValueError(f'u must be float64 ({state.shape[0]}, shots >= 1) on the device of the state, got '
+                         f'{u.dtype} {tuple(u.shape)} on {u.device}')
+    if not _use_hip(state):
+        _suffix(state)
+        with torch.no_grad():
+            return _sample_indices_double(state, u)
+    u = u.contiguous()
+    out = torch.empty(u.shape, dtype=torch.int64, device=state.device)
+    lib = _lib.load()
+    fn = getattr(lib, f'dq_sample_{_suffix(state)}')
+    max_b = 65535                                            # (dq_sample_*'s limit on the batch)
+    for lo in range(0, state.shape[0], max_b):
+        hi = min(state.shape[0], lo + max_b)
+        nbytes = lib.dq_sample_ws_bytes(n, hi - lo, int(state.dtype == torch.complex128))
+        if nbytes < 0:
+            raise ValueError(f'sample_indices: bad shape (n={n}, batch={hi - lo})')
+        ws = _sample_workspace(state, hi - lo, n, nbytes)
+        pin_if_capturing(ws)
+        rc = fn(_ptr(state[lo:hi]), n, hi - lo, _ptr(u[lo:hi]), u.shape[1], _ptr(out[lo:hi]), _ptr(ws), nbytes,
+                _stream(state))
+        _lib.check(rc, 'dq_sample')
+    return out
+
+
+def _sample_indices_double(probs_or_state: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """The contract of ``sample_indices`` in torch, for the CPU test double and for the (small) diagonal of a density
+    matrix: float64 ``cumsum`` + ``searchsorted(right=True)``, then the clamp onto the last entry of non-zero
+    probability.  A real input is taken as the probabilities, a complex one as amplitudes."""
+    if probs_or_state.is_complex():
+        p = probs_or_state.real.to(torch.float64) ** 2 + probs_or_state.imag.to(torch.float64) ** 2
+    else:
+        p = probs_or_state.to(torch.float64)
+    c = torch.cumsum(p, dim=-1)
+    idx = torch.searchsorted(c, (u * c[:, -1:]).contiguous(), right=True)
+    # the last index of non-zero probability == the number of entries below the total: nothing beyond it is returned
+    last = (c < c[:, -1:]).sum(-1, keepdim=True)
+    return torch.minimum(idx, last)

@@ -327,7 +327,7 @@ class QubitCircuit(Operation):
 
     # ---- read-out -----------------------------------------------------------------------------------
     def measure(self, shots: int | None = None, with_prob: bool = False, wires: int | list[int] | None = None,
-                block_size: int = 2**24) -> dict | list[dict] | None:
+                block_size: int = 2**24, sampler: str = 'multinomial') -> dict | list[dict] | None:
         if shots is None:
             shots = self.shots
         else:
@@ -338,7 +338,24 @@ class QubitCircuit(Operation):
         if self.state is None:
             return None
         return qmath.measure(self.state, shots=shots, with_prob=with_prob, wires=self.wires_measure,
-                             den_mat=self.den_mat, block_size=block_size)
+                             den_mat=self.den_mat, block_size=block_size, sampler=sampler)
+
+    def sample(self, shots: int | None = None, wires: int | list[int] | None = None,
+               generator: torch.Generator | None = None) -> torch.Tensor | None:
+        """Raw measurement outcomes of the final state of the last forward as a device tensor: int64 (shots,), or
+        (B, shots) for a batch -- see :func:`qmath.sample` for the outcome convention and ``generator``.  ``shots`` is
+        kept as in :meth:`measure`."""
+        if shots is None:
+            shots = self.shots
+        else:
+            self.shots = shots
+        if wires is None:
+            wires = list(range(self.nqubit))
+        self.wires_measure = self._convert_indices(wires)
+        if self.state is None:
+            return None
+        return qmath.sample(self.state, self.nqubit, shots=shots, wires=self.wires_measure, generator=generator,
+                            den_mat=self.den_mat)
 
     def reduced_density_matrix(self, wires: int | list[int]) -> torch.Tensor:
         """Reduced density matrix of ``wires`` (in that matrix order, ``wires[0]`` the most significant bit) of the final

@@ -178,9 +178,16 @@ def measure(
     wires: int | list[int] | None = None,
     den_mat: bool = False,
     block_size: int = 2**24,
+    sampler: str = 'multinomial',
 ) -> dict | list[dict]:
     """Sample bit strings from |psi|^2 (reference: qmath.py:568-638).  Probabilities and marginals are
-    computed by the HIP reduction kernels; sampling stays ``torch.multinomial`` on the device."""
+    computed by the HIP reduction kernels; sampling stays ``torch.multinomial`` on the device.
+    ``sampler='inverse_cdf'`` draws with :func:`sample` instead (no |psi|^2 temporary; ``block_size`` is unused) and
+    returns the same dict format."""
+    if sampler == 'inverse_cdf':
+        return _measure_inverse_cdf(state, shots, with_prob, wires, den_mat)
+    if sampler != 'multinomial':
+        raise ValueError(f"measure: sampler must be 'multinomial' or 'inverse_cdf', got {sampler!r}")
     if den_mat:
         assert is_density_matrix(state), 'Please input density matrices'
         state = state.diagonal(dim1=-2, dim2=-1)
@@ -218,6 +225,115 @@ def measure(
                 res[k] = res[k], probs[int(k, 2)]
         results.append(res)
     return results[0] if batch == 1 else results
+
+
+def _density_diagonal(state: torch.Tensor, nqubit: int, what: str) -> tuple[torch.Tensor, bool]:
+    """(2**n, 2**n) or (B, 2**n, 2**n) density matrices -> their real diagonals (B, 2**n) and whether it was a single one."""
+    dim = 1 << nqubit
+    if not isinstance(state, torch.Tensor) or state.ndim not in (2, 3) or tuple(state.shape[-2:]) != (dim, dim):
+        raise ValueError(f'{what}: a density matrix of {nqubit} qubits must have the shape (2**n, 2**n) or (B, 2**n, 2**n); '
+                         f'got {tuple(getattr(state, "shape", ()))}')
+    diag = state.diagonal(dim1=-2, dim2=-1)
+    diag = diag.real if diag.is_complex() else diag
+    return diag.reshape(-1, dim), state.ndim == 2
+
+
+def sample(
+    state: torch.Tensor,
+    nqubit: int,
+    shots: int = 1024,
+    wires: int | list[int] | None = None,
+    generator: torch.Generator | None = None,
+    den_mat: bool = False,
+) -> torch.Tensor:
+    """Raw measurement outcomes as a device tensor: int64 (shots,) for a single state, (B, shots) for a batch.
+
+    ``state`` is (2**n,), (2**n, 1), (B, 2**n), (B, 2**n, 1) or (B, 2, ..., 2); with ``den_mat=True`` (2**n, 2**n) or
+    (B, 2**n, 2**n).  It need not be normalised.  An outcome is the integer whose binary string over the measured wires
+    in ascending wire order is the key :func:`measure` gives: ``bin(v)[2:].zfill(len(wires))``; ``wires=None`` measures
+    all of them.  The uniforms are ``torch.rand(B, shots, dtype=float64, device=state.device, generator=generator)``,
+    so the same generator state gives the same samples; outcome s of sample b is the smallest index i whose cumulative
+    probability exceeds ``u[b, s]`` (``backend.sample_indices``: a tree of partial sums, 1.6 % of a complex64 state, no
+    |psi|^2 temporary and no host synchronisation).  A subset of wires keeps those bits of the full index -- an exact
+    sample of the marginal without forming it.  Runs under ``no_grad``."""
+    from .state import DistributedQubitState
+
+    if isinstance(state, DistributedQubitState):
+        raise NotImplementedError('sample: sharded states are not supported (measure_dist is the sharded route)')
+    n = int(nqubit)
+    shots = int(shots)
+    if shots < 1:
+        raise ValueError(f'sample: shots must be >= 1, got {shots}')
+    with torch.no_grad():
+        if den_mat:
+            if n < 1 or n > 15:
+                raise ValueError(f'sample: nqubit={nqubit} out of range for a density matrix (1..15)')
+            flat, single = _density_diagonal(state, n, 'sample')
+        else:
+            flat, single = _state_batch(state, n, 'sample')
+            if not flat.is_contiguous():
+                flat = flat.contiguous()
+        wires = sorted(_wire_list(wires, n, 'sample')) if wires is not None else None
+        u = torch.rand(flat.shape[0], shots, dtype=torch.float64, device=flat.device, generator=generator)
+        if den_mat:       # the diagonal already holds the probabilities: the contract in torch, no kernel
+            idx = backend._sample_indices_double(flat.clamp_min(0), u)
+        else:
+            idx = backend.sample_indices(flat, u)
+        if wires is not None and len(wires) != n:
+            k = len(wires)
+            val = torch.zeros_like(idx)
+            for j, w in enumerate(wires):
+                val |= ((idx >> (n - 1 - w)) & 1) << (k - 1 - j)
+            idx = val
+    return idx[0] if single else idx
+
+
+def _measure_inverse_cdf(state, shots, with_prob, wires, den_mat):
+    """``measure`` drawing with :func:`sample`: the dict(s) of ``measure``, the outcomes counted on the device."""
+    if den_mat:
+        assert is_density_matrix(state), 'Please input density matrices'
+        dim = state.shape[-1]
+        single = state.ndim == 2
+    else:
+        single = state.ndim == 1 or (state.ndim == 2 and state.shape[-1] == 1)
+        dim = state.numel() if single else state[0].numel()
+    assert is_power_of_two(dim), 'The length of the quantum state is not in the form of 2^n'
+    n = dim.bit_length() - 1
+    if isinstance(wires, int):
+        wires = [wires]
+    wires = sorted(wires) if wires else None
+    part = wires is not None and len(wires) != n
+    nbits = len(wires) if wires else n
+    outcomes = sample(state, n, shots=shots, wires=wires, den_mat=den_mat)
+    outcomes = outcomes.reshape(1, -1) if single else outcomes
+    probs = None
+    if with_prob:
+        with torch.no_grad():
+            if den_mat:
+                probs = torch.abs(_density_diagonal(state, n, 'measure')[0])
+                if part:
+                    axes = [w + 1 for w in wires]
+                    pm = [0] + axes + [i for i in range(1, n + 1) if i not in axes]
+                    probs = probs.reshape([-1] + [2] * n).permute(pm).reshape(probs.shape[0], 2 ** len(wires), -1).sum(-1)
+            else:
+                flat = _state_batch(state, n, 'measure')[0]
+                flat = flat if flat.is_contiguous() else flat.contiguous()
+                if part:       # one read of the state whatever the number of wires (dq_marginal_*)
+                    probs = backend.marginal(flat, [n - 1 - w for w in wires]).to(flat.real.dtype)
+    results = []
+    for i in range(outcomes.shape[0]):
+        keys, counts = torch.unique(outcomes[i], return_counts=True)
+        res = {bin(k)[2:].zfill(nbits): v for k, v in zip(keys.tolist(), counts.tolist(), strict=True)}
+        if with_prob:
+            if probs is not None:
+                pk = probs[i][keys]
+            else:              # all wires of a state vector: |psi[idx]|^2 of the distinct outcomes only
+                a = flat[i][keys]
+                pk = a.real * a.real + a.imag * a.imag
+            for j, k in enumerate(res):
+                res[k] = res[k], pk[j]
+        results.append(res)
+    return results[0] if len(results) == 1 else results      # (a batch of one gives a dict, as on the default route)
 
 
 def expectation(state: torch.Tensor, observable: 'Observable', den_mat: bool = False, chi: int | None = None) -> torch.Tensor:

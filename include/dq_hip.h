@@ -45,7 +45,7 @@ typedef enum {
     DQ_ERR_UNSUPPORTED = -3  /* valid request outside what this build implements */
 } DqStatus;
 
-#define DQ_ABI_VERSION 27
+#define DQ_ABI_VERSION 28
 
 int dq_abi_version(void);
 /* Thread-local, never NULL. */
@@ -501,6 +501,25 @@ int dq_rdmk_cross_c64(const void* x, const void* gy, int n, const int* targets, 
                       int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
 int dq_rdmk_cross_c128(const void* x, const void* gy, int n, const int* targets, int k, const int* controls, int nc,
                        int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 7. Shot sampling by inverse CDF (ABI 28; csrc/dq_sample.hip).  Replaces the |psi|^2 temporary and the
+ *    torch.multinomial calls of qmath.measure / block_sample (qmath.py:543-638) where raw outcomes are wanted.
+ *        p_j = |psi[b, j]|^2,  C(i) = sum_{j <= i} p_j,  T = C(2^n - 1)   (double for both precisions)
+ *        out[b, s] = the smallest i with C(i) > u[b, s] * T
+ *    The state need not be normalised.  An index with p_i == 0 is never returned and a result is always in [0, 2^n),
+ *    whatever the rounding.  1 <= n <= 40, 1 <= batch <= 65535, 1 <= shots; psi 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of device workspace dq_sample_* needs (a 64-ary tree of partial sums: 2^n / 63 doubles per sample, nothing for
+ * n <= 6; at most 2 % of the state); -1 on a bad argument. */
+int64_t dq_sample_ws_bytes(int n, int64_t batch, int is_c128);
+/* u: DEVICE double [batch, shots] in [0, 1); out: DEVICE int64 [batch, shots], flat amplitude indices (wire 0 = the
+ * most significant bit), fully overwritten.  `ws` (at least dq_sample_ws_bytes bytes; may be NULL when that is 0) is
+ * rebuilt from one read of the state on every call.  No atomics, no host synchronisation: bitwise reproducible. */
+int dq_sample_c64(const void* psi, int n, int64_t batch, const double* u, int64_t shots, int64_t* out, void* ws,
+                  int64_t ws_bytes, dq_stream_t stream);
+int dq_sample_c128(const void* psi, int n, int64_t batch, const double* u, int64_t shots, int64_t* out, void* ws,
+                   int64_t ws_bytes, dq_stream_t stream);
 
 #ifdef __cplusplus
 }
