@@ -1,4 +1,5 @@
-"""Mirrors of the launchers' grid arithmetic, for the large-grid tests (test_grid_paths_gpu.py).
+"""Mirrors of the launchers' grid arithmetic, for the large-grid tests (test_grid_paths_gpu.py) and the path-by-path tests
+(test_pass_paths_*.py, test_rdmk_paths_*.py, test_gate_paths_*.py).
 
 Each function copies what one launcher in ``deepquantum_amd/csrc`` (or ``backend.py``) computes from a shape: how many
 workgroups it launches and so how many times a workgroup goes round its loop, whether the streaming (non-temporal)
@@ -21,25 +22,66 @@ def _csize(c128: bool) -> int:
 
 
 # ---- dq_dense.hip, apply_dense_mfma (k = 5..10 on the matrix cores) -----------------------------------------------------
-def dense(n: int, k: int, nc: int, batch: int, c128: bool, shared: bool, bit0_used: bool) -> dict:
+def dense(n: int, k: int, nc: int, batch: int, c128: bool, shared: bool, bit0_used: bool, *, dense_nt: int | None = None,
+          dense5: int = 1, dense5_blocks: int = 0, dense_big: int = 0, dense_rows_fast: int = 1, launch: bool = False) -> dict:
     """dq_dense.hip:380-435.  ``bit0_used``: index bit 0 is a target or a control.  Returns the route ('dense56', 'staged1'
-    = apply_dense_mfma_kernel<T, 1>, 'staged2' = <T, 2>), whether the non-temporal instantiation runs, and for dense56 the
-    column groups, the groups one pass of the grid covers and the loop iterations of a workgroup."""
+    = apply_dense_mfma_kernel<T, 1>, 'staged2' = <T, 2>, 'big128' = <T, 2, NT, 4, 4>), whether the non-temporal
+    instantiation runs, and for dense56 the column groups, the groups one pass of the grid covers and the loop iterations
+    of a workgroup.
+
+    The keywords stand for the process-wide knobs DQ_DENSE_NT (None: unset), DQ_DENSE5, DQ_DENSE5_BLOCKS, DQ_DENSE_BIG and
+    DQ_DENSE_ROWS_FAST as the launcher parses them (atoi), at their defaults unless given.  With ``launch`` (or any knob
+    off its default) the dict also holds the launch itself: ``grid`` (x, y, z), ``rows_fast`` (bit 30 of the shift word:
+    row tiles vary fastest), ``ncols``, ``col_shift`` (-1: per-sample matrices) and ``row_tile`` / ``col_tile`` (rows of U
+    and columns a workgroup -- dense56: a wave -- owns at a time)."""
     d = 1 << k
     colbits = n - k - nc
     ncols = (batch if shared else 1) << colbits
-    nt = (batch << n) * _csize(c128) >= GIB                                   # dq_dense.hip:394
+    shift = colbits if shared else -1                                         # dq_dense.hip:390
+    gz = 1 if shared else batch
+    nt = dense_nt != 0 if dense_nt is not None and dense_nt >= 0 else (batch << n) * _csize(c128) >= GIB      # dq_dense.hip:393-394
+    more = launch or (dense_nt, dense5, dense5_blocks, dense_big, dense_rows_fast) != (None, 1, 0, 0, 1)
     cpl = 1 if c128 else 2
     cg = 16 * cpl
-    if (d == 32 or (d == 64 and not c128)) and ncols % cg == 0 and (c128 or not bit0_used):     # dq_dense.hip:398
+    if (d == 32 or (d == 64 and not c128)) and dense5 and ncols % cg == 0 and (c128 or not bit0_used):     # dq_dense.hip:399
         ngroups = ncols // cg
-        resident = 256 * (3 if (not c128 and d == 32) else 2)               # dq_dense.hip:402
+        resident = 256 * (3 if (not c128 and d == 32) else 2)               # dq_dense.hip:403
         per_wg = 4 if d == 32 else 2
-        blocks = min(_cdiv(ngroups, per_wg), resident)
+        blocks = min(_cdiv(ngroups, per_wg), dense5_blocks if dense5_blocks > 0 else resident)      # dq_dense.hip:405
         per_pass = blocks * per_wg
-        return dict(route='dense56', nt=nt, ngroups=ngroups, col_group=cg, per_pass=per_pass,
-                    iterations=_cdiv(ngroups, per_pass))
-    return dict(route='staged1' if d == 32 else 'staged2', nt=nt, iterations=1)
+        out = dict(route='dense56', nt=nt, ngroups=ngroups, col_group=cg, per_pass=per_pass,
+                   iterations=_cdiv(ngroups, per_pass))
+        extra = dict(grid=(blocks, gz, 1), rows_fast=False, row_tile=32, col_tile=cg)
+    elif d == 32:                                                             # dq_dense.hip:414
+        out = dict(route='staged1', nt=nt, iterations=1)
+        extra = dict(grid=(_cdiv(ncols, 128), 1, gz), rows_fast=False, row_tile=32, col_tile=128)
+    elif not c128 and d >= 256 and dense_big and ncols % 128 == 0:            # dq_dense.hip:421
+        out = dict(route='big128', nt=nt, iterations=1)
+        extra = dict(grid=(ncols // 128, d // 128, gz), rows_fast=shared, row_tile=128, col_tile=128)
+    else:
+        out = dict(route='staged2', nt=nt, iterations=1)
+        extra = dict(grid=(_cdiv(ncols, 64), d // 64, gz), rows_fast=bool(dense_rows_fast) and shared,      # dq_dense.hip:430-432
+                     row_tile=64, col_tile=64)
+    if more:
+        out.update(extra, ncols=ncols, col_shift=shift)
+    return out
+
+
+# ---- dq_gate.hip, apply_small_kernel (k <= 4) -----------------------------------------------------------------------------
+def small_gate(n: int, k: int, nc: int, c128: bool, bit0_used: bool, in_place: bool) -> dict:
+    """dq_gate.hip:187-226.  ``wide``: the complex64 instantiation that takes the two groups differing in index bit 0 per
+    thread (k <= 3, bit 0 neither target nor control, at least one free bit); ``groups``: what the grid is sized for --
+    pairs of groups when wide; ``blocks`` workgroups of 256 per sample and the ``iterations`` of their grid-stride loop;
+    ``copy``: copy_uncontrolled_kernel runs first (out of place with controls)."""
+    assert 1 <= k <= 4
+    na = k + nc
+    groups = 1 << (n - na)                                                    # dq_gate.hip:194
+    wide = not c128 and k <= 3 and na < 16 and n - na >= 1 and not bit0_used   # dq_gate.hip:198
+    if wide:
+        groups >>= 1
+    blocks = min(_cdiv(groups, 256), 1 << 20)                                 # dq_gate.hip:206-207
+    return dict(wide=wide, groups=groups, blocks=blocks, iterations=_cdiv(groups, blocks * 256),
+                copy=not in_place and nc > 0)                                 # dq_gate.hip:188
 
 
 # ---- dq_gate.hip, copy_uncontrolled_kernel (controlled gates out of place) ----------------------------------------------
@@ -222,11 +264,11 @@ def rdmk(n: int, k: int, nc: int, batch: int, c128: bool, herm: bool) -> dict:
 
 
 # ---- dq_dist.hip: permute_bits, pack, unpack_axpby -------------------------------------------------------------------------
-def permute(nl: int, src_of_dst, batch: int, c128: bool) -> dict:
+def permute(nl: int, src_of_dst, batch: int, c128: bool, lds: bool = True) -> dict:
     """dq_dist.hip:198-259: the variant ('lds', 'tiled_pair', 'tiled', 'elementwise'), its workgroups, their loop
-    iterations and (tiled kernels) the streaming flag."""
+    iterations and (tiled kernels) the streaming flag.  ``lds`` False: under DQ_PERMUTE_LDS=0 (the LDS kernel is off)."""
     low_in_place = all(src_of_dst[p] < 5 for p in range(min(5, nl)))
-    if nl >= 12 and not low_in_place:
+    if nl >= 12 and not low_in_place and lds:
         ntile = 1 << (nl - 10)
         nblk = min(ntile, 256 * 16)
         return dict(variant='lds', blocks=nblk, iterations=_cdiv(ntile, nblk), nt=False)

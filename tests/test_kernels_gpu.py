@@ -444,17 +444,12 @@ def test_permute_bits_against_index_arithmetic(dtype, n, batch):
     """dq_permute_bits (the relayout before an all-to-all, the canonical order afterwards): out[i] = in[sigma(i)], every kernel
     variant -- per-element below 2^12, tiled with 16-byte pairs when bit 0 stays (complex64) and without, through LDS tiles
     when the low destination bits come from high source bits."""
-    import random
+    from _gate_cases import index_test_permutations      # (shared with the DQ_PERMUTE_LDS=0 run of test_gate_paths_gpu.py)
 
-    rng = random.Random(n)
     g = torch.Generator().manual_seed(n)
     x = (torch.randn(batch, 1 << n, generator=g, dtype=torch.float64) + 1j * torch.randn(batch, 1 << n, generator=g, dtype=torch.float64)).to(dtype)
     idx = torch.arange(1 << n)
-    perms = [list(range(n)), rng.sample(range(n), n), [0] + [1 + q for q in rng.sample(range(n - 1), n - 1)],
-             list(range(1, n)) + [0], [q for q in range(n) if q not in (n - 3, n - 2)] + [n - 3, n - 2],
-             list(range(n))[::-1], [n - 1] + list(range(n - 1)), [1, 0] + list(range(2, n))]
-    perms += [rng.sample(range(n), n) for _ in range(5 if n <= 17 else 1)]
-    for src_of_dst in perms:
+    for src_of_dst in index_test_permutations(n):
         sidx = torch.zeros(1 << n, dtype=torch.long)
         for p, sp in enumerate(src_of_dst):
             sidx |= ((idx >> p) & 1) << sp
