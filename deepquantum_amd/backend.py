@@ -375,10 +375,10 @@ def scale_z_signs(state: torch.Tensor, zmasks: Sequence[int], coef: torch.Tensor
     if not _use_hip(state):
         with torch.no_grad():
             return _scale_z_signs_double(state, zmasks, coef, n)
-    lib = _lib.load()
-    fn = getattr(lib, f'dq_scale_zsigns_{_suffix(state)}')
-    coef = coef.to(torch.float64).contiguous()
-    out = None
+    if state.dtype == torch.complex64 and len(zmasks) > 32:
+        return _scale_z_signs_wide(state, zmasks, coef, n)      # (several launches: their sum is formed in double)
+    fn = getattr(_lib.load(), f'dq_scale_zsigns_{_suffix(state)}')
+    out, coef = None, coef.to(torch.float64).contiguous()
     for lo in range(0, len(zmasks), 32):
         grp = zmasks[lo:lo + 32]
         part = torch.empty_like(state)
@@ -806,3 +806,34 @@ def _sample_indices_double(probs_or_state: torch.Tensor, u: torch.Tensor) -> tor
     # the last index of non-zero probability == the number of entries below the total: nothing beyond it is returned
     last = (c < c[:, -1:]).sum(-1, keepdim=True)
     return torch.minimum(idx, last)
+
+
+_WIDE_BYTES = 256 << 20
+
+
+def _scale_z_signs_wide(state: torch.Tensor, zmasks: Sequence[int], coef: torch.Tensor, n: int) -> torch.Tensor:
+    """``scale_z_signs`` of a complex64 state with more than 32 strings.  A launch takes 32 strings; adding the launches'
+    complex64 results would round three times or more where one launch rounds once.  So a slice at a time is widened,
+    goes through the complex128 kernel once per 32 strings, is added up in complex128 and rounded to complex64 once: the
+    error of a single launch, at about three times its traffic.
+
+    A slice is about ``_WIDE_BYTES`` of complex128: whole samples, or, where one sample is larger, runs of 2^m amplitudes
+    of it -- the sign of the index bits above m is constant over a run and goes into the run's coefficients, exactly.
+    Three slices of complex128 (the widened input, the sum, one launch's result) are alive at a time, whatever n."""
+    k = len(zmasks)
+    m = min(n, max(8, (_WIDE_BYTES // 16).bit_length() - 1))
+    coef = coef.to(torch.float64).reshape(state.shape[0], k)
+    if m < n:
+        h = torch.arange(1 << (n - m), device=state.device)
+        par = torch.stack([h & (int(z) >> m) for z in zmasks], dim=1)
+        for sh in (32, 16, 8, 4, 2, 1):
+            par = par ^ (par >> sh)
+        coef = (coef[:, None, :] * (1 - 2 * (par & 1)).to(torch.float64)[None]).reshape(-1, k)
+        zmasks = [int(z) & ((1 << m) - 1) for z in zmasks]
+    out = torch.empty_like(state)
+    src, dst = state.reshape(-1, 1 << m), out.view(-1, 1 << m)
+    rows = max(1, min(65535, _WIDE_BYTES // (16 << m)))
+    for r0 in range(0, src.shape[0], rows):
+        wide = scale_z_signs(src[r0:r0 + rows].to(torch.complex128), zmasks, coef[r0:r0 + rows])
+        dst[r0:r0 + rows].copy_(wide)
+    return out

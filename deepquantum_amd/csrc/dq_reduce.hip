@@ -145,8 +145,8 @@ __global__ __launch_bounds__(256) void probs_kernel(const cx<T>* __restrict__ ps
     }
 }
 
-// Marginals: a block owns a "chunk" of 2^c amplitudes (c = min(12, n)) whose index bits are the low L bits
-// (1 KiB of contiguous state) plus UNMEASURED bits above them as far as there are any (then measured ones, lowest outcome
+// Marginals: a block owns a "chunk" of 2^c amplitudes (c = min(12, n)) whose index bits are the low L bits (L = 6 for
+// complex64, 7 for complex128) plus UNMEASURED bits above them as far as there are any (then measured ones, lowest outcome
 // bit first), so as much of the sum over the unmeasured bits as possible happens inside the block.  A thread holds the
 // 16 amplitudes that differ in the chunk-local bits 8..11 (the unmeasured candidates go there first), issues all 16
 // loads before it uses any, adds them up, and adds the sum into an LDS histogram over the measured chunk bits; the
@@ -634,7 +634,7 @@ static int marginal_impl(const void* psi, int n, const int* bits, int nw, int64_
     {
         constexpr int VEC = sizeof(T) == 4 ? 2 : 1;
         const int c = n < 12 ? n : 12;
-        const int low = n < 8 - VEC ? n : 8 - VEC;          // 1 KiB of contiguous state: 7 bits complex64, 6 complex128
+        const int low = n < 8 - VEC ? n : 8 - VEC;          // contiguous bits: 6 complex64, 7 complex128
         uint64_t measured = 0, in_chunk = 0;
         for (int i = 0; i < nw; ++i) measured |= 1ull << bits[i];
         MargGeom g{};

@@ -1,5 +1,5 @@
 """Mirrors of the launchers' grid arithmetic, for the large-grid tests (test_grid_paths_gpu.py) and the path-by-path tests
-(test_pass_paths_*.py, test_rdmk_paths_*.py, test_gate_paths_*.py).
+(test_pass_paths_*.py, test_rdmk_paths_*.py, test_gate_paths_*.py, test_reduce_paths_*.py).
 
 Each function copies what one launcher in ``deepquantum_amd/csrc`` (or ``backend.py``) computes from a shape: how many
 workgroups it launches and so how many times a workgroup goes round its loop, whether the streaming (non-temporal)
@@ -121,12 +121,26 @@ def scale_zsigns(n: int) -> dict:
     return dict(blocks=nb, chunk=1024, iterations=_cdiv(1 << n, nb * 1024))
 
 
+def scale_zsigns_waves(n: int) -> dict:
+    """dq_reduce.hip:512 (scale_zsigns_mfma_kernel): wave w of workgroup b starts at amplitude (4 b + w) << 8 and has no
+    work when that lies past the state.  ``idle_waves``: (workgroup, wave) pairs that never enter the loop."""
+    g = scale_zsigns(n)
+    idle = [(b, w) for b in range(g['blocks']) for w in range(4) if (b * 4 + w) << 8 >= 1 << n]
+    return dict(g, idle_waves=idle)
+
+
 def expect_zmulti(n: int, c128: bool) -> dict:
     """backend.py:361 picks the workgroups; dq_reduce.hip (expect_zmulti_mfma_kernel) reads U slices of 256 amplitudes
-    per workgroup and iteration, U = 8 (complex64) / 4 (complex128)."""
+    per workgroup and iteration, U = 8 (complex64) / 4 (complex128).  ``slices``: per workgroup, the slice numbers u of
+    its FIRST iteration that lie inside the state (dq_reduce.hip:415-420: i0 + 256 u < 2^n; the same for its four waves,
+    256 divides 2^n from n = 8 on); ``idle_blocks``: workgroups whose first slice is already past the end."""
     nb = max(1, min(2048, (1 << n) // 1024))
     u = 4 if c128 else 8
-    return dict(blocks=nb, window=u * RED_THREADS, iterations=_cdiv(1 << n, u * nb * RED_THREADS))
+    out = dict(blocks=nb, window=u * RED_THREADS, iterations=_cdiv(1 << n, u * nb * RED_THREADS), u=u)
+    if n >= 8 and nb <= 64:                                                   # (the table is for the small shapes)
+        out['slices'] = [[s for s in range(u) if b * u * RED_THREADS + s * RED_THREADS < 1 << n] for b in range(nb)]
+        out['idle_blocks'] = [b for b, s in enumerate(out['slices']) if not s]
+    return out
 
 
 def probs(count: int) -> dict:
@@ -137,7 +151,10 @@ def probs(count: int) -> dict:
 
 def marginal(n: int, bits: list[int], batch: int, c128: bool) -> dict:
     """dq_reduce.hip:634-691: the chunk's bits, and ``run``: how many bits of the chunk number a workgroup loops over
-    (2^run chunks each).  ``chunk_bits``: the index bits inside a chunk; ``cpos``: the chunk number's bits, low first."""
+    (2^run chunks each).  ``chunk_bits``: the index bits inside a chunk; ``cpos``: the chunk number's bits, low first;
+    ``low`` / ``c``: the contiguous run and the chunk's size in bits; ``nlo`` / ``nhi``: measured bits inside / outside the
+    chunk; ``qmask``, ``exclusive``: as in MargGeom; ``run_bits``: unmeasured bits outside the chunk (``run`` before the cut
+    of :691); ``geom``: the whole MargGeom (dq_reduce.hip:156-164) in the padded form the kernel receives."""
     vec = 1 if c128 else 2
     c = min(n, 12)
     low = min(n, 8 - vec)
@@ -153,9 +170,35 @@ def marginal(n: int, bits: list[int], batch: int, c128: bool) -> dict:
             if b not in in_chunk and ((measured >> b) & 1) == pas:
                 cpos.append(b)
                 run += pas == 0
-    while run > 0 and (1 << (n - c - run)) * batch < 2048:
+    while run > 0 and (1 << (n - c - run)) * batch < 2048:                    # dq_reduce.hip:691
         run -= 1
-    return dict(run=run, chunk_bits=sorted(in_chunk), cpos=cpos, blocks=1 << (n - c - run))
+    # the whole MargGeom as the kernel receives it (dq_reduce.hip:156-164), pads included: :642-645
+    pos, local_of, nxt = [62] * 12, {}, 0
+    for b in range(low):                                                      # :658-662
+        pos[b], local_of[b] = b, b
+    for pas in (0, 1):                                                        # :663-668: the thread-held bits 8..11 first
+        for x in (range(8, c) if pas == 0 else range(low, min(c, 8))):
+            pos[x], local_of[cand[nxt]] = cand[nxt], x
+            nxt += 1
+    assert set(local_of) == in_chunk
+    lo_x, lo_out, hi_pos, hi_out, qmask = [], [], [], [], 0
+    for o in range(nw):                                                       # :670-682
+        b = bits[nw - 1 - o]
+        if b in in_chunk:
+            lo_x.append(local_of[b])
+            lo_out.append(o)
+            if local_of[b] >= 8:
+                qmask |= 1 << (local_of[b] - 8)
+        else:
+            hi_pos.append(b)
+            hi_out.append(o)
+    nlo, nhi = len(lo_x), len(hi_pos)
+    geom = dict(c=c, nlo=nlo, run=run, exclusive=int(nhi == n - c), qmask=qmask, pos=pos,       # :683
+                cpos=cpos + [63] * (28 - len(cpos)), lo_x=lo_x + [31] * (12 - nlo), lo_out=lo_out + [0] * (12 - nlo),
+                hi_pos=hi_pos + [63] * (40 - nhi), hi_out=hi_out + [0] * (40 - nhi))
+    return dict(run=run, chunk_bits=sorted(in_chunk), cpos=cpos, blocks=1 << (n - c - run), low=low, c=c, nlo=nlo, nhi=nhi,
+                qmask=qmask, exclusive=bool(geom['exclusive']), run_bits=sum(not (measured >> b) & 1 for b in cpos),
+                lds_bytes=8 << nlo, geom=geom)
 
 
 def gate_grad(n: int, k: int, nc: int) -> dict:
@@ -168,9 +211,13 @@ def gate_grad(n: int, k: int, nc: int) -> dict:
 def gate_grad_multi(n: int, c128: bool, gates) -> list[dict]:
     """backend.py:489-517 (how the gates are packed into launches and the workgroups) and dq_reduce.hip:818-859 (the
     tile's bits: the low L, the launch's targets at or above L, then the lowest free bits above L).  One dict per
-    launch: its gate indices, the tile bits (ascending), the tiles and how many a workgroup visits at most."""
+    launch: its gate indices, the tile bits (ascending), the tiles and how many a workgroup visits at most, ``route``
+    ('tile'; below the tile backend.py:491 goes gate by gate: one dict per gate, route 'gate_grad'), ``high_sorted`` (the
+    gathered bits), ``high_targets`` (those of them that are targets), ``outside`` (the index bits that number the tiles) and
+    ``desc``: tbit / cin / cout of every gate as the launcher fills GradMultiDesc."""
     tile, per_call, low = (10, 4, 3) if c128 else (11, 8, 4)
-    assert n >= tile
+    if n < tile:                                                              # backend.py:491: gate by gate through gate_grad
+        return [dict(route='gate_grad', gates=[i]) for i in range(len(gates))]
     nblocks = min(1 << (n - tile), 1536)
     out, start = [], 0
     while start < len(gates):
@@ -188,8 +235,17 @@ def gate_grad_multi(n: int, c128: bool, gates) -> list[dict]:
                 hb.add(p)
             p += 1
         ntiles = 1 << (n - tile)
-        out.append(dict(gates=list(range(start, stop)), tile_bits=sorted(set(range(low)) | hb), blocks=nblocks,
-                        ntiles=ntiles, iterations=_cdiv(ntiles, nblocks), pairs_per_thread=(1 << (tile - 1)) // RED_THREADS))
+        tile_bits = sorted(set(range(low)) | hb)
+        local = {p: q for q, p in enumerate(tile_bits)}                       # dq_reduce.hip:852-864
+        desc = []
+        for gi in range(start, stop):                                         # :865-878: tbit, cin, cout of every gate
+            t, ctrl = int(gates[gi][0]), [int(q) for q in gates[gi][1]]
+            desc.append(dict(tbit=local[t], cin=sum(1 << local[q] for q in ctrl if q in local),
+                             cout=sum(1 << q for q in ctrl if q not in local)))
+        out.append(dict(route='tile', gates=list(range(start, stop)), tile_bits=tile_bits, blocks=nblocks,
+                        ntiles=ntiles, iterations=_cdiv(ntiles, nblocks), pairs_per_thread=(1 << (tile - 1)) // RED_THREADS,
+                        high_sorted=sorted(hb), high_targets=sorted(high), outside=[p for p in range(n) if p not in tile_bits],
+                        desc=desc))
         start = stop
     return out
 

@@ -282,8 +282,9 @@ def test_batches_wider_than_a_grid_dimension_go_in_slices(monkeypatch):
 @pytest.mark.parametrize('dtype', [torch.complex64, torch.complex128])
 def test_many_z_strings_in_one_read(dtype, n):
     """dq_expect_zmulti_* / dq_scale_zsigns_*: 40 random Z-type strings (two launches of <= 32) against the
-    single-string kernel and against the diagonal operator applied amplitude by amplitude (n = 9: the grid stride is
-    more than a quarter of the state, so the kernels take their element-by-element sign path)."""
+    single-string kernel and against the diagonal operator applied amplitude by amplitude (n = 9: one workgroup of the
+    matrix-core kernels, some of whose slices -- and two of the scaling kernel's four waves -- lie past the end of the
+    state; test_reduce_paths_gpu.py holds these sizes bit for bit)."""
     b = 3
     x = rand_state(b, n, dtype, 41)
     xd = x.to(dev())
