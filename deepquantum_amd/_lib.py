@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DQHIP_LIBRARY') or os.path.join(_HERE, 'libdqhip.so')
 
 DQ_OK = 0
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 # enum DqFusedKind / DqBitLoc (include/dq_hip.h)
 FG_GEN1, FG_X1, FG_DIAG1, FG_GEN2, FG_DIAG2, FG_RESERVED5, FG_GRAD, FG_EXPZ = range(8)
@@ -85,6 +85,15 @@ class DqFusedPass(C.Structure):
     ]
 
 
+class DqPlanParams(C.Structure):
+    """include/dq_hip.h, DqPlanParams: the parameters of dq_dag_plan."""
+
+    _fields_ = [('low', C.c_uint64), ('known_zero', C.c_uint64), ('seed', C.c_int64),
+                ('hcap', C.c_int32), ('cap', C.c_int32), ('width', C.c_int32), ('branch', C.c_int32),
+                ('far_bit', C.c_int32), ('max_far', C.c_int32), ('free_low', C.c_int32), ('priced', C.c_int32),
+                ('gate_valu', C.c_void_p), ('pass_valu', C.c_double), ('tiles_full', C.c_double), ('rate', C.c_double)]
+
+
 _vp, _i, _i64, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64
 _ip = C.POINTER(C.c_int)
 
@@ -101,6 +110,11 @@ _SIGNATURES = {
     'dq_dag_closure': (_i, [_vp, _u64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     'dq_dag_rank': (_i, [_vp, _u64, _i, _vp, _vp, _i, _vp, _i, _vp]),
     'dq_dag_grow_step': (_i, [_vp, _u64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'dq_dag_plan': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    'dq_plan_pass_ms': (C.c_double, [C.c_double, C.c_double]),
+    'dq_wave_pass_cost': (_i, [C.POINTER(DqFusedPass), _i, _u64, _vp, _vp]),
+    'dq_wave_handler_valu': (_i, [_i, _i]),
+    'dq_wave_gate_valu': (_i, [_i, _i]),
     'dq_set_dense_path': (_i, [_i]),
     'dq_reduce_ws_bytes': (_i64, [_i64]),
     'dq_apply_gate_{s}': (_i, [_vp, _vp, _vp, _i64, _i, _ip, _i, _ip, _i, _i64, _vp]),

@@ -4,6 +4,7 @@
 // 10-12 s for the headline circuit, here it is a tight loop over flat arrays.  No device code; the reference has no
 // counterpart (it applies gates one by one, circuit.py:261).
 #include "dq_common.hpp"
+#include <algorithm>
 #include <vector>
 #include <string.h>
 
@@ -15,6 +16,7 @@ struct Dag {
     std::vector<uint64_t> targets;      // qubits the gate needs inside the tile (0 for diagonal gates: they run anywhere)
     std::vector<uint8_t> fusable;
     std::vector<int> cur, touched, stack;      // scratch
+    int* retired = nullptr;                    // when set: closure lists the gates it retires here, in order
 };
 
 // Exactly fusion._closure: depth-first from `ready` (last first), a gate retires while fewer than `cap` have, it is
@@ -32,6 +34,7 @@ int closure(Dag& d, uint64_t tile, int cap, const int* indeg, const int* ready, 
             ++ns;
             continue;
         }
+        if (d.retired) d.retired[count] = i;
         ++count;
         for (int e = d.succ_off[i]; e < d.succ_off[i + 1]; ++e) {
             const int s = d.succ[e];
@@ -128,4 +131,295 @@ extern "C" int dq_dag_grow_step(void* dag, uint64_t tile, int cap, const int* in
         cand_count[c] = closure(d, tile | (1ull << order[c]), cap, indeg, ready, nready, nullptr, nullptr, nullptr, nullptr, nullptr);
     }
     return nq;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The whole beam search of fusion._plan_tiles in one call, optionally PRICED.
+//
+// The pass-cost model.  ONE place for its constants; fusion.py reads them through dq_plan_pass_ms.  A FULL pass of the headline
+// (n = 28, batch 16, complex64: 68.7 GB moved) takes  max(11.1, 5.8 + 1.71e-3 * VALU instructions per tile)  milliseconds,
+// and a pass that moves less -- behind |0..0>, or a smaller state -- that times its share of those bytes:
+//     ms = bytes moved * max(FLOOR_MS_PER_BYTE, FIXED_MS_PER_BYTE + VALU_MS_PER_BYTE * VALU instructions per tile)
+//  - slope and intercept: profiles/r05/pass_cost_model.txt, the straight line through the full passes of the headline above
+//    the plateau (residual 0.24 ms rms);
+//  - floor: profiles/r06/passes_headline.txt, the lightest full passes: 11.1 ms for 68.7 GB (6.2 TB/s).
+// Nobody has measured them for complex128: its tile holds as many bytes as a complex64 tile (2^11 x 16 = 2^12 x 8), so the
+// complex64 figures are used per byte as they stand.  The model leaves out what the last pass pays for restoring the
+// canonical order (3 ms on the headline): every schedule has one such pass.
+namespace {
+
+constexpr double kHeadlineBytes = 68719476736.0;                 // 16 samples x 2^28 amplitudes x 8 bytes, read + written
+constexpr double kFixedMsPerByte = 5.8 / kHeadlineBytes;
+constexpr double kValuMsPerByte = 1.71e-3 / kHeadlineBytes;
+constexpr double kFloorMsPerByte = 11.1 / kHeadlineBytes;
+constexpr double kTileBytes = 32768.0;
+
+double pass_ms(double valu, double bytes_moved) {
+    const double alu = kFixedMsPerByte + kValuMsPerByte * valu;
+    return bytes_moved * (alu > kFloorMsPerByte ? alu : kFloorMsPerByte);
+}
+
+// random.Random(seed).randrange(n) of CPython for 0 <= seed < 2^32 and n < 2^32: MT19937 seeded by init_by_array with the
+// one-word key {seed}; randrange(n) draws getrandbits(bit_length(n)) = next word >> (32 - k) until the value is below n.
+struct PyRandom {
+    uint32_t mt[624];
+    int idx;
+    explicit PyRandom(uint32_t seed) {
+        mt[0] = 19650218u;
+        for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+        int i = 1;
+        for (int k = 624; k; --k) {         // (key length 1: j stays 0)
+            mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1664525u)) + seed;
+            if (++i >= 624) { mt[0] = mt[623]; i = 1; }
+        }
+        for (int k = 623; k; --k) {
+            mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1566083941u)) - (uint32_t)i;
+            if (++i >= 624) { mt[0] = mt[623]; i = 1; }
+        }
+        mt[0] = 0x80000000u;
+        idx = 624;
+    }
+    uint32_t next() {
+        if (idx >= 624) {
+            for (int k = 0; k < 624; ++k) {
+                const uint32_t y = (mt[k] & 0x80000000u) | (mt[(k + 1) % 624] & 0x7fffffffu);
+                mt[k] = mt[(k + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+            }
+            idx = 0;
+        }
+        uint32_t y = mt[idx++];
+        y ^= y >> 11;
+        y ^= (y << 7) & 0x9d2c5680u;
+        y ^= (y << 15) & 0xefc60000u;
+        y ^= y >> 18;
+        return y;
+    }
+    uint32_t randrange(uint32_t n) {
+        const int k = 32 - __builtin_clz(n);
+        uint32_t r;
+        do r = next() >> (32 - k); while (r >= n);
+        return r;
+    }
+};
+
+struct Cand {
+    int c, w, q;
+};
+
+struct PlanCtx {
+    Dag* d;
+    const DqPlanParams* prm;
+    PyRandom rng;
+    std::vector<int> stuck, cidx, cval;
+    PlanCtx(Dag* d_, const DqPlanParams* p) : d(d_), prm(p), rng((uint32_t)p->seed), stuck((size_t)d_->n + 1), cidx((size_t)d_->n + 1), cval((size_t)d_->n + 1) {}
+
+    // fusion._grow_tile
+    uint64_t grow(uint64_t low, int hcap, const std::vector<int>& indeg, const std::vector<int>& ready, bool jitter, bool has_prev,
+                  uint64_t prev, int need, uint64_t start = 0) {
+        const int cap = prm->cap;
+        uint64_t chosen = start;        // (qubits the tile must hold whatever the gates ask for)
+        const uint64_t farmask = prm->far_bit < 64 ? ~((1ull << prm->far_bit) - 1ull) : 0ull;
+        while (__builtin_popcountll(chosen) < hcap) {
+            const uint64_t tile = low | chosen;
+            int ns = 0;
+            const int base = closure(*d, tile, cap, indeg.data(), ready.data(), (int)ready.size(), stuck.data(), &ns, nullptr, nullptr, nullptr);
+            if (base >= cap) break;
+            int w[64] = {0}, order[64], nq = 0;
+            for (int k = 0; k < ns; ++k) {
+                const int i = stuck[k];
+                if (!d->fusable[i]) continue;
+                uint64_t miss = d->targets[i] & ~tile;
+                while (miss) {
+                    const int q = __builtin_ctzll(miss);
+                    miss &= miss - 1;
+                    if (w[q]++ == 0) order[nq++] = q;
+                }
+            }
+            const bool far_spent = prm->max_far >= 0 && __builtin_popcountll(chosen & farmask) >= prm->max_far;
+            const bool only_prev = has_prev && hcap - __builtin_popcountll(chosen) <= need - __builtin_popcountll(chosen & prev);
+            Cand cands[64];
+            int nc = 0;
+            for (int c = 0; c < nq; ++c) {
+                const int q = order[c];
+                if (far_spent && q >= prm->far_bit) continue;
+                if (only_prev && !((prev >> q) & 1ull)) continue;
+                cands[nc].q = q;
+                cands[nc].w = w[q];
+                cands[nc].c = closure(*d, tile | (1ull << q), cap, indeg.data(), ready.data(), (int)ready.size(), nullptr, nullptr, nullptr, nullptr, nullptr);
+                ++nc;
+            }
+            if (!nc) break;
+            // descending by (count, waiting gates, -qubit)
+            std::sort(cands, cands + nc, [](const Cand& a, const Cand& b) {
+                if (a.c != b.c) return a.c > b.c;
+                if (a.w != b.w) return a.w > b.w;
+                return a.q < b.q;
+            });
+            const int pick = jitter ? (int)rng.randrange((uint32_t)(nc < 3 ? nc : 3)) : 0;
+            chosen |= 1ull << cands[pick].q;
+        }
+        if (has_prev) {
+            uint64_t rest = prev & ~chosen;
+            while (rest) {
+                if (__builtin_popcountll(chosen & prev) >= need || __builtin_popcountll(chosen) >= hcap) break;
+                chosen |= rest & (~rest + 1ull);
+                rest &= rest - 1;
+            }
+        }
+        return chosen;
+    }
+};
+
+struct BeamState {
+    int done;
+    double ms;
+    uint64_t zero;              // qubits still known to be |0> (priced search)
+    std::vector<int> indeg, ready;
+    std::vector<uint64_t> hist;
+    uint64_t prev;
+};
+
+}  // namespace
+
+extern "C" double dq_plan_pass_ms(double valu, double bytes_moved) { return pass_ms(valu, bytes_moved); }
+
+extern "C" int dq_dag_plan(void* dag, const DqPlanParams* prm, const int* indeg, const int* ready, int nready, uint64_t* tiles_out,
+                           int max_tiles, double* model_ms) {
+    if (!dag || !prm || !indeg || (nready > 0 && !ready) || !tiles_out) {
+        dq::set_error("dq_dag_plan: null pointer");
+        return DQ_ERR_ARG;
+    }
+    Dag& d = *static_cast<Dag*>(dag);
+    if (prm->width < 1 || prm->branch < 1 || prm->hcap < 0 || prm->hcap + prm->free_low > 64 || (prm->priced && !prm->gate_valu) ||
+        prm->seed < 0 || prm->seed > 0xffffffffll) {
+        dq::set_error("dq_dag_plan: bad parameters");
+        return DQ_ERR_ARG;
+    }
+    PlanCtx ctx(&d, prm);
+    const int cap = prm->cap, L = prm->free_low;
+    const uint64_t lowmask = prm->low;
+    std::vector<BeamState> beam(1), nxt;
+    beam[0].done = 0;
+    beam[0].ms = 0.0;
+    beam[0].zero = prm->known_zero;
+    beam[0].indeg.assign(indeg, indeg + d.n);
+    beam[0].ready.assign(ready, ready + nready);
+    beam[0].prev = lowmask;
+    std::vector<int> retired((size_t)d.n + 1);
+    for (;;) {
+        nxt.clear();
+        for (const BeamState& st : beam) {
+            if (st.done >= d.n) {
+                const int len = (int)st.hist.size();
+                if (len > max_tiles) {
+                    dq::set_error("dq_dag_plan: %d passes, room for %d", len, max_tiles);
+                    return DQ_ERR_ARG;
+                }
+                for (int i = 0; i < len; ++i) tiles_out[i] = st.hist[i];
+                if (model_ms) *model_ms = st.ms;
+                return len;
+            }
+            uint64_t seen[128];
+            int nseen = 0;
+            const int nb = prm->width > 1 ? prm->branch : 1;
+            for (int b = 0; b < nb && b < 64; ++b) {
+                uint64_t bits, whole;
+                if (L) {
+                    bits = ctx.grow(0, prm->hcap + L, st.indeg, st.ready, b != 0, true, st.prev, L);
+                    whole = bits;
+                } else {
+                    bits = ctx.grow(lowmask, prm->hcap, st.indeg, st.ready, b != 0, false, 0, 0);
+                    whole = lowmask | bits;
+                }
+                bool dup = false;
+                for (int k = 0; k < nseen; ++k) dup = dup || seen[k] == bits;
+                if (dup) continue;
+                seen[nseen++] = bits;
+                int ns = 0, nc = 0, nret = 0;
+                d.retired = prm->priced ? retired.data() : nullptr;
+                int count = closure(d, whole, cap, st.indeg.data(), st.ready.data(), (int)st.ready.size(), ctx.stuck.data(), &ns,
+                                    ctx.cidx.data(), ctx.cval.data(), &nc);
+                if (prm->priced && L && st.done + count >= d.n && __builtin_popcountll(whole | lowmask) > prm->hcap + L) {
+                    // this tile would end the circuit, but the LAST pass restores the canonical order and needs the qubits
+                    // that belong on the contiguous low bits in its tile: no room for them here, so the tile is grown again
+                    // around them (it may then leave gates for one more pass)
+                    bits = ctx.grow(0, prm->hcap + L, st.indeg, st.ready, b != 0, true, st.prev, L, lowmask);
+                    whole = bits;
+                    dup = false;
+                    for (int k = 0; k < nseen; ++k) dup = dup || seen[k] == bits;
+                    if (dup) { d.retired = nullptr; continue; }
+                    seen[nseen++] = bits;
+                    count = closure(d, whole, cap, st.indeg.data(), st.ready.data(), (int)st.ready.size(), ctx.stuck.data(), &ns,
+                                    ctx.cidx.data(), ctx.cval.data(), &nc);
+                }
+                d.retired = nullptr;
+                nret = count;
+                nxt.emplace_back();
+                BeamState& o = nxt.back();
+                o.indeg = st.indeg;
+                for (int k = 0; k < nc; ++k) o.indeg[ctx.cidx[k]] = ctx.cval[k];
+                o.ready.assign(ctx.stuck.begin(), ctx.stuck.begin() + ns);
+                o.hist = st.hist;
+                o.ms = st.ms;
+                o.zero = st.zero;
+                if (count == 0) {       // nothing fusable at the front: the lowest ready gate runs on its own
+                    int at = 0;
+                    for (int k = 1; k < ns; ++k)
+                        if (o.ready[k] < o.ready[at]) at = k;
+                    const int i = o.ready[at];
+                    o.ready.erase(o.ready.begin() + at);
+                    for (int e = d.succ_off[i]; e < d.succ_off[i + 1]; ++e)
+                        if (--o.indeg[d.succ[e]] == 0) o.ready.push_back(d.succ[e]);
+                    o.done = st.done + 1;
+                    o.hist.push_back(~0ull);
+                    o.prev = st.prev;
+                    if (prm->priced) {      // a gate on its own reads and writes the whole state
+                        o.ms += pass_ms(0.0, 2.0 * kTileBytes * prm->tiles_full);
+                        o.zero &= ~d.targets[i];
+                    }
+                    break;
+                }
+                o.done = st.done + count;
+                o.hist.push_back(bits);
+                o.prev = whole;
+                if (prm->priced) {
+                    // the estimate: per-gate costs by kind and mode + a fixed part per pass; the pass runs the tiles in which
+                    // no known-|0> qubit outside its tile is 1 and reads, of each, what known-|0> qubits inside leave
+                    double valu = prm->pass_valu;
+                    uint64_t hit = 0;
+                    for (int k = 0; k < nret; ++k) {
+                        valu += prm->gate_valu[retired[k]];
+                        hit |= d.targets[retired[k]];
+                    }
+                    const uint64_t z = st.zero & ~lowmask;
+                    const int outside = __builtin_popcountll(z & ~whole), inside = __builtin_popcountll(z & whole);
+                    const double tiles = prm->tiles_full / (double)(1ull << outside);
+                    o.ms += pass_ms(valu, tiles * kTileBytes * (1.0 + 1.0 / (double)(1ull << inside)));
+                    o.zero = st.zero & ~hit;        // known |0> until a non-diagonal gate targets it
+                }
+            }
+        }
+        if (prm->priced == 2) {
+            // against a known rate (ms per gate of a schedule already in hand): the states that are the most AHEAD of it
+            const double rate = prm->rate;
+            std::stable_sort(nxt.begin(), nxt.end(), [rate](const BeamState& a, const BeamState& b) {
+                const double ra = a.ms - rate * (double)a.done, rb = b.ms - rate * (double)b.done;
+                if (ra != rb) return ra < rb;
+                return a.done > b.done;
+            });
+        } else if (prm->priced)
+            std::stable_sort(nxt.begin(), nxt.end(), [](const BeamState& a, const BeamState& b) {
+                const double ra = a.ms * (double)b.done, rb = b.ms * (double)a.done;      // ms per retired gate, cross-multiplied
+                if (ra != rb) return ra < rb;
+                return a.done > b.done;
+            });
+        else
+            std::stable_sort(nxt.begin(), nxt.end(), [](const BeamState& a, const BeamState& b) { return a.done > b.done; });
+        if ((int)nxt.size() > prm->width) nxt.resize((size_t)prm->width);
+        beam.swap(nxt);
+        if (beam.empty()) {
+            dq::set_error("dq_dag_plan: the beam ran empty");
+            return DQ_ERR_ARG;
+        }
+    }
 }

@@ -32,6 +32,8 @@ namespace dq {
 
 #include "dq_wave_asm.inc"
 #include "dq_wave_asm64.inc"
+#include "dq_wave_valu.inc"
+#include "dq_wave_valu64.inc"
 
 constexpr int WAVE_LANES = 6;
 constexpr int WAVE_MAX_REC = 112;      // records that travel in the kernel-argument segment (4 KiB)
@@ -755,4 +757,72 @@ extern "C" int dq_wave_descriptor(const DqFusedPass* pass, int n, uint64_t known
         if (max_bytes > head) memcpy((char*)out + head, scratch, (size_t)((bytes < max_bytes ? bytes : max_bytes) - head));
     }
     return bytes;
+}
+
+// The pass-cost model's two inputs for `pass` (no GPU needed): the VALU instructions a wave executes per tile -- the
+// generated per-handler table (kWaveValu / kWave64Valu) summed over the records the translator makes, the second record
+// of a layout change counting nothing -- and the bytes the pass moves per sample, from the `zext` word: 2^(zext & 63)
+// tiles, each WRITTEN whole and READ less the halves that `known_zero` bits inside the tile leave unloaded.
+namespace dq {
+template <class W>
+static int wave_pass_cost(const DqFusedPass* pass, int n, uint64_t known_zero, const unsigned short* table, int nids,
+                          int64_t* valu, double* bytes_moved) {
+    static thread_local WaveRec scratch[WAVE_EXT_REC];
+    WaveKernPass kp;
+    const int rc = wave_translate<W>(pass, n, &kp, known_zero, scratch, WAVE_EXT_REC);
+    if (rc) return rc;
+    int64_t v = 0;
+    const unsigned nrec = kp.nrec_bytes / 32u;
+    for (unsigned r = 0; r < nrec; ++r) {
+        const uint32_t id = scratch[r].w[0];
+        if (id < (uint32_t)nids) v += table[id];
+        if (id >= (uint32_t)W::ID_TRIP0 && id < (uint32_t)W::ID_SWAP) ++r;      // (a trip's second record holds addresses)
+    }
+    if (valu) *valu = v;
+    if (bytes_moved) {
+        const double nt = (double)(1ull << (kp.zext & 63u));
+        const int unloaded = __builtin_popcount((kp.zext >> 8) & 0x3f3fu);
+        *bytes_moved = nt * (double)W::ELEM * ((double)(1u << W::M) + (double)((1u << W::M) >> unloaded));
+    }
+    return DQ_OK;
+}
+}  // namespace dq
+
+extern "C" int dq_wave_pass_cost(const DqFusedPass* pass, int n, uint64_t known_zero, int64_t* valu, double* bytes_moved) {
+    if (!pass) {
+        dq::set_error("dq_wave_pass_cost: null pointer");
+        return DQ_ERR_ARG;
+    }
+    if (pass->m == 12 && pass->slots == 6)
+        return dq::wave_pass_cost<dq::WaveC64>(pass, n, known_zero, dq::kWaveValu, DQ_WAVE_NIDS, valu, bytes_moved);
+    if (pass->m == 11 && pass->slots == 5)
+        return dq::wave_pass_cost<dq::WaveC128>(pass, n, known_zero, dq::kWave64Valu, DQ_WAVE64_NIDS, valu, bytes_moved);
+    dq::set_error("dq_wave_pass_cost: not a wave-tile pass (m = %d, %d slots)", pass->m, pass->slots);
+    return DQ_ERR_ARG;
+}
+
+// One entry of the generated table: VALU instructions of handler `id` (complex128: c128 != 0); -1 beyond the last id.
+extern "C" int dq_wave_handler_valu(int c128, int id) {
+    if (id < 0 || id >= (c128 ? DQ_WAVE64_NIDS : DQ_WAVE_NIDS)) return -1;
+    return c128 ? dq::kWave64Valu[id] : dq::kWaveValu[id];
+}
+
+namespace dq {
+template <class W>
+static int wave_gate_valu(const unsigned short* table, int opclass) {
+    const int q = W::R / 2;     // (a middle slot: the bodies of a family differ by a few instructions at most)
+    switch (opclass) {
+        case 0: return 0;
+        case 1: case 2: case 3: case 4: return table[W::ID_GEN_U + W::R * (opclass - 1) + q];
+        case 5: return table[W::ID_GEN_C + q];
+        case 6: return table[W::ID_X_U + q];
+        case 7: return (table[W::ID_X_C + q] + table[W::ID_X_R1 + (W::R - 1) * q]) / 2;   // (control on a lane or on a register)
+        case 8: return table[W::trip_id((1u << W::MAXK) - 1u)];
+        default: return -1;
+    }
+}
+}  // namespace dq
+
+extern "C" int dq_wave_gate_valu(int c128, int opclass) {
+    return c128 ? dq::wave_gate_valu<dq::WaveC128>(dq::kWave64Valu, opclass) : dq::wave_gate_valu<dq::WaveC64>(dq::kWaveValu, opclass);
 }

@@ -88,6 +88,9 @@ class Geometry:
     plan_restarts: int = 3    # beam searches with different random branches (states of >= 2^plan_restart_bits amplitudes)
     plan_restart_bits: int = 26
     plan_min_bits: int = 20   # states below 2^plan_min_bits amplitudes: greedy (width 1) -- planning time matters there
+    # the searches also run PRICED (beam states ranked by modelled time per retired gate, csrc/dq_plan.hip) and the schedule
+    # with the lowest exact modelled time wins (`schedule`); False: the count-driven choice alone
+    plan_priced: bool = True
     far_bit: int = 19         # index bits >= far_bit are "far": every one gathered doubles the number of
     max_far: int | None = None  # distant address streams of a tile; None = no limit
     # positions (in the layout the LAST pass leaves, i.e. after ``final_perm``) whose qubits that pass keeps out of its tile
@@ -334,6 +337,7 @@ def _plan_tiles(dag: '_Dag', low: set[int], hcap: int, cap: int, width: int, bra
     (a front of the DAG) is extended by the greedy tile and by ``branch - 1`` randomised ones (one of the three best
     candidates at each growth step, fixed seed), the ``width`` states that have retired the most gates survive.
     ``None`` entries stand for a gate that cannot be fused and runs on its own.  width = 1: plain greedy.
+    (The scheduler calls `_plan_tiles_native`, the same search as one native call; this one is its reference in the tests.)
 
     ``free_low`` = L > 0: the entries are WHOLE tiles (up to hcap + L qubits, none of them fixed), each sharing at
     least L qubits with the one before (the first with ``low``): see `_grow_tile`."""
@@ -384,6 +388,90 @@ def _plan_tiles(dag: '_Dag', low: set[int], hcap: int, cap: int, width: int, bra
 
 
 @dataclass
+class _Price:
+    """What a PRICED beam search needs to know of the run (`_plan_tiles_native`); ``estimate`` is what it answers: its own
+    estimate of the plan's modelled milliseconds per sample."""
+
+    n: int
+    m: int
+    c128: bool
+    known_zero: int | None = None     # index bits known to be |0> in the input; None: all of them (a circuit's own |0..0>)
+    rate: float | None = None         # rank by the lead over THIS many ms per gate instead of by time per retired gate
+    estimate: float = 0.0
+
+
+def _op_class(op: PrimOp) -> int:
+    """A gate's class for the planner's price estimate (include/dq_hip.h, dq_wave_gate_valu)."""
+    if op.kind == 'diag' or op.k != 1:
+        return 0 if op.kind in ('diag', 'expz') else 1      # (two-target gates and reductions: priced like a dense 2x2)
+    if op.kind == 'x':
+        return 7 if op.controls else 6
+    return 5 if op.controls else 1 + (op.mode if 0 <= op.mode <= 3 else 0)
+
+
+def _plan_tiles_native(dag: '_Dag', low: set[int], hcap: int, cap: int, width: int, branch: int, seed: int = 20250929,
+                       far: tuple[int, int] | None = None, free_low: int = 0, price: '_Price | None' = None) -> list:
+    """`_plan_tiles` as ONE native call (csrc/dq_plan.hip, dq_dag_plan): the same tile lists, seed for seed.  With ``price``
+    the beam is PRICED: states are ranked by modelled milliseconds per retired gate (the pass-cost model of
+    csrc/dq_plan.hip) instead of by gates retired, and ``price.estimate`` receives the search's estimate for its plan."""
+    import ctypes as C
+
+    import numpy as np
+
+    lib, h = dag.native()[:2]
+    prm = _lib.DqPlanParams(low=_mask(low), known_zero=0, seed=seed, hcap=hcap, cap=cap, width=width, branch=branch,
+                       far_bit=far[0] if far else 64, max_far=far[1] if far else -1, free_low=free_low, priced=0,
+                       gate_valu=None, pass_valu=0.0, tiles_full=0.0, rate=0.0)
+    keep = None
+    if price is not None:
+        per_class = [float(lib.dq_wave_gate_valu(int(price.c128), c)) for c in range(9)]
+        keep = np.array([per_class[_op_class(op)] for op in dag.ops] or [0.0], dtype=np.float32)
+        prm.priced, prm.gate_valu = (2 if price.rate else 1), keep.ctypes.data
+        prm.rate = float(price.rate or 0.0)
+        prm.known_zero = ((1 << price.n) - 1) if price.known_zero is None else price.known_zero
+        prm.pass_valu = 3.0 * per_class[8]          # (a typical pass changes its layout three times)
+        prm.tiles_full = float(1 << max(price.n - price.m, 0))
+    indeg = np.ascontiguousarray(dag.indeg, dtype=np.int32)
+    ready = np.array(dag.ready or [0], dtype=np.int32)
+    out = np.empty(dag.n_ops + 1, dtype=np.uint64)
+    ms = C.c_double(0.0)
+    cnt = lib.dq_dag_plan(h, C.addressof(prm), indeg.ctypes.data, ready.ctypes.data, len(dag.ready), out.ctypes.data, len(out), C.addressof(ms))
+    if cnt < 0:
+        raise RuntimeError('dq_dag_plan failed: ' + lib.dq_last_error().decode())
+    if price is not None:
+        price.estimate = ms.value
+    none = (1 << 64) - 1
+    return [None if int(t) == none else {b for b in range(64) if (int(t) >> b) & 1} for t in out[:cnt]]
+
+
+def modelled_ms(steps: Sequence, n: int, known_zero: int | None = None, batch: int = 1) -> tuple[float, list]:
+    """The exact modelled time of a schedule run behind |0..0> (``known_zero``: behind a state with THESE index bits |0>):
+    the pass-cost model (csrc/dq_plan.hip, dq_plan_pass_ms) over what the library itself says of every finished pass
+    (dq_wave_pass_cost: VALU instructions per tile from the generated table, bytes moved under the pass's known-zero
+    mask).  A gate that runs on its own counts one read and one write of the state.  Returns (milliseconds,
+    per-pass rows (valu, bytes, ms))."""
+    import ctypes as C
+
+    lib = _lib.load()
+    masks = zero_state_masks(steps, n, known_zero) or [0] * len(steps)
+    total, rows = 0.0, []
+    for st, kz in zip(steps, masks):
+        if isinstance(st, FusedStep):
+            v, b = C.c_int64(0), C.c_double(0.0)
+            rc = lib.dq_wave_pass_cost(C.byref(st.desc), n, kz, C.addressof(v), C.addressof(b))
+            if rc < 0:
+                raise RuntimeError('dq_wave_pass_cost failed: ' + lib.dq_last_error().decode())
+            row = (v.value, b.value * batch)
+        else:
+            amp = 8 if any(isinstance(s_, FusedStep) and s_.c64 for s_ in steps) else 16
+            row = (0, 2.0 * amp * (1 << n) * batch)
+        ms = lib.dq_plan_pass_ms(float(row[0]), float(row[1]))
+        rows.append(row + (ms,))
+        total += ms
+    return total, rows
+
+
+@dataclass
 class _Round:
     slots: list[int] = field(default_factory=list)  # global bits that must be register slots
     ops: list[int] = field(default_factory=list)
@@ -410,24 +498,47 @@ def schedule(ops: Sequence[PrimOp], n: int, geom: Geometry, fuse: bool = True,
     if not fuse or n < geom.m:
         return Steps(SingleStep(i) for i in range(len(ops)))
     width = geom.plan_width if n >= geom.plan_min_bits else min(geom.plan_width, 1)
+    # every feasible schedule the searches below come by, the priced ones included (`_schedule`); states below
+    # 2^plan_min_bits amplitudes keep the greedy path alone, and so does a reverse sweep: the model was fitted to passes of
+    # gates, and what a sweep's pass costs is its reductions (accumulators in LDS, atomics), which it does not know
+    priced = geom.plan_priced and width > 1 and wave_supports(ops) and not any(op.kind == 'grad' for op in ops)
+    pool: list | None = [] if priced else None
     best = _schedule(ops, n, geom, 0, final_perm)
 
     def cost(steps):
         return (not steps.applied_final_perm, len(steps), sum(s_.ntranspose for s_ in steps if isinstance(s_, FusedStep)))
 
     several = sum(isinstance(s_, FusedStep) for s_ in best) > 1
+    force = geom.free_low == 'force'          # (a testing aid: take the free-low candidate below whenever it exists)
+    # (the priced searches run in ONE family of tiles, the last that is tried: with free low bits where those are allowed)
+    free_family = bool(geom.free_low and geom.permute_store and several and (width > 1 or force))
     if width and several:
-        cand = _schedule(ops, n, geom, width, final_perm)
+        cand = _schedule(ops, n, geom, width, final_perm, pool=None if free_family else pool)
         if cost(cand) < cost(best):
             best = cand
-    force = geom.free_low == 'force'          # (a testing aid: take the candidate below whenever it exists)
-    if geom.free_low and geom.permute_store and several and (width > 1 or force):
+    if free_family:
         # every pass picks ALL its tile qubits (the stores also re-label the contiguous low bits): fewer passes
         # when the circuit does not keep coming back to the same low qubits; None: it could not restore the
         # canonical order with its last pass, or a gate had to run on its own
-        cand = _schedule(ops, n, geom, max(width, 2), final_perm, free_low=True)
+        cand = _schedule(ops, n, geom, max(width, 2), final_perm, free_low=True, pool=None if force else pool)
         if cand is not None and (cost(cand) < cost(best) or force):
             best = cand
+    if pool and not force:
+        # the count-driven choice above is one candidate among all that were carried out: the one with the lowest EXACT
+        # modelled time wins (`modelled_ms`: the pass-cost model over the finished descriptors), so the result is never
+        # worse than the count-driven one by the model.  One plan serves the runs behind |0..0> (most: a circuit's default)
+        # and the runs on any other state (a caller's state, the reverse sweep), so a candidate must be cheaper for the
+        # first and no dearer for the second, where every pass moves the whole state
+        def price(steps):
+            return modelled_ms(steps, n, geom.known_zero)[0], modelled_ms(steps, n, 0)[0]
+
+        best_ms = price(best)
+        for cand in pool:
+            if cand is best or cand.applied_final_perm != best.applied_final_perm:
+                continue
+            ms = price(cand)
+            if ms[0] < best_ms[0] * (1.0 - 1e-9) and ms[1] <= best_ms[1]:
+                best, best_ms = cand, ms
     return best
 
 
@@ -438,17 +549,21 @@ class Steps(list):
 
 
 def _schedule(ops: Sequence[PrimOp], n: int, geom: Geometry, width: int,
-              final_perm: Sequence[int] | None = None, free_low: bool = False) -> 'Steps | None':
+              final_perm: Sequence[int] | None = None, free_low: bool = False, pool: list | None = None) -> 'Steps | None':
     """The planner's restarts give several tile sequences: tried shortest first, the first that can be carried out wins
-    (with free low bits a sequence may turn out infeasible -- `_schedule_planned` -- and the next one often is not)."""
+    (with free low bits a sequence may turn out infeasible -- `_schedule_planned` -- and the next one often is not).
+
+    ``pool`` collects every schedule that could be carried out, and with it the searches are run a second time PRICED
+    (`_plan_tiles_native`: beam states ranked by modelled time per retired gate) and their schedules join the pool:
+    `schedule` keeps the pool's cheapest by the exact model."""
     if not width:
         return _schedule_planned(ops, n, geom, width, final_perm, free_low, None)
     dag = _Dag(ops, n)
     L = geom.min_low
     restarts = geom.plan_restarts if width > 1 and n >= geom.plan_restart_bits else 1
     far = (geom.far_bit, geom.max_far) if geom.max_far is not None else None
-    plans = [_plan_tiles(dag, set(range(L)), geom.m - L, geom.max_gates, width, geom.plan_branch, 20250929 + r, far,
-                         free_low=L if free_low else 0) for r in range(restarts)]
+    plans = [_plan_tiles_native(dag, set(range(L)), geom.m - L, geom.max_gates, width, geom.plan_branch, 20250929 + r, far,
+                                free_low=L if free_low else 0) for r in range(restarts)]
     seen = []
     best = None
     for plan in sorted(plans, key=len):
@@ -464,8 +579,31 @@ def _schedule(ops: Sequence[PrimOp], n: int, geom: Geometry, width: int,
             key = (len(out), zero_state_cost(out, n, geom.known_zero), sum(s_.ntranspose for s_ in out if isinstance(s_, FusedStep)))
             if best is None or key < best[0]:
                 best = (key, out)
+            if pool is not None:
+                pool.append(out)
         if len(seen) >= 4 and best is not None or len(seen) >= 8:
             break
+    if pool is not None and width > 1:
+        # the same searches PRICED, twice as many seeds as restarts and two rankings each: by modelled time per retired
+        # gate, and by the lead over the rate of the count-driven schedule in hand (its modelled time per gate).  A search
+        # returns its own estimate of the plan's time, within about a millisecond of the exact figure on the headline;
+        # the three cheapest by that estimate are carried out
+        rates = [None]
+        if best is not None and ops:
+            rates.append(modelled_ms(best[1], n, geom.known_zero)[0] / len(ops))
+        found = []
+        for rate in rates:
+            for r in range(2 * restarts):
+                price = _Price(n, geom.m, geom.vb == 0, geom.known_zero, rate)
+                plan = _plan_tiles_native(dag, set(range(L)), geom.m - L, geom.max_gates, width, geom.plan_branch, 20250929 + r,
+                                          far, free_low=L if free_low else 0, price=price)
+                if plan not in seen and all(plan != f_[1] for f_ in found):
+                    found.append((price.estimate, plan))
+        found.sort(key=lambda f_: f_[0])
+        for _est, plan in found[:3]:
+            out = _schedule_planned(ops, n, geom, width, final_perm, free_low, list(plan))
+            if out is not None:
+                pool.append(out)
     return None if best is None else best[1]
 
 

@@ -45,7 +45,7 @@ typedef enum {
     DQ_ERR_UNSUPPORTED = -3  /* valid request outside what this build implements */
 } DqStatus;
 
-#define DQ_ABI_VERSION 28
+#define DQ_ABI_VERSION 29
 
 int dq_abi_version(void);
 /* Thread-local, never NULL. */
@@ -253,6 +253,33 @@ int dq_dag_rank(void* dag, uint64_t tile, int cap, const int* indeg, const int* 
  * Returns the number of candidates (0 when the pass is full: *base >= cap). */
 int dq_dag_grow_step(void* dag, uint64_t tile, int cap, const int* indeg, const int* ready, int nready, int* base, int* cand_q,
                      int* cand_w, int* cand_count);
+/* ABI 29.  The whole beam search over tiles in one call (fusion._plan_tiles: every beam state -- a front of the DAG -- is
+ * extended by the greedy tile and by branch - 1 randomised ones, `width` states survive), from the front (indeg, ready).
+ * Writes one mask per pass to tiles_out -- the gathered qubits, or with free_low = L > 0 the WHOLE tile, which then shares
+ * at least L qubits with the tile before (the first with `low`); ~0 = a gate that runs on its own -- and returns how many.
+ * priced = 0: the states that have retired the most gates survive (the tile lists of the Python search, seed for seed).
+ * priced = 1: a state also carries modelled milliseconds (dq_plan_pass_ms), and the states with the least modelled time per
+ * retired gate survive (equal: more gates).  A tile's price there is an estimate: pass_valu + the gate_valu of the gates it
+ * retires for the VALU side, and for the memory side the qubits of `known_zero` that no non-diagonal gate has targeted yet
+ * -- outside the tile each halves the tiles that run, inside it each halves what a tile reads.  tiles_full = tiles of a
+ * full pass (all samples).  *model_ms (may be NULL) = the estimate for the returned plan. */
+typedef struct DqPlanParams {
+    uint64_t low;        /* the contiguous low qubits */
+    uint64_t known_zero; /* priced: qubits known to be |0> in the input */
+    int64_t seed;        /* of the randomised branches, 0 .. 2^32 - 1 */
+    int32_t hcap, cap, width, branch;
+    int32_t far_bit, max_far; /* at most max_far gathered qubits >= far_bit; max_far < 0: no limit */
+    int32_t free_low, priced;
+    const float* gate_valu; /* priced: VALU instructions per tile of every gate (dq_wave_gate_valu) */
+    double pass_valu;       /* priced: ... of a pass's layout changes */
+    double tiles_full;
+    double rate; /* priced = 2: milliseconds per gate of a schedule in hand; the states most ahead of that rate survive */
+} DqPlanParams;
+int dq_dag_plan(void* dag, const DqPlanParams* prm, const int* indeg, const int* ready, int nready, uint64_t* tiles_out,
+                int max_tiles, double* model_ms);
+/* The pass-cost model (constants and their sources: csrc/dq_plan.hip): milliseconds of a wave-tile pass that executes `valu`
+ * VALU instructions per tile and moves `bytes_moved` bytes (all samples together). */
+double dq_plan_pass_ms(double valu, double bytes_moved);
 
 /* The deferred form of the uncontrolled Rx-like gates of a complex64 pass (DQ_MODE_RX above), in place, in the matrix
  * buffer the passes will read: for every sample b < batch and every k < count the block of four complex numbers at
@@ -272,6 +299,18 @@ int dq_defer_rx_c64(void* mats, int64_t mat_batch_stride, const int64_t* index, 
  * read / write base; zero here) + 3 reserved words, then the 32-byte records (word 0 = handler id, csrc/dq_wave_asm.inc).  At most `max_bytes` are copied to `out` (may be NULL); returns the size,
  * or a negative DqStatus.  tests/_wave_emulator.py executes such a descriptor on the CPU. */
 int dq_wave_descriptor(const DqFusedPass* pass, int n, uint64_t known_zero, void* out, int max_bytes);
+/* ABI 29, no device needed: what the pass-cost model needs to know of `pass` run on a state whose index bits `known_zero`
+ * (read side) are |0>.  *valu = VALU instructions a wave executes per tile: the generated per-handler table
+ * (dq_wave_handler_valu) summed over the pass's records; *bytes_moved = bytes read + written PER SAMPLE, from the
+ * descriptor's zero-extension word: the tiles that run are written whole and read less what known-|0> bits inside the tile
+ * leave unloaded.  Either may be NULL. */
+int dq_wave_pass_cost(const DqFusedPass* pass, int n, uint64_t known_zero, int64_t* valu, double* bytes_moved);
+/* One entry of that table (tools/gen_wave_asm.py, gen_wave_asm64.py: handler_valu); -1 for an id the kernel does not have. */
+int dq_wave_handler_valu(int is_c128, int id);
+/* The planner's per-gate estimate: the table's entry for a gate of `opclass` on a middle slot -- 0 diagonal, 1 + mode a
+ * 2x2 matrix without controls (mode 0 .. 3), 5 a 2x2 matrix with controls, 6 X, 7 X with controls, 8 a layout change of the
+ * widest kind; -1 otherwise. */
+int dq_wave_gate_valu(int is_c128, int opclass);
 /* `pass` is a HOST pointer; it is copied into the kernel argument segment.  in == out allowed.
  * Requires n >= pass->m. */
 int dq_apply_fused_c64(const void* in, void* out, const void* mats, int64_t mat_batch_stride, int n,

@@ -251,6 +251,21 @@ def handlers():
     return h
 
 
+def handler_valu():
+    """VALU instructions a wave EXECUTES in the body of every handler id (0 for the ids whose bodies are not in
+    `handlers()`: diagonal gates and two-target gates, reached through their own entry code).  The pass-cost model's
+    counting rule (tools/pass_cost_model.py): a masked body runs whole; of the two variants of a deferred Rx body one
+    runs (each has half the instructions less the shared factor update); a handler with controls pays two more for
+    its exec mask.  Emitted as kWaveValu into dq_wave_valu.inc, where dq_wave_pass_cost reads it."""
+    out_ = [0] * NIDS
+    for i, (ctl, lines) in handlers().items():
+        v = sum(1 for ln in lines if ln.lstrip().startswith('v_'))
+        if ID_GEN_U + 2 * R <= i < ID_GEN_U + 3 * R:
+            v = v // 2 - 1
+        out_[i] = v + (2 if ctl else 0)
+    return out_
+
+
 PH0, PH1 = 'v[10:11]', 'v[12:13]'
 
 
@@ -779,4 +794,10 @@ out += ['// kg = address of the records, gend = their size in bytes; mb + moff =
         '}', '// clang-format on', '']
 path = os.environ.get('DQ_ASM_OUT') or os.path.join(os.path.dirname(__file__), '..', 'deepquantum_amd', 'csrc', 'dq_wave_asm.inc')
 open(path, 'w').write('\n'.join(out))
+# the pass-cost model's table in a small file of its own, next to the kernel body (a scratch output keeps it beside itself)
+vpath = path + '.valu' if os.environ.get('DQ_ASM_OUT') else os.path.join(os.path.dirname(path), 'dq_wave_valu.inc')
+open(vpath, 'w').write('\n'.join([
+    '// GENERATED by tools/gen_wave_asm.py -- do not edit by hand.',
+    '// VALU instructions a wave executes per handler id (handler_valu in the generator): the pass-cost model',
+    'static const unsigned short kWaveValu[DQ_WAVE_NIDS] = {' + ', '.join(str(v) for v in handler_valu()) + '};', '']))
 print('generated', len(out), 'lines;', NIDS, 'handler ids;', sum(len(v[1]) for v in handlers().values()), 'handler instructions')

@@ -184,6 +184,16 @@ def handlers():
     return h
 
 
+def handler_valu():
+    """VALU instructions a wave EXECUTES in the body of every handler id, by the counting rule of the complex64 generator
+    (0 for ids without a body in `handlers()`; masked bodies whole; two more for a handler with controls).  No body here
+    has two variants.  Emitted as kWave64Valu into dq_wave_valu64.inc."""
+    out_ = [0] * NIDS
+    for i, (ctl, lines) in handlers().items():
+        out_[i] = sum(1 for ln in lines if ln.lstrip().startswith('v_')) + (2 if ctl else 0)
+    return out_
+
+
 PH0, PH1 = ('v[6:7]', 'v[8:9]'), ('v[32:33]', 'v[34:35]')        # (re, im) as f64 pairs
 
 
@@ -601,4 +611,9 @@ if __name__ == '__main__' or os.environ.get('DQ_ASM_OUT'):
             '}', '// clang-format on', '']
     path = os.environ.get('DQ_ASM_OUT') or os.path.join(os.path.dirname(__file__), '..', 'deepquantum_amd', 'csrc', 'dq_wave_asm64.inc')
     open(path, 'w').write('\n'.join(out))
+    vpath = path + '.valu' if os.environ.get('DQ_ASM_OUT') else os.path.join(os.path.dirname(path), 'dq_wave_valu64.inc')
+    open(vpath, 'w').write('\n'.join([
+        '// GENERATED by tools/gen_wave_asm64.py -- do not edit by hand.',
+        '// VALU instructions a wave executes per handler id (handler_valu in the generator): the pass-cost model',
+        'static const unsigned short kWave64Valu[DQ_WAVE64_NIDS] = {' + ', '.join(str(v) for v in handler_valu()) + '};', '']))
     print('generated', NIDS, 'handler ids;', sum(len(v[1]) for v in handlers().values()), 'handler instructions')

@@ -12,16 +12,18 @@ import _wave_emulator as emu
 
 
 def handler_costs(g):
-    """{handler id: (VALU, DS, SALU) instructions a wave EXECUTES in its body}: masked bodies run whole; of the two variants
-    of a deferred Rx body (f [[1, it], [it, 1]] / f [[it, 1], [1, it]]) one runs."""
+    """{handler id: (VALU, DS, SALU) instructions a wave EXECUTES in its body}.  The VALU column is the library's own table
+    (dq_wave_handler_valu: emitted by the generators into csrc/dq_wave_valu*.inc, the one dq_wave_pass_cost sums), so this tool and
+    the planner cannot disagree; its rule: masked bodies run whole; of the two variants of a deferred Rx body
+    (f [[1, it], [it, 1]] / f [[it, 1], [1, it]]) one runs; a handler with controls pays two more for its exec mask."""
+    from deepquantum_amd import _lib
+    lib = _lib.load()
+    c128 = 1 if getattr(g, 'ELEM', 8) == 16 else 0
     out = {}
     for i, (ctl, lines) in g.handlers().items():
-        v = sum(1 for ln in lines if ln.lstrip().startswith('v_'))
-        if g.ID_GEN_U + 12 <= i < g.ID_GEN_U + 18:
-            v = v // 2 - 1
         d = sum(1 for ln in lines if ln.lstrip().startswith('ds_'))
         s = sum(1 for ln in lines if ln.lstrip().startswith('s_'))
-        out[i] = (v + (2 if ctl else 0), d, s + (6 if ctl else 0))
+        out[i] = (lib.dq_wave_handler_valu(c128, i), d, s + (6 if ctl else 0))
     return out
 
 
@@ -47,16 +49,25 @@ def headline_steps(n=28, depth=40, seed=1234, wide=True):
 
 
 def pass_counts(steps, n):
+    """Per pass: records, VALU instructions per tile (dq_wave_pass_cost), DS instructions, the handler ids in walking order
+    (a layout change is two records; the second holds addresses, not an id)."""
+    import ctypes as C
+    from deepquantum_amd import _lib
+    lib = _lib.load()
     g = emu.gen()
     hc = handler_costs(g)
     rows = []
     for st in steps:
         kp = emu.descriptor(st.desc, n)
-        ids = [kp.rec[j][0] for j in range(kp.nrec_bytes // 32)]
-        v = sum(hc.get(i, (0, 0, 0))[0] for i in ids)
+        ids, j, nrec = [], 0, kp.nrec_bytes // 32
+        while j < nrec:
+            ids.append(kp.rec[j][0])
+            j += 2 if g.ID_TRIP0 <= ids[-1] < g.ID_SWAP else 1
+        v = C.c_int64(0)
+        assert lib.dq_wave_pass_cost(C.byref(st.desc), n, 0, C.addressof(v), None) == 0
         d = sum(hc.get(i, (0, 0, 0))[1] for i in ids)
         unknown = [i for i in ids if i not in hc]
-        rows.append({'records': len(ids), 'valu': v, 'ds': d, 'unknown': len(unknown), 'ids': ids})
+        rows.append({'records': nrec, 'valu': v.value, 'ds': d, 'unknown': len(unknown), 'ids': ids})
     return rows
 
 
