@@ -24,7 +24,7 @@ from .channel import (
     AmplitudeDamping, BitFlip, Depolarizing, GeneralizedAmplitudeDamping, Pauli, PhaseDamping, PhaseFlip,
 )
 from .gate import (
-    CNOT, ArbitraryGate, Barrier, CombinedSingleGate, DoubleControlGate, DoubleGate, Fredkin, Hadamard,
+    CNOT, ArbitraryGate, Barrier, CombinedSingleGate, CostPhase, DiagonalGate, DoubleControlGate, DoubleGate, Fredkin, Hadamard,
     HamiltonianGate, Identity, ImaginarySwap, LatentGate, ParametricDoubleGate, ParametricSingleGate, PauliX, PauliY,
     PauliZ, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate,
     SingleGate, Swap, TDaggerGate, TGate, Toffoli, TripleGate, U3Gate, UAnyGate,
@@ -34,7 +34,7 @@ from .layer import (
     U3Layer, XLayer, YLayer, ZLayer,
 )
 from .operation import Channel, Gate, Layer, Operation
-from .qmath import amplitude_encoding, expectation, measure, meyer_wallach_measure, multi_kron, partial_trace
+from .qmath import amplitude_encoding, expectation, expectation_cost, ising_cost, measure, meyer_wallach_measure, multi_kron, partial_trace
 from .state import DistributedQubitState, QubitState
 from .utils import CapturedGraph, dtype_map
 from . import qasm3  # noqa: E402  (after the circuit classes it builds on)

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DQHIP_LIBRARY') or os.path.join(_HERE, 'libdqhip.so')
 
 DQ_OK = 0
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 # enum DqFusedKind / DqBitLoc (include/dq_hip.h)
 FG_GEN1, FG_X1, FG_DIAG1, FG_GEN2, FG_DIAG2, FG_RESERVED5, FG_GRAD, FG_EXPZ = range(8)
@@ -33,6 +33,7 @@ ROUND_TRANSPOSE = 0x01
 ROUND_TRANSPOSE_AFTER = 0x02
 FAST_NONE = 0xFFFFFFFF
 MAT_PAD = 16
+COST_PHASE, COST_SCALE = range(2)      # op of dq_apply_cost_*
 
 
 class DqFusedGate(C.Structure):
@@ -147,6 +148,10 @@ _SIGNATURES = {
     'dq_rdmk_cross_{s}': (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),
     'dq_sample_ws_bytes': (_i64, [_i, _i64, _i]),
     'dq_sample_{s}': (_i, [_vp, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    'dq_apply_diag_{s}': (_i, [_vp, _vp, _vp, _i64, _i, _ip, _i, _ip, _i, _i64, _vp]),
+    'dq_apply_cost_{s}': (_i, [_vp, _vp, _vp, _vp, _i, _i, _ip, _i, _ip, _i, _i64, _vp]),
+    'dq_cost_cross_ws_bytes': (_i64, [_i, _i64, _i, _i]),
+    'dq_cost_cross_{s}': (_i, [_vp, _vp, _vp, _i, _ip, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

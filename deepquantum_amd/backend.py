@@ -837,3 +837,189 @@ def _scale_z_signs_wide(state: torch.Tensor, zmasks: Sequence[int], coef: torch.
         wide = scale_z_signs(src[r0:r0 + rows].to(torch.complex128), zmasks, coef[r0:r0 + rows])
         dst[r0:r0 + rows].copy_(wide)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Diagonal operators on any number of wires (csrc/dq_diag.hip): table index sub(i) = sum_j bit_{bits[j]}(i) << (k-1-j)
+def _diag_args(state: torch.Tensor, bits: Sequence[int], controls: Sequence[int], what: str) -> tuple[int, list[int], list[int]]:
+    n = _nqubit(state)
+    bits, controls = [int(b) for b in bits], [int(c) for c in controls]
+    if not state.is_contiguous():
+        raise ValueError(f'{what}: state must be contiguous')
+    if not bits:
+        raise ValueError(f'{what}: at least one table bit is needed')
+    both = bits + controls
+    if len(set(both)) != len(both) or any(p < 0 or p >= n for p in both):
+        raise ValueError(f'{what}: bits {bits} / controls {controls} must be distinct positions in [0, {n})')
+    return n, bits, controls
+
+
+def _diag_table(table: torch.Tensor, like: torch.Tensor, dtype: torch.dtype, k: int, what: str, batched: bool) -> torch.Tensor:
+    """The table in ``dtype`` on the state's device, contiguous and 16-byte aligned: (2^k,), or (B, 2^k) when ``batched``
+    admits one table per sample."""
+    d = 1 << k
+    ok = table.shape == (d,) or (batched and table.ndim == 2 and table.shape[1] == d and table.shape[0] in (1, like.shape[0]))
+    if not ok:
+        raise ValueError(f'{what}: a table over {k} bits has {d} entries' + (f', or ({like.shape[0]}, {d})' if batched else '')
+                         + f'; got {tuple(table.shape)}')
+    if table.requires_grad:
+        raise ValueError(f'{what}: the table is a constant -- gradients with respect to its entries are not supported; '
+                         'detach() it')
+    table = table.to(device=like.device, dtype=dtype).resolve_conj().resolve_neg().contiguous()
+    if table.is_cuda and table.data_ptr() % 16:
+        table = table.clone()
+    return table
+
+
+def _sub_index(n: int, bits: Sequence[int], controls: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor]:
+    """sub(i) and the control test for every i (CPU test double only)."""
+    i = torch.arange(1 << n)
+    k = len(bits)
+    sub = torch.zeros_like(i)
+    for j, p in enumerate(bits):
+        sub |= ((i >> p) & 1) << (k - 1 - j)
+    cmask = sum(1 << c for c in controls)
+    return sub, (i & cmask) == cmask
+
+
+def apply_diag(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = (),
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[b, i] = diag[b, sub(i)] * state[b, i] on the amplitudes whose ``controls`` are all 1 (the others pass through):
+    a diagonal operator on k = len(bits) index bits, ``bits[0]`` the most significant bit of the table index, in one read
+    and one write of the state (``dq_apply_diag_*``).  ``diag``: complex (2^k,) or (B, 2^k); ``out`` may be ``state``."""
+    n, bits, controls = _diag_args(state, bits, controls, 'apply_diag')
+    k = len(bits)
+    diag = _diag_table(diag, state, state.dtype, k, 'apply_diag', True)
+    if out is None:
+        out = torch.empty_like(state)
+    if not _use_hip(state):
+        return _diag_double(lambda: _apply_diag_double(state, diag, n, bits, controls, out))
+    stride = (1 << k) if (diag.ndim == 2 and diag.shape[0] > 1) else 0
+    fn = getattr(_lib.load(), f'dq_apply_diag_{_suffix(state)}')
+    for lo in range(0, state.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, state.shape[0])
+        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(diag[lo:hi] if stride else diag), stride, n, _lib.int_array(bits), k,
+                _lib.int_array(controls), len(controls), hi - lo, _stream(state))
+        _lib.check(rc, 'dq_apply_diag')
+    return out
+
+
+def _diag_double(fn):
+    """The plain-torch complex128 stand-ins below, for the CPU test double (tests only): like the double itself
+    (``_NoGraph``) they build no graph and carry no forward-mode tangent."""
+    was = torch._C._is_fwd_grad_enabled()
+    torch._C._set_fwd_grad_enabled(False)
+    try:
+        with torch.no_grad():
+            return fn()
+    finally:
+        torch._C._set_fwd_grad_enabled(was)
+
+
+def _apply_diag_double(state, diag, n, bits, controls, out):
+    k = len(bits)
+    sub, ok = _sub_index(n, bits, controls)
+    f = diag.reshape(-1, 1 << k).to(torch.complex128)[:, sub]
+    out.copy_(torch.where(ok, f * state.to(torch.complex128), state.to(torch.complex128)).to(state.dtype))
+    return out
+
+
+#: complex128 PHASE goes through a table of phases when the table has at most 2^16 entries, the state at least 2^8
+#: amplitudes per entry and at least 2^24 amplitudes per sample: the table route is three launches for one, and up to
+#: n = 22 it measured 1.2 to 1.6 times slower than forming the phase in flight, at n = 24 1.3 times faster (`apply_cost`;
+#: the sweep over n is in DESIGN.md section 4.8)
+PHASE_TABLE_MAX_BITS, PHASE_TABLE_MIN_REST, PHASE_TABLE_MIN_QUBITS = 16, 8, 24
+
+
+def apply_cost(state: torch.Tensor, cost: torch.Tensor, par: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = (),
+               op: str = 'phase', out: torch.Tensor | None = None) -> torch.Tensor:
+    """A real table ``cost`` (2^k,) over the index bits ``bits`` applied to the state (``dq_apply_cost_*``):
+
+    * ``op='phase'``: out[b, i] = exp(-i par[b] cost[sub(i)]) state[b, i], ``par`` real (B,); amplitudes outside the
+      controls pass through.  The angle is formed and reduced in double for both precisions.
+    * ``op='scale'``: out[b, i] = par[b] cost[sub(i)] state[b, i], ``par`` complex (B,); amplitudes outside the controls
+      come out as 0 (the cotangent of :func:`cost_cross`, which leaves them out)."""
+    if op not in ('phase', 'scale'):
+        raise ValueError(f"apply_cost: op must be 'phase' or 'scale', got {op!r}")
+    n, bits, controls = _diag_args(state, bits, controls, 'apply_cost')
+    k = len(bits)
+    cost = _diag_table(cost, state, state.real.dtype, k, 'apply_cost', False)
+    if par.shape != (state.shape[0],):
+        raise ValueError(f'apply_cost: one parameter per sample, ({state.shape[0]},), expected; got {tuple(par.shape)}')
+    if op == 'phase' and par.is_complex():
+        raise ValueError('apply_cost: the phase parameter is real')
+    if out is None:
+        out = torch.empty_like(state)
+    if not _use_hip(state):
+        def double():
+            sub, ok = _sub_index(n, bits, controls)
+            c = cost.to(torch.float64)[sub]
+            x = state.to(torch.complex128)
+            if op == 'phase':
+                y = torch.where(ok, torch.exp(-1j * par.to(torch.float64).reshape(-1, 1) * c) * x, x)
+            else:
+                y = torch.where(ok, par.to(torch.complex128).reshape(-1, 1) * c * x, torch.zeros_like(x))
+            out.copy_(y.to(state.dtype))
+            return out
+
+        return _diag_double(double)
+    if op == 'phase':
+        p = par.to(device=state.device, dtype=torch.float64).contiguous()
+    else:
+        p = torch.view_as_real(par.to(device=state.device, dtype=torch.complex128).resolve_conj().resolve_neg().contiguous())
+    fn = getattr(_lib.load(), f'dq_apply_cost_{_suffix(state)}')
+    code = _lib.COST_PHASE if op == 'phase' else _lib.COST_SCALE
+    # complex128 phases of a small table: exp(-i t cost) once per table entry and sample -- the same kernel on a vector of
+    # ones over the k table bits -- then the diagonal kernel, so that no double-precision sine and cosine is taken per
+    # amplitude (measured: DESIGN.md section 4.8).  complex64 forms the phase in flight at every k: it is the faster there.
+    via_table = (op == 'phase' and state.dtype == torch.complex128 and k <= PHASE_TABLE_MAX_BITS
+                 and n >= max(k + PHASE_TABLE_MIN_REST, PHASE_TABLE_MIN_QUBITS))
+    for lo in range(0, state.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, state.shape[0])
+        if via_table:
+            table = torch.ones(hi - lo, 1 << k, dtype=state.dtype, device=state.device)
+            rc = fn(_ptr(table), _ptr(table), _ptr(cost), _ptr(p[lo:hi]), code, k, _lib.int_array(range(k - 1, -1, -1)), k,
+                    _lib.int_array([]), 0, hi - lo, _stream(state))
+            _lib.check(rc, 'dq_apply_cost')
+            rc = getattr(_lib.load(), f'dq_apply_diag_{_suffix(state)}')(
+                _ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(table), 1 << k, n, _lib.int_array(bits), k,
+                _lib.int_array(controls), len(controls), hi - lo, _stream(state))
+            _lib.check(rc, 'dq_apply_diag')
+            continue
+        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(cost), _ptr(p[lo:hi]), code, n, _lib.int_array(bits), k,
+                _lib.int_array(controls), len(controls), hi - lo, _stream(state))
+        _lib.check(rc, 'dq_apply_cost')
+    return out
+
+
+def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: Sequence[int],
+               controls: Sequence[int] = ()) -> torch.Tensor:
+    """out[b] = sum over the amplitudes whose ``controls`` are all 1 of cost[sub(i)] conj(bra[b, i]) ket[b, i]: complex128
+    (B,), accumulated in double, bitwise reproducible (``dq_cost_cross_*``).  ``bra`` and ``ket`` the same buffer: one read
+    of the state, the expectation value <C>.  The workspace comes from PyTorch's allocator (legal under capture)."""
+    n, bits, controls = _diag_args(ket, bits, controls, 'cost_cross')
+    k = len(bits)
+    if bra.shape != ket.shape or bra.dtype != ket.dtype:
+        raise ValueError('cost_cross: bra/ket must be (batch, 2**n) tensors of one shape and dtype')
+    if not bra.is_contiguous():
+        raise ValueError('cost_cross: bra must be contiguous')
+    cost = _diag_table(cost, ket, ket.real.dtype, k, 'cost_cross', False)
+    if not _use_hip(ket):
+        def double():
+            sub, ok = _sub_index(n, bits, controls)
+            w = cost.to(torch.float64)[sub] * ok
+            return (w * bra.to(torch.complex128).conj() * ket.to(torch.complex128)).sum(dim=-1)
+
+        return _diag_double(double)
+    lib = _lib.load()
+    fn = getattr(lib, f'dq_cost_cross_{_suffix(ket)}')
+    same = bra.data_ptr() == ket.data_ptr()
+    out = torch.empty(ket.shape[0], 2, dtype=torch.float64, device=ket.device)
+    for lo in range(0, ket.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, ket.shape[0])
+        nbytes = lib.dq_cost_cross_ws_bytes(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
+        rc = fn(_ptr(bra[lo:hi]), _ptr(ket[lo:hi]), _ptr(cost), n, _lib.int_array(bits), k, _lib.int_array(controls),
+                len(controls), hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
+        _lib.check(rc, 'dq_cost_cross')
+    return torch.view_as_complex(out)

@@ -26,7 +26,7 @@ from torch import nn
 
 from . import _functorch, executor, ops, qmath
 from .gate import (
-    CNOT, Barrier, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, PauliX, PauliY, PauliZ,
+    CNOT, Barrier, CostPhase, DiagonalGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, PauliX, PauliY, PauliZ,
     PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
     TDaggerGate, TGate, Toffoli, U3Gate, UAnyGate,
 )
@@ -37,6 +37,12 @@ from .channel import (
 from .operation import Channel, Gate, Layer, Operation
 from .qmath import amplitude_encoding, sample2expval, slice_state_vector
 from .state import DistributedQubitState, QubitState
+
+
+def _runs_flat(op: Any) -> bool:
+    """The operator has no matrix primitive: it runs through ``apply_flat`` between two fused stretches -- ``Reset``
+    (``_state_dependent``: its matrices depend on the state) and the diagonal gates (``_runs_flat``: a stand-alone pass)."""
+    return getattr(op, '_state_dependent', False) or getattr(op, '_runs_flat', False)
 
 
 class QubitCircuit(Operation):
@@ -146,7 +152,7 @@ class QubitCircuit(Operation):
 
     def _run_operators(self, flat: torch.Tensor, zero: bool = False) -> torch.Tensor:
         """All operators on a (B, 2**n) state: maximal stretches of gates go to the executor (fused passes),
-        state-dependent operations (``Reset``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
+        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
         density matrix alike: index 0 is 1, everything else 0)."""
         if self.den_mat:
             prims = []
@@ -157,8 +163,7 @@ class QubitCircuit(Operation):
         last = id(self.operators[-1]) if nops else 0
         dep = self.__dict__.get('_state_dep')          # (operators it was computed for: how many, the last one; answer)
         if dep is None or dep[0] != nops or dep[1] != last:
-            dep = self.__dict__['_state_dep'] = (nops, last,
-                                                  any(getattr(op, '_state_dependent', False) for op in self.operators))
+            dep = self.__dict__['_state_dep'] = (nops, last, any(_runs_flat(op) for op in self.operators))
         if not dep[2]:
             # no-grad runs: the Z-type observables' values come out of the last pass (executor.run(expect_z=...))
             self._expz = None
@@ -173,7 +178,7 @@ class QubitCircuit(Operation):
             return out
         x, pending = flat, []
         for op in self.operators:
-            if getattr(op, '_state_dependent', False):
+            if _runs_flat(op):
                 if pending:
                     x, pending = executor.run(x, pending, zero_state=zero), []
                 zero = False
@@ -386,6 +391,15 @@ class QubitCircuit(Operation):
         val = qmath._entropy_of(rho, alpha, base, tau).to(rho.real.dtype)
         return val.squeeze(0) if single else val
 
+    def expectation_cost(self, cost: torch.Tensor, wires: int | list[int] | None = None) -> torch.Tensor:
+        """``<C> = sum_i cost[sub(i)] |psi_i|^2`` of the final state of the last forward for a classical cost table over
+        ``wires`` (all by default): (B,) real, or 0-d for a single state; see :func:`qmath.expectation_cost`."""
+        if self.state is None:
+            raise RuntimeError('expectation_cost: run the circuit first')
+        if self.den_mat:
+            raise NotImplementedError('expectation_cost: den_mat=True (density matrices) is not supported')
+        return qmath.expectation_cost(self.state, self.nqubit, cost, wires)
+
     def expectation(self, shots: int | None = None) -> torch.Tensor:
         """Expectation value of every registered observable, stacked on the last dimension
         (reference: circuit.py:381-428)."""
@@ -470,6 +484,11 @@ class QubitCircuit(Operation):
         ops_ = [op for op in self.operators if not isinstance(op, Barrier)]
         if not ops_:
             return torch.eye(2**self.nqubit, dtype=torch.cfloat)
+        flat = [op for op in ops_ if getattr(op, '_runs_flat', False)]
+        if flat:             # (no matrix primitive: the columns of the identity go through the circuit as a batch)
+            dtype, device = flat[0]._state_like()
+            cols = self._run_operators(torch.eye(2**self.nqubit, dtype=dtype, device=device))
+            return cols.T.contiguous() if not cols.requires_grad else cols.T
         prims = self.prims(decompose=True)
         if not prims:
             return torch.eye(2**self.nqubit, dtype=torch.cfloat)
@@ -717,6 +736,19 @@ class QubitCircuit(Operation):
         self.add(HamiltonianGate(hamiltonian=hamiltonian, t=t, nqubit=self.nqubit, wires=wires, minmax=minmax,
                                  controls=controls, name=name, requires_grad=requires_grad), encode=encode)
 
+    def diagonal(self, diag, wires=None, minmax=None, controls=None, name='diagonal'):
+        """A fixed diagonal unitary given by its 2^k entries (``wires[0]`` = the entry index's most significant bit; all
+        wires by default): see :class:`DiagonalGate`."""
+        self.add(DiagonalGate(diag=diag, nqubit=self.nqubit, wires=wires, minmax=minmax, controls=controls, name=name,
+                              den_mat=self.den_mat))
+
+    def cost_phase(self, cost, wires=None, minmax=None, inputs=None, controls=None, encode=False, name='cost_phase'):
+        """``exp(-i t diag(cost))`` for a table of 2^k real costs (all wires by default) with one parameter ``t``: trainable,
+        given by ``inputs``, or fed from ``data`` with ``encode=True``: see :class:`CostPhase`."""
+        requires_grad = (not encode) and inputs is None
+        self.add(CostPhase(cost=cost, nqubit=self.nqubit, wires=wires, minmax=minmax, inputs=inputs, controls=controls,
+                           name=name, den_mat=self.den_mat, requires_grad=requires_grad), encode=encode)
+
     # layers
     def xlayer(self, wires=None):
         self.add(XLayer(nqubit=self.nqubit, wires=wires))
@@ -770,6 +802,9 @@ class QubitCircuit(Operation):
         """OpenQASM 2.0 text of the circuit (reference: circuit.py:570-627)."""
         from .qasm3 import cir_to_qasm2
 
+        for op in self.operators:
+            if getattr(op, '_runs_flat', False):
+                op.qasm_refusal()
         return cir_to_qasm2(self)
 
     # noise channels (density matrices only; reference: circuit.py:1540-1601) ---------------------------

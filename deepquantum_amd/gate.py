@@ -906,6 +906,159 @@ class HamiltonianGate(ArbitraryGate):
         self.update_matrix()
 
 
+class _FlatGate:
+    """Mixin of the gates that have no matrix primitive and run through ``apply_flat`` -- (B, 2**n) -> (B, 2**n) -- between
+    two fused stretches of a circuit (``QubitCircuit._run_operators``; ``Reset`` uses the same seam under its older
+    name ``_state_dependent``).  What has no route yet is refused by name."""
+
+    _runs_flat = True
+
+    def _refuse(self, what: str):
+        raise NotImplementedError(f'{type(self).__name__}: {what} is not supported (the gate runs as a stand-alone pass over '
+                                  'a state vector on one device)')
+
+    def prims(self, decompose: bool = True) -> list[Prim]:
+        self._refuse('a matrix primitive -- fused passes, DistributedQubitCircuit (sharded states) --')
+
+    def dm_prims(self, decompose: bool = True) -> list[Prim]:
+        self._refuse('den_mat=True (density matrices)')
+
+    def op_den_mat(self, x: torch.Tensor) -> torch.Tensor:
+        self._refuse('den_mat=True (density matrices)')
+
+    def op_dist_state(self, x):
+        self._refuse('DistributedQubitCircuit (a sharded state)')
+
+    def qasm_refusal(self):
+        self._refuse('qasm()')
+
+    def op_state(self, x: torch.Tensor) -> torch.Tensor:
+        shape = x.shape
+        return self.apply_flat(x.reshape(shape[0], -1)).reshape(shape)
+
+    def _state_like(self) -> tuple[torch.dtype, torch.device]:
+        """Complex dtype and device of the states the gate's table belongs to."""
+        t = self._table()
+        return (t.dtype if t.is_complex() else (torch.complex128 if t.dtype == torch.float64 else torch.complex64)), t.device
+
+    def get_unitary(self) -> torch.Tensor:
+        dtype, device = self._state_like()
+        with torch.no_grad():
+            cols = self.apply_flat(torch.eye(2**self.nqubit, dtype=dtype, device=device))
+        return cols.T.contiguous()
+
+
+class DiagonalGate(_FlatGate, ArbitraryGate):
+    """A fixed diagonal unitary on ``wires`` / ``minmax`` given by its 2^k complex entries, ``wires[0]`` the most significant
+    bit of the entry index (the matrix convention of ``UAnyGate``): one multiplication per amplitude, one read and one write
+    of the state for any k up to n (``dq_apply_diag_*``) -- a phase oracle over all wires, where a dense matrix has no
+    route beyond 10.  The entries' moduli are checked to the 1e-4 that ``UAnyGate`` applies to its matrix."""
+
+    def __init__(self, diag, nqubit=1, wires=None, minmax=None, controls=None, name='DiagonalGate', den_mat=False,
+                 tsr_mode=False):
+        super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
+                         tsr_mode=tsr_mode)
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        if not isinstance(diag, torch.Tensor):
+            diag = torch.tensor(diag, dtype=torch.cfloat)
+        if diag.requires_grad:
+            raise ValueError('DiagonalGate: the table is a constant -- gradients with respect to its entries are not '
+                             'supported; detach() it')
+        if not diag.is_complex():
+            diag = diag.to(torch.cdouble if diag.dtype == torch.float64 else torch.cfloat)
+        diag = diag.reshape(-1)
+        assert diag.shape[0] == 2 ** len(self.wires), f'a diagonal on {len(self.wires)} wires has {2 ** len(self.wires)} entries'
+        assert torch.allclose(diag.abs(), torch.ones_like(diag.real), rtol=1e-5, atol=1e-4), 'Please check the diagonal entries'
+        self.register_buffer('diag', diag)
+
+    def _table(self) -> torch.Tensor:
+        return self.diag
+
+    def _apply(self, fn: Any, *args, **kwargs):
+        from .utils import complex_apply
+
+        held = {'diag': self._buffers.pop('diag')}
+        nn.Module._apply(self, fn, *args, **kwargs)
+        for key, value in complex_apply(fn, held).items():
+            self.register_buffer(key, value)
+        return self
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        diag = self.diag.conj().resolve_conj() if self.inv_mode else self.diag
+        return ops.diag_mul(x, diag, self._bits(self.wires), self._bits(self.controls))
+
+
+class CostPhase(_FlatGate, ArbitraryGate):
+    """``exp(-i t diag(cost))`` with one parameter ``t`` and a classical cost table of 2^k real entries over ``wires`` /
+    ``minmax`` (``wires[0]`` the most significant bit of the entry index): a whole QAOA cost layer -- any cost, not only a
+    short Ising polynomial -- in one read and one write of the state (``dq_apply_cost_*``).  ``t`` is trainable
+    (``requires_grad=True``), fixed (``inputs``), or fed from the circuit's data (``encode=True``; a batch of data gives one
+    ``t`` per sample).  The table is a constant: it carries no gradient.  The kernels read it in the state's real
+    precision, so keep it in that precision (``.to()`` of the circuit converts it along) to spare a conversion per
+    forward."""
+
+    _param_names = ('t',)
+
+    def __init__(self, cost, nqubit=1, wires=None, minmax=None, inputs=None, controls=None, name='CostPhase',
+                 den_mat=False, tsr_mode=False, requires_grad=False):
+        super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
+                         tsr_mode=tsr_mode)
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        if not isinstance(cost, torch.Tensor):
+            cost = torch.tensor(cost, dtype=torch.float)
+        if cost.requires_grad:
+            raise ValueError('CostPhase: the cost table is a constant -- gradients with respect to its entries are not '
+                             'supported; detach() it')
+        if cost.is_complex() or not cost.is_floating_point():
+            raise ValueError(f'CostPhase: the cost table must be real floating point, got {cost.dtype}')
+        cost = cost.reshape(-1)
+        assert cost.shape[0] == 2 ** len(self.wires), f'a cost on {len(self.wires)} wires has {2 ** len(self.wires)} entries'
+        self.register_buffer('cost', cost)
+        self.npara = 1
+        self.requires_grad = requires_grad
+        self.init_para(inputs)
+
+    def _table(self) -> torch.Tensor:
+        return self.cost
+
+    def inputs_to_tensor(self, inputs: Any = None) -> torch.Tensor:
+        while isinstance(inputs, list):
+            inputs = inputs[0]
+        if inputs is None:
+            return torch.rand(())
+        return _as_param_tensor(inputs)
+
+    def init_para(self, inputs: Any = None) -> None:
+        t = self.inputs_to_tensor(inputs)
+        if t.device != self.cost.device and not isinstance(t, nn.Parameter):
+            t = t.to(self.cost.device)
+        if self.requires_grad:
+            self.t = nn.Parameter(t)
+        else:
+            self.register_buffer('t', t)
+
+    def inverse(self) -> 'CostPhase':
+        return ArbitraryGate.inverse(self)          # (the copy shares t; `inv_mode` negates it where it is used)
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        t = -self.t if self.inv_mode else self.t
+        return ops.cost_phase(x, self.cost, t, self._bits(self.wires), self._bits(self.controls))
+
+    def extra_repr(self) -> str:
+        t = -self.t if self.inv_mode else self.t
+        val = t.item() if t.numel() == 1 else f'<batch of {t.numel()}>'
+        s = f'wires={self.wires}, t={val}'
+        return s if self.controls == [] else s + f', controls={self.controls}'
+
+
 class Reset(Gate):
     r"""Reset qubits to :math:`|0\rangle` (reference: gate.py:3027-3094).
 

@@ -631,3 +631,265 @@ def wire_sum(state: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
     if not _is_batched(mats):
         mats = mats.resolve_conj().resolve_neg().contiguous()
     return _WireSum.apply(state, mats)
+
+
+# ---- diagonal operators on any number of wires (csrc/dq_diag.hip) -------------------------------------------------------
+# Three operations with a real table c over the index bits `bits` (sub(i): backend.apply_diag), closed under
+# differentiation -- every backward and every jvp below is written with the other two -- so derivatives of any order
+# exist by construction:
+#     phase(x, c, t)[i] = exp(-i t c[sub(i)]) x[i]        (outside the controls: x[i])
+#     cross(a, b, c)    = sum_i c[sub(i)] conj(a[i]) b[i] (outside the controls: left out)
+#     scale(x, c, s)[i] = s c[sub(i)] x[i]                (outside the controls: 0)
+# The tables are constants: they carry no gradient.
+def _const_table(table: torch.Tensor, what: str) -> torch.Tensor:
+    if not isinstance(table, torch.Tensor):
+        raise ValueError(f'{what}: the table must be a tensor, got {type(table).__name__}')
+    if table.requires_grad:
+        raise ValueError(f'{what}: the table is a constant -- gradients with respect to its entries are not supported; '
+                         'detach() it')
+    return table
+
+
+def _unmapped_table(in_dim, what: str) -> None:
+    if in_dim is not None:
+        raise RuntimeError(f'deepquantum_amd: {what} under torch.vmap: the table must not be a mapped argument')
+
+
+def _per_sample(p: torch.Tensor, batch: int, dtype: torch.dtype, what: str) -> torch.Tensor:
+    """A 0-d, (1,) or (B,) parameter as (B,) in ``dtype`` (differentiably: a shared value gets the sum of the samples'
+    gradients from ``expand``)."""
+    p = p.to(dtype).reshape(-1)
+    if p.shape[0] == 1 and batch != 1:
+        p = p.expand(batch)
+    if p.shape[0] != batch:
+        raise ValueError(f'{what}: one parameter, or one per sample ({batch}), expected; got {p.shape[0]}')
+    return p
+
+
+class _CostPhase(torch.autograd.Function):
+    """y = exp(-i t c) x with t real (B,): cotangents gx = phase(gy, c, -t) and gt = Im cross(gy, y, c) (dy/dt = -i c y on
+    the controlled amplitudes, 0 elsewhere -- which cross leaves out)."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, cost: torch.Tensor, t: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
+        return backend.apply_cost(_plain(state), cost, _plain(t), bits, controls, 'phase')
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, cost, t, ctx.bits, ctx.controls = inputs
+        ctx.save_for_backward(state, cost, t)
+        ctx.save_for_forward(state, cost, t)
+
+    @staticmethod
+    def jvp(ctx, state_t, _cost_t, t_t, _bits_t, _controls_t):
+        _single_forward_level()
+        state, cost, t = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = cost_phase(state_t, cost, t, ctx.bits, ctx.controls)
+        if t_t is not None:
+            y = cost_phase(state, cost, t, ctx.bits, ctx.controls)
+            term = cost_scale(y, cost, -1j * t_t.to(torch.complex128), ctx.bits, ctx.controls)
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, cost, t = ctx.saved_tensors
+        gstate = gt = None
+        if ctx.needs_input_grad[0]:
+            gstate = cost_phase(gy, cost, -t, ctx.bits, ctx.controls)
+        if ctx.needs_input_grad[2]:
+            y = cost_phase(state, cost, t, ctx.bits, ctx.controls)
+            gt = cost_cross(gy, y, cost, ctx.bits, ctx.controls).imag.to(t.dtype)
+        return gstate, None, gt, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, cost, t, bits, controls):
+        _unmapped_table(in_dims[1], 'cost_phase')
+        v = info.batch_size
+        sf = _fold(state, in_dims[0], v)
+        out = _CostPhase.apply(sf, cost, _fold(t, in_dims[2], v), bits, controls)
+        return out.reshape(v, -1, out.shape[-1]), 0
+
+
+class _CostCross(torch.autograd.Function):
+    """z = sum_i c conj(a_i) b_i, complex128 (B,): anti-linear in a, linear in b; cotangents g_b = scale(a, c, gz) and
+    g_a = scale(b, c, conj(gz))."""
+
+    @staticmethod
+    def forward(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
+        pk = _plain(ket)
+        return backend.cost_cross(pk if bra is ket else _plain(bra), pk, cost, bits, controls)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        bra, ket, cost, ctx.bits, ctx.controls = inputs
+        ctx.save_for_backward(bra, ket, cost)
+        ctx.save_for_forward(bra, ket, cost)
+
+    @staticmethod
+    def jvp(ctx, bra_t, ket_t, _cost_t, _bits_t, _controls_t):
+        _single_forward_level()
+        bra, ket, cost = ctx.saved_tensors
+        out = None
+        if bra_t is not None:
+            out = cost_cross(bra_t, ket, cost, ctx.bits, ctx.controls)
+        if ket_t is not None:
+            term = cost_cross(bra, ket_t, cost, ctx.bits, ctx.controls)
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gz: torch.Tensor):
+        bra, ket, cost = ctx.saved_tensors
+        gz = gz.to(torch.complex128)
+        gbra = cost_scale(ket, cost, gz.conj(), ctx.bits, ctx.controls) if ctx.needs_input_grad[0] else None
+        gket = cost_scale(bra, cost, gz, ctx.bits, ctx.controls) if ctx.needs_input_grad[1] else None
+        return gbra, gket, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, bra, ket, cost, bits, controls):
+        _unmapped_table(in_dims[2], 'cost_cross')
+        v = info.batch_size
+        same = bra is ket and in_dims[0] == in_dims[1]
+        kf = _fold(ket, in_dims[1], v)
+        bf = kf if same else _fold(bra, in_dims[0], v)
+        out = _CostCross.apply(bf, kf, cost, bits, controls)
+        return out.reshape(v, -1), 0
+
+
+class _CostScale(torch.autograd.Function):
+    """y = s c x with s complex128 (B,), 0 outside the controls: cotangents gx = scale(gy, c, conj(s)) and
+    gs = cross(x, gy, c)."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, cost: torch.Tensor, s: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
+        return backend.apply_cost(_plain(state), cost, _plain(s), bits, controls, 'scale')
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, cost, s, ctx.bits, ctx.controls = inputs
+        ctx.save_for_backward(state, cost, s)
+        ctx.save_for_forward(state, cost, s)
+
+    @staticmethod
+    def jvp(ctx, state_t, _cost_t, s_t, _bits_t, _controls_t):
+        _single_forward_level()
+        state, cost, s = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = cost_scale(state_t, cost, s, ctx.bits, ctx.controls)
+        if s_t is not None:
+            term = cost_scale(state, cost, s_t, ctx.bits, ctx.controls)
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, cost, s = ctx.saved_tensors
+        gstate = gs = None
+        if ctx.needs_input_grad[0]:
+            gstate = cost_scale(gy, cost, s.conj(), ctx.bits, ctx.controls)
+        if ctx.needs_input_grad[2]:
+            gs = cost_cross(state, gy, cost, ctx.bits, ctx.controls).to(s.dtype)
+        return gstate, None, gs, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, cost, s, bits, controls):
+        _unmapped_table(in_dims[1], 'cost_scale')
+        v = info.batch_size
+        sf = _fold(state, in_dims[0], v)
+        out = _CostScale.apply(sf, cost, _fold(s, in_dims[2], v), bits, controls)
+        return out.reshape(v, -1, out.shape[-1]), 0
+
+
+class _DiagMul(torch.autograd.Function):
+    """y = d[sub(i)] x with a complex table d, (2^k,) or one per sample (B, 2^k): linear in x, cotangent
+    gx = diag_mul(gy, conj(d))."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, diag: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
+        return backend.apply_diag(_plain(state), _plain(diag), bits, controls)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _state, diag, ctx.bits, ctx.controls = inputs
+        ctx.save_for_backward(diag)
+        ctx.save_for_forward(diag)
+
+    @staticmethod
+    def jvp(ctx, state_t, _diag_t, _bits_t, _controls_t):
+        _single_forward_level()
+        (diag,) = ctx.saved_tensors
+        return diag_mul(state_t, diag, ctx.bits, ctx.controls)
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        (diag,) = ctx.saved_tensors
+        return diag_mul(gy, diag.conj(), ctx.bits, ctx.controls), None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, diag, bits, controls):
+        _unmapped_table(in_dims[1], 'diag_mul')
+        v = info.batch_size
+        sf = _fold(state, in_dims[0], v)
+        if diag.ndim == 2 and diag.shape[0] > 1:
+            diag = diag.unsqueeze(0).expand(v, *diag.shape).reshape(-1, diag.shape[-1])
+        out = _DiagMul.apply(sf, diag, bits, controls)
+        return out.reshape(v, -1, out.shape[-1]), 0
+
+
+def _flat_arg(x: torch.Tensor) -> torch.Tensor:
+    return x if _is_batched(x) or x.is_contiguous() else x.contiguous()
+
+
+def _bit_args(bits: Sequence[int], controls: Sequence[int]) -> tuple[tuple, tuple]:
+    return tuple(int(b) for b in bits), tuple(int(c) for c in controls)
+
+
+def cost_phase(state: torch.Tensor, cost: torch.Tensor, t: torch.Tensor, bits: Sequence[int],
+               controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable ``exp(-i t diag(cost))`` on a (B, 2**n) state: ``cost`` a constant real table (2^k,) over the index
+    bits ``bits`` (``bits[0]`` = its most significant bit), ``t`` real, one value or one per sample.  One read and one
+    write of the state whatever k is."""
+    _no_legacy(state, t)
+    cost = _const_table(cost, 'cost_phase')
+    bits, controls = _bit_args(bits, controls)
+    t = _per_sample(t, state.shape[-2], torch.float64, 'cost_phase')
+    return _CostPhase.apply(_flat_arg(state), cost, t, bits, controls)
+
+
+def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: Sequence[int],
+               controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable ``sum_i cost[sub(i)] conj(bra_i) ket_i`` of two (B, 2**n) states: complex128 (B,).  Pass the same
+    tensor twice for ``<C>`` (one read of the state; the imaginary part is exactly 0)."""
+    _no_legacy(bra, ket)
+    cost = _const_table(cost, 'cost_cross')
+    if bra.dtype != ket.dtype:
+        raise ValueError('cost_cross: bra and ket must have one dtype')
+    bits, controls = _bit_args(bits, controls)
+    same = bra is ket
+    ket = _flat_arg(ket)
+    bra = ket if same else _flat_arg(bra)
+    return _CostCross.apply(bra, ket, cost, bits, controls)
+
+
+def cost_scale(state: torch.Tensor, cost: torch.Tensor, s: torch.Tensor, bits: Sequence[int],
+               controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable ``s diag(cost)`` on a (B, 2**n) state, ``s`` complex, one value or one per sample; amplitudes
+    outside the controls come out as 0 (the cotangent of :func:`cost_cross`)."""
+    _no_legacy(state, s)
+    cost = _const_table(cost, 'cost_scale')
+    bits, controls = _bit_args(bits, controls)
+    s = _per_sample(s, state.shape[-2], torch.complex128, 'cost_scale')
+    return _CostScale.apply(_flat_arg(state), cost, s, bits, controls)
+
+
+def diag_mul(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable (in the state) diagonal operator: ``diag`` a constant complex table (2^k,) or (B, 2^k) over the
+    index bits ``bits``; amplitudes outside the controls pass through."""
+    _no_legacy(state)
+    diag = _const_table(diag, 'diag_mul')
+    bits, controls = _bit_args(bits, controls)
+    return _DiagMul.apply(_flat_arg(state), diag, bits, controls)

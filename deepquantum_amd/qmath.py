@@ -503,6 +503,57 @@ def reduced_density_matrix(state: torch.Tensor, nqubit: int, wires: int | list[i
     return rho.squeeze(0) if single else rho
 
 
+def _cost_table(cost: Any, k: int, what: str) -> torch.Tensor:
+    if not isinstance(cost, torch.Tensor):
+        cost = torch.tensor(cost, dtype=torch.float)
+    if cost.is_complex() or not cost.is_floating_point():
+        raise ValueError(f'{what}: the cost table must be real floating point, got {cost.dtype}')
+    if cost.shape != (1 << k,):
+        raise ValueError(f'{what}: a cost over {k} wires has shape ({1 << k},), got {tuple(cost.shape)}')
+    return cost
+
+
+def expectation_cost(state: torch.Tensor, nqubit: int, cost: torch.Tensor, wires: int | list[int] | None = None) -> torch.Tensor:
+    """``<C> = sum_i cost[sub(i)] |psi_i|^2`` for a classical cost given as a real table of 2^k entries over ``wires``
+    (``wires[0]`` the most significant bit of the entry index; all n wires by default): (B,) real in the state's
+    precision, or 0-d for a single state.  ``state`` in the forms of :func:`reduced_density_matrix`.  One read of the
+    state, accumulated in double (``dq_cost_cross_*``); differentiable to any order in the state (the table is a
+    constant).  Not normalised: a state of norm r gives r^2 <C>."""
+    flat, single = _state_batch(state, nqubit, 'expectation_cost')
+    n = int(nqubit)
+    wires = list(range(n)) if wires is None else _wire_list(wires, n, 'expectation_cost')
+    cost = _cost_table(cost, len(wires), 'expectation_cost')
+    val = ops.cost_cross(flat, flat, cost, [n - 1 - w for w in wires]).real.to(flat.real.dtype)
+    return val.squeeze(0) if single else val
+
+
+def ising_cost(nqubit: int, terms: list, dtype: torch.dtype | None = None, device: Any = None) -> torch.Tensor:
+    """The table ``c[i] = sum_j w_j (-1)^popcount(i & zmask_j)`` over all ``nqubit`` wires of the Ising polynomial
+    ``terms = [(weight, [wires...]), ...]`` (a term's sign is the product of Z eigenvalues of its wires in basis state i,
+    wire 0 the most significant bit): real (2**nqubit,), built on ``device`` by the Z-string kernel
+    (``dq_scale_zsigns_*`` on a vector of ones, 32 terms per pass).  ``dtype``: torch.float32 (default) or float64."""
+    n = int(nqubit)
+    if n < 1 or n > 40:
+        raise ValueError(f'ising_cost: nqubit={nqubit} out of range')
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f'ising_cost: dtype must be torch.float32 or torch.float64, got {dtype}')
+    zmasks, weights = [], []
+    try:
+        for w, wires in terms:
+            weights.append(float(w))
+            wires = [wires] if isinstance(wires, int) else list(wires)
+            zmasks.append(sum(1 << (n - 1 - q) for q in _wire_list(wires, n, 'ising_cost')) if wires else 0)
+    except TypeError:
+        raise ValueError('ising_cost: terms must be a list of (weight, [wires...]) pairs') from None
+    if not zmasks:
+        raise ValueError('ising_cost: no terms')
+    cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
+    ones = torch.ones(1, 1 << n, dtype=cdtype, device=device)
+    coef = torch.tensor([weights], dtype=torch.float64, device=device)
+    return backend.scale_z_signs(ones, zmasks, coef).real.reshape(-1).contiguous()
+
+
 def _entropy_of(rho: torch.Tensor, alpha: float, base: float | None, tau: float) -> torch.Tensor:
     """Entropy of (B, D, D) Hermitian matrices, normalised by their trace first: (B,) float64."""
     rho = rho.to(torch.complex128)

@@ -45,7 +45,7 @@ typedef enum {
     DQ_ERR_UNSUPPORTED = -3  /* valid request outside what this build implements */
 } DqStatus;
 
-#define DQ_ABI_VERSION 29
+#define DQ_ABI_VERSION 30
 
 int dq_abi_version(void);
 /* Thread-local, never NULL. */
@@ -559,6 +559,50 @@ int dq_sample_c64(const void* psi, int n, int64_t batch, const double* u, int64_
                   int64_t ws_bytes, dq_stream_t stream);
 int dq_sample_c128(const void* psi, int n, int64_t batch, const double* u, int64_t shots, int64_t* out, void* ws,
                    int64_t ws_bytes, dq_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 8. Diagonal operators on any number of wires (ABI 30; csrc/dq_diag.hip): one multiplication per amplitude, one read
+ *    and one write of the state whatever k is -- what UAnyGate / HamiltonianGate need a dense 4^k matrix and k <= 10
+ *    for (gate.py:2745-3024), and what a QAOA cost layer spells as one Rzz per edge (examples/qaoa.py:31-44).
+ *        sub(i) = sum_j bit_{bits[j]}(i) << (k - 1 - j)
+ *    `bits`: HOST array of k distinct index-bit positions, bits[0] = the table index's most significant bit (as in
+ *    dq_marginal_*); `controls` / `nc` as in dq_apply_gate_*: an amplitude whose control bits are not all 1 passes
+ *    through unchanged (diag, PHASE) or is left out of the sum (cross).  1 <= k, k + nc <= n <= 40, 1 <= batch <= 65535; state
+ *    and table pointers 16-byte aligned; in == out is allowed everywhere.  bits = n-1 .. 0 without controls streams the
+ *    table beside the state (no gather).
+ * ------------------------------------------------------------------------------------------ */
+/* out[b, i] = diag[b * diag_batch_stride + sub(i)] * in[b, i]; diag: DEVICE complex in the state's precision, 2^k entries
+ * per table; diag_batch_stride = 0 (one table for the batch) or 2^k. */
+int dq_apply_diag_c64(const void* in, void* out, const void* diag, int64_t diag_batch_stride, int n, const int* bits, int k,
+                      const int* controls, int nc, int64_t batch, dq_stream_t stream);
+int dq_apply_diag_c128(const void* in, void* out, const void* diag, int64_t diag_batch_stride, int n, const int* bits, int k,
+                       const int* controls, int nc, int64_t batch, dq_stream_t stream);
+
+#define DQ_COST_PHASE 0
+#define DQ_COST_SCALE 1
+/* cost: DEVICE real table in the state's real precision, 2^k entries, shared by the batch.
+ *   op = DQ_COST_PHASE: out[b, i] = exp(-i t[b] cost[sub(i)]) * in[b, i], t = DEVICE double [batch].  The angle is
+ *        double(t) * double(cost), reduced to a fraction of a turn in double for BOTH precisions; sine and cosine of that
+ *        fraction in the state's real precision (an angle of 1e4 rad formed in float is off by more than 1e-4).
+ *   op = DQ_COST_SCALE: out[b, i] = s[b] * cost[sub(i)] * in[b, i], s = DEVICE double [batch][2] (re, im): the
+ *        cotangent of dq_cost_cross_*, which leaves the amplitudes outside the controls out of its sum -- so here, and
+ *        only here, they come out as 0 instead of passing through. */
+int dq_apply_cost_c64(const void* in, void* out, const void* cost, const double* t, int op, int n, const int* bits, int k,
+                      const int* controls, int nc, int64_t batch, dq_stream_t stream);
+int dq_apply_cost_c128(const void* in, void* out, const void* cost, const double* t, int op, int n, const int* bits, int k,
+                       const int* controls, int nc, int64_t batch, dq_stream_t stream);
+
+/* Bytes of device workspace dq_cost_cross_* needs (one partial sum per workgroup and sample: at most 32 KiB per
+ * sample; `cross` != 0: bra != ket, the same amount); -1 on a bad argument. */
+int64_t dq_cost_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross);
+/* out[b] = sum over i with controls = 1 of cost[sub(i)] * conj(bra[b, i]) * ket[b, i]: DEVICE double [batch][2] (re, im),
+ * fully overwritten, accumulated in double.  bra == ket reads the state once: <C>, imaginary part exactly 0.
+ * Workgroups write fixed-order partial sums into `ws` (at least dq_cost_cross_ws_bytes bytes, 16-byte aligned) and a
+ * second kernel adds them: no atomics, results are bitwise reproducible. */
+int dq_cost_cross_c64(const void* bra, const void* ket, const void* cost, int n, const int* bits, int k, const int* controls,
+                      int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+int dq_cost_cross_c128(const void* bra, const void* ket, const void* cost, int n, const int* bits, int k, const int* controls,
+                       int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
 
 #ifdef __cplusplus
 }
