@@ -1023,3 +1023,139 @@ def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: S
                 len(controls), hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
         _lib.check(rc, 'dq_cost_cross')
     return torch.view_as_complex(out)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Pauli strings on any number of wires (csrc/dq_pauli.hip): (P psi)[i] = i^ny (-1)^popc((i ^ x) & z) psi[i ^ x]
+def _pauli_args(state: torch.Tensor, xmask: int, zmask: int, controls: Sequence[int], what: str) -> tuple[int, int, int, list[int]]:
+    n = _nqubit(state)
+    xmask, zmask, controls = int(xmask), int(zmask), [int(c) for c in controls]
+    if not state.is_contiguous():
+        raise ValueError(f'{what}: state must be contiguous')
+    if xmask < 0 or zmask < 0 or (xmask | zmask) >> n:
+        raise ValueError(f'{what}: xmask={xmask:#x} / zmask={zmask:#x} must lie in [0, 2**{n})')
+    if len(set(controls)) != len(controls) or any(c < 0 or c >= n for c in controls):
+        raise ValueError(f'{what}: controls {controls} must be distinct positions in [0, {n})')
+    if any(((xmask | zmask) >> c) & 1 for c in controls):
+        raise ValueError(f'{what}: controls {controls} must be disjoint from the Pauli string ({xmask | zmask:#x})')
+    return n, xmask, zmask, controls
+
+
+def _pauli_coef(p, like: torch.Tensor, what: str) -> torch.Tensor:
+    """One complex coefficient, or one per sample, as complex128 (B,) on the state's device."""
+    p = torch.as_tensor(p, device=like.device).to(torch.complex128).reshape(-1)
+    if p.shape[0] == 1 and like.shape[0] != 1:
+        p = p.expand(like.shape[0])
+    if p.shape[0] != like.shape[0]:
+        raise ValueError(f'{what}: one coefficient, or one per sample ({like.shape[0]}), expected; got {p.shape[0]}')
+    return p.resolve_conj().resolve_neg()
+
+
+def _pauli_out(state: torch.Tensor, out: torch.Tensor | None, what: str) -> torch.Tensor:
+    """``out`` checked: a contiguous tensor of the state's shape, dtype and device that is the state's own buffer or shares
+    no byte with it (a unit of work owns both ends of a pair, which makes the one safe, not a shifted overlap)."""
+    if out is None:
+        return torch.empty_like(state)
+    if out.shape != state.shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous tensor of the state's shape, dtype and device")
+    nbytes = state.numel() * state.element_size()
+    if out.data_ptr() != state.data_ptr() and abs(out.data_ptr() - state.data_ptr()) < nbytes:
+        raise ValueError(f'{what}: out overlaps the state without being the same buffer')
+    return out
+
+
+def _pauli_gather(n: int, xmask: int, zmask: int, controls: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Source index i ^ x, factor i^ny (-1)^popc((i ^ x) & z) and the control test for every i (CPU test double only)."""
+    i = torch.arange(1 << n)
+    j = i ^ xmask
+    par = j & zmask
+    for sh in (32, 16, 8, 4, 2, 1):
+        par = par ^ (par >> sh)
+    factor = (1j ** (bin(xmask & zmask).count('1') % 4)) * (1 - 2 * (par & 1)).to(torch.complex128)
+    cmask = sum(1 << c for c in controls)
+    return j, factor, (i & cmask) == cmask
+
+
+def apply_pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, controls: Sequence[int] = (), mode: str = 'gate',
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[b] = a[b] state[b] + c[b] P state[b] for the Pauli string P = (xmask, zmask) -- a Y sets its bit in both -- on
+    the amplitudes whose ``controls`` are all 1, in one read and one write of the state whatever the weight of P
+    (``dq_apply_pauli_axpby_*``).  ``a``, ``c``: complex, one value or one per sample.
+
+    * ``mode='gate'``: amplitudes outside the controls pass through.
+    * ``mode='map'``: they come out as 0 (the cotangent of :func:`pauli_cross`, which leaves them out).
+
+    ``out`` may be ``state``."""
+    if mode not in ('gate', 'map'):
+        raise ValueError(f"apply_pauli_axpby: mode must be 'gate' or 'map', got {mode!r}")
+    n, xmask, zmask, controls = _pauli_args(state, xmask, zmask, controls, 'apply_pauli_axpby')
+    a, c = _pauli_coef(a, state, 'apply_pauli_axpby'), _pauli_coef(c, state, 'apply_pauli_axpby')
+    out = _pauli_out(state, out, 'apply_pauli_axpby')
+    if not _use_hip(state):
+        def double():
+            j, factor, ok = _pauli_gather(n, xmask, zmask, controls)
+            x = state.to(torch.complex128)
+            y = a.reshape(-1, 1) * x + c.reshape(-1, 1) * factor * x[:, j]
+            out.copy_(torch.where(ok, y, x if mode == 'gate' else torch.zeros_like(x)).to(state.dtype))
+            return out
+
+        return _diag_double(double)
+    coef = torch.view_as_real(torch.stack([a, c], dim=1)).reshape(-1, 4).contiguous()
+    return _pauli_launch(state, out, xmask, zmask, coef, _lib.PAULI_GATE if mode == 'gate' else _lib.PAULI_MAP, n, controls)
+
+
+def _pauli_launch(state, out, xmask, zmask, coef, code, n, controls):
+    fn = getattr(_lib.load(), f'dq_apply_pauli_axpby_{_suffix(state)}')
+    for lo in range(0, state.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, state.shape[0])
+        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), xmask, zmask, _ptr(coef[lo:hi]), code, n, _lib.int_array(controls),
+                len(controls), hi - lo, _stream(state))
+        _lib.check(rc, 'dq_apply_pauli_axpby')
+    return out
+
+
+def apply_pauli_rot(state: torch.Tensor, xmask: int, zmask: int, theta: torch.Tensor, controls: Sequence[int] = (),
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """exp(-i theta/2 P) state: :func:`apply_pauli_axpby` in 'gate' mode with a = cos(theta/2), c = -i sin(theta/2), the
+    four real coefficients formed in double from the real ``theta`` (B,) without a detour through complex tensors."""
+    n, xmask, zmask, controls = _pauli_args(state, xmask, zmask, controls, 'apply_pauli_rot')
+    if theta.is_complex() or theta.shape != (state.shape[0],):
+        raise ValueError(f'apply_pauli_rot: one real angle per sample, ({state.shape[0]},), expected; got '
+                         f'{theta.dtype} {tuple(theta.shape)}')
+    half = theta.to(device=state.device, dtype=torch.float64) * 0.5
+    if not _use_hip(state):
+        return apply_pauli_axpby(state, xmask, zmask, torch.cos(half), -1j * torch.sin(half), controls, 'gate', out)
+    out = _pauli_out(state, out, 'apply_pauli_rot')
+    zero = torch.zeros_like(half)
+    coef = torch.stack([torch.cos(half), zero, zero, -torch.sin(half)], dim=1)
+    return _pauli_launch(state, out, xmask, zmask, coef, _lib.PAULI_GATE, n, controls)
+
+
+def pauli_cross(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, controls: Sequence[int] = ()) -> torch.Tensor:
+    """out[b] = sum over the amplitudes whose ``controls`` are all 1 of conj(bra[b, i]) (P ket[b])[i]: complex128 (B,),
+    accumulated in double, bitwise reproducible (``dq_pauli_cross_*``).  ``bra`` and ``ket`` the same buffer: one read of
+    the state.  ``xmask = zmask = 0``: the inner product over the controlled amplitudes.  The workspace comes from
+    PyTorch's allocator (legal under capture)."""
+    n, xmask, zmask, controls = _pauli_args(ket, xmask, zmask, controls, 'pauli_cross')
+    if bra.shape != ket.shape or bra.dtype != ket.dtype:
+        raise ValueError('pauli_cross: bra/ket must be (batch, 2**n) tensors of one shape and dtype')
+    if not bra.is_contiguous():
+        raise ValueError('pauli_cross: bra must be contiguous')
+    if not _use_hip(ket):
+        def double():
+            j, factor, ok = _pauli_gather(n, xmask, zmask, controls)
+            return (ok * bra.to(torch.complex128).conj() * factor * ket.to(torch.complex128)[:, j]).sum(dim=-1)
+
+        return _diag_double(double)
+    lib = _lib.load()
+    fn = getattr(lib, f'dq_pauli_cross_{_suffix(ket)}')
+    same = bra.data_ptr() == ket.data_ptr()
+    out = torch.empty(ket.shape[0], 2, dtype=torch.float64, device=ket.device)
+    for lo in range(0, ket.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, ket.shape[0])
+        nbytes = lib.dq_pauli_cross_ws_bytes(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
+        rc = fn(_ptr(bra[lo:hi]), _ptr(ket[lo:hi]), xmask, zmask, n, _lib.int_array(controls), len(controls), hi - lo,
+                _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
+        _lib.check(rc, 'dq_pauli_cross')
+    return torch.view_as_complex(out)

@@ -26,8 +26,8 @@ from torch import nn
 
 from . import _functorch, executor, ops, qmath
 from .gate import (
-    CNOT, Barrier, CostPhase, DiagonalGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, PauliX, PauliY, PauliZ,
-    PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
+    CNOT, Barrier, CostPhase, DiagonalGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, PauliEvolution, PauliRot,
+    PauliX, PauliY, PauliZ, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
     TDaggerGate, TGate, Toffoli, U3Gate, UAnyGate,
 )
 from .layer import CnotLayer, CnotRing, HLayer, Observable, RxLayer, RyLayer, RzLayer, U3Layer, XLayer, YLayer, ZLayer
@@ -152,7 +152,7 @@ class QubitCircuit(Operation):
 
     def _run_operators(self, flat: torch.Tensor, zero: bool = False) -> torch.Tensor:
         """All operators on a (B, 2**n) state: maximal stretches of gates go to the executor (fused passes),
-        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
+        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
         density matrix alike: index 0 is 1, everything else 0)."""
         if self.den_mat:
             prims = []
@@ -748,6 +748,21 @@ class QubitCircuit(Operation):
         requires_grad = (not encode) and inputs is None
         self.add(CostPhase(cost=cost, nqubit=self.nqubit, wires=wires, minmax=minmax, inputs=inputs, controls=controls,
                            name=name, den_mat=self.den_mat, requires_grad=requires_grad), encode=encode)
+
+    def pauli_rot(self, pauli, wires=None, inputs=None, controls=None, encode=False, name='pauli_rot'):
+        """``exp(-i theta/2 P)`` for the Pauli string ``pauli`` (one letter of ``xyzi`` per wire of ``wires``; all wires by
+        default) with one parameter ``theta``: trainable, given by ``inputs``, or fed from ``data`` with ``encode=True``:
+        see :class:`PauliRot`."""
+        requires_grad = (not encode) and inputs is None
+        self.add(PauliRot(pauli=pauli, nqubit=self.nqubit, wires=wires, inputs=inputs, controls=controls, name=name,
+                          den_mat=self.den_mat, requires_grad=requires_grad), encode=encode)
+
+    def pauli_evolution(self, hamiltonian, t=None, steps=1, order=1, encode=False, name='pauli_evolution'):
+        """A first- or second-order Trotter product of ``steps`` slices for ``exp(-i H t)``, ``H`` a list such as
+        ``[[0.5, 'x0y1'], [-1, 'z3y1']]``, with one parameter ``t``: see :class:`PauliEvolution`."""
+        requires_grad = (not encode) and t is None
+        self.add(PauliEvolution(hamiltonian=hamiltonian, t=t, nqubit=self.nqubit, steps=steps, order=order, name=name,
+                                den_mat=self.den_mat, requires_grad=requires_grad), encode=encode)
 
     # layers
     def xlayer(self, wires=None):

@@ -1059,6 +1059,172 @@ class CostPhase(_FlatGate, ArbitraryGate):
         return s if self.controls == [] else s + f', controls={self.controls}'
 
 
+class _OneAngle:
+    """One real parameter, trainable, fixed or encoded, of a gate that has no table: ``_state_like`` comes from the
+    parameter's device and precision (``.to()`` of the circuit converts it along)."""
+
+    def _one_angle(self, inputs: Any, requires_grad: bool) -> None:
+        self.npara = 1
+        self.requires_grad = requires_grad
+        self.init_para(inputs)
+
+    def inputs_to_tensor(self, inputs: Any = None) -> torch.Tensor:
+        while isinstance(inputs, list):
+            inputs = inputs[0]
+        if inputs is None:
+            return torch.rand(())
+        return _as_param_tensor(inputs)
+
+    def init_para(self, inputs: Any = None) -> None:
+        name = self._param_names[0]
+        value = self.inputs_to_tensor(inputs)
+        old = getattr(self, name, None)
+        if old is not None and not isinstance(value, nn.Parameter):
+            # (the parameter stays in the precision `.to()` of the circuit gave it -- `_state_like` reads the circuit's
+            # precision from it -- whatever the precision of fresh random values or of encoded data)
+            value = value.to(device=old.device, dtype=old.dtype)
+        if self.requires_grad:
+            setattr(self, name, nn.Parameter(value))
+        else:
+            self.register_buffer(name, value)
+
+    def _angle(self) -> torch.Tensor:
+        value = getattr(self, self._param_names[0])
+        return -value if self.inv_mode else value
+
+    def _state_like(self) -> tuple[torch.dtype, torch.device]:
+        value = getattr(self, self._param_names[0])
+        return (torch.complex128 if value.dtype == torch.float64 else torch.complex64), value.device
+
+    def inverse(self):
+        return ArbitraryGate.inverse(self)          # (the copy shares the parameter; `inv_mode` negates it where it is used)
+
+    def extra_repr(self) -> str:
+        value = self._angle()
+        val = value.item() if value.numel() == 1 else f'<batch of {value.numel()}>'
+        s = f'wires={self.wires}, {self._param_names[0]}={val}'
+        return s if self.controls == [] else s + f', controls={self.controls}'
+
+
+def _pauli_letters(pauli: str, what: str) -> str:
+    if not isinstance(pauli, str) or any(ch not in 'xyzi' for ch in pauli.lower()):
+        raise ValueError(f'{what}: a Pauli string is written with the letters x, y, z, i; got {pauli!r}')
+    return pauli.lower()
+
+
+def _pauli_bit_masks(nqubit: int, letters: str, wires: list[int]) -> tuple[int, int]:
+    """(xmask, zmask) over index bits -- wire 0 is the most significant bit, a Y sets its bit in both."""
+    xmask = zmask = 0
+    for ch, w in zip(letters, wires):
+        bit = 1 << (nqubit - 1 - w)
+        if ch in 'xy':
+            xmask |= bit
+        if ch in 'yz':
+            zmask |= bit
+    return xmask, zmask
+
+
+class PauliRot(_OneAngle, _FlatGate, ArbitraryGate):
+    """``exp(-i theta/2 P)`` for a Pauli string ``P``: ``pauli`` holds one letter of ``xyzi`` (either case) per wire of
+    ``wires`` (all wires by default).  One read and one write of the state whatever the weight of P, on any wires of the
+    register (``dq_apply_pauli_axpby_*``) -- where a dense matrix has no route beyond a span of 10.  ``theta`` is trainable
+    (``requires_grad=True``), fixed (``inputs``), or fed from the circuit's data (``encode=True``; a batch of data gives one
+    ``theta`` per sample).  The gate's ``wires`` are those with a letter other than ``i``."""
+
+    _param_names = ('theta',)
+    get_matrix = None                                   # (no matrix: not one of the circuit's vectorised one-angle gates)
+
+    def __init__(self, pauli, nqubit=1, wires=None, inputs=None, controls=None, name='PauliRot', den_mat=False,
+                 tsr_mode=False, requires_grad=False):
+        letters = _pauli_letters(pauli, 'PauliRot')
+        if wires is None:
+            wires = list(range(nqubit))
+        if isinstance(wires, int):
+            wires = [wires]
+        if len(letters) != len(wires):
+            raise ValueError(f'PauliRot: {len(letters)} letters for {len(wires)} wires')
+        if set(letters) <= {'i'}:
+            raise ValueError('PauliRot: the string is the identity -- a global phase, not a gate')
+        self.pauli = ''.join(ch for ch in letters if ch != 'i')
+        super().__init__(name=name, nqubit=nqubit, wires=[w for ch, w in zip(letters, wires) if ch != 'i'], controls=controls,
+                         den_mat=den_mat, tsr_mode=tsr_mode)
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        self._one_angle(inputs, requires_grad)
+
+    def masks(self) -> tuple[int, int]:
+        return _pauli_bit_masks(self.nqubit, self.pauli, self.wires)
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        xmask, zmask = self.masks()
+        return ops.pauli_rot(x, xmask, zmask, self._angle(), self._bits(self.controls))
+
+    def extra_repr(self) -> str:
+        return f'pauli={self.pauli!r}, ' + _OneAngle.extra_repr(self)
+
+
+class PauliEvolution(_OneAngle, _FlatGate, ArbitraryGate):
+    """A Trotter product for ``exp(-i H t)``, ``H = sum_j coef_j P_j`` given as ``HamiltonianGate`` takes it --
+    ``[[0.5, 'x0y1'], [-1, 'z3y1']]``, real coefficients, wires anywhere in the register -- with one parameter ``t``:
+    ``steps`` slices of Pauli rotations ``exp(-i coef_j (t / steps) P_j)`` (``order=1``: the terms in the order given;
+    ``order=2``: the symmetric product, half angles out and back), each rotation one read and one write of the state
+    (:class:`PauliRot`).  Exact when the terms commute; differentiable through ``t``."""
+
+    _param_names = ('t',)
+
+    def __init__(self, hamiltonian, t=None, nqubit=1, steps=1, order=1, name='PauliEvolution', den_mat=False, tsr_mode=False,
+                 requires_grad=False):
+        if not isinstance(hamiltonian, list) or not hamiltonian:
+            raise ValueError("PauliEvolution: the Hamiltonian is a list such as [[0.5, 'x0y1'], [-1, 'z3y1']]")
+        if order not in (1, 2):
+            raise ValueError(f'PauliEvolution: order must be 1 or 2, got {order!r}')
+        if not isinstance(steps, int) or steps < 1:
+            raise ValueError(f'PauliEvolution: steps must be a positive integer, got {steps!r}')
+        self.terms = []
+        for coef, factors in HamiltonianGate._terms(hamiltonian):
+            ws = [w for _, w in factors]
+            if isinstance(coef, complex) or not factors:
+                raise ValueError(f'PauliEvolution: a term is a real coefficient and a non-empty Pauli string, got {coef!r}')
+            if len(set(ws)) != len(ws):
+                raise ValueError(f'PauliEvolution: a wire is repeated within one string (wires {ws})')
+            if any(w < 0 or w >= nqubit for w in ws):
+                raise ValueError(f'PauliEvolution: wires {ws} outside the register of {nqubit} qubits')
+            self.terms.append((float(coef), ''.join(p for p, _ in factors), ws))
+        self.steps, self.order = steps, order
+        super().__init__(name=name, nqubit=nqubit, wires=sorted({w for _, _, ws in self.terms for w in ws}), den_mat=den_mat,
+                         tsr_mode=tsr_mode)
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        self._one_angle([t], requires_grad)
+
+    def slice_sequence(self) -> list[tuple[int, float]]:
+        """(term, share of its angle) of one slice, in the order applied."""
+        m = len(self.terms)
+        if self.order == 1 or m == 1:
+            seq = [(j, 1.0) for j in range(m)]
+        else:                                           # (the last term's two halves meet: one rotation)
+            seq = [(j, 0.5) for j in range(m - 1)] + [(m - 1, 1.0)] + [(j, 0.5) for j in range(m - 2, -1, -1)]
+        return seq[::-1] if self.inv_mode else seq
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        t = self._angle()
+        masks = [_pauli_bit_masks(self.nqubit, letters, ws) for _, letters, ws in self.terms]
+        seq = self.slice_sequence()
+        for _ in range(self.steps):
+            for j, share in seq:
+                x = ops.pauli_rot(x, masks[j][0], masks[j][1], t * (2.0 * self.terms[j][0] * share / self.steps))
+        return x
+
+    def extra_repr(self) -> str:
+        return f'terms={len(self.terms)}, steps={self.steps}, order={self.order}, ' + _OneAngle.extra_repr(self)
+
+
 class Reset(Gate):
     r"""Reset qubits to :math:`|0\rangle` (reference: gate.py:3027-3094).
 

@@ -893,3 +893,203 @@ def diag_mul(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], contr
     diag = _const_table(diag, 'diag_mul')
     bits, controls = _bit_args(bits, controls)
     return _DiagMul.apply(_flat_arg(state), diag, bits, controls)
+
+
+# ---- Pauli strings on any number of wires (csrc/dq_pauli.hip) -----------------------------------------------------------
+# P = (xmask, zmask) over index bits, a Y in both, Hermitian; (P x)[i] = i^ny (-1)^popc((i ^ xmask) & zmask) x[i ^ xmask].
+# Two operations closed under differentiation -- every backward and every jvp below is written with them -- so derivatives
+# of any order exist by construction, and the rotation as a node of its own on top of them:
+#     axpby(x; a, c)[i] = a x[i] + c (P x)[i]             (outside the controls: x[i] in 'gate' mode, 0 in 'map' mode)
+#     cross(u, v)       = sum_i conj(u[i]) (P v)[i]       (outside the controls: left out)
+#     rot(x; theta)     = axpby(x; cos(theta/2), -i sin(theta/2)) in 'gate' mode = exp(-i theta/2 P) x
+class _PauliAxpby(torch.autograd.Function):
+    """y = a x + c P x with a, c complex128 (B,): cotangents gx = axpby(gy; conj a, conj c) in the same mode,
+    ga = cross_I(x, gy), gc = cross_P(x, gy).  A tangent in a or c moves the controlled amplitudes only: a 'map' term."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, a: torch.Tensor, c: torch.Tensor, xmask: int, zmask: int, controls: tuple,
+                mode: str) -> torch.Tensor:
+        return backend.apply_pauli_axpby(_plain(state), xmask, zmask, _plain(a), _plain(c), controls, mode)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, a, c, ctx.xmask, ctx.zmask, ctx.controls, ctx.mode = inputs
+        ctx.save_for_backward(state, a, c)
+        ctx.save_for_forward(state, a, c)
+
+    @staticmethod
+    def jvp(ctx, state_t, a_t, c_t, *_):
+        _single_forward_level()
+        state, a, c = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = pauli_axpby(state_t, ctx.xmask, ctx.zmask, a, c, ctx.controls, ctx.mode)
+        if a_t is not None or c_t is not None:
+            zero = torch.zeros_like(a)
+            term = pauli_axpby(state, ctx.xmask, ctx.zmask, zero if a_t is None else a_t, zero if c_t is None else c_t,
+                               ctx.controls, 'map')
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, a, c = ctx.saved_tensors
+        gstate = ga = gc = None
+        if ctx.needs_input_grad[0]:
+            gstate = pauli_axpby(gy, ctx.xmask, ctx.zmask, a.conj(), c.conj(), ctx.controls, ctx.mode)
+        if ctx.needs_input_grad[1]:
+            ga = pauli_cross(state, gy, 0, 0, ctx.controls).to(a.dtype)
+        if ctx.needs_input_grad[2]:
+            gc = pauli_cross(state, gy, ctx.xmask, ctx.zmask, ctx.controls).to(c.dtype)
+        return gstate, ga, gc, None, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, a, c, xmask, zmask, controls, mode):
+        v = info.batch_size
+        sf = _fold(state, in_dims[0], v)
+        out = _PauliAxpby.apply(sf, _fold(a, in_dims[1], v), _fold(c, in_dims[2], v), xmask, zmask, controls, mode)
+        return out.reshape(v, -1, out.shape[-1]), 0
+
+
+class _PauliCross(torch.autograd.Function):
+    """z = sum_i conj(u_i) (P v)_i, complex128 (B,): anti-linear in u, linear in v; cotangents g_v = map(u; 0, gz) and
+    g_u = map(v; 0, conj(gz))."""
+
+    @staticmethod
+    def forward(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, controls: tuple) -> torch.Tensor:
+        pk = _plain(ket)
+        return backend.pauli_cross(pk if bra is ket else _plain(bra), pk, xmask, zmask, controls)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        bra, ket, ctx.xmask, ctx.zmask, ctx.controls = inputs
+        ctx.save_for_backward(bra, ket)
+        ctx.save_for_forward(bra, ket)
+
+    @staticmethod
+    def jvp(ctx, bra_t, ket_t, *_):
+        _single_forward_level()
+        bra, ket = ctx.saved_tensors
+        out = None
+        if bra_t is not None:
+            out = pauli_cross(bra_t, ket, ctx.xmask, ctx.zmask, ctx.controls)
+        if ket_t is not None:
+            term = pauli_cross(bra, ket_t, ctx.xmask, ctx.zmask, ctx.controls)
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gz: torch.Tensor):
+        bra, ket = ctx.saved_tensors
+        gz = gz.to(torch.complex128)
+        zero = torch.zeros_like(gz)
+        gbra = gket = None
+        if ctx.needs_input_grad[0]:
+            gbra = pauli_axpby(ket, ctx.xmask, ctx.zmask, zero, gz.conj(), ctx.controls, 'map')
+        if ctx.needs_input_grad[1]:
+            gket = pauli_axpby(bra, ctx.xmask, ctx.zmask, zero, gz, ctx.controls, 'map')
+        return gbra, gket, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, bra, ket, xmask, zmask, controls):
+        v = info.batch_size
+        same = bra is ket and in_dims[0] == in_dims[1]
+        kf = _fold(ket, in_dims[1], v)
+        bf = kf if same else _fold(bra, in_dims[0], v)
+        out = _PauliCross.apply(bf, kf, xmask, zmask, controls)
+        return out.reshape(v, -1), 0
+
+
+class _PauliRot(torch.autograd.Function):
+    """y = U x, U = exp(-i theta/2 P), theta real (B,): cotangents gx = rot(gy, -theta) = U^dagger gy and gtheta =
+    1/2 Im cross_P(gy, y) (dy/dtheta = -(i/2) P y on the controlled amplitudes, 0 elsewhere -- which cross leaves out).  U
+    commutes with P, so cross_P(gy, U x) = cross_P(U^dagger gy, x) = cross_P(gx, x): the cross takes the two tensors the
+    backward holds already and y is not formed again -- one axpby and one cross per backward."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, theta: torch.Tensor, xmask: int, zmask: int, controls: tuple) -> torch.Tensor:
+        return backend.apply_pauli_rot(_plain(state), xmask, zmask, _plain(theta), controls)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, theta, ctx.xmask, ctx.zmask, ctx.controls = inputs
+        ctx.save_for_backward(state, theta)
+        ctx.save_for_forward(state, theta)
+
+    @staticmethod
+    def jvp(ctx, state_t, theta_t, *_):
+        _single_forward_level()
+        state, theta = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = pauli_rot(state_t, ctx.xmask, ctx.zmask, theta, ctx.controls)
+        if theta_t is not None:
+            y = pauli_rot(state, ctx.xmask, ctx.zmask, theta, ctx.controls)
+            half = -0.5j * theta_t.to(torch.complex128)
+            term = pauli_axpby(y, ctx.xmask, ctx.zmask, torch.zeros_like(half), half, ctx.controls, 'map')
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, theta = ctx.saved_tensors
+        gstate = pauli_rot(gy, ctx.xmask, ctx.zmask, -theta, ctx.controls)
+        gtheta = None
+        if ctx.needs_input_grad[1]:
+            gtheta = (0.5 * pauli_cross(gstate, state, ctx.xmask, ctx.zmask, ctx.controls).imag).to(theta.dtype)
+        return (gstate if ctx.needs_input_grad[0] else None), gtheta, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, theta, xmask, zmask, controls):
+        v = info.batch_size
+        sf = _fold(state, in_dims[0], v)
+        out = _PauliRot.apply(sf, _fold(theta, in_dims[1], v), xmask, zmask, controls)
+        return out.reshape(v, -1, out.shape[-1]), 0
+
+
+def _pauli_masks(xmask: int, zmask: int, controls: Sequence[int]) -> tuple[int, int, tuple]:
+    return int(xmask), int(zmask), tuple(int(c) for c in controls)
+
+
+def _pauli_param(p, state: torch.Tensor, dtype: torch.dtype, what: str) -> torch.Tensor:
+    if not isinstance(p, torch.Tensor):
+        p = torch.as_tensor(p, device=state.device)
+    return _per_sample(p, state.shape[-2], dtype, what)
+
+
+def pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, controls: Sequence[int] = (),
+                mode: str = 'gate') -> torch.Tensor:
+    """Differentiable ``a x + c P x`` on a (B, 2**n) state for the Pauli string ``P = (xmask, zmask)`` over index bits (a Y
+    sets its bit in both); ``a``, ``c`` complex, one value or one per sample.  Amplitudes outside the controls pass
+    through (``mode='gate'``) or come out as 0 (``mode='map'``, the cotangent of :func:`pauli_cross`).  One read and one
+    write of the state whatever the weight of P."""
+    _no_legacy(state)
+    if mode not in ('gate', 'map'):
+        raise ValueError(f"pauli_axpby: mode must be 'gate' or 'map', got {mode!r}")
+    xmask, zmask, controls = _pauli_masks(xmask, zmask, controls)
+    a = _pauli_param(a, state, torch.complex128, 'pauli_axpby')
+    c = _pauli_param(c, state, torch.complex128, 'pauli_axpby')
+    return _PauliAxpby.apply(_flat_arg(state), a, c, xmask, zmask, controls, mode)
+
+
+def pauli_cross(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable ``sum_i conj(bra_i) (P ket)_i`` of two (B, 2**n) states over the amplitudes inside the controls:
+    complex128 (B,).  Pass the same tensor twice for ``<P>`` (one read of the state); ``xmask = zmask = 0`` is the
+    inner product."""
+    _no_legacy(bra, ket)
+    if bra.dtype != ket.dtype:
+        raise ValueError('pauli_cross: bra and ket must have one dtype')
+    xmask, zmask, controls = _pauli_masks(xmask, zmask, controls)
+    same = bra is ket
+    ket = _flat_arg(ket)
+    bra = ket if same else _flat_arg(bra)
+    return _PauliCross.apply(bra, ket, xmask, zmask, controls)
+
+
+def pauli_rot(state: torch.Tensor, xmask: int, zmask: int, theta, controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable ``exp(-i theta/2 P)`` on a (B, 2**n) state: ``theta`` real, one value or one per sample; cosine and
+    sine of ``theta / 2`` are formed in double for both precisions.  One read and one write of the state."""
+    _no_legacy(state)
+    xmask, zmask, controls = _pauli_masks(xmask, zmask, controls)
+    theta = _pauli_param(theta, state, torch.float64, 'pauli_rot')
+    return _PauliRot.apply(_flat_arg(state), theta, xmask, zmask, controls)

@@ -604,6 +604,39 @@ int dq_cost_cross_c64(const void* bra, const void* ket, const void* cost, int n,
 int dq_cost_cross_c128(const void* bra, const void* ket, const void* cost, int n, const int* bits, int k, const int* controls,
                        int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 9. Pauli strings on any number of wires (csrc/dq_pauli.hip; added within ABI 30, presence is checked by symbol): the
+ *    non-diagonal half of section 8 -- exp(-i theta/2 P) = cos(theta/2) - i sin(theta/2) P, what HamiltonianGate needs
+ *    a dense 4^span matrix and a span <= 10 for (gate.py:2867-3024) -- in one read and one write of the state whatever
+ *    the weight of P.
+ *        (P psi)[i] = i^ny * (-1)^popc((i ^ xmask) & zmask) * psi[i ^ xmask],   ny = popc(xmask & zmask)
+ *    `xmask` / `zmask` over index bits as in dq_expect_pauli_* (a Y sets its bit in both); `controls` / `nc` as in
+ *    dq_apply_gate_*, disjoint from xmask | zmask.  1 <= n <= 40, 1 <= batch <= 65535; state pointers 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+#define DQ_PAULI_GATE 0
+#define DQ_PAULI_MAP 1
+/* out[b, i] = a[b] * in[b, i] + c[b] * (P in_b)[i] on the amplitudes whose control bits are all 1; coef = DEVICE double
+ * [batch][4] = (Re a, Im a, Re c, Im c), rounded once to the state's real precision.
+ *   mode = DQ_PAULI_GATE: the amplitudes outside the controls pass through bitwise.
+ *   mode = DQ_PAULI_MAP:  they come out as 0 (the cotangent of dq_pauli_cross_*, which leaves them out).
+ * in == out is allowed: one unit of work owns both ends of a pair i, i ^ xmask. */
+int dq_apply_pauli_axpby_c64(const void* in, void* out, uint64_t xmask, uint64_t zmask, const double* coef, int mode, int n,
+                             const int* controls, int nc, int64_t batch, dq_stream_t stream);
+int dq_apply_pauli_axpby_c128(const void* in, void* out, uint64_t xmask, uint64_t zmask, const double* coef, int mode, int n,
+                              const int* controls, int nc, int64_t batch, dq_stream_t stream);
+
+/* Bytes of device workspace dq_pauli_cross_* needs (one partial sum per workgroup and sample: at most 32 KiB per
+ * sample, whatever the masks; `cross` != 0: bra != ket, the same amount); -1 on a bad argument. */
+int64_t dq_pauli_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross);
+/* out[b] = sum over i with controls = 1 of conj(bra[b, i]) * (P ket_b)[i]: DEVICE double [batch][2] (re, im), fully
+ * overwritten, accumulated in double.  bra == ket reads the state once; xmask = zmask = 0 is the inner product over the
+ * controlled amplitudes.  Workgroups write fixed-order partial sums into `ws` (at least dq_pauli_cross_ws_bytes bytes,
+ * 16-byte aligned) and a second kernel adds them: no atomics, results are bitwise reproducible. */
+int dq_pauli_cross_c64(const void* bra, const void* ket, uint64_t xmask, uint64_t zmask, int n, const int* controls, int nc,
+                       int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+int dq_pauli_cross_c128(const void* bra, const void* ket, uint64_t xmask, uint64_t zmask, int n, const int* controls, int nc,
+                        int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
