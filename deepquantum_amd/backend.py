@@ -692,16 +692,24 @@ def rdm1_cross(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
         raise ValueError('bra/ket must be contiguous')
     if not _use_hip(ket):
         return _test_backend.rdm1_cross(bra, ket)
-    same = bra.data_ptr() == ket.data_ptr()
+    return _cross_reduce('dq_rdm1_cross', 'dq_rdm1_ws_bytes', bra, ket, (n,), (n, 2, 2))
+
+
+def _cross_reduce(entry: str, sizer: str, bra: torch.Tensor, ket: torch.Tensor, mid: tuple, shape: tuple[int, ...] = ()) -> torch.Tensor:
+    """A cross reduction of the library, ``<entry>_<suffix>(bra, ket, *mid, batch, out, ws, ws_bytes, stream)``, over the
+    batch in slices of at most MAX_BATCH samples: complex128 (B, *shape).  Each slice's float64 workspace is sized by
+    ``<sizer>(n, batch, is_c128, bra is not ket)`` and comes from PyTorch's allocator (legal under capture)."""
     lib = _lib.load()
-    fn = getattr(lib, f'dq_rdm1_cross_{_suffix(ket)}')
-    out = torch.empty(ket.shape[0], n, 2, 2, 2, dtype=torch.float64, device=ket.device)
+    fn = getattr(lib, f'{entry}_{_suffix(ket)}')
+    n = _nqubit(ket)
+    same = bra.data_ptr() == ket.data_ptr()
+    out = torch.empty(ket.shape[0], *shape, 2, dtype=torch.float64, device=ket.device)
     for lo in range(0, ket.shape[0], MAX_BATCH):
         hi = min(lo + MAX_BATCH, ket.shape[0])
-        nbytes = lib.dq_rdm1_ws_bytes(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
+        nbytes = getattr(lib, sizer)(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
-        rc = fn(_ptr(bra[lo:hi]), _ptr(ket[lo:hi]), n, hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
-        _lib.check(rc, 'dq_rdm1_cross')
+        rc = fn(_ptr(bra[lo:hi]), _ptr(ket[lo:hi]), *mid, hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
+        _lib.check(rc, entry)
     return torch.view_as_complex(out)
 
 
@@ -841,6 +849,10 @@ def _scale_z_signs_wide(state: torch.Tensor, zmasks: Sequence[int], coef: torch.
 
 # ---------------------------------------------------------------------------------------------------
 # Diagonal operators on any number of wires (csrc/dq_diag.hip): table index sub(i) = sum_j bit_{bits[j]}(i) << (k-1-j)
+def _distinct_positions(positions: Sequence[int], n: int) -> bool:
+    return len(set(positions)) == len(positions) and not any(p < 0 or p >= n for p in positions)
+
+
 def _diag_args(state: torch.Tensor, bits: Sequence[int], controls: Sequence[int], what: str) -> tuple[int, list[int], list[int]]:
     n = _nqubit(state)
     bits, controls = [int(b) for b in bits], [int(c) for c in controls]
@@ -848,8 +860,7 @@ def _diag_args(state: torch.Tensor, bits: Sequence[int], controls: Sequence[int]
         raise ValueError(f'{what}: state must be contiguous')
     if not bits:
         raise ValueError(f'{what}: at least one table bit is needed')
-    both = bits + controls
-    if len(set(both)) != len(both) or any(p < 0 or p >= n for p in both):
+    if not _distinct_positions(bits + controls, n):
         raise ValueError(f'{what}: bits {bits} / controls {controls} must be distinct positions in [0, {n})')
     return n, bits, controls
 
@@ -1011,18 +1022,8 @@ def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: S
             return (w * bra.to(torch.complex128).conj() * ket.to(torch.complex128)).sum(dim=-1)
 
         return _diag_double(double)
-    lib = _lib.load()
-    fn = getattr(lib, f'dq_cost_cross_{_suffix(ket)}')
-    same = bra.data_ptr() == ket.data_ptr()
-    out = torch.empty(ket.shape[0], 2, dtype=torch.float64, device=ket.device)
-    for lo in range(0, ket.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, ket.shape[0])
-        nbytes = lib.dq_cost_cross_ws_bytes(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
-        rc = fn(_ptr(bra[lo:hi]), _ptr(ket[lo:hi]), _ptr(cost), n, _lib.int_array(bits), k, _lib.int_array(controls),
-                len(controls), hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
-        _lib.check(rc, 'dq_cost_cross')
-    return torch.view_as_complex(out)
+    mid = (_ptr(cost), n, _lib.int_array(bits), k, _lib.int_array(controls), len(controls))
+    return _cross_reduce('dq_cost_cross', 'dq_cost_cross_ws_bytes', bra, ket, mid)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1034,7 +1035,7 @@ def _pauli_args(state: torch.Tensor, xmask: int, zmask: int, controls: Sequence[
         raise ValueError(f'{what}: state must be contiguous')
     if xmask < 0 or zmask < 0 or (xmask | zmask) >> n:
         raise ValueError(f'{what}: xmask={xmask:#x} / zmask={zmask:#x} must lie in [0, 2**{n})')
-    if len(set(controls)) != len(controls) or any(c < 0 or c >= n for c in controls):
+    if not _distinct_positions(controls, n):
         raise ValueError(f'{what}: controls {controls} must be distinct positions in [0, {n})')
     if any(((xmask | zmask) >> c) & 1 for c in controls):
         raise ValueError(f'{what}: controls {controls} must be disjoint from the Pauli string ({xmask | zmask:#x})')
@@ -1147,15 +1148,5 @@ def pauli_cross(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, co
             return (ok * bra.to(torch.complex128).conj() * factor * ket.to(torch.complex128)[:, j]).sum(dim=-1)
 
         return _diag_double(double)
-    lib = _lib.load()
-    fn = getattr(lib, f'dq_pauli_cross_{_suffix(ket)}')
-    same = bra.data_ptr() == ket.data_ptr()
-    out = torch.empty(ket.shape[0], 2, dtype=torch.float64, device=ket.device)
-    for lo in range(0, ket.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, ket.shape[0])
-        nbytes = lib.dq_pauli_cross_ws_bytes(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
-        rc = fn(_ptr(bra[lo:hi]), _ptr(ket[lo:hi]), xmask, zmask, n, _lib.int_array(controls), len(controls), hi - lo,
-                _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
-        _lib.check(rc, 'dq_pauli_cross')
-    return torch.view_as_complex(out)
+    mid = (xmask, zmask, n, _lib.int_array(controls), len(controls))
+    return _cross_reduce('dq_pauli_cross', 'dq_pauli_cross_ws_bytes', bra, ket, mid)

@@ -8,11 +8,13 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 srcs=(dq_capi.hip dq_gate.hip dq_dense.hip dq_pass.hip dq_wave.hip dq_reduce.hip dq_dist.hip dq_plan.hip dq_entangle.hip dq_rdm.hip dq_sample.hip dq_diag.hip dq_pauli.hip)
 objs=()
 mkdir -p "${here}/build"
+# any header of this directory newer than object $1?
+newer_hpp() { local h; for h in "${here}"/*.hpp; do [[ "$h" -nt "$1" ]] && return 0; done; return 1; }
 pids=()
 for s in "${srcs[@]}"; do
   o="${here}/build/${s%.hip}.o"
   objs+=("$o")
-  if [[ ! -f "$o" || "${here}/$s" -nt "$o" || "${here}/dq_common.hpp" -nt "$o" || "${here}/../../include/dq_hip.h" -nt "$o" || ( "$s" == dq_wave.hip && ( "${here}/dq_wave_asm.inc" -nt "$o" || "${here}/dq_wave_asm64.inc" -nt "$o" || "${here}/dq_wave_valu.inc" -nt "$o" || "${here}/dq_wave_valu64.inc" -nt "$o" ) ) ]]; then
+  if newer_hpp "$o" || [[ ! -f "$o" || "${here}/$s" -nt "$o" || "${here}/../../include/dq_hip.h" -nt "$o" || ( "$s" == dq_wave.hip && ( "${here}/dq_wave_asm.inc" -nt "$o" || "${here}/dq_wave_asm64.inc" -nt "$o" || "${here}/dq_wave_valu.inc" -nt "$o" || "${here}/dq_wave_valu64.inc" -nt "$o" ) ) ]]; then
     if [[ "$s" == dq_wave.hip ]]; then
       "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -Wno-unused-value -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-uniform-regions -Rpass-analysis=kernel-resource-usage ${DQ_HIPCC_EXTRA:-} -c "${here}/$s" -o "$o" 2> "${here}/build/dq_wave.usage" &
     else

@@ -8,14 +8,11 @@
 // on the amplitudes whose control bits are all 1; the others pass through (diag, PHASE), are left out (cross) or come
 // out as 0 (SCALE: the cotangent of a sum that leaves them out).
 //
-// Geometry.  A lane moves 16 bytes (two complex64 or one complex128 amplitude) per load, a workgroup of 256 lanes
-// takes DG_UNROLL = 4 such wave-rows per iteration -- a chunk of 1024 vectors, 16 KiB, every load of the chunk in
-// flight before the first multiplication -- and at most DG_BLOCKS workgroups per sample stride over the chunks;
-// the sample is the grid's y dimension.
+// Geometry.  That of dq_stream.hpp with a vector as the item: a chunk is a unit of 1024 vectors, 16 KiB.
 //
 // Gather.  sub() is OR-separable over the index bits.  The host cuts the bit list into runs of consecutive positions
 // (a run is one shift, one mask, one shift) and splits them at the chunk size: the runs below it depend on the lane
-// alone and are evaluated once, before the loop (DG_UNROLL * 2 table offsets per lane at most); the runs above depend
+// alone and are evaluated once, before the loop (ST_UNROLL * 2 table offsets per lane at most); the runs above depend
 // on the chunk index alone, which is uniform over the workgroup: scalar arithmetic, once per iteration.  The control
 // mask is split the same way: a chunk whose high control bits are not all set is copied (or skipped, in place)
 // without a table access.  With bits = n-1 .. 0 and no controls sub(i) = i: the table is read with vector loads beside
@@ -27,19 +24,13 @@
 // of ones over the table bits and hands the result to dq_apply_diag where that measured faster).  DESIGN.md section 4.8
 // has the instruction count against the bytes.
 //
-// Reduction.  Lanes accumulate in double over their chunks, a wave adds its lanes with an xor butterfly, wave 0's
-// first lane adds the four waves in order and writes the workgroup's partial sum; a second kernel adds the partial
-// sums of a sample the same way.  No atomics, every sum in a fixed order: bitwise reproducible.
-#include "dq_common.hpp"
+// Reduction.  Lanes accumulate in double over their chunks; the rest is dq_stream.hpp's fixed-order scheme.
+#include "dq_stream.hpp"
 
 namespace dq {
 
 namespace {
 
-constexpr int DG_THREADS = 256;
-constexpr int DG_UNROLL = 4;                            // 16-byte vectors per lane and iteration
-constexpr int DG_CHUNK_BITS = 10;                       // log2(DG_THREADS * DG_UNROLL): vectors of a chunk
-constexpr unsigned DG_BLOCKS = 2048;                    // workgroups per sample striding over its chunks
 constexpr int DG_MAX_RUNS = 42;                         // 40 single bits, one of them split at the chunk size
 
 enum { MODE_DIAG = 0, MODE_PHASE = 1, MODE_SCALE = 2 };
@@ -51,20 +42,6 @@ struct Gather {
     uint8_t src[DG_MAX_RUNS], len[DG_MAX_RUNS], dst[DG_MAX_RUNS];
     uint64_t cmask;
 };
-
-template <typename T> struct Vec16;
-template <> struct Vec16<float> { using type = float4; };
-template <> struct Vec16<double> { using type = double2; };
-
-template <typename T> __device__ __forceinline__ cx<T> vec_get(const typename Vec16<T>::type& q, int e);
-template <> __device__ __forceinline__ float2 vec_get<float>(const float4& q, int e) {
-    return e ? make_float2(q.z, q.w) : make_float2(q.x, q.y);
-}
-template <> __device__ __forceinline__ double2 vec_get<double>(const double2& q, int) { return q; }
-__device__ __forceinline__ void vec_set(float4& q, int e, float2 a) {
-    if (e) { q.z = a.x; q.w = a.y; } else { q.x = a.x; q.y = a.y; }
-}
-__device__ __forceinline__ void vec_set(double2& q, int, double2 a) { q = a; }
 
 __device__ __forceinline__ void sincos_turns(float halfturns, float* s, float* c) { sincospif(halfturns, s, c); }
 __device__ __forceinline__ void sincos_turns(double halfturns, double* s, double* c) { sincospi(halfturns, s, c); }
@@ -105,7 +82,7 @@ template <typename E, int VEC> __device__ __forceinline__ void load_beside(const
 
 // What a lane keeps across the loop: the low part of sub() and the low control test of each of its amplitudes.
 template <int VEC> struct LaneLow {
-    uint64_t sub[DG_UNROLL][VEC];
+    uint64_t sub[ST_UNROLL][VEC];
     unsigned ok;                                        // bit u * VEC + e
 };
 
@@ -115,10 +92,10 @@ __device__ __forceinline__ void lane_low(const Gather& g, int sbits, LaneLow<VEC
     const uint64_t cl = g.cmask & ((1ull << sbits) - 1ull);
     ll.ok = 0;
 #pragma unroll
-    for (int u = 0; u < DG_UNROLL; ++u) {
+    for (int u = 0; u < ST_UNROLL; ++u) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-            const uint64_t low = ((uint64_t)(u * DG_THREADS + (int)threadIdx.x) << VB) | (uint64_t)e;
+            const uint64_t low = ((uint64_t)(u * ST_THREADS + (int)threadIdx.x) << VB) | (uint64_t)e;
             uint64_t s = 0;
             for (int r = 0; r < g.nlow; ++r) s |= ((low >> g.src[r]) & ((1ull << g.len[r]) - 1ull)) << g.dst[r];
             ll.sub[u][e] = s;
@@ -136,7 +113,7 @@ __device__ __forceinline__ uint64_t chunk_high(const Gather& g, int sbits, uint6
 
 // in and out may be the same buffer: no __restrict__ on them
 template <typename T, int MODE, bool IDENT>
-__global__ __launch_bounds__(DG_THREADS) void diag_apply_kernel(const cx<T>* in, cx<T>* out, const void* __restrict__ table,
+__global__ __launch_bounds__(ST_THREADS) void diag_apply_kernel(const cx<T>* in, cx<T>* out, const void* __restrict__ table,
                                                                 int64_t table_bstride, const double* __restrict__ par, Gather g,
                                                                 int n, uint64_t nchunks) {
     using Q = typename Vec16<T>::type;
@@ -144,7 +121,7 @@ __global__ __launch_bounds__(DG_THREADS) void diag_apply_kernel(const cx<T>* in,
     using E = typename F::entry;
     constexpr int VEC = 16 / (int)sizeof(cx<T>);
     constexpr int VB = VEC == 2 ? 1 : 0;
-    constexpr int SBITS = DG_CHUNK_BITS + VB;           // amplitudes of a chunk
+    constexpr int SBITS = ST_UNIT_BITS + VB;            // amplitudes of a chunk
     const uint64_t b = blockIdx.y;
     const uint64_t nvec = 1ull << (n - VB);
     const Q* src = reinterpret_cast<const Q*>(in + (b << n));
@@ -157,19 +134,19 @@ __global__ __launch_bounds__(DG_THREADS) void diag_apply_kernel(const cx<T>* in,
     if (!IDENT) lane_low<VEC>(g, SBITS, ll);
     const uint64_t ch = g.cmask >> SBITS;
     for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        const uint64_t v0 = (chunk << DG_CHUNK_BITS) + threadIdx.x;
-        Q q[DG_UNROLL];
-        E d[DG_UNROLL][VEC];
+        const uint64_t v0 = (chunk << ST_UNIT_BITS) + threadIdx.x;
+        Q q[ST_UNROLL];
+        E d[ST_UNROLL][VEC];
 #pragma unroll
-        for (int u = 0; u < DG_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * DG_THREADS);
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
             if (v < nvec) q[u] = src[v];
         }
         if (!IDENT && (chunk & ch) != ch) {             // a high control bit is 0: the whole chunk passes through (is zero)
             if (MODE == MODE_SCALE || src != dst) {
 #pragma unroll
-                for (int u = 0; u < DG_UNROLL; ++u) {
-                    const uint64_t v = v0 + (uint64_t)(u * DG_THREADS);
+                for (int u = 0; u < ST_UNROLL; ++u) {
+                    const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
                     if (v < nvec) dst[v] = MODE == MODE_SCALE ? Q{} : q[u];
                 }
             }
@@ -177,8 +154,8 @@ __global__ __launch_bounds__(DG_THREADS) void diag_apply_kernel(const cx<T>* in,
         }
         const uint64_t high = IDENT ? 0 : chunk_high(g, SBITS, chunk);
 #pragma unroll
-        for (int u = 0; u < DG_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * DG_THREADS);
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
             if (v < nvec) {
                 if (IDENT) {
                     load_beside<E, VEC>(tab, v, d[u]);
@@ -189,8 +166,8 @@ __global__ __launch_bounds__(DG_THREADS) void diag_apply_kernel(const cx<T>* in,
             }
         }
 #pragma unroll
-        for (int u = 0; u < DG_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * DG_THREADS);
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
             if (v < nvec) {
                 Q r = MODE == MODE_SCALE ? Q{} : q[u];
 #pragma unroll
@@ -203,42 +180,16 @@ __global__ __launch_bounds__(DG_THREADS) void diag_apply_kernel(const cx<T>* in,
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// the workgroup's sum of (re, im), in thread 0; fixed order
-__device__ __forceinline__ void block_sum(double& re, double& im, double (*sh)[2]) {
-    re = wave_sum(re);
-    im = wave_sum(im);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        sh[wave][0] = re;
-        sh[wave][1] = im;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        re = sh[0][0];
-        im = sh[0][1];
-        for (int w = 1; w < DG_THREADS / 64; ++w) {
-            re += sh[w][0];
-            im += sh[w][1];
-        }
-    }
-}
-
 // ws[b, blockIdx.x] = this workgroup's part of sum_i cost[sub(i)] conj(bra_i) ket_i
 template <typename T, bool SAME, bool IDENT>
-__global__ __launch_bounds__(DG_THREADS) void cost_cross_kernel(const cx<T>* __restrict__ bra, const cx<T>* __restrict__ ket,
+__global__ __launch_bounds__(ST_THREADS) void cost_cross_kernel(const cx<T>* __restrict__ bra, const cx<T>* __restrict__ ket,
                                                                 const T* __restrict__ cost, Gather g, int n, uint64_t nchunks,
                                                                 double* __restrict__ ws) {
     using Q = typename Vec16<T>::type;
     constexpr int VEC = 16 / (int)sizeof(cx<T>);
     constexpr int VB = VEC == 2 ? 1 : 0;
-    constexpr int SBITS = DG_CHUNK_BITS + VB;
-    __shared__ double sh[DG_THREADS / 64][2];
+    constexpr int SBITS = ST_UNIT_BITS + VB;
+    __shared__ double sh[ST_THREADS / 64][2];
     const uint64_t b = blockIdx.y;
     const uint64_t nvec = 1ull << (n - VB);
     const Q* pb = reinterpret_cast<const Q*>(bra + (b << n));
@@ -249,13 +200,13 @@ __global__ __launch_bounds__(DG_THREADS) void cost_cross_kernel(const cx<T>* __r
     double re = 0.0, im = 0.0;
     for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         if (!IDENT && (chunk & ch) != ch) continue;     // (uniform over the workgroup)
-        const uint64_t v0 = (chunk << DG_CHUNK_BITS) + threadIdx.x;
+        const uint64_t v0 = (chunk << ST_UNIT_BITS) + threadIdx.x;
         const uint64_t high = IDENT ? 0 : chunk_high(g, SBITS, chunk);
-        Q qk[DG_UNROLL], qb[DG_UNROLL];
-        T c[DG_UNROLL][VEC];
+        Q qk[ST_UNROLL], qb[ST_UNROLL];
+        T c[ST_UNROLL][VEC];
 #pragma unroll
-        for (int u = 0; u < DG_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * DG_THREADS);
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
             if (v < nvec) {
                 qk[u] = pk[v];
                 if (!SAME) qb[u] = pb[v];
@@ -268,8 +219,8 @@ __global__ __launch_bounds__(DG_THREADS) void cost_cross_kernel(const cx<T>* __r
             }
         }
 #pragma unroll
-        for (int u = 0; u < DG_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * DG_THREADS);
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
             if (v < nvec) {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
@@ -289,37 +240,8 @@ __global__ __launch_bounds__(DG_THREADS) void cost_cross_kernel(const cx<T>* __r
             }
         }
     }
-    block_sum(re, im, sh);
-    if (threadIdx.x == 0) {
-        double* p = ws + (b * gridDim.x + blockIdx.x) * 2;
-        p[0] = re;
-        p[1] = im;
-    }
+    write_partial(re, im, sh, ws);
 }
-
-// out[b] = the sum of the nparts partial sums of sample b
-__global__ __launch_bounds__(DG_THREADS) void cost_cross_finish_kernel(const double* __restrict__ ws, unsigned nparts,
-                                                                       double* __restrict__ out) {
-    __shared__ double sh[DG_THREADS / 64][2];
-    const uint64_t b = blockIdx.x;
-    double re = 0.0, im = 0.0;
-    for (unsigned p = threadIdx.x; p < nparts; p += DG_THREADS) {
-        re += ws[(b * nparts + p) * 2];
-        im += ws[(b * nparts + p) * 2 + 1];
-    }
-    block_sum(re, im, sh);
-    if (threadIdx.x == 0) {
-        out[2 * b] = re;
-        out[2 * b + 1] = im;
-    }
-}
-
-uint64_t chunks_of(int n, bool is_c128) {
-    const int sbits = DG_CHUNK_BITS + (is_c128 ? 0 : 1);
-    return n > sbits ? 1ull << (n - sbits) : 1ull;
-}
-
-unsigned blocks_of(uint64_t nchunks) { return (unsigned)(nchunks < DG_BLOCKS ? nchunks : DG_BLOCKS); }
 
 // Validates the lists and builds the runs; `ident`: bits = n-1 .. 0 and no controls.
 int plan_gather(const char* what, int n, const int* bits, int k, const int* controls, int nc, int64_t batch, bool is_c128,
@@ -329,13 +251,10 @@ int plan_gather(const char* what, int n, const int* bits, int k, const int* cont
         return DQ_ERR_ARG;
     }
     if (int rc = validate_bits(n, bits, k, controls, nc)) return rc;
-    if (batch < 1 || batch > 65535) {
-        set_error("%s: batch=%lld outside [1, 65535]", what, (long long)batch);
-        return DQ_ERR_ARG;
-    }
-    const int sbits = DG_CHUNK_BITS + (is_c128 ? 0 : 1);
+    if (int rc = check_batch(what, batch)) return rc;
+    const int sbits = ST_UNIT_BITS + (is_c128 ? 0 : 1);
     *g = Gather{};
-    for (int c = 0; c < nc; ++c) g->cmask |= 1ull << controls[c];
+    g->cmask = control_mask(controls, nc);
     *ident = nc == 0 && k == n;
     for (int j = 0; j < k && *ident; ++j) *ident = bits[j] == n - 1 - j;
     // runs of consecutive positions, split at the chunk size
@@ -368,8 +287,6 @@ int plan_gather(const char* what, int n, const int* bits, int k, const int* cont
     return DQ_OK;
 }
 
-bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 template <typename T, int MODE>
 int apply_impl(const char* what, const void* in, void* out, const void* table, int64_t table_bstride, const double* par, int n,
                const int* bits, int k, const int* controls, int nc, int64_t batch, dq_stream_t stream) {
@@ -389,17 +306,17 @@ int apply_impl(const char* what, const void* in, void* out, const void* table, i
         set_error("%s: table batch stride %lld, 0 (shared) or 2^k expected", what, (long long)table_bstride);
         return DQ_ERR_ARG;
     }
-    const uint64_t nchunks = chunks_of(n, C128);
-    const dim3 grid(blocks_of(nchunks), (unsigned)batch);
+    const uint64_t nvec = vectors_of(n, C128);
+    const dim3 grid(blocks_of(nvec), (unsigned)batch);
     const cx<T>* pi = static_cast<const cx<T>*>(in);
     cx<T>* po = static_cast<cx<T>*>(out);
     hipStream_t s = as_stream(stream);
     if (ident)
-        hipLaunchKernelGGL((diag_apply_kernel<T, MODE, true>), grid, dim3(DG_THREADS), 0, s, pi, po, table, table_bstride, par, g, n,
-                           nchunks);
+        hipLaunchKernelGGL((diag_apply_kernel<T, MODE, true>), grid, dim3(ST_THREADS), 0, s, pi, po, table, table_bstride, par, g, n,
+                           units_of(nvec));
     else
-        hipLaunchKernelGGL((diag_apply_kernel<T, MODE, false>), grid, dim3(DG_THREADS), 0, s, pi, po, table, table_bstride, par, g, n,
-                           nchunks);
+        hipLaunchKernelGGL((diag_apply_kernel<T, MODE, false>), grid, dim3(ST_THREADS), 0, s, pi, po, table, table_bstride, par, g, n,
+                           units_of(nvec));
     return check_launch(what);
 }
 
@@ -430,13 +347,9 @@ int cross_impl(const void* bra, const void* ket, const void* cost, int n, const 
         set_error("%s: bra, ket, cost and ws must be 16-byte aligned", what);
         return DQ_ERR_ARG;
     }
-    const uint64_t nchunks = chunks_of(n, C128);
-    const unsigned nblk = blocks_of(nchunks);
-    const int64_t need = batch * (int64_t)nblk * 2 * (int64_t)sizeof(double);
-    if (ws_bytes < need) {
-        set_error("%s: workspace of %lld bytes, %lld needed (dq_cost_cross_ws_bytes)", what, (long long)ws_bytes, (long long)need);
-        return DQ_ERR_ARG;
-    }
+    if (int rc = check_cross_ws(what, ws_bytes, n, batch, C128)) return rc;
+    const uint64_t nvec = vectors_of(n, C128);
+    const unsigned nblk = blocks_of(nvec);
     const dim3 grid(nblk, (unsigned)batch);
     const cx<T>* pb = static_cast<const cx<T>*>(bra);
     const cx<T>* pk = static_cast<const cx<T>*>(ket);
@@ -445,14 +358,13 @@ int cross_impl(const void* bra, const void* ket, const void* cost, int n, const 
     hipStream_t s = as_stream(stream);
     const bool same = bra == ket;
 #define DQ_CROSS(SAME, ID) \
-    hipLaunchKernelGGL((cost_cross_kernel<T, SAME, ID>), grid, dim3(DG_THREADS), 0, s, pb, pk, pc, g, n, nchunks, part)
+    hipLaunchKernelGGL((cost_cross_kernel<T, SAME, ID>), grid, dim3(ST_THREADS), 0, s, pb, pk, pc, g, n, units_of(nvec), part)
     if (same && ident) DQ_CROSS(true, true);
     else if (same) DQ_CROSS(true, false);
     else if (ident) DQ_CROSS(false, true);
     else DQ_CROSS(false, false);
 #undef DQ_CROSS
-    hipLaunchKernelGGL(cost_cross_finish_kernel, dim3((unsigned)batch), dim3(DG_THREADS), 0, s, part, nblk, out);
-    return check_launch(what);
+    return finish_cross(what, part, nblk, batch, out, s);
 }
 
 }  // namespace
@@ -481,7 +393,7 @@ extern "C" int dq_apply_cost_c128(const void* in, void* out, const void* cost, c
 extern "C" int64_t dq_cost_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross) {
     (void)cross;        // bra != ket reads twice as much and writes the same partial sums
     if (n < 1 || n > 40 || batch < 1 || batch > 65535) return -1;
-    return batch * (int64_t)dq::blocks_of(dq::chunks_of(n, is_c128 != 0)) * 2 * (int64_t)sizeof(double);
+    return dq::cross_ws_bytes(n, batch, is_c128 != 0);
 }
 
 extern "C" int dq_cost_cross_c64(const void* bra, const void* ket, const void* cost, int n, const int* bits, int k,

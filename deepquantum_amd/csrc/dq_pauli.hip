@@ -8,35 +8,27 @@
 // the sum that leaves them out) or are left out (cross).  The controls are disjoint from x | z, so both ends of a pair
 // i, i ^ x are inside the controls or both are outside.
 //
-// Geometry.  A lane moves 16 bytes (two complex64 or one complex128 amplitude) per load; vx = x >> VB is the flip over
-// vector indices and x0 (complex64 only) the flip inside a vector, a swap of registers.
-//   * vx != 0: the unit of work is a PAIR of vectors.  Pair P of the 2^(nv - 1) pairs of a sample is
+// Geometry.  That of dq_stream.hpp; vx = x >> VB is the flip over vector indices and x0 (complex64 only) the flip
+// inside a vector, a swap of registers.  Both kernels are written once, with the item as the template parameter PAIR:
+//   * vx != 0: the item is a PAIR of vectors.  Pair P of the 2^(nv - 1) pairs of a sample is
 //         vA = P with a zero inserted at the top set bit of vx,        vB = vA ^ vx
 //     so every vector belongs to exactly one pair whatever vx is -- a flip above, inside or across any tile size is
-//     the same line of code.  A lane owns PL_UNROLL = 4 pairs per iteration: it loads both ends of all four (eight
+//     the same line of code.  A lane owns ST_UNROLL = 4 pairs per iteration: it loads both ends of all four (eight
 //     loads in flight), computes both outputs of each and stores both.  Nobody else reads or writes them: in == out
 //     is safe, and the traffic is one read and one write.
-//   * vx == 0 (x = 0, or complex64 x = 1): no partner, a lane owns four vectors per iteration.
-// A workgroup of 256 lanes takes a unit of 1024 pairs (vectors) per iteration, at most PL_BLOCKS workgroups per sample
-// stride over the units; the sample is the grid's y dimension.
+//   * vx == 0 (x = 0, or complex64 x = 1): no partner, the item is a vector: the partner of an amplitude is itself
+//     or (complex64, x0) its neighbour in the vector.
 //
 // Arithmetic.  i^ny and the sign are a swap and two negations of components; a and c arrive as doubles and are
 // rounded once to the state's real precision.  No table, no trigonometry.
 //
-// Reduction.  As in dq_diag.hip: lanes accumulate in double, a wave adds its lanes with an xor butterfly, lane 0 adds
-// the four waves in order and writes the workgroup's partial sum; a second kernel adds a sample's partial sums the
-// same way.  No atomics, every sum in a fixed order: bitwise reproducible.  bra == ket loads each pair once and adds
-// both of its terms.
-#include "dq_common.hpp"
+// Reduction.  Lanes accumulate in double over their items; the rest is dq_stream.hpp's fixed-order scheme.  bra == ket
+// loads each pair once and adds both of its terms.
+#include "dq_stream.hpp"
 
 namespace dq {
 
 namespace {
-
-constexpr int PL_THREADS = 256;
-constexpr int PL_UNROLL = 4;                            // pairs (vx != 0) or vectors (vx == 0) per lane and iteration
-constexpr int PL_UNIT_BITS = 10;                        // log2(PL_THREADS * PL_UNROLL)
-constexpr unsigned PL_BLOCKS = 2048;                    // workgroups per sample striding over its units
 
 struct Pauli {
     uint64_t vx;                                        // xmask over vector indices
@@ -45,20 +37,6 @@ struct Pauli {
     int x0;                                             // complex64: bit 0 of xmask, the flip inside a vector
     int ny;                                             // popc(xmask & zmask) mod 4
 };
-
-template <typename T> struct Vec16;
-template <> struct Vec16<float> { using type = float4; };
-template <> struct Vec16<double> { using type = double2; };
-
-template <typename T> __device__ __forceinline__ cx<T> vec_get(const typename Vec16<T>::type& q, int e);
-template <> __device__ __forceinline__ float2 vec_get<float>(const float4& q, int e) {
-    return e ? make_float2(q.z, q.w) : make_float2(q.x, q.y);
-}
-template <> __device__ __forceinline__ double2 vec_get<double>(const double2& q, int) { return q; }
-__device__ __forceinline__ void vec_set(float4& q, int e, float2 a) {
-    if (e) { q.z = a.x; q.w = a.y; } else { q.x = a.x; q.y = a.y; }
-}
-__device__ __forceinline__ void vec_set(double2& q, int, double2 a) { q = a; }
 
 // i^ny (-1)^popc(j & z) s: what the source amplitude s at index j contributes to (P psi)[j ^ x]
 template <typename V> __device__ __forceinline__ V pauli_term(V s, uint64_t j, const Pauli& p) {
@@ -84,10 +62,15 @@ template <typename T> __device__ __forceinline__ void load_coef(const double* co
     c = mk<T>((T)coef[4 * b + 2], (T)coef[4 * b + 3]);
 }
 
-// vx != 0.  in and out may be the same buffer: no __restrict__ on them
-template <typename T, int MODE>
-__global__ __launch_bounds__(PL_THREADS) void pauli_pair_kernel(const cx<T>* in, cx<T>* out, const double* __restrict__ coef,
-                                                                Pauli p, int n, uint64_t npairs) {
+// The first (PAIR: lower) vector of item `it`
+template <bool PAIR> __device__ __forceinline__ uint64_t item_vector(uint64_t it, const Pauli& p) {
+    return PAIR ? insert_zero(it, p.top) : it;
+}
+
+// in and out may be the same buffer: no __restrict__ on them
+template <typename T, int MODE, bool PAIR>
+__global__ __launch_bounds__(ST_THREADS) void pauli_axpby_kernel(const cx<T>* in, cx<T>* out, const double* __restrict__ coef,
+                                                                 Pauli p, int n, uint64_t items) {
     using Q = typename Vec16<T>::type;
     constexpr int VEC = 16 / (int)sizeof(cx<T>);
     constexpr int VB = VEC == 2 ? 1 : 0;
@@ -96,99 +79,37 @@ __global__ __launch_bounds__(PL_THREADS) void pauli_pair_kernel(const cx<T>* in,
     Q* dst = reinterpret_cast<Q*>(out + (b << n));
     cx<T> a, c;
     load_coef<T>(coef, b, a, c);
-    for (uint64_t unit = blockIdx.x; (unit << PL_UNIT_BITS) < npairs; unit += gridDim.x) {
-        const uint64_t p0 = (unit << PL_UNIT_BITS) + threadIdx.x;
-        Q qa[PL_UNROLL], qb[PL_UNROLL];
+    for (uint64_t unit = blockIdx.x; (unit << ST_UNIT_BITS) < items; unit += gridDim.x) {
+        const uint64_t i0 = (unit << ST_UNIT_BITS) + threadIdx.x;
+        Q qa[ST_UNROLL], qb[ST_UNROLL];                 // (qb: PAIR only)
 #pragma unroll
-        for (int u = 0; u < PL_UNROLL; ++u) {
-            const uint64_t pr = p0 + (uint64_t)(u * PL_THREADS);
-            if (pr < npairs) {
-                const uint64_t va = insert_zero(pr, p.top);
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t it = i0 + (uint64_t)(u * ST_THREADS);
+            if (it < items) {
+                const uint64_t va = item_vector<PAIR>(it, p);
                 qa[u] = src[va];
-                qb[u] = src[va ^ p.vx];
+                if constexpr (PAIR) qb[u] = src[va ^ p.vx];
             }
         }
 #pragma unroll
-        for (int u = 0; u < PL_UNROLL; ++u) {
-            const uint64_t pr = p0 + (uint64_t)(u * PL_THREADS);
-            if (pr < npairs) {
-                const uint64_t va = insert_zero(pr, p.top), vb = va ^ p.vx;
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t it = i0 + (uint64_t)(u * ST_THREADS);
+            if (it < items) {
+                const uint64_t va = item_vector<PAIR>(it, p), vb = PAIR ? va ^ p.vx : va;
+                const Q& qo = PAIR ? qb[u] : qa[u];     // where the partners of qa's amplitudes are
                 Q ra, rb;
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     const int f = VEC == 2 ? e ^ p.x0 : 0;          // the partner's element
                     const uint64_t ia = (va << VB) | (uint64_t)e, ja = (vb << VB) | (uint64_t)f, jb = (va << VB) | (uint64_t)f;
                     const bool ok = (ia & p.cmask) == p.cmask;      // (the same for both ends)
-                    vec_set(ra, e, combine<T, MODE>(vec_get<T>(qa[u], e), pauli_term(vec_get<T>(qb[u], f), ja, p), a, c, ok));
-                    vec_set(rb, e, combine<T, MODE>(vec_get<T>(qb[u], e), pauli_term(vec_get<T>(qa[u], f), jb, p), a, c, ok));
+                    vec_set(ra, e, combine<T, MODE>(vec_get<T>(qa[u], e), pauli_term(vec_get<T>(qo, f), ja, p), a, c, ok));
+                    if constexpr (PAIR)
+                        vec_set(rb, e, combine<T, MODE>(vec_get<T>(qb[u], e), pauli_term(vec_get<T>(qa[u], f), jb, p), a, c, ok));
                 }
                 dst[va] = ra;
-                dst[vb] = rb;
+                if constexpr (PAIR) dst[vb] = rb;
             }
-        }
-    }
-}
-
-// vx == 0: the partner is the amplitude itself or (complex64, x0) its neighbour in the vector
-template <typename T, int MODE>
-__global__ __launch_bounds__(PL_THREADS) void pauli_self_kernel(const cx<T>* in, cx<T>* out, const double* __restrict__ coef,
-                                                                Pauli p, int n, uint64_t nvec) {
-    using Q = typename Vec16<T>::type;
-    constexpr int VEC = 16 / (int)sizeof(cx<T>);
-    constexpr int VB = VEC == 2 ? 1 : 0;
-    const uint64_t b = blockIdx.y;
-    const Q* src = reinterpret_cast<const Q*>(in + (b << n));
-    Q* dst = reinterpret_cast<Q*>(out + (b << n));
-    cx<T> a, c;
-    load_coef<T>(coef, b, a, c);
-    for (uint64_t unit = blockIdx.x; (unit << PL_UNIT_BITS) < nvec; unit += gridDim.x) {
-        const uint64_t v0 = (unit << PL_UNIT_BITS) + threadIdx.x;
-        Q q[PL_UNROLL];
-#pragma unroll
-        for (int u = 0; u < PL_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * PL_THREADS);
-            if (v < nvec) q[u] = src[v];
-        }
-#pragma unroll
-        for (int u = 0; u < PL_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * PL_THREADS);
-            if (v < nvec) {
-                Q r;
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const int f = VEC == 2 ? e ^ p.x0 : 0;
-                    const uint64_t i = (v << VB) | (uint64_t)e, j = (v << VB) | (uint64_t)f;
-                    const bool ok = (i & p.cmask) == p.cmask;
-                    vec_set(r, e, combine<T, MODE>(vec_get<T>(q[u], e), pauli_term(vec_get<T>(q[u], f), j, p), a, c, ok));
-                }
-                dst[v] = r;
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// the workgroup's sum of (re, im), in thread 0; fixed order
-__device__ __forceinline__ void block_sum(double& re, double& im, double (*sh)[2]) {
-    re = wave_sum(re);
-    im = wave_sum(im);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        sh[wave][0] = re;
-        sh[wave][1] = im;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        re = sh[0][0];
-        im = sh[0][1];
-        for (int w = 1; w < PL_THREADS / 64; ++w) {
-            re += sh[w][0];
-            im += sh[w][1];
         }
     }
 }
@@ -202,125 +123,52 @@ template <typename V> __device__ __forceinline__ void cross_add(V a, V w, bool o
     }
 }
 
-__device__ __forceinline__ void write_partial(double re, double im, double (*sh)[2], double* ws) {
-    block_sum(re, im, sh);
-    if (threadIdx.x == 0) {
-        double* part = ws + ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-        part[0] = re;
-        part[1] = im;
-    }
-}
-
-// ws[b, blockIdx.x] = this workgroup's part of sum_i conj(bra_i) (P ket)_i, vx != 0
-template <typename T, bool SAME>
-__global__ __launch_bounds__(PL_THREADS) void pauli_cross_pair_kernel(const cx<T>* __restrict__ bra, const cx<T>* __restrict__ ket,
-                                                                      Pauli p, int n, uint64_t npairs, double* __restrict__ ws) {
+// ws[b, blockIdx.x] = this workgroup's part of sum_i conj(bra_i) (P ket)_i
+template <typename T, bool SAME, bool PAIR>
+__global__ __launch_bounds__(ST_THREADS) void pauli_cross_kernel(const cx<T>* __restrict__ bra, const cx<T>* __restrict__ ket,
+                                                                 Pauli p, int n, uint64_t items, double* __restrict__ ws) {
     using Q = typename Vec16<T>::type;
     constexpr int VEC = 16 / (int)sizeof(cx<T>);
     constexpr int VB = VEC == 2 ? 1 : 0;
-    __shared__ double sh[PL_THREADS / 64][2];
+    __shared__ double sh[ST_THREADS / 64][2];
     const uint64_t b = blockIdx.y;
     const Q* pb = reinterpret_cast<const Q*>(bra + (b << n));
     const Q* pk = reinterpret_cast<const Q*>(ket + (b << n));
     double re = 0.0, im = 0.0;
-    for (uint64_t unit = blockIdx.x; (unit << PL_UNIT_BITS) < npairs; unit += gridDim.x) {
-        const uint64_t p0 = (unit << PL_UNIT_BITS) + threadIdx.x;
-        Q ka[PL_UNROLL], kb[PL_UNROLL], ba[PL_UNROLL], bb[PL_UNROLL];
+    for (uint64_t unit = blockIdx.x; (unit << ST_UNIT_BITS) < items; unit += gridDim.x) {
+        const uint64_t i0 = (unit << ST_UNIT_BITS) + threadIdx.x;
+        Q ka[ST_UNROLL], kb[ST_UNROLL], ba[ST_UNROLL], bb[ST_UNROLL];           // (kb, bb: PAIR only; ba, bb: !SAME only)
 #pragma unroll
-        for (int u = 0; u < PL_UNROLL; ++u) {
-            const uint64_t pr = p0 + (uint64_t)(u * PL_THREADS);
-            if (pr < npairs) {
-                const uint64_t va = insert_zero(pr, p.top), vb = va ^ p.vx;
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t it = i0 + (uint64_t)(u * ST_THREADS);
+            if (it < items) {
+                const uint64_t va = item_vector<PAIR>(it, p), vb = va ^ p.vx;
                 ka[u] = pk[va];
-                kb[u] = pk[vb];
-                if (!SAME) {
-                    ba[u] = pb[va];
-                    bb[u] = pb[vb];
-                }
+                if constexpr (PAIR) kb[u] = pk[vb];
+                if constexpr (!SAME) ba[u] = pb[va];
+                if constexpr (!SAME && PAIR) bb[u] = pb[vb];
             }
         }
 #pragma unroll
-        for (int u = 0; u < PL_UNROLL; ++u) {
-            const uint64_t pr = p0 + (uint64_t)(u * PL_THREADS);
-            if (pr < npairs) {
-                const uint64_t va = insert_zero(pr, p.top), vb = va ^ p.vx;
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            const uint64_t it = i0 + (uint64_t)(u * ST_THREADS);
+            if (it < items) {
+                const uint64_t va = item_vector<PAIR>(it, p), vb = PAIR ? va ^ p.vx : va;
+                const Q& ko = PAIR ? kb[u] : ka[u];     // where the partners of ka's amplitudes are
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     const int f = VEC == 2 ? e ^ p.x0 : 0;
                     const uint64_t ia = (va << VB) | (uint64_t)e, ja = (vb << VB) | (uint64_t)f, jb = (va << VB) | (uint64_t)f;
                     const bool ok = (ia & p.cmask) == p.cmask;
-                    cross_add(vec_get<T>(SAME ? ka[u] : ba[u], e), pauli_term(vec_get<T>(kb[u], f), ja, p), ok, re, im);
-                    cross_add(vec_get<T>(SAME ? kb[u] : bb[u], e), pauli_term(vec_get<T>(ka[u], f), jb, p), ok, re, im);
+                    cross_add(vec_get<T>(SAME ? ka[u] : ba[u], e), pauli_term(vec_get<T>(ko, f), ja, p), ok, re, im);
+                    if constexpr (PAIR)
+                        cross_add(vec_get<T>(SAME ? kb[u] : bb[u], e), pauli_term(vec_get<T>(ka[u], f), jb, p), ok, re, im);
                 }
             }
         }
     }
     write_partial(re, im, sh, ws);
 }
-
-// the same with vx == 0
-template <typename T, bool SAME>
-__global__ __launch_bounds__(PL_THREADS) void pauli_cross_self_kernel(const cx<T>* __restrict__ bra, const cx<T>* __restrict__ ket,
-                                                                      Pauli p, int n, uint64_t nvec, double* __restrict__ ws) {
-    using Q = typename Vec16<T>::type;
-    constexpr int VEC = 16 / (int)sizeof(cx<T>);
-    constexpr int VB = VEC == 2 ? 1 : 0;
-    __shared__ double sh[PL_THREADS / 64][2];
-    const uint64_t b = blockIdx.y;
-    const Q* pb = reinterpret_cast<const Q*>(bra + (b << n));
-    const Q* pk = reinterpret_cast<const Q*>(ket + (b << n));
-    double re = 0.0, im = 0.0;
-    for (uint64_t unit = blockIdx.x; (unit << PL_UNIT_BITS) < nvec; unit += gridDim.x) {
-        const uint64_t v0 = (unit << PL_UNIT_BITS) + threadIdx.x;
-        Q qk[PL_UNROLL], qb[PL_UNROLL];
-#pragma unroll
-        for (int u = 0; u < PL_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * PL_THREADS);
-            if (v < nvec) {
-                qk[u] = pk[v];
-                if (!SAME) qb[u] = pb[v];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PL_UNROLL; ++u) {
-            const uint64_t v = v0 + (uint64_t)(u * PL_THREADS);
-            if (v < nvec) {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const int f = VEC == 2 ? e ^ p.x0 : 0;
-                    const uint64_t i = (v << VB) | (uint64_t)e, j = (v << VB) | (uint64_t)f;
-                    cross_add(vec_get<T>(SAME ? qk[u] : qb[u], e), pauli_term(vec_get<T>(qk[u], f), j, p), (i & p.cmask) == p.cmask,
-                              re, im);
-                }
-            }
-        }
-    }
-    write_partial(re, im, sh, ws);
-}
-
-// out[b] = the sum of the nparts partial sums of sample b
-__global__ __launch_bounds__(PL_THREADS) void pauli_cross_finish_kernel(const double* __restrict__ ws, unsigned nparts,
-                                                                        double* __restrict__ out) {
-    __shared__ double sh[PL_THREADS / 64][2];
-    const uint64_t b = blockIdx.x;
-    double re = 0.0, im = 0.0;
-    for (unsigned q = threadIdx.x; q < nparts; q += PL_THREADS) {
-        re += ws[(b * nparts + q) * 2];
-        im += ws[(b * nparts + q) * 2 + 1];
-    }
-    block_sum(re, im, sh);
-    if (threadIdx.x == 0) {
-        out[2 * b] = re;
-        out[2 * b + 1] = im;
-    }
-}
-
-unsigned blocks_of(uint64_t items) {
-    const uint64_t units = (items + (1ull << PL_UNIT_BITS) - 1) >> PL_UNIT_BITS;
-    return (unsigned)(units < PL_BLOCKS ? units : PL_BLOCKS);
-}
-
-uint64_t vectors_of(int n, bool is_c128) { return 1ull << (n - (is_c128 ? 0 : 1)); }          // (n >= 1)
 
 // Validates the masks and the controls and splits the string for the kernels.
 int plan_pauli(const char* what, uint64_t xmask, uint64_t zmask, int n, const int* controls, int nc, int64_t batch, bool is_c128,
@@ -331,12 +179,9 @@ int plan_pauli(const char* what, uint64_t xmask, uint64_t zmask, int n, const in
                   (unsigned long long)zmask, n);
         return DQ_ERR_ARG;
     }
-    if (batch < 1 || batch > 65535) {
-        set_error("%s: batch=%lld outside [1, 65535]", what, (long long)batch);
-        return DQ_ERR_ARG;
-    }
+    if (int rc = check_batch(what, batch)) return rc;
     *p = Pauli{};
-    for (int c = 0; c < nc; ++c) p->cmask |= 1ull << controls[c];
+    p->cmask = control_mask(controls, nc);
     if (p->cmask & (xmask | zmask)) {
         set_error("%s: a control lies inside the Pauli string (controls 0x%llx, string 0x%llx)", what,
                   (unsigned long long)p->cmask, (unsigned long long)(xmask | zmask));
@@ -350,8 +195,6 @@ int plan_pauli(const char* what, uint64_t xmask, uint64_t zmask, int n, const in
     p->top = p->vx ? 63 - __builtin_clzll(p->vx) : 0;
     return DQ_OK;
 }
-
-bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 template <typename T>
 int axpby_impl(const void* in, void* out, uint64_t xmask, uint64_t zmask, const double* coef, int mode, int n, const int* controls,
@@ -378,17 +221,14 @@ int axpby_impl(const void* in, void* out, uint64_t xmask, uint64_t zmask, const 
     const cx<T>* pi = static_cast<const cx<T>*>(in);
     cx<T>* po = static_cast<cx<T>*>(out);
     hipStream_t s = as_stream(stream);
-#define DQ_AXPBY(KERNEL, MODE) hipLaunchKernelGGL((KERNEL<T, MODE>), grid, dim3(PL_THREADS), 0, s, pi, po, coef, p, n, items)
-    if (p.vx && mode == DQ_PAULI_GATE) DQ_AXPBY(pauli_pair_kernel, DQ_PAULI_GATE);
-    else if (p.vx) DQ_AXPBY(pauli_pair_kernel, DQ_PAULI_MAP);
-    else if (mode == DQ_PAULI_GATE) DQ_AXPBY(pauli_self_kernel, DQ_PAULI_GATE);
-    else DQ_AXPBY(pauli_self_kernel, DQ_PAULI_MAP);
+#define DQ_AXPBY(MODE, PAIR) \
+    hipLaunchKernelGGL((pauli_axpby_kernel<T, MODE, PAIR>), grid, dim3(ST_THREADS), 0, s, pi, po, coef, p, n, items)
+    if (p.vx && mode == DQ_PAULI_GATE) DQ_AXPBY(DQ_PAULI_GATE, true);
+    else if (p.vx) DQ_AXPBY(DQ_PAULI_MAP, true);
+    else if (mode == DQ_PAULI_GATE) DQ_AXPBY(DQ_PAULI_GATE, false);
+    else DQ_AXPBY(DQ_PAULI_MAP, false);
 #undef DQ_AXPBY
     return check_launch(what);
-}
-
-int64_t cross_ws_bytes(int n, int64_t batch, bool is_c128) {
-    return batch * (int64_t)blocks_of(vectors_of(n, is_c128)) * 2 * (int64_t)sizeof(double);
 }
 
 template <typename T>
@@ -406,11 +246,7 @@ int cross_impl(const void* bra, const void* ket, uint64_t xmask, uint64_t zmask,
         set_error("%s: bra, ket and ws must be 16-byte aligned, out 8-byte aligned", what);
         return DQ_ERR_ARG;
     }
-    const int64_t need = cross_ws_bytes(n, batch, C128);
-    if (ws_bytes < need) {
-        set_error("%s: workspace of %lld bytes, %lld needed (dq_pauli_cross_ws_bytes)", what, (long long)ws_bytes, (long long)need);
-        return DQ_ERR_ARG;
-    }
+    if (int rc = check_cross_ws(what, ws_bytes, n, batch, C128)) return rc;
     const uint64_t nvec = vectors_of(n, C128);
     const uint64_t items = p.vx ? nvec >> 1 : nvec;
     const unsigned nblk = blocks_of(items);             // (at most what the workspace was sized for)
@@ -420,14 +256,14 @@ int cross_impl(const void* bra, const void* ket, uint64_t xmask, uint64_t zmask,
     double* part = static_cast<double*>(ws);
     hipStream_t s = as_stream(stream);
     const bool same = bra == ket;
-#define DQ_CROSS(KERNEL, SAME) hipLaunchKernelGGL((KERNEL<T, SAME>), grid, dim3(PL_THREADS), 0, s, pb, pk, p, n, items, part)
-    if (p.vx && same) DQ_CROSS(pauli_cross_pair_kernel, true);
-    else if (p.vx) DQ_CROSS(pauli_cross_pair_kernel, false);
-    else if (same) DQ_CROSS(pauli_cross_self_kernel, true);
-    else DQ_CROSS(pauli_cross_self_kernel, false);
+#define DQ_CROSS(SAME, PAIR) \
+    hipLaunchKernelGGL((pauli_cross_kernel<T, SAME, PAIR>), grid, dim3(ST_THREADS), 0, s, pb, pk, p, n, items, part)
+    if (p.vx && same) DQ_CROSS(true, true);
+    else if (p.vx) DQ_CROSS(false, true);
+    else if (same) DQ_CROSS(true, false);
+    else DQ_CROSS(false, false);
 #undef DQ_CROSS
-    hipLaunchKernelGGL(pauli_cross_finish_kernel, dim3((unsigned)batch), dim3(PL_THREADS), 0, s, part, nblk, out);
-    return check_launch(what);
+    return finish_cross(what, part, nblk, batch, out, s);
 }
 
 }  // namespace

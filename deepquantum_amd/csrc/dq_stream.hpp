@@ -1,0 +1,142 @@
+// The core of the streaming primitives (dq_diag.hip, dq_pauli.hip): kernels that read a state once in 16-byte vectors,
+// do a little arithmetic per amplitude and either write the state back or reduce it to one complex number per sample.
+// Each including file gets its own copy of what is here (the library is built without relocatable device code).
+//
+// Geometry.  A lane moves 16 bytes (two complex64 or one complex128 amplitude) per load, a workgroup of ST_THREADS
+// lanes takes ST_UNROLL items per lane and iteration -- a unit of 2^ST_UNIT_BITS items, every load of the unit in
+// flight before the first use -- and at most ST_BLOCKS workgroups per sample stride over the units; the sample is the
+// grid's y dimension.  An item is whatever the primitive gives a lane to own: a vector, or a pair of vectors.
+//
+// Reduction.  Lanes accumulate in double over their units, a wave adds its lanes with an xor butterfly (offsets 1, 2,
+// 4, .., 32), wave 0's first lane adds the four waves in order 0..3 and writes the workgroup's partial sum
+// (write_partial); cross_finish_kernel then adds the partial sums of a sample, strided by ST_THREADS over the lanes,
+// the same way.  No atomics, every sum in a fixed order: bitwise reproducible, and that promise lives here alone.
+// The reductions of dq_reduce.hip (a __shfl_down tree from offset 32 downward: another order of additions, other
+// bits), dq_entangle.hip, dq_sample.hip and dq_rdm.hip (shaped by their own tiles) are deliberately not built on this.
+#pragma once
+#include "dq_common.hpp"
+
+namespace dq {
+
+namespace {
+
+constexpr int ST_THREADS = 256;
+constexpr int ST_UNROLL = 4;                            // items per lane and iteration
+constexpr int ST_UNIT_BITS = 10;                        // log2(ST_THREADS * ST_UNROLL): items of a unit
+constexpr unsigned ST_BLOCKS = 2048;                    // workgroups per sample striding over its units
+
+template <typename T> struct Vec16;
+template <> struct Vec16<float> { using type = float4; };
+template <> struct Vec16<double> { using type = double2; };
+
+template <typename T> __device__ __forceinline__ cx<T> vec_get(const typename Vec16<T>::type& q, int e);
+template <> __device__ __forceinline__ float2 vec_get<float>(const float4& q, int e) {
+    return e ? make_float2(q.z, q.w) : make_float2(q.x, q.y);
+}
+template <> __device__ __forceinline__ double2 vec_get<double>(const double2& q, int) { return q; }
+__device__ __forceinline__ void vec_set(float4& q, int e, float2 a) {
+    if (e) { q.z = a.x; q.w = a.y; } else { q.x = a.x; q.y = a.y; }
+}
+__device__ __forceinline__ void vec_set(double2& q, int, double2 a) { q = a; }
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the workgroup's sum of (re, im), in thread 0; fixed order
+__device__ __forceinline__ void block_sum(double& re, double& im, double (*sh)[2]) {
+    re = wave_sum(re);
+    im = wave_sum(im);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        sh[wave][0] = re;
+        sh[wave][1] = im;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        re = sh[0][0];
+        im = sh[0][1];
+        for (int w = 1; w < ST_THREADS / 64; ++w) {
+            re += sh[w][0];
+            im += sh[w][1];
+        }
+    }
+}
+
+// ws[blockIdx.y, blockIdx.x] = the workgroup's sum.  re and im are summed in the caller's own variables, as the kernels
+// of dq_diag.hip always did: taken by value, four cost_cross_kernel instantiations are scheduled differently.
+__device__ __forceinline__ void write_partial(double& re, double& im, double (*sh)[2], double* ws) {
+    block_sum(re, im, sh);
+    if (threadIdx.x == 0) {
+        double* part = ws + ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+        part[0] = re;
+        part[1] = im;
+    }
+}
+
+// out[b] = the sum of the nparts partial sums of sample b
+__global__ __launch_bounds__(ST_THREADS) void cross_finish_kernel(const double* __restrict__ ws, unsigned nparts,
+                                                                  double* __restrict__ out) {
+    __shared__ double sh[ST_THREADS / 64][2];
+    const uint64_t b = blockIdx.x;
+    double re = 0.0, im = 0.0;
+    for (unsigned p = threadIdx.x; p < nparts; p += ST_THREADS) {
+        re += ws[(b * nparts + p) * 2];
+        im += ws[(b * nparts + p) * 2 + 1];
+    }
+    block_sum(re, im, sh);
+    if (threadIdx.x == 0) {
+        out[2 * b] = re;
+        out[2 * b + 1] = im;
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------
+bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// the sample is the grid's y dimension
+int check_batch(const char* what, int64_t batch) {
+    if (batch >= 1 && batch <= 65535) return DQ_OK;
+    set_error("%s: batch=%lld outside [1, 65535]", what, (long long)batch);
+    return DQ_ERR_ARG;
+}
+
+uint64_t control_mask(const int* controls, int nc) {
+    uint64_t m = 0;
+    for (int c = 0; c < nc; ++c) m |= 1ull << controls[c];
+    return m;
+}
+
+uint64_t vectors_of(int n, bool is_c128) { return 1ull << (n - (is_c128 ? 0 : 1)); }          // (n >= 1)
+
+uint64_t units_of(uint64_t items) { return (items + (1ull << ST_UNIT_BITS) - 1) >> ST_UNIT_BITS; }
+
+unsigned blocks_of(uint64_t items) {
+    const uint64_t units = units_of(items);
+    return (unsigned)(units < ST_BLOCKS ? units : ST_BLOCKS);
+}
+
+// The workspace of a cross reduction: one partial sum per workgroup, sized for a sample's vectors as items (a
+// primitive whose items are pairs launches half as many workgroups and leaves the rest unused).
+int64_t cross_ws_bytes(int n, int64_t batch, bool is_c128) {
+    return batch * (int64_t)blocks_of(vectors_of(n, is_c128)) * 2 * (int64_t)sizeof(double);
+}
+
+// `what` names the entry point; its sizing function is <what>_ws_bytes
+int check_cross_ws(const char* what, int64_t ws_bytes, int n, int64_t batch, bool is_c128) {
+    const int64_t need = cross_ws_bytes(n, batch, is_c128);
+    if (ws_bytes >= need) return DQ_OK;
+    set_error("%s: workspace of %lld bytes, %lld needed (%s_ws_bytes)", what, (long long)ws_bytes, (long long)need, what);
+    return DQ_ERR_ARG;
+}
+
+// out[b] = the sum of the nparts partial sums that the first kernel left in ws[b, :]
+int finish_cross(const char* what, const double* ws, unsigned nparts, int64_t batch, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(cross_finish_kernel, dim3((unsigned)batch), dim3(ST_THREADS), 0, s, ws, nparts, out);
+    return check_launch(what);
+}
+
+}  // namespace
+}  // namespace dq

@@ -187,6 +187,23 @@ def test_cost_cross_exact(case, same, dt):
     assert torch.equal(torch.view_as_real(out), torch.view_as_real(again))
 
 
+@pytest.mark.parametrize('dt', ['c64', 'c128'])
+@pytest.mark.parametrize('same', [True, False], ids=['expect', 'cross'])
+def test_cost_cross_finish_second_stride_exact(same, dt):
+    """512 partial sums per sample, batch 2: the finish kernel's lanes take a second stride of 256 partial sums and a
+    second sample's row of the workspace (512 chunks: n = 20 complex64 / 19 complex128, full width).  Integer states in
+    [-4, 4] and integer costs in [-16, 16]: every term is an integer of magnitude <= 512 and every sum of the 2^20 at most
+    stays below 2^29 < 2^53, so the reference is exact in any order."""
+    n = {'c64': 20, 'c128': 19}[dt]
+    ket, kr = integer_state(n, 2, dt)
+    bra, br = (ket, kr) if same else integer_state(n, 2, dt, seed=5)
+    cr = np.random.default_rng(n).integers(-16, 17, 1 << n).astype(np.float64)
+    c = torch.from_numpy(cr).to(DTYPES[dt].to_real()).cuda()
+    out = backend.cost_cross(bra, ket, c, full(n))
+    assert out.dtype == torch.complex128 and out.shape == (2,)
+    assert np.array_equal(out.cpu().numpy(), (cr * br.conj() * kr).sum(-1))
+
+
 # ---- seeded Gaussian rows -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('dt', ['c64', 'c128'])
 @pytest.mark.parametrize('n', FULL_N + ('big',))

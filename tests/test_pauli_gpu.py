@@ -226,6 +226,22 @@ def test_pauli_cross_exact(case, same, dt):
 
 @pytest.mark.parametrize('dt', ['c64', 'c128'])
 @pytest.mark.parametrize('same', [True, False], ids=['expect', 'cross'])
+def test_pauli_cross_finish_second_stride_exact(same, dt):
+    """512 partial sums per sample, batch 2: the finish kernel's lanes take a second stride of 256 partial sums and a
+    second sample's row of the workspace (2^19 pairs of vectors: n = 21 complex64 / 20 complex128 with the top bit
+    flipped).  Integer states in [-4, 4]: every term is an integer of magnitude <= 32 and every sum of the 2^21 at most
+    stays below 2^26 < 2^53, so the reference is exact in any order."""
+    n = {'c64': 21, 'c128': 20}[dt]
+    xmask, zmask, controls = 1 << (n - 1) | 1 << 3, 1 << (n - 1) | 1 << 6, (2,)
+    ket, kr = integer_state(n, 2, dt)
+    bra, br = (ket, kr) if same else integer_state(n, 2, dt, seed=5)
+    out = backend.pauli_cross(bra, ket, xmask, zmask, controls)
+    assert out.dtype == torch.complex128 and out.shape == (2,)
+    assert np.array_equal(out.cpu().numpy(), cross_ref(br, kr, xmask, zmask, controls))
+
+
+@pytest.mark.parametrize('dt', ['c64', 'c128'])
+@pytest.mark.parametrize('same', [True, False], ids=['expect', 'cross'])
 @pytest.mark.parametrize('case', list(CROSS_CASES))
 def test_pauli_cross_gaussian(case, same, dt):
     n, xmask, zmask, controls, batch = CROSS_CASES[case]
