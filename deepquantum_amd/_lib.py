@@ -35,6 +35,7 @@ FAST_NONE = 0xFFFFFFFF
 MAT_PAD = 16
 COST_PHASE, COST_SCALE = range(2)      # op of dq_apply_cost_*
 PAULI_GATE, PAULI_MAP = range(2)       # mode of dq_apply_pauli_axpby_*
+PERM_AUTO, PERM_GATHER, PERM_LOCAL = range(3)      # path of dq_apply_permutation_*
 
 
 class DqFusedGate(C.Structure):
@@ -156,6 +157,8 @@ _SIGNATURES = {
     'dq_apply_pauli_axpby_{s}': (_i, [_vp, _vp, _u64, _u64, _vp, _i, _i, _ip, _i, _i64, _vp]),
     'dq_pauli_cross_ws_bytes': (_i64, [_i, _i64, _i, _i]),
     'dq_pauli_cross_{s}': (_i, [_vp, _vp, _u64, _u64, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),
+    'dq_apply_permutation_{s}': (_i, [_vp, _vp, _vp, _i, _ip, _i, _ip, _i, _i64, _i, _vp]),
+    'dq_permutation_local_bits': (_i, [_i]),
 }
 
 

@@ -1150,3 +1150,77 @@ def pauli_cross(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, co
         return _diag_double(double)
     mid = (xmask, zmask, n, _lib.int_array(controls), len(controls))
     return _cross_reduce('dq_pauli_cross', 'dq_pauli_cross_ws_bytes', bra, ket, mid)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Basis-state permutations on any number of wires (csrc/dq_perm.hip): out[b, j] = in[b, put(j, src[sub(j)])], where
+# put(j, v) is j with the table bits replaced by the bits of v
+PERM_PATHS = {'auto': _lib.PERM_AUTO, 'gather': _lib.PERM_GATHER, 'local': _lib.PERM_LOCAL}
+PERM_MAX_BITS = 31
+
+
+def permutation_local_bits(dtype: torch.dtype) -> int:
+    """log2 of the amplitudes of a chunk of the 'local' path: every table bit must lie below it."""
+    return _lib.load().dq_permutation_local_bits(int(dtype == torch.complex128))
+
+
+def _perm_table(src: torch.Tensor, like: torch.Tensor, k: int, what: str) -> torch.Tensor:
+    """The table as int32 on the state's device, contiguous and 16-byte aligned.  Its entries are not looked at here (no
+    synchronisation): the kernels mask them to k bits, and whoever builds a table checks that it is a bijection
+    (``PermutationGate``)."""
+    if not isinstance(src, torch.Tensor) or src.is_floating_point() or src.is_complex() or src.dtype == torch.bool:
+        raise ValueError(f'{what}: the table must be an integer tensor')
+    if src.shape != (1 << k,):
+        raise ValueError(f'{what}: a table over {k} bits has {1 << k} entries; got {tuple(src.shape)}')
+    src = src.to(device=like.device, dtype=torch.int32).contiguous()
+    if src.is_cuda and src.data_ptr() % 16:
+        src = src.clone()
+    return src
+
+
+def apply_permutation(state: torch.Tensor, src: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = (),
+                      out: torch.Tensor | None = None, path: str = 'auto') -> torch.Tensor:
+    """out[b, j] = state[b, put(j, src[sub(j)])] on the amplitudes whose ``controls`` are all 1 (the others are copied): the
+    basis-state permutation |x> -> |perm(x)> on k = len(bits) index bits in gather form, ``src`` = perm^-1 an integer table
+    of 2^k entries, ``bits[0]`` the most significant bit of its index -- one read and one write of the state, amplitudes
+    copied bit for bit (``dq_apply_permutation_*``).  Out of place only: ``out`` must not overlap ``state``.  ``path``:
+    'gather', 'local' (every table bit below :func:`permutation_local_bits`) or 'auto'."""
+    n, bits, controls = _diag_args(state, bits, controls, 'apply_permutation')
+    k = len(bits)
+    if k > PERM_MAX_BITS:
+        raise ValueError(f'apply_permutation: at most {PERM_MAX_BITS} table bits, got {k}')
+    if path not in PERM_PATHS:
+        raise ValueError(f"apply_permutation: path must be 'auto', 'gather' or 'local', got {path!r}")
+    _suffix(state)
+    src = _perm_table(src, state, k, 'apply_permutation')
+    if out is None:
+        out = torch.empty_like(state)
+    else:
+        if out.shape != state.shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
+            raise ValueError("apply_permutation: out must be a contiguous tensor of the state's shape, dtype and device")
+        if abs(out.data_ptr() - state.data_ptr()) < state.numel() * state.element_size():
+            raise ValueError('apply_permutation: out overlaps the state (the permutation is out of place only)')
+    if path == 'local' and max(bits) >= permutation_local_bits(state.dtype):
+        raise ValueError(f"apply_permutation: path='local' needs every table bit below "
+                         f'{permutation_local_bits(state.dtype)}, got {bits}')
+    if not _use_hip(state):
+        return _diag_double(lambda: _apply_permutation_double(state, src, n, bits, controls, out))
+    fn = getattr(_lib.load(), f'dq_apply_permutation_{_suffix(state)}')
+    for lo in range(0, state.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, state.shape[0])
+        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(src), n, _lib.int_array(bits), k, _lib.int_array(controls),
+                len(controls), hi - lo, PERM_PATHS[path], _stream(state))
+        _lib.check(rc, 'dq_apply_permutation')
+    return out
+
+
+def _apply_permutation_double(state, src, n, bits, controls, out):
+    k = len(bits)
+    sub, ok = _sub_index(n, bits, controls)
+    v = src.to(torch.int64)[sub] & ((1 << k) - 1)
+    i = torch.arange(1 << n)
+    index = i & ~sum(1 << p for p in bits)
+    for j, p in enumerate(bits):
+        index = index | (((v >> (k - 1 - j)) & 1) << p)
+    out.copy_(state[:, torch.where(ok, index, i)])
+    return out

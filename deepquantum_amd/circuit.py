@@ -27,7 +27,7 @@ from torch import nn
 from . import _functorch, executor, ops, qmath
 from .gate import (
     CNOT, Barrier, CostPhase, DiagonalGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, PauliEvolution, PauliRot,
-    PauliX, PauliY, PauliZ, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
+    PauliX, PauliY, PauliZ, PermutationGate, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
     TDaggerGate, TGate, Toffoli, U3Gate, UAnyGate,
 )
 from .layer import CnotLayer, CnotRing, HLayer, Observable, RxLayer, RyLayer, RzLayer, U3Layer, XLayer, YLayer, ZLayer
@@ -152,7 +152,7 @@ class QubitCircuit(Operation):
 
     def _run_operators(self, flat: torch.Tensor, zero: bool = False) -> torch.Tensor:
         """All operators on a (B, 2**n) state: maximal stretches of gates go to the executor (fused passes),
-        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
+        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
         density matrix alike: index 0 is 1, everything else 0)."""
         if self.den_mat:
             prims = []
@@ -741,6 +741,42 @@ class QubitCircuit(Operation):
         wires by default): see :class:`DiagonalGate`."""
         self.add(DiagonalGate(diag=diag, nqubit=self.nqubit, wires=wires, minmax=minmax, controls=controls, name=name,
                               den_mat=self.den_mat))
+
+    def permutation(self, perm, wires=None, minmax=None, controls=None, name='permutation'):
+        """The classical reversible map ``|x> -> |perm(x)>`` given by its table of 2^k integers, a bijection of
+        ``range(2^k)`` (``wires[0]`` = the most significant bit of ``x``; all wires by default): see
+        :class:`PermutationGate`."""
+        self.add(PermutationGate(perm=perm, nqubit=self.nqubit, wires=wires, minmax=minmax, controls=controls, name=name,
+                                 den_mat=self.den_mat))
+
+    def bit_oracle(self, f, xwires, ywires, controls=None, name='bit_oracle'):
+        """``|x>|y> -> |x>|y xor f(x)>`` for a table ``f`` of 2^len(xwires) integers below 2^len(ywires), as one
+        :class:`PermutationGate` on ``xwires + ywires`` (the first wire of each list = its most significant bit)."""
+        xwires = [xwires] if isinstance(xwires, int) else list(xwires)
+        ywires = [ywires] if isinstance(ywires, int) else list(ywires)
+        f = torch.as_tensor(f).reshape(-1)
+        if f.is_floating_point() or f.is_complex() or f.dtype == torch.bool:
+            raise ValueError(f'bit_oracle: the table must hold integers, got {f.dtype}')
+        f = f.to(torch.int64).cpu()
+        kx, ky = len(xwires), len(ywires)
+        if kx < 1 or ky < 1 or kx + ky > 31:
+            raise ValueError(f'bit_oracle: at least one wire of each kind and at most 31 in all, got {kx} + {ky}')
+        if f.shape[0] != 2**kx:
+            raise ValueError(f'bit_oracle: f over {kx} wires has {2**kx} entries, got {f.shape[0]}')
+        if int(f.min()) < 0 or int(f.max()) >= 2**ky:
+            raise ValueError(f'bit_oracle: the values of f must lie in [0, {2**ky}), got {int(f.min())} .. {int(f.max())}')
+        x = torch.arange(2**kx, dtype=torch.int64).reshape(-1, 1)
+        y = torch.arange(2**ky, dtype=torch.int64).reshape(1, -1)
+        perm = ((x << ky) | (y ^ f.reshape(-1, 1))).reshape(-1)
+        self.permutation(perm, wires=xwires + ywires, controls=controls, name=name)
+
+    def modmul(self, a, mod, wires=None, controls=None, name='modmul'):
+        """``|x> -> |a x mod N>`` for ``x < N`` (``x >= N`` stays) on ``wires`` (all by default; the first = the most
+        significant bit) in one pass and without ancillas; ``gcd(a, N) = 1`` and ``N <= 2^k`` are required."""
+        if wires is None:
+            wires = list(range(self.nqubit))
+        wires = [wires] if isinstance(wires, int) else list(wires)
+        self.permutation(qmath.modmul_table(a, mod, len(wires)), wires=wires, controls=controls, name=name)
 
     def cost_phase(self, cost, wires=None, minmax=None, inputs=None, controls=None, encode=False, name='cost_phase'):
         """``exp(-i t diag(cost))`` for a table of 2^k real costs (all wires by default) with one parameter ``t``: trainable,

@@ -10,13 +10,11 @@
 //
 // Geometry.  That of dq_stream.hpp with a vector as the item: a chunk is a unit of 1024 vectors, 16 KiB.
 //
-// Gather.  sub() is OR-separable over the index bits.  The host cuts the bit list into runs of consecutive positions
-// (a run is one shift, one mask, one shift) and splits them at the chunk size: the runs below it depend on the lane
-// alone and are evaluated once, before the loop (ST_UNROLL * 2 table offsets per lane at most); the runs above depend
-// on the chunk index alone, which is uniform over the workgroup: scalar arithmetic, once per iteration.  The control
-// mask is split the same way: a chunk whose high control bits are not all set is copied (or skipped, in place)
-// without a table access.  With bits = n-1 .. 0 and no controls sub(i) = i: the table is read with vector loads beside
-// the state and nothing is gathered (the IDENT instantiations).
+// Gather.  dq_stream.hpp's: sub() in runs of consecutive positions split at the chunk size, the low runs evaluated once
+// per lane before the loop (ST_UNROLL * 2 table offsets per lane at most), the high runs once per chunk in scalar
+// arithmetic.  A chunk whose high control bits are not all set is copied (or skipped, in place) without a table
+// access.  With bits = n-1 .. 0 and no controls sub(i) = i: the table is read with vector loads beside the state and
+// nothing is gathered (the IDENT instantiations).
 //
 // Phase.  The angle is double(t) * double(cost) for both precisions, turned into a fraction of a turn in double
 // (times 1 / 2 pi, minus the nearest integer); only that fraction, in [-1/2, 1/2], goes to sincospi in the state's
@@ -31,17 +29,7 @@ namespace dq {
 
 namespace {
 
-constexpr int DG_MAX_RUNS = 42;                         // 40 single bits, one of them split at the chunk size
-
 enum { MODE_DIAG = 0, MODE_PHASE = 1, MODE_SCALE = 2 };
-
-// sub(i) = OR over the runs of ((i >> src) & (2^len - 1)) << dst; runs [0, nlow) lie below the chunk size, the rest
-// at or above it.
-struct Gather {
-    int nruns, nlow;
-    uint8_t src[DG_MAX_RUNS], len[DG_MAX_RUNS], dst[DG_MAX_RUNS];
-    uint64_t cmask;
-};
 
 __device__ __forceinline__ void sincos_turns(float halfturns, float* s, float* c) { sincospif(halfturns, s, c); }
 __device__ __forceinline__ void sincos_turns(double halfturns, double* s, double* c) { sincospi(halfturns, s, c); }
@@ -78,37 +66,6 @@ template <typename E, int VEC> __device__ __forceinline__ void load_beside(const
     const Row r = reinterpret_cast<const Row*>(tab)[v];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) d[e] = r.e[e];
-}
-
-// What a lane keeps across the loop: the low part of sub() and the low control test of each of its amplitudes.
-template <int VEC> struct LaneLow {
-    uint64_t sub[ST_UNROLL][VEC];
-    unsigned ok;                                        // bit u * VEC + e
-};
-
-template <int VEC>
-__device__ __forceinline__ void lane_low(const Gather& g, int sbits, LaneLow<VEC>& ll) {
-    constexpr int VB = VEC == 2 ? 1 : 0;
-    const uint64_t cl = g.cmask & ((1ull << sbits) - 1ull);
-    ll.ok = 0;
-#pragma unroll
-    for (int u = 0; u < ST_UNROLL; ++u) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const uint64_t low = ((uint64_t)(u * ST_THREADS + (int)threadIdx.x) << VB) | (uint64_t)e;
-            uint64_t s = 0;
-            for (int r = 0; r < g.nlow; ++r) s |= ((low >> g.src[r]) & ((1ull << g.len[r]) - 1ull)) << g.dst[r];
-            ll.sub[u][e] = s;
-            if ((low & cl) == cl) ll.ok |= 1u << (u * VEC + e);
-        }
-    }
-}
-
-// the chunk's part of sub() (uniform over the workgroup)
-__device__ __forceinline__ uint64_t chunk_high(const Gather& g, int sbits, uint64_t chunk) {
-    uint64_t s = 0;
-    for (int r = g.nlow; r < g.nruns; ++r) s |= ((chunk >> (g.src[r] - sbits)) & ((1ull << g.len[r]) - 1ull)) << g.dst[r];
-    return s;
 }
 
 // in and out may be the same buffer: no __restrict__ on them
@@ -241,50 +198,6 @@ __global__ __launch_bounds__(ST_THREADS) void cost_cross_kernel(const cx<T>* __r
         }
     }
     write_partial(re, im, sh, ws);
-}
-
-// Validates the lists and builds the runs; `ident`: bits = n-1 .. 0 and no controls.
-int plan_gather(const char* what, int n, const int* bits, int k, const int* controls, int nc, int64_t batch, bool is_c128,
-                Gather* g, bool* ident) {
-    if (k < 1) {
-        set_error("%s: k=%d, at least one table bit is needed", what, k);
-        return DQ_ERR_ARG;
-    }
-    if (int rc = validate_bits(n, bits, k, controls, nc)) return rc;
-    if (int rc = check_batch(what, batch)) return rc;
-    const int sbits = ST_UNIT_BITS + (is_c128 ? 0 : 1);
-    *g = Gather{};
-    g->cmask = control_mask(controls, nc);
-    *ident = nc == 0 && k == n;
-    for (int j = 0; j < k && *ident; ++j) *ident = bits[j] == n - 1 - j;
-    // runs of consecutive positions, split at the chunk size
-    struct Run { int src, len, dst; };
-    Run low[DG_MAX_RUNS], high[DG_MAX_RUNS];
-    int nl = 0, nh = 0;
-    for (int j = 0; j < k;) {
-        int e = j;
-        while (e + 1 < k && bits[e + 1] == bits[e] - 1) ++e;
-        Run r{bits[e], e - j + 1, k - 1 - e};
-        if (r.src < sbits && r.src + r.len > sbits) {
-            const int ll = sbits - r.src;
-            low[nl++] = Run{r.src, ll, r.dst};
-            high[nh++] = Run{sbits, r.len - ll, r.dst + ll};
-        } else if (r.src < sbits) {
-            low[nl++] = r;
-        } else {
-            high[nh++] = r;
-        }
-        j = e + 1;
-    }
-    g->nlow = nl;
-    g->nruns = nl + nh;
-    for (int r = 0; r < nl + nh; ++r) {
-        const Run& x = r < nl ? low[r] : high[r - nl];
-        g->src[r] = (uint8_t)x.src;
-        g->len[r] = (uint8_t)x.len;
-        g->dst[r] = (uint8_t)x.dst;
-    }
-    return DQ_OK;
 }
 
 template <typename T, int MODE>

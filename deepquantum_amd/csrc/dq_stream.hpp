@@ -1,5 +1,6 @@
-// The core of the streaming primitives (dq_diag.hip, dq_pauli.hip): kernels that read a state once in 16-byte vectors,
-// do a little arithmetic per amplitude and either write the state back or reduce it to one complex number per sample.
+// The core of the streaming primitives (dq_diag.hip, dq_pauli.hip, dq_perm.hip): kernels that read a state once in
+// 16-byte vectors, do a little arithmetic per amplitude (or none) and either write the state back or reduce it to one
+// complex number per sample.
 // Each including file gets its own copy of what is here (the library is built without relocatable device code).
 //
 // Geometry.  A lane moves 16 bytes (two complex64 or one complex128 amplitude) per load, a workgroup of ST_THREADS
@@ -93,6 +94,53 @@ __global__ __launch_bounds__(ST_THREADS) void cross_finish_kernel(const double* 
     }
 }
 
+// ---- gather over a list of index bits (dq_diag.hip, dq_perm.hip) -----------------------------------
+// sub(i) = sum_j bit_{bits[j]}(i) << (k - 1 - j) is OR-separable over the index bits.  The host cuts the bit list into
+// runs of consecutive positions (a run is one shift, one mask, one shift) and splits them at the size of a unit of
+// vectors: the runs below it depend on the lane alone and are evaluated once, before the loop; the runs above depend on
+// the unit's index alone, which is uniform over the workgroup: scalar arithmetic, once per iteration.  The control mask
+// is split the same way.
+constexpr int ST_MAX_RUNS = 42;                         // 40 single bits, one of them split at the unit size
+
+// sub(i) = OR over the runs of ((i >> src) & (2^len - 1)) << dst; runs [0, nlow) lie below the unit size, the rest
+// at or above it.
+struct Gather {
+    int nruns, nlow;
+    uint8_t src[ST_MAX_RUNS], len[ST_MAX_RUNS], dst[ST_MAX_RUNS];
+    uint64_t cmask;
+};
+
+// What a lane keeps across the loop: the low part of sub() and the low control test of each of its amplitudes.
+template <int VEC> struct LaneLow {
+    uint64_t sub[ST_UNROLL][VEC];
+    unsigned ok;                                        // bit u * VEC + e
+};
+
+template <int VEC>
+__device__ __forceinline__ void lane_low(const Gather& g, int sbits, LaneLow<VEC>& ll) {
+    constexpr int VB = VEC == 2 ? 1 : 0;
+    const uint64_t cl = g.cmask & ((1ull << sbits) - 1ull);
+    ll.ok = 0;
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const uint64_t low = ((uint64_t)(u * ST_THREADS + (int)threadIdx.x) << VB) | (uint64_t)e;
+            uint64_t s = 0;
+            for (int r = 0; r < g.nlow; ++r) s |= ((low >> g.src[r]) & ((1ull << g.len[r]) - 1ull)) << g.dst[r];
+            ll.sub[u][e] = s;
+            if ((low & cl) == cl) ll.ok |= 1u << (u * VEC + e);
+        }
+    }
+}
+
+// the unit's part of sub() (uniform over the workgroup)
+__device__ __forceinline__ uint64_t chunk_high(const Gather& g, int sbits, uint64_t chunk) {
+    uint64_t s = 0;
+    for (int r = g.nlow; r < g.nruns; ++r) s |= ((chunk >> (g.src[r] - sbits)) & ((1ull << g.len[r]) - 1ull)) << g.dst[r];
+    return s;
+}
+
 // ---- host side ---------------------------------------------------------------------------------
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
@@ -107,6 +155,50 @@ uint64_t control_mask(const int* controls, int nc) {
     uint64_t m = 0;
     for (int c = 0; c < nc; ++c) m |= 1ull << controls[c];
     return m;
+}
+
+// Validates the lists and builds the runs; `ident`: bits = n-1 .. 0 and no controls.
+int plan_gather(const char* what, int n, const int* bits, int k, const int* controls, int nc, int64_t batch, bool is_c128,
+                Gather* g, bool* ident) {
+    if (k < 1) {
+        set_error("%s: k=%d, at least one table bit is needed", what, k);
+        return DQ_ERR_ARG;
+    }
+    if (int rc = validate_bits(n, bits, k, controls, nc)) return rc;
+    if (int rc = check_batch(what, batch)) return rc;
+    const int sbits = ST_UNIT_BITS + (is_c128 ? 0 : 1);
+    *g = Gather{};
+    g->cmask = control_mask(controls, nc);
+    *ident = nc == 0 && k == n;
+    for (int j = 0; j < k && *ident; ++j) *ident = bits[j] == n - 1 - j;
+    // runs of consecutive positions, split at the unit size
+    struct Run { int src, len, dst; };
+    Run low[ST_MAX_RUNS], high[ST_MAX_RUNS];
+    int nl = 0, nh = 0;
+    for (int j = 0; j < k;) {
+        int e = j;
+        while (e + 1 < k && bits[e + 1] == bits[e] - 1) ++e;
+        Run r{bits[e], e - j + 1, k - 1 - e};
+        if (r.src < sbits && r.src + r.len > sbits) {
+            const int ll = sbits - r.src;
+            low[nl++] = Run{r.src, ll, r.dst};
+            high[nh++] = Run{sbits, r.len - ll, r.dst + ll};
+        } else if (r.src < sbits) {
+            low[nl++] = r;
+        } else {
+            high[nh++] = r;
+        }
+        j = e + 1;
+    }
+    g->nlow = nl;
+    g->nruns = nl + nh;
+    for (int r = 0; r < nl + nh; ++r) {
+        const Run& x = r < nl ? low[r] : high[r - nl];
+        g->src[r] = (uint8_t)x.src;
+        g->len[r] = (uint8_t)x.len;
+        g->dst[r] = (uint8_t)x.dst;
+    }
+    return DQ_OK;
 }
 
 uint64_t vectors_of(int n, bool is_c128) { return 1ull << (n - (is_c128 ? 0 : 1)); }          // (n >= 1)

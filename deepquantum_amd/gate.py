@@ -992,6 +992,65 @@ class DiagonalGate(_FlatGate, ArbitraryGate):
         return ops.diag_mul(x, diag, self._bits(self.wires), self._bits(self.controls))
 
 
+class PermutationGate(_FlatGate, ArbitraryGate):
+    """A classical reversible map ``|x> -> |perm(x)>`` on ``wires`` / ``minmax`` given by its table of 2^k integers,
+    ``wires[0]`` the most significant bit of ``x`` (the matrix convention of ``UAnyGate``: the gate is the 0/1 matrix
+    ``M[perm[x], x] = 1``) -- a bit oracle, a modular multiplication, a shift: one read and one write of the state for any
+    k up to 31, amplitudes copied bit for bit (``dq_apply_permutation_*``), where a dense matrix does 2^k multiply-adds per
+    amplitude and has no route beyond 10 wires.  ``perm`` must be a bijection of ``range(2^k)``; it is checked here, once.
+    The gate keeps ``perm`` and its inverse ``inv`` as int32 buffers."""
+
+    def __init__(self, perm, nqubit=1, wires=None, minmax=None, controls=None, name='PermutationGate', den_mat=False,
+                 tsr_mode=False):
+        super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
+                         tsr_mode=tsr_mode)
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        k = len(self.wires)
+        if k > 31:
+            raise ValueError(f'PermutationGate: at most 31 wires, got {k}')
+        if isinstance(perm, torch.Tensor):
+            if perm.is_floating_point() or perm.is_complex() or perm.dtype == torch.bool:
+                raise ValueError(f'PermutationGate: the table must hold integers, got {perm.dtype}')
+            table = perm.detach().reshape(-1).to(torch.int64)
+        else:
+            entries = list(perm)
+            if any(int(v) != v for v in entries):
+                raise ValueError('PermutationGate: the table must hold integers')
+            table = torch.tensor([int(v) for v in entries], dtype=torch.int64)
+        if table.shape[0] != 2**k:
+            raise ValueError(f'PermutationGate: a permutation on {k} wires has {2**k} entries, got {table.shape[0]}')
+        if int(table.min()) < 0 or int(table.max()) >= 2**k:
+            raise ValueError(f'PermutationGate: the entries must lie in [0, {2**k}), got {int(table.min())} .. {int(table.max())}')
+        inv = torch.full_like(table, -1)
+        inv[table] = torch.arange(2**k, dtype=torch.int64, device=table.device)
+        if int(inv.min()) < 0:
+            raise ValueError(f'PermutationGate: the table is not a bijection: it repeats entries and never reaches '
+                             f'{int((inv < 0).nonzero()[0])}')
+        self.register_buffer('perm', table.to(torch.int32))
+        self.register_buffer('inv', inv.to(torch.int32))
+        # (integer tables have no precision: this marker follows `.to()` / `.double()` of the circuit for `_state_like`)
+        self.register_buffer('_like', torch.zeros((), device=table.device), persistent=False)
+
+    def tables(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """(perm, perm^-1) of the gate as it stands: ``inverse()`` swaps them."""
+        return (self.inv, self.perm) if self.inv_mode else (self.perm, self.inv)
+
+    def _state_like(self) -> tuple[torch.dtype, torch.device]:
+        return (torch.complex128 if self._like.dtype == torch.float64 else torch.complex64), self.perm.device
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        perm, inv = self.tables()
+        return ops.permute_basis(x, perm, self._bits(self.wires), self._bits(self.controls), inv=inv)
+
+    def extra_repr(self) -> str:
+        s = f'wires={self.wires}, entries={self.perm.numel()}'
+        return s if self.controls == [] else s + f', controls={self.controls}'
+
+
 class CostPhase(_FlatGate, ArbitraryGate):
     """``exp(-i t diag(cost))`` with one parameter ``t`` and a classical cost table of 2^k real entries over ``wires`` /
     ``minmax`` (``wires[0]`` the most significant bit of the entry index): a whole QAOA cost layer -- any cost, not only a

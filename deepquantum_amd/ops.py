@@ -1093,3 +1093,64 @@ def pauli_rot(state: torch.Tensor, xmask: int, zmask: int, theta, controls: Sequ
     xmask, zmask, controls = _pauli_masks(xmask, zmask, controls)
     theta = _pauli_param(theta, state, torch.float64, 'pauli_rot')
     return _PauliRot.apply(_flat_arg(state), theta, xmask, zmask, controls)
+
+
+# ---- basis-state permutations on any number of wires (csrc/dq_perm.hip) --------------------------------------------------
+# P |x> = |perm(x)> on the table bits, inside the controls: a real permutation matrix, so its adjoint is its inverse.  One
+# operation closed under differentiation: the backward and the jvp are the function itself.
+class _PermuteBasis(torch.autograd.Function):
+    """y = P x, in gather form y[j] = x[put(j, inv[sub(j)])] with inv = perm^-1: linear in x, cotangent gx = P^T gy -- the
+    permutation by the inverse table, which is the same function with the two tables swapped."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, perm: torch.Tensor, inv: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
+        return backend.apply_permutation(_plain(state), _plain(inv), bits, controls)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _state, perm, inv, ctx.bits, ctx.controls = inputs
+        ctx.save_for_backward(perm, inv)
+        ctx.save_for_forward(perm, inv)
+
+    @staticmethod
+    def jvp(ctx, state_t, *_):
+        _single_forward_level()
+        perm, inv = ctx.saved_tensors
+        return _PermuteBasis.apply(_flat_arg(state_t), perm, inv, ctx.bits, ctx.controls)
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        perm, inv = ctx.saved_tensors
+        return _PermuteBasis.apply(_flat_arg(gy), inv, perm, ctx.bits, ctx.controls), None, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, perm, inv, bits, controls):
+        _unmapped_table(in_dims[1], 'permute_basis')
+        _unmapped_table(in_dims[2], 'permute_basis')
+        v = info.batch_size
+        sf = _fold(state, in_dims[0], v)
+        out = _PermuteBasis.apply(sf, perm, inv, bits, controls)
+        return out.reshape(v, -1, out.shape[-1]), 0
+
+
+def invert_table(perm: torch.Tensor) -> torch.Tensor:
+    """perm^-1 of a bijection of range(len(perm)) (not checked here: ``PermutationGate`` checks what it is given)."""
+    inv = torch.empty_like(perm)
+    inv[perm.long()] = torch.arange(perm.shape[0], dtype=perm.dtype, device=perm.device)
+    return inv
+
+
+def permute_basis(state: torch.Tensor, perm: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = (),
+                  inv: torch.Tensor | None = None) -> torch.Tensor:
+    """Differentiable (in the state) basis-state permutation ``|x> -> |perm(x)>`` on a (B, 2**n) state: ``perm`` a constant
+    integer table of 2^k entries, a bijection of ``range(2^k)``, over the index bits ``bits`` (``bits[0]`` = its most
+    significant bit); amplitudes outside the controls pass through.  One read and one write of the state, amplitudes
+    copied bit for bit.  ``inv``: perm^-1 where the caller holds it already (it is formed here otherwise)."""
+    _no_legacy(state)
+    for t in (perm, inv):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.ndim != 1):
+            raise ValueError('permute_basis: the table must be a 1-D integer tensor')
+    bits, controls = _bit_args(bits, controls)
+    if inv is None:
+        inv = invert_table(perm)
+    return _PermuteBasis.apply(_flat_arg(state), perm, inv, bits, controls)

@@ -29,6 +29,20 @@ def inverse_permutation(permute_shape: list[int]) -> list[int]:
     return inv
 
 
+def modmul_table(a: int, mod: int, k: int) -> torch.Tensor:
+    """The table of ``x -> a x mod N`` on k bits as a bijection of ``range(2^k)``: ``a x mod N`` for ``x < N`` and ``x``
+    itself for ``x >= N`` (int64, (2^k,)).  ``gcd(a, N) = 1`` makes it one; ``1 <= N <= 2^k``."""
+    a, mod, k = int(a), int(mod), int(k)
+    if k < 1 or k > 31:
+        raise ValueError(f'modmul_table: k={k} outside [1, 31]')
+    if mod < 1 or mod > 2**k:
+        raise ValueError(f'modmul_table: the modulus {mod} must lie in [1, 2^{k} = {2**k}]')
+    if math.gcd(a, mod) != 1:
+        raise ValueError(f'modmul_table: gcd({a}, {mod}) = {math.gcd(a, mod)}: x -> {a} x mod {mod} is not reversible')
+    x = torch.arange(2**k, dtype=torch.int64)
+    return torch.where(x < mod, (x * (a % mod)) % mod, x)           # (a mod N < 2^31 and x < 2^31: no overflow)
+
+
 def amplitude_encoding(data: Any, nqubit: int) -> torch.Tensor:
     """Normalised state(s) of ``nqubit`` qubits from raw amplitudes, zero padded or truncated
     (reference: qmath.py:456-482).  Returns (batch, 2**n, 1)."""

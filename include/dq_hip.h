@@ -637,6 +637,29 @@ int dq_pauli_cross_c64(const void* bra, const void* ket, uint64_t xmask, uint64_
 int dq_pauli_cross_c128(const void* bra, const void* ket, uint64_t xmask, uint64_t zmask, int n, const int* controls, int nc,
                         int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 10. Basis-state permutations on any number of wires (csrc/dq_perm.hip; added within ABI 30, presence is checked by
+ *     symbol): the classical reversible maps |x> -> |perm(x)> -- bit oracles, modular arithmetic, shifts -- in one read and
+ *     one write of the state, with no arithmetic: amplitudes are copied bit for bit.
+ *         sub(i) as in section 8; put(i, v) = i with the k table bits replaced by the bits of v (sub(put(i, v)) = v)
+ *         out[b, j] = in[b, put(j, src[sub(j)])]     where all control bits of j are 1, in[b, j] elsewhere
+ *     `src`: DEVICE table of 2^k entries, the INVERSE of perm (gather form), shared by the batch, 4-byte aligned.  Every
+ *     entry is masked with 2^k - 1 before use: a table that is no bijection gives a wrong state and never a load outside
+ *     the sample.  `bits` / `controls` / `nc` as in section 8.  1 <= n <= 40, 1 <= k <= min(n, 31), 1 <= batch <= 65535;
+ *     state pointers 16-byte aligned.  OUT OF PLACE ONLY: [in, in + batch * 2^n) and [out, ..) must not overlap.
+ *     `path`: DQ_PERM_GATHER always applies; DQ_PERM_LOCAL (the permutation stays inside a 16-KiB chunk, which goes
+ *     through LDS) needs every table bit below dq_permutation_local_bits; DQ_PERM_AUTO takes LOCAL where it applies.
+ * ------------------------------------------------------------------------------------------ */
+#define DQ_PERM_AUTO 0
+#define DQ_PERM_GATHER 1
+#define DQ_PERM_LOCAL 2
+int dq_apply_permutation_c64(const void* in, void* out, const uint32_t* src, int n, const int* bits, int k, const int* controls,
+                             int nc, int64_t batch, int path, dq_stream_t stream);
+int dq_apply_permutation_c128(const void* in, void* out, const uint32_t* src, int n, const int* bits, int k, const int* controls,
+                              int nc, int64_t batch, int path, dq_stream_t stream);
+/* log2 of the amplitudes of a LOCAL chunk: 11 (complex64) / 10 (complex128). */
+int dq_permutation_local_bits(int is_c128);
+
 #ifdef __cplusplus
 }
 #endif
