@@ -25,7 +25,7 @@ from .channel import (
 )
 from .gate import (
     CNOT, ArbitraryGate, Barrier, CombinedSingleGate, CostPhase, DiagonalGate, DoubleControlGate, DoubleGate, Fredkin, Hadamard,
-    HamiltonianGate, Identity, ImaginarySwap, LatentGate, ParametricDoubleGate, ParametricSingleGate, PauliEvolution, PauliRot, PauliX, PauliY,
+    HamiltonianGate, Identity, ImaginarySwap, LatentGate, MultiplexedGate, MultiplexedRotation, ParametricDoubleGate, ParametricSingleGate, PauliEvolution, PauliRot, PauliX, PauliY,
     PauliZ, PermutationGate, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate,
     SingleGate, Swap, TDaggerGate, TGate, Toffoli, TripleGate, U3Gate, UAnyGate,
 )

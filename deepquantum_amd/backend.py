@@ -1224,3 +1224,89 @@ def _apply_permutation_double(state, src, n, bits, controls, out):
         index = index | (((v >> (k - 1 - j)) & 1) << p)
     out.copy_(state[:, torch.where(ok, index, i)])
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Multiplexed one-qubit gates on any number of select wires (csrc/dq_mux.hip): for every pair i0 (target bit 0),
+# i1 = i0 | 1 << target inside the controls, (out[i0], out[i1]) = M[sub(i0)] (in[i0], in[i1])
+MUX_KINDS = {'u': _lib.MUX_U, 'ry': _lib.MUX_RY}
+
+
+def _mux_table(table: torch.Tensor, like: torch.Tensor, kind: str, k: int, what: str) -> torch.Tensor:
+    """The table in the state's precision on its device, contiguous and 16-byte aligned: complex (2^k, 2, 2) for 'u', real
+    (2^k, 2) rows (c, s) for 'ry'.  Its entries are not looked at here (no synchronisation)."""
+    if not isinstance(table, torch.Tensor):
+        raise ValueError(f'{what}: the table must be a tensor, got {type(table).__name__}')
+    d = 1 << k
+    if kind == 'u':
+        if table.shape != (d, 2, 2) or not table.is_complex():
+            raise ValueError(f"{what}: a 'u' table over {k} select bits is complex ({d}, 2, 2); got {table.dtype} "
+                             f'{tuple(table.shape)}')
+        dtype = like.dtype
+    else:
+        if table.shape != (d, 2) or not table.is_floating_point():
+            raise ValueError(f"{what}: an 'ry' table over {k} select bits is real ({d}, 2), rows (c, s); got {table.dtype} "
+                             f'{tuple(table.shape)}')
+        dtype = torch.float64 if like.dtype == torch.complex128 else torch.float32
+    if table.requires_grad:
+        raise ValueError(f'{what}: the table is a constant -- gradients with respect to its entries are not supported; '
+                         'detach() it')
+    table = table.to(device=like.device, dtype=dtype).resolve_conj().resolve_neg().contiguous()
+    if table.is_cuda and table.data_ptr() % 16:
+        table = table.clone()
+    return table
+
+
+def apply_mux(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, bits: Sequence[int], controls: Sequence[int] = (),
+              dagger: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+    """A multiplexed (uniformly controlled) one-qubit gate: for every value s = sub(i) of the k = len(bits) select bits
+    (``bits[0]`` the most significant bit of s) the 2x2 matrix M[s] on index bit ``target``, on the amplitudes whose
+    ``controls`` are all 1 (the others pass through bitwise) -- one read and one write of the state whatever k is
+    (``dq_apply_mux_*``).  ``kind='u'``: ``table`` complex (2^k, 2, 2); ``kind='ry'``: real (2^k, 2) rows (c, s) for
+    M = [[c, -s], [s, c]].  One table for the whole batch.  ``dagger`` applies the conjugate transpose of every entry from
+    the same table.  ``out`` may be ``state``."""
+    what = 'apply_mux'
+    if kind not in MUX_KINDS:
+        raise ValueError(f"{what}: kind must be 'u' or 'ry', got {kind!r}")
+    n, bits, controls = _diag_args(state, bits, controls, what)
+    target = int(target)
+    if not _distinct_positions(bits + controls + [target], n):
+        raise ValueError(f'{what}: target {target} / bits {bits} / controls {controls} must be distinct positions in [0, {n})')
+    k = len(bits)
+    _suffix(state)
+    table = _mux_table(table, state, kind, k, what)
+    if out is None:
+        out = torch.empty_like(state)
+    elif out is not state:
+        if out.shape != state.shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous tensor of the state's shape, dtype and device")
+        if out.data_ptr() != state.data_ptr() and abs(out.data_ptr() - state.data_ptr()) < state.numel() * state.element_size():
+            raise ValueError(f'{what}: out overlaps the state without being the state')
+    if not _use_hip(state):
+        return _diag_double(lambda: _apply_mux_double(state, table, kind, n, target, bits, controls, bool(dagger), out))
+    fn = getattr(_lib.load(), f'dq_apply_mux_{_suffix(state)}')
+    for lo in range(0, state.shape[0], MAX_BATCH):
+        hi = min(lo + MAX_BATCH, state.shape[0])
+        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(table), MUX_KINDS[kind], int(bool(dagger)), n, target,
+                _lib.int_array(bits), k, _lib.int_array(controls), len(controls), hi - lo, _stream(state))
+        _lib.check(rc, 'dq_apply_mux')
+    return out
+
+
+def _apply_mux_double(state, table, kind, n, target, bits, controls, dagger, out):
+    sub, ok = _sub_index(n, bits, controls)
+    if kind == 'ry':
+        c, s = table[:, 0].to(torch.complex128), table[:, 1].to(torch.complex128)
+        m = torch.stack([torch.stack([c, -s], -1), torch.stack([s, c], -1)], -2)
+    else:
+        m = table.to(torch.complex128)
+    if dagger:
+        m = m.mH.resolve_conj()
+    m = m[sub]                                          # (2^n, 2, 2)
+    i = torch.arange(1 << n)
+    x = state.to(torch.complex128)
+    x0, x1 = x[:, i & ~(1 << target)], x[:, i | (1 << target)]
+    t = (i >> target) & 1
+    row = m[i, t]                                       # (2^n, 2): the row of M that makes amplitude i
+    out.copy_(torch.where(ok, row[:, 0] * x0 + row[:, 1] * x1, x).to(state.dtype))
+    return out

@@ -26,8 +26,8 @@ from torch import nn
 
 from . import _functorch, executor, ops, qmath
 from .gate import (
-    CNOT, Barrier, CostPhase, DiagonalGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, PauliEvolution, PauliRot,
-    PauliX, PauliY, PauliZ, PermutationGate, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
+    CNOT, Barrier, CostPhase, DiagonalGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, MultiplexedGate, MultiplexedRotation, PauliEvolution,
+    PauliRot, PauliX, PauliY, PauliZ, PermutationGate, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
     TDaggerGate, TGate, Toffoli, U3Gate, UAnyGate,
 )
 from .layer import CnotLayer, CnotRing, HLayer, Observable, RxLayer, RyLayer, RzLayer, U3Layer, XLayer, YLayer, ZLayer
@@ -152,7 +152,7 @@ class QubitCircuit(Operation):
 
     def _run_operators(self, flat: torch.Tensor, zero: bool = False) -> torch.Tensor:
         """All operators on a (B, 2**n) state: maximal stretches of gates go to the executor (fused passes),
-        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
+        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
         density matrix alike: index 0 is 1, everything else 0)."""
         if self.den_mat:
             prims = []
@@ -777,6 +777,57 @@ class QubitCircuit(Operation):
             wires = list(range(self.nqubit))
         wires = [wires] if isinstance(wires, int) else list(wires)
         self.permutation(qmath.modmul_table(a, mod, len(wires)), wires=wires, controls=controls, name=name)
+
+    def multiplexer(self, unitaries, wires, controls=None, name='multiplexer'):
+        """A multiplexer (uniformly controlled gate): ``unitaries[s]``, a table of shape (2^k, 2, 2), on the LAST wire of
+        ``wires`` for every value s of the k wires before it (``wires[0]`` = the most significant bit of s): see
+        :class:`MultiplexedGate`."""
+        self.add(MultiplexedGate(unitaries=unitaries, nqubit=self.nqubit, wires=wires, controls=controls, name=name,
+                                 den_mat=self.den_mat))
+
+    def ucr(self, axis, angles, wires, controls=None, name=None):
+        """A multiplexed rotation: ``R_axis(angles[s])`` (``axis`` one of 'x', 'y', 'z') on the LAST wire of ``wires`` for
+        every value s of the k wires before it (``wires[0]`` = the most significant bit of s), 2^k fixed angles: see
+        :class:`MultiplexedRotation`."""
+        self.add(MultiplexedRotation(axis=axis, angles=angles, nqubit=self.nqubit, wires=wires, controls=controls,
+                                     name=name or f'ucr{axis}', den_mat=self.den_mat))
+
+    def ucrx(self, angles, wires, controls=None):
+        self.ucr('x', angles, wires, controls=controls)
+
+    def ucry(self, angles, wires, controls=None):
+        self.ucr('y', angles, wires, controls=controls)
+
+    def ucrz(self, angles, wires, controls=None):
+        self.ucr('z', angles, wires, controls=controls)
+
+    def prepare_state(self, state, wires=None, controls=None):
+        """Appends the gates that map ``|0..0>`` of ``wires`` (all by default) to the vector ``state`` of 2^k entries,
+        ``wires[0]`` the most significant bit of its index -- anywhere in a circuit, on some of the wires, under controls:
+        one ``ry``, k - 1 multiplexed Ry of 1 .. k - 1 select wires, and a diagonal of the phases (left out for a real
+        non-negative vector).  The vector is normalised, and the angles are formed, in float64."""
+        if wires is None:
+            wires = list(range(self.nqubit))
+        wires = [wires] if isinstance(wires, int) else list(wires)
+        k = len(wires)
+        phi = torch.as_tensor(state).detach().cpu().reshape(-1)
+        phi = phi.to(torch.complex128)
+        if k < 1 or phi.shape[0] != 2**k:
+            raise ValueError(f'prepare_state: a state on {k} wires has {2**k} entries, got {phi.shape[0]}')
+        norm = float(torch.linalg.vector_norm(phi))
+        if not norm > 0.0 or norm == float('inf'):
+            raise ValueError('prepare_state: the vector must have a finite, non-zero norm')
+        phi = phi / norm
+        p = phi.real**2 + phi.imag**2
+        for j in range(k):
+            pj = p.reshape(2**j, 2, -1).sum(-1)
+            theta = 2 * torch.atan2(pj[:, 1].sqrt(), pj[:, 0].sqrt())           # (an empty branch: atan2(0, 0) = 0)
+            if j == 0:
+                self.ry(wires[0], inputs=theta[0], controls=controls)
+            else:
+                self.ucry(theta, wires[:j] + [wires[j]], controls=controls)
+        if bool((phi.imag != 0).any()) or bool((phi.real < 0).any()):
+            self.diagonal(torch.exp(1j * torch.angle(phi)), wires=wires, controls=controls, name='prepare_state_phase')
 
     def cost_phase(self, cost, wires=None, minmax=None, inputs=None, controls=None, encode=False, name='cost_phase'):
         """``exp(-i t diag(cost))`` for a table of 2^k real costs (all wires by default) with one parameter ``t``: trainable,

@@ -1,4 +1,4 @@
-// The core of the streaming primitives (dq_diag.hip, dq_pauli.hip, dq_perm.hip): kernels that read a state once in
+// The core of the streaming primitives (dq_diag.hip, dq_pauli.hip, dq_perm.hip, dq_mux.hip): kernels that read a state once in
 // 16-byte vectors, do a little arithmetic per amplitude (or none) and either write the state back or reduce it to one
 // complex number per sample.
 // Each including file gets its own copy of what is here (the library is built without relocatable device code).
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(ST_THREADS) void cross_finish_kernel(const double* 
     }
 }
 
-// ---- gather over a list of index bits (dq_diag.hip, dq_perm.hip) -----------------------------------
+// ---- gather over a list of index bits (dq_diag.hip, dq_perm.hip, dq_mux.hip) -------------------------
 // sub(i) = sum_j bit_{bits[j]}(i) << (k - 1 - j) is OR-separable over the index bits.  The host cuts the bit list into
 // runs of consecutive positions (a run is one shift, one mask, one shift) and splits them at the size of a unit of
 // vectors: the runs below it depend on the lane alone and are evaluated once, before the loop; the runs above depend on

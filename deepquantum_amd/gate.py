@@ -1051,6 +1051,145 @@ class PermutationGate(_FlatGate, ArbitraryGate):
         return s if self.controls == [] else s + f', controls={self.controls}'
 
 
+def _mux_wires(gate: 'ArbitraryGate', name: str) -> int:
+    """k of a multiplexer on ``gate.wires`` = k select wires, most significant first, then the target."""
+    k = len(gate.wires) - 1
+    if k < 1:
+        raise ValueError(f'{name}: wires lists at least one select wire and then the target, got {gate.wires}')
+    return k
+
+
+class MultiplexedGate(_FlatGate, ArbitraryGate):
+    """A multiplexer (uniformly controlled gate): for every value s of the k select wires its own one-qubit unitary
+    ``unitaries[s]`` on the target.  ``wires`` lists the select wires, the most significant bit of s first, and then the
+    target as the LAST wire, so that the gate equals ``UAnyGate(block_diag(U_0, .., U_{2^k - 1}), wires=wires)`` -- but
+    runs as one read and one write of the state for any k up to n - 1 (``dq_apply_mux_*``), where the dense matrix does
+    2^(k+1) multiply-adds per amplitude and has no route beyond 10 wires.  Every block is checked for unitarity to the
+    1e-4 that ``UAnyGate`` applies to its matrix.  The table is a constant: it carries no gradient."""
+
+    def __init__(self, unitaries, nqubit=1, wires=None, minmax=None, controls=None, name='MultiplexedGate', den_mat=False,
+                 tsr_mode=False):
+        super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
+                         tsr_mode=tsr_mode)
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        k = _mux_wires(self, 'MultiplexedGate')
+        if not isinstance(unitaries, torch.Tensor):
+            unitaries = torch.tensor(unitaries, dtype=torch.cfloat)
+        if unitaries.requires_grad:
+            raise ValueError('MultiplexedGate: the table is a constant -- gradients with respect to its entries are not '
+                             'supported; detach() it')
+        if not unitaries.is_complex():
+            unitaries = unitaries.to(torch.cdouble if unitaries.dtype == torch.float64 else torch.cfloat)
+        if unitaries.shape != (2**k, 2, 2):
+            raise ValueError(f'MultiplexedGate: {k} select wires take a table of shape ({2**k}, 2, 2), got '
+                             f'{tuple(unitaries.shape)}')
+        eye = torch.eye(2, dtype=unitaries.dtype, device=unitaries.device)
+        if not torch.allclose(unitaries @ unitaries.mH, eye.expand_as(unitaries), rtol=1e-5, atol=1e-4):
+            raise ValueError('MultiplexedGate: a block of the table is not unitary')
+        self.register_buffer('unitaries', unitaries.resolve_conj().contiguous())
+
+    def _table(self) -> torch.Tensor:
+        return self.unitaries
+
+    def _apply(self, fn: Any, *args, **kwargs):
+        from .utils import complex_apply
+
+        held = {'unitaries': self._buffers.pop('unitaries')}
+        nn.Module._apply(self, fn, *args, **kwargs)
+        for key, value in complex_apply(fn, held).items():
+            self.register_buffer(key, value)
+        return self
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        (target,) = self._bits(self.wires[-1:])
+        return ops.mux_apply(x, self.unitaries, 'u', target, self._bits(self.wires[:-1]), self._bits(self.controls),
+                             dagger=self.inv_mode)
+
+    def extra_repr(self) -> str:
+        s = f'select={self.wires[:-1]}, target={self.wires[-1]}'
+        return s if self.controls == [] else s + f', controls={self.controls}'
+
+
+class MultiplexedRotation(_FlatGate, ArbitraryGate):
+    """A multiplexed rotation (uniformly controlled Rx / Ry / Rz): ``R_axis(angles[s])`` on the target for every value s of
+    the k select wires.  ``wires`` lists the select wires, the most significant bit of s first, and then the target as
+    the LAST wire: the gate equals ``UAnyGate(block_diag(R(angles[0]), ..), wires=wires)``, and equals the 2^k
+    multi-controlled rotations with X flips it replaces -- in one read and one write of the state.  Cosine and sine of
+    ``angles / 2`` are taken in the dtype of the angle buffer, on the host side; the tables made of them -- rows (c, s) for
+    'y' (``DQ_MUX_RY``), 2x2 blocks for 'x' (``DQ_MUX_U``), phases over ``wires`` for 'z' (a diagonal operator:
+    ``ops.diag_mul``, no multiplexer kernel) -- are formed once per precision and direction and kept.  The angles are
+    constants: they carry no gradient."""
+
+    def __init__(self, axis, angles, nqubit=1, wires=None, minmax=None, controls=None, name='MultiplexedRotation',
+                 den_mat=False, tsr_mode=False):
+        super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
+                         tsr_mode=tsr_mode)
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        k = _mux_wires(self, 'MultiplexedRotation')
+        if axis not in ('x', 'y', 'z'):
+            raise ValueError(f"MultiplexedRotation: axis must be 'x', 'y' or 'z', got {axis!r}")
+        self.axis = axis
+        angles = _as_param_tensor(angles)
+        if angles.requires_grad:
+            raise ValueError('MultiplexedRotation: the angles are constants -- gradients with respect to them are not '
+                             'supported; detach() them')
+        if angles.is_complex() or not angles.is_floating_point():
+            angles = angles.real.to(torch.float) if angles.is_complex() else angles.to(torch.float)
+        angles = angles.detach().reshape(-1)
+        if angles.shape[0] != 2**k:
+            raise ValueError(f'MultiplexedRotation: {k} select wires take {2**k} angles, got {angles.shape[0]}')
+        self.register_buffer('angles', angles.contiguous())
+        # (the angles may be float64 in a complex64 circuit: this marker follows `.to()` / `.double()` for `_state_like`)
+        self.register_buffer('_like', torch.zeros((), device=angles.device), persistent=False)
+
+    def _state_like(self) -> tuple[torch.dtype, torch.device]:
+        return (torch.complex128 if self._like.dtype == torch.float64 else torch.complex64), self.angles.device
+
+    def table(self, dtype: torch.dtype) -> torch.Tensor:
+        """The table of the gate as it stands for states of complex ``dtype``: 'y' (2^k, 2) real rows (c, s), 'x' complex
+        (2^k, 2, 2), 'z' complex (2^(k+1),) phases over ``wires`` (the only one that depends on the direction)."""
+        a = self.angles
+        key = (dtype, a.device, self.inv_mode and self.axis == 'z')
+        cache = self.__dict__.get('_mux_tables')
+        ver = tensor_version(a)
+        if cache is None or cache[0] is not a or ver is None or cache[1] != ver:
+            cache = self.__dict__['_mux_tables'] = (a, ver, {})
+        t = cache[2].get(key)
+        if t is None:
+            real = torch.float64 if dtype == torch.complex128 else torch.float32
+            if self.axis == 'z':
+                half = (-a if self.inv_mode else a) / 2
+                t = torch.stack([torch.exp(-1j * half), torch.exp(1j * half)], dim=-1).reshape(-1).to(dtype)
+            else:
+                c, s = torch.cos(a / 2), torch.sin(a / 2)
+                if self.axis == 'y':
+                    t = torch.stack([c, s], dim=-1).to(real)
+                else:
+                    t = torch.stack([c + 0j, -1j * s, -1j * s, c + 0j], dim=-1).reshape(-1, 2, 2).to(dtype)
+            cache[2][key] = t = t.contiguous()
+        return t
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        t = self.table(x.dtype)
+        if self.axis == 'z':
+            return ops.diag_mul(x, t, self._bits(self.wires), self._bits(self.controls))
+        (target,) = self._bits(self.wires[-1:])
+        return ops.mux_apply(x, t, 'ry' if self.axis == 'y' else 'u', target, self._bits(self.wires[:-1]),
+                             self._bits(self.controls), dagger=self.inv_mode)
+
+    def extra_repr(self) -> str:
+        s = f"axis='{self.axis}', select={self.wires[:-1]}, target={self.wires[-1]}"
+        return s if self.controls == [] else s + f', controls={self.controls}'
+
+
 class CostPhase(_FlatGate, ArbitraryGate):
     """``exp(-i t diag(cost))`` with one parameter ``t`` and a classical cost table of 2^k real entries over ``wires`` /
     ``minmax`` (``wires[0]`` the most significant bit of the entry index): a whole QAOA cost layer -- any cost, not only a

@@ -1154,3 +1154,57 @@ def permute_basis(state: torch.Tensor, perm: torch.Tensor, bits: Sequence[int], 
     if inv is None:
         inv = invert_table(perm)
     return _PermuteBasis.apply(_flat_arg(state), perm, inv, bits, controls)
+
+
+# ---- multiplexed one-qubit gates on any number of select wires (csrc/dq_mux.hip) -----------------------------------------
+# M = sum_s |s><s| (x) M[s] on the select bits and the target, inside the controls: linear in the state, and its adjoint is
+# the same map with every entry daggered -- which the kernel applies from the same table.  One operation closed under
+# differentiation: the backward and the jvp are the function itself.
+class _MuxApply(torch.autograd.Function):
+    """y = M x: cotangent gx = M^+ gy, the same function with ``dagger`` toggled; the tangent is M x_t."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, bits: tuple, controls: tuple,
+                dagger: bool) -> torch.Tensor:
+        return backend.apply_mux(_plain(state), _plain(table), kind, target, bits, controls, dagger)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _state, table, ctx.kind, ctx.target, ctx.bits, ctx.controls, ctx.dagger = inputs
+        ctx.save_for_backward(table)
+        ctx.save_for_forward(table)
+
+    @staticmethod
+    def jvp(ctx, state_t, *_):
+        _single_forward_level()
+        (table,) = ctx.saved_tensors
+        return _MuxApply.apply(_flat_arg(state_t), table, ctx.kind, ctx.target, ctx.bits, ctx.controls, ctx.dagger)
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        (table,) = ctx.saved_tensors
+        gx = _MuxApply.apply(_flat_arg(gy), table, ctx.kind, ctx.target, ctx.bits, ctx.controls, not ctx.dagger)
+        return gx, None, None, None, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, table, kind, target, bits, controls, dagger):
+        _unmapped_table(in_dims[1], 'mux_apply')
+        v = info.batch_size
+        sf = _fold(state, in_dims[0], v)
+        out = _MuxApply.apply(sf, table, kind, target, bits, controls, dagger)
+        return out.reshape(v, -1, out.shape[-1]), 0
+
+
+def mux_apply(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, bits: Sequence[int],
+              controls: Sequence[int] = (), dagger: bool = False) -> torch.Tensor:
+    """Differentiable (in the state) multiplexed one-qubit gate on a (B, 2**n) state: for every value of the select bits
+    ``bits`` (``bits[0]`` = the table index's most significant bit) its own 2x2 matrix on index bit ``target``; amplitudes
+    outside the controls pass through.  ``kind='u'``: ``table`` a constant complex (2^k, 2, 2); ``kind='ry'``: a constant
+    real (2^k, 2) of rows (c, s), M = [[c, -s], [s, c]].  ``dagger`` applies the conjugate transposes from the same table.
+    One read and one write of the state whatever k is."""
+    _no_legacy(state)
+    table = _const_table(table, 'mux_apply')
+    if kind not in ('u', 'ry'):
+        raise ValueError(f"mux_apply: kind must be 'u' or 'ry', got {kind!r}")
+    bits, controls = _bit_args(bits, controls)
+    return _MuxApply.apply(_flat_arg(state), table, kind, int(target), bits, controls, bool(dagger))

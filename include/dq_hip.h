@@ -660,6 +660,28 @@ int dq_apply_permutation_c128(const void* in, void* out, const uint32_t* src, in
 /* log2 of the amplitudes of a LOCAL chunk: 11 (complex64) / 10 (complex128). */
 int dq_permutation_local_bits(int is_c128);
 
+/* ------------------------------------------------------------------------------------------
+ * 11. Multiplexed (uniformly controlled) one-qubit gates on any number of select wires (csrc/dq_mux.hip; added within
+ *     ABI 30, presence is checked by symbol): for every value of k select bits its own 2x2 matrix on one target bit --
+ *     the non-diagonal sibling of section 8 -- in one read and one write of the state whatever k is.
+ *         sub(i) as in section 8, over the select bits `bits`
+ *         (out[b, i0], out[b, i1]) = M[sub(i0)] (in[b, i0], in[b, i1])      i0: target bit 0, i1 = i0 | 1 << target
+ *     where all control bits are 1; the other amplitudes pass through bitwise.  `table`: DEVICE, 2^k entries in the
+ *     state's precision, 16-byte aligned, shared by the batch:
+ *         kind = DQ_MUX_U:  an entry is u00 u01 u10 u11, complex (32 / 64 bytes)
+ *         kind = DQ_MUX_RY: an entry is (c, s), real, M = [[c, -s], [s, c]] (8 / 16 bytes)
+ *     dagger = 1 applies the conjugate transpose of every entry from the same table.  The kernel does no trigonometry,
+ *     and no address depends on the table's contents.  `bits`, `controls` and `target` are pairwise distinct positions;
+ *     2 <= n <= 40, 1 <= k <= n - 1, 1 <= batch <= 65535; state pointers 16-byte aligned.  in == out is allowed (one unit
+ *     of work owns both ends of a pair); any other overlap is refused.
+ * ------------------------------------------------------------------------------------------ */
+#define DQ_MUX_U 0
+#define DQ_MUX_RY 1
+int dq_apply_mux_c64(const void* in, void* out, const void* table, int kind, int dagger, int n, int target, const int* bits,
+                     int k, const int* controls, int nc, int64_t batch, dq_stream_t stream);
+int dq_apply_mux_c128(const void* in, void* out, const void* table, int kind, int dagger, int n, int target, const int* bits,
+                      int k, const int* controls, int nc, int64_t batch, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
