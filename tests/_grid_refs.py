@@ -350,3 +350,148 @@ def tile_grad_sums(x, idx, free, t, s, controls=()):
             z = torch.zeros(x.shape[0], 2, 2, dtype=C128, device=x.device)
             return z, z.real.clone()
     return grad_sums(x[:, idx], free.index(t), free.index(s), [free.index(c) for c in inside])
+
+
+# ---- the one-wire entanglement kernels path by path (dq_entangle.hip; rows in _entangle_cases.py) ----------------------------
+_M32 = 0xFFFFFFFF
+
+
+def _mix32(x: torch.Tensor) -> torch.Tensor:
+    """An integer hash of the low 32 bits of an int64 tensor; every intermediate stays below 2^63, so CPU and GPU agree."""
+    x = x & _M32
+    for _ in range(2):
+        x = x ^ (x >> 16)
+        x = (x * 0x45D9F3B) & _M32
+    return x ^ (x >> 16)
+
+
+def int_parts(seed: int, stream: int, samples: torch.Tensor, attempt: int, count: int) -> torch.Tensor:
+    """(len(samples), count) int64 in -2 .. 2: a counter-based generator, a function of (seed, stream, sample number,
+    attempt, position) alone -- not of the device, the dtype or the batch the sample sits in."""
+    h = _mix32(_mix32(_mix32(torch.full_like(samples, seed * 4 + stream)) ^ samples) ^ attempt)
+    pos = (torch.arange(count, device=samples.device) * 0x9E3779B1) & _M32
+    return _mix32(h[:, None] ^ pos[None, :]) % 5 - 2
+
+
+def int_state(n: int, samples: torch.Tensor, seed: int, stream: int = 0, attempt: int = 0) -> torch.Tensor:
+    """Amplitudes with integer real and imaginary parts in -2 .. 2 for the sample numbers ``samples``: complex128
+    (len(samples), 2^n), made in chunks of at most 2^22 amplitudes."""
+    out = torch.empty(len(samples), 1 << n, dtype=C128, device=samples.device)
+    real = torch.view_as_real(out)
+    step = max(1, (1 << 22) >> n)
+    for lo in range(0, len(samples), step):
+        part = int_parts(seed, stream, samples[lo : lo + step], attempt, 2 << n)
+        real[lo : lo + step] = part.reshape(-1, 1 << n, 2).to(torch.float64)
+    return out
+
+
+def rdm1_exact(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    """rdm1_cross without S, for integer amplitudes: wire by wire, elementwise products and sums in complex128, every
+    partial sum an integer below 2^53 whatever the order.  A few samples at a time (the host's caches)."""
+    b, n = ket.shape[0], _nbits(ket)
+    t = torch.empty(b, n, 2, 2, dtype=C128, device=ket.device)
+    step = max(1, (1 << 18) >> n) if ket.device.type == 'cpu' else b
+    for lo in range(0, b, step):
+        x, y = bra[lo : lo + step].to(C128), ket[lo : lo + step].to(C128)
+        for k in range(n):
+            xv, yv = x.reshape(x.shape[0], 1 << k, 2, -1), y.reshape(x.shape[0], 1 << k, 2, -1)
+            for a in (0, 1):
+                for c in (0, 1):
+                    t[lo : lo + step, k, a, c] = (xv[:, :, a].conj() * yv[:, :, c]).sum((1, 2))
+    return t
+
+
+def rdm1_inputs_ok(t: torch.Tensor, cross: bool) -> torch.Tensor:
+    """Per sample: the n matrices T_k differ pairwise, T00 != T11 and T01 != 0 in each, and for a cross reduction
+    T01 != conj(T10) -- so that no exchange of wires, of components or of bra and ket leaves T as it is."""
+    b, n = t.shape[:2]
+    ok = (t[:, :, 0, 0] != t[:, :, 1, 1]).all(1) & (t[:, :, 0, 1] != 0).all(1)
+    if cross:
+        ok &= (t[:, :, 0, 1] != t[:, :, 1, 0].conj()).all(1)
+    flat = t.reshape(b, n, 4)
+    differ = (flat[:, :, None] != flat[:, None, :]).any(-1) | torch.eye(n, dtype=torch.bool, device=t.device)
+    return ok & differ.all((1, 2))
+
+
+def exact_states(n: int, batch: int, seed: int, cross: bool, device) -> tuple[torch.Tensor, torch.Tensor]:
+    """(bra, ket) with integer parts for the exact criterion, complex128; ``bra is ket`` unless ``cross``.  The seed of a
+    sample is chosen: sample b takes the first attempt = 0, 1, .. whose amplitudes pass rdm1_inputs_ok (a same-state
+    sample of 2^13 amplitudes has T00 == T11 on some wire about once in 50 draws; at n = 2 half the draws fail)."""
+    todo = torch.arange(batch, device=device)
+    ket = torch.empty(batch, 1 << n, dtype=C128, device=device)
+    bra = torch.empty_like(ket) if cross else ket
+    for attempt in range(64):
+        k = int_state(n, todo, seed, 0, attempt)
+        x = int_state(n, todo, seed, 1, attempt) if cross else k
+        ok = rdm1_inputs_ok(rdm1_exact(x, k), cross)
+        ket[todo[ok]] = k[ok]
+        if cross:
+            bra[todo[ok]] = x[ok]
+        todo = todo[~ok]
+        if not len(todo):
+            return bra, ket
+    raise AssertionError(f'no seed found for {len(todo)} samples at n = {n}')
+
+
+def int_mats(n: int, batch: int, seed: int, device) -> torch.Tensor:
+    """One-wire operators with integer parts in -2 .. 2: complex128 (batch, n, 2, 2), mended so that in every matrix
+    M01 != 0, M10 != 0, M10 != M01 and M11 != M00 (a dropped or exchanged entry changes the operator)."""
+    parts = int_parts(seed, 2, torch.arange(batch, device=device), 0, n * 8).reshape(batch, n, 2, 2, 2)
+    m = torch.view_as_complex(parts.to(torch.float64).contiguous())
+    m[:, :, 0, 1] = torch.where(m[:, :, 0, 1] == 0, torch.ones_like(m[:, :, 0, 1]), m[:, :, 0, 1])
+    m[:, :, 1, 0] = torch.where((m[:, :, 1, 0] == 0) | (m[:, :, 1, 0] == m[:, :, 0, 1]), -m[:, :, 0, 1], m[:, :, 1, 0])
+    shift = torch.where(m[:, :, 0, 0].real < 2, 1.0, -1.0).to(C128)
+    m[:, :, 1, 1] = torch.where(m[:, :, 1, 1] == m[:, :, 0, 0], m[:, :, 0, 0] + shift, m[:, :, 1, 1])
+    return m
+
+
+def wire_sum(state: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
+    """sum_k (mats[b, k] on wire k) state[b] in complex128, wire by wire with elementwise products: exact for integer
+    parts in -2 .. 2 (|out| parts <= 16 n)."""
+    b, n = state.shape[0], _nbits(state)
+    y, m = state.to(C128), mats.to(device=state.device, dtype=C128)
+    out = torch.zeros_like(y)
+    for k in range(n):
+        yv, ov = y.reshape(b, 1 << k, 2, -1), out.view(b, 1 << k, 2, -1)
+        for a in (0, 1):
+            for c in (0, 1):
+                ov[:, :, a] += m[:, k, a, c].reshape(b, 1, 1) * yv[:, :, c]
+    return out
+
+
+def wire_offdiag(state_row: torch.Tensor, mats_row: torch.Tensor, p: int) -> torch.Tensor:
+    """What the off-diagonal entries of the operator on wire bit p (wire n - 1 - p) add to wire_sum for one sample: (2^n,)."""
+    n = state_row.shape[-1].bit_length() - 1
+    y, m = state_row.to(C128).reshape(-1, 2, 1 << p), mats_row[n - 1 - p].to(C128)
+    out = torch.empty_like(y)
+    out[:, 0], out[:, 1] = m[0, 1] * y[:, 1], m[1, 0] * y[:, 0]
+    return out.reshape(-1)
+
+
+def ent_tile_indices(p: dict, base: int, device) -> torch.Tensor:
+    """The amplitude indices of one tile of pass ``p`` (_launch_geometry.entangle_passes) in tile-local order, ``base``
+    from _launch_geometry.ent_tile_base: the low s local bits contiguous, the others at lo, lo + 1, .."""
+    l = torch.arange(1 << p['m'], device=device)                            # noqa: E741
+    return base | (l & ((1 << p['s']) - 1)) | ((l >> p['s']) << p['lo'])
+
+
+def rdm1_tile_share(bra_row: torch.Tensor, ket_row: torch.Tensor, plan: dict, which: int, base: int, tile: int):
+    """What tile number ``tile`` (index bits ``base``) of pass ``which`` of ``plan`` adds to rdm1_cross of ONE sample:
+    the pairs along the tile bits the pass settles and, in pass 0, the diagonals -- of a wire inside the tile by its
+    local bit, of a wire outside it the tile's whole sum, at the entry its bit of the tile number names.  (n, 2, 2)."""
+    p, n, m0 = plan['passes'][which], len(plan['diag']), plan['m0']
+    idx = ent_tile_indices(p, base, ket_row.device)
+    xs, ys = bra_row[idx].to(C128), ket_row[idx].to(C128)
+    d = torch.zeros(n, 2, 2, dtype=C128, device=ket_row.device)
+    for wp, j, _ in p['settles']:
+        xv, yv = xs.reshape(-1, 2, 1 << j), ys.reshape(-1, 2, 1 << j)
+        for a in (0, 1):
+            for c in (0, 1):
+                if a != c or p['first']:
+                    d[n - 1 - wp, a, c] = (xv[:, a].conj() * yv[:, c]).sum()
+    if p['first']:
+        total = (xs.conj() * ys).sum()
+        for wp in range(m0, n):
+            a = (tile >> (wp - m0)) & 1
+            d[n - 1 - wp, a, a] = total
+    return d

@@ -1,5 +1,5 @@
 """Mirrors of the launchers' grid arithmetic, for the large-grid tests (test_grid_paths_gpu.py) and the path-by-path tests
-(test_pass_paths_*.py, test_rdmk_paths_*.py, test_gate_paths_*.py, test_reduce_paths_*.py).
+(test_pass_paths_*.py, test_rdmk_paths_*.py, test_gate_paths_*.py, test_reduce_paths_*.py, test_entangle_paths_*.py).
 
 Each function copies what one launcher in ``deepquantum_amd/csrc`` (or ``backend.py``) computes from a shape: how many
 workgroups it launches and so how many times a workgroup goes round its loop, whether the streaming (non-temporal)
@@ -286,6 +286,63 @@ def rdm1_ws_bytes(n: int, batch: int, c128: bool, cross: bool) -> int:
     if ps[0]['ntiles'] > 1:
         total += batch * ps[0]['ntiles'] * 2
     return 8 * total
+
+
+def entangle_passes(n: int, c128: bool, cross: bool) -> dict:
+    """dq_entangle.hip:376-391 (ent_tile_bits, ent_plan) in full, for the path-by-path tests (_entangle_cases.py).  The
+    wire-sum kernel plans with ``cross`` False: its tile is always 12 bits.
+
+    ``M``: the LDS tile's bits (12; 11 for the complex128 cross reduction), ``m0`` = min(n, M), ``gmax`` the most bits a
+    pass gathers, ``pad``: 'sub_workgroup' (n < 8: threads past the tile hold zeros), 'sub_tile' (8 <= n < M: register
+    slots past the tile hold zeros) or None.  ``diag[p]``: where the diagonal of wire bit p comes from, 'tile' (p < m0)
+    or 'tile_sums' (the per-tile sums of pass 0).  ``passes``: per pass m, s, lo, jlo, gathered = m - s, ntiles, first,
+    and ``settles``: the (wire bit p, tile bit j, via) whose pairs it reduces / applies, via = 'lds' for j < 8 (the
+    partner read from the LDS tile) and 'reg' for j >= 8 (a register pair of the thread's slots t + 256 k)."""
+    m_tile = 11 if (c128 and cross) else 12                                   # dq_entangle.hip:376
+    m0 = min(n, m_tile)
+    gmax = m_tile - (3 if c128 else 4)                                        # :383
+
+    def one(m, s, lo, jlo, ntiles, first):                                    # (EntPass, :32-41; jmask = tile bits jlo .. m - 1)
+        settles = [(j if j < s else lo + (j - s), j, 'lds' if j < 8 else 'reg') for j in range(jlo, m)]      # :448-449
+        return dict(m=m, s=s, lo=lo, jlo=jlo, gathered=m - s, ntiles=ntiles, first=first, settles=settles)
+
+    passes = [one(m0, m0, m0, 0, 1 << (n - m0), True)]                        # :385
+    lo = m0
+    while lo < n:                                                             # :386-389
+        gb = min(n - lo, gmax)
+        passes.append(one(m_tile, m_tile - gb, lo, m_tile - gb, 1 << (n - m_tile), False))
+        lo += gmax
+    return dict(M=m_tile, m0=m0, gmax=gmax, pad='sub_workgroup' if n < 8 else ('sub_tile' if n < m_tile else None),
+                diag=['tile' if p < m0 else 'tile_sums' for p in range(n)], passes=passes)
+
+
+def entangle_launch(n: int, batch: int, c128: bool, cross: bool) -> dict:
+    """entangle_passes with ent_nwg (dq_entangle.hip:393-397) for ONE launch of ``batch`` <= 65535 samples.  Every pass
+    gains ``nwg`` (workgroups per sample), ``iterations`` (of the busiest workgroup's tile loop, :104 / :319), ``ragged``
+    (workgroups with different tile counts), ``tiles_per_wg`` and ``last_tile_wg0`` (the tile workgroup 0 takes in its
+    last iteration).  ``finish``: whether the two strided loops of rdm1_finish_kernel (256 threads) take a second
+    stride: ``rows`` (:268, over the workgroup rows of some pass: nwg > 256) and ``tile_sums`` (:275, ntiles0 > 256)."""
+    plan = entangle_passes(n, c128, cross)
+    for p in plan['passes']:
+        nwg = ent_nwg(p['ntiles'], batch)
+        per = [len(range(w, p['ntiles'], nwg)) for w in range(nwg)] if nwg <= 4096 else None
+        p.update(nwg=nwg, iterations=_cdiv(p['ntiles'], nwg), ragged=p['ntiles'] % nwg != 0, tiles_per_wg=per,
+                 last_tile_wg0=((p['ntiles'] - 1) // nwg) * nwg)
+    nt0 = plan['passes'][0]['ntiles']
+    plan['finish'] = dict(rows=any(p['nwg'] > 256 for p in plan['passes']), tile_sums=nt0 > 1 and nt0 > 256)
+    return plan
+
+
+def ent_tile_base(p: dict, o: int) -> int:
+    """dq_entangle.hip:43-47 (tile_base): the index bits of tile number ``o`` of pass ``p`` -- its low lo - s bits sit
+    between the contiguous part and the gathered range, the rest above the gathered range."""
+    mid = p['lo'] - p['s']
+    return ((o & ((1 << mid) - 1)) << p['s']) | ((o >> mid) << (p['lo'] + p['gathered']))
+
+
+def ent_tile_index(p: dict, base: int, l: int) -> int:                        # noqa: E741
+    """dq_entangle.hip:49-51 (tile_index): the amplitude index of tile-local index ``l``."""
+    return base | (l & ((1 << p['s']) - 1)) | ((l >> p['s']) << p['lo'])
 
 
 # ---- dq_rdm.hip: rdmk_cross (k = 3..10 on the matrix cores) ----------------------------------------------------------------
