@@ -82,12 +82,13 @@ def _stream(t: torch.Tensor) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def _ptr(t: torch.Tensor | None) -> C.c_void_p:
+def _ptr(t: torch.Tensor | None, row: int = 0) -> C.c_void_p:
+    """The address of ``t[row:]`` (no view is made for it)."""
     # a lazily conjugated / negated view (x.mH of a column-major matrix is "contiguous" AND unconjugated in memory) must
     # never reach a kernel as a raw pointer
     if t is not None and (t.is_conj() or t.is_neg()):
         raise ValueError('tensor with a pending conjugation / negation: resolve_conj() / resolve_neg() it first')
-    return C.c_void_p(0 if t is None else t.data_ptr())
+    return C.c_void_p(0 if t is None else t.data_ptr() + (row and row * t.stride(0) * t.element_size()))
 
 
 def _nqubit(state: torch.Tensor) -> int:
@@ -117,6 +118,48 @@ def _check_mats(state: torch.Tensor, mats: torch.Tensor, k: int) -> tuple[torch.
 MAX_BATCH = 32768     # slices of a batch wider than the 65535 a grid dimension can hold
 
 
+def _slices(batch: int, step: int | None = None):
+    """``(lo, hi)`` over a batch in slices of at most ``step`` samples: ``MAX_BATCH`` as it is when called, or the 65535 of
+    an entry point whose batch is a grid axis of its own."""
+    step = MAX_BATCH if step is None else step
+    for lo in range(0, batch, step):
+        yield lo, min(lo + step, batch)
+
+
+def _call(entry: str, t: torch.Tensor, *args) -> None:
+    """``<entry>_<c64 | c128>(*args, stream)`` for the dtype and the current stream of ``t``, checked."""
+    _lib.check(getattr(_lib.load(), f'{entry}_{_suffix(t)}')(*args, _stream(t)), entry)
+
+
+def _check_out(state: torch.Tensor, out: torch.Tensor | None, what: str, in_place: bool = True) -> torch.Tensor:
+    """``out`` checked (``None``: a new tensor): a contiguous tensor of the state's shape, dtype and device that shares no
+    byte with the state or, where ``in_place`` says that a unit of work owns what it reads and writes, is the state's own
+    buffer.  A shifted overlap is safe for nobody."""
+    if out is None:
+        return torch.empty_like(state)
+    if out.shape != state.shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous tensor of the state's shape, dtype and device")
+    apart = abs(out.data_ptr() - state.data_ptr())
+    if apart < state.nbytes and not (in_place and apart == 0):
+        raise ValueError(f'{what}: out overlaps the state '
+                         + ('without being the same buffer' if in_place else '(out of place only)'))
+    return out
+
+
+def _finish_table(table: torch.Tensor, like: torch.Tensor, dtype: torch.dtype, what: str) -> torch.Tensor:
+    """A constant table as the kernels read it: in ``dtype`` on the state's device, conjugation and negation resolved,
+    contiguous and 16-byte aligned (a misaligned view is copied, not refused)."""
+    if table.requires_grad:
+        raise ValueError(f'{what}: the table is a constant -- gradients with respect to its entries are not supported; '
+                         'detach() it')
+    if table.dtype != dtype or table.device != like.device:
+        table = table.to(device=like.device, dtype=dtype)
+    table = table.resolve_conj().resolve_neg().contiguous()
+    if table.is_cuda and table.data_ptr() % 16:
+        table = table.clone()
+    return table
+
+
 # ---------------------------------------------------------------------------------------------------
 def apply_gate(
     state: torch.Tensor,
@@ -142,15 +185,11 @@ def apply_gate(
     if not _use_hip(state):
         return _test_backend.apply_gate(state, mats, targets, controls, out)
     if state.shape[0] > MAX_BATCH:       # the batch is a grid dimension (<= 65535): very wide batches go in slices
-        for lo in range(0, state.shape[0], MAX_BATCH):
-            hi = min(lo + MAX_BATCH, state.shape[0])
+        for lo, hi in _slices(state.shape[0]):
             apply_gate(state[lo:hi], mats[lo:hi] if stride else mats, targets, controls, out[lo:hi])
         return out
-    lib = _lib.load()
-    fn = getattr(lib, f'dq_apply_gate_{_suffix(state)}')
-    rc = fn(_ptr(state), _ptr(out), _ptr(mats), stride, n, _lib.int_array(targets), k,
-            _lib.int_array(controls), len(controls), state.shape[0], _stream(state))
-    _lib.check(rc, 'dq_apply_gate')
+    _call('dq_apply_gate', state, _ptr(state), _ptr(out), _ptr(mats), stride, n, _lib.int_array(targets), k,
+          _lib.int_array(controls), len(controls), state.shape[0])
     return out
 
 
@@ -276,8 +315,7 @@ def apply_fused(
         return out
     if out.shape[0] > MAX_BATCH:
         rows = mats.reshape(-1, mat_batch_stride) if mat_batch_stride else None
-        for lo in range(0, out.shape[0], MAX_BATCH):
-            hi = min(lo + MAX_BATCH, out.shape[0])
+        for lo, hi in _slices(out.shape[0]):
             apply_fused(state if broadcast else state[lo:hi], rows[lo:hi].reshape(-1) if rows is not None else mats,
                         mat_batch_stride, desc, out[lo:hi], known_zero=known_zero)
         return out
@@ -439,14 +477,9 @@ def marginal(state: torch.Tensor, bits: Sequence[int]) -> torch.Tensor:
         return _test_backend.marginal(state, bits)
     nw = len(bits)
     b = state.shape[0]
-    lib = _lib.load()
-    fn = getattr(lib, f'dq_marginal_{_suffix(state)}')
-    max_b = 65535                                            # (the batch is a grid axis of its own)
     out = torch.zeros(b, 1 << nw, dtype=torch.float64, device=state.device)
-    for lo in range(0, b, max_b):
-        hi = min(b, lo + max_b)
-        rc = fn(_ptr(state[lo:hi]), n, _lib.int_array(bits), nw, hi - lo, _ptr(out[lo:hi]), _stream(state))
-        _lib.check(rc, 'dq_marginal')
+    for lo, hi in _slices(b, 65535):                         # (the batch is a grid axis of its own)
+        _call('dq_marginal', state, _ptr(state, lo), n, _lib.int_array(bits), nw, hi - lo, _ptr(out, lo))
     return out
 
 
@@ -543,17 +576,14 @@ def rdmk_cross(
     same = x.data_ptr() == gy.data_ptr()
     d = 1 << k
     lib = _lib.load()
-    fn = getattr(lib, f'dq_rdmk_cross_{_suffix(x)}')
     out = torch.empty(x.shape[0], d, d, 2, dtype=torch.float64, device=x.device)
-    for lo in range(0, x.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, x.shape[0])
+    for lo, hi in _slices(x.shape[0]):
         nbytes = lib.dq_rdmk_ws_bytes(n, k, len(controls), hi - lo, int(x.dtype == torch.complex128), int(same))
         if nbytes < 0:
             raise ValueError(f'rdmk_cross: bad shape (n={n}, k={k}, controls={len(controls)})')
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
-        rc = fn(_ptr(x[lo:hi]), _ptr(gy[lo:hi]), n, _lib.int_array(targets), k, _lib.int_array(controls), len(controls),
-                hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(x))
-        _lib.check(rc, 'dq_rdmk_cross')
+        _call('dq_rdmk_cross', x, _ptr(x, lo), _ptr(gy, lo), n, _lib.int_array(targets), k, _lib.int_array(controls),
+              len(controls), hi - lo, _ptr(out, lo), _ptr(ws), nbytes)
     return torch.view_as_complex(out)
 
 
@@ -624,11 +654,8 @@ def defer_rx(flat: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
     assert flat.dtype == torch.complex64 and flat.ndim == 2 and flat.stride(1) == 1 and index.dtype == torch.long
     assert index.device == flat.device and index.is_contiguous()
     pin_if_capturing(index)
-    lib = _lib.load()
-    for lo in range(0, flat.shape[0], MAX_BATCH):          # (the batch is a grid dimension)
-        rows = flat[lo : lo + MAX_BATCH]
-        _lib.check(lib.dq_defer_rx_c64(_ptr(rows), flat.stride(0), _ptr(index), index.numel(), rows.shape[0],
-                                       _stream(flat)), 'dq_defer_rx_c64')
+    for lo, hi in _slices(flat.shape[0]):                  # (the batch is a grid dimension)
+        _call('dq_defer_rx', flat, _ptr(flat, lo), flat.stride(0), _ptr(index), index.numel(), hi - lo)
     return flat
 
 
@@ -699,17 +726,13 @@ def _cross_reduce(entry: str, sizer: str, bra: torch.Tensor, ket: torch.Tensor, 
     """A cross reduction of the library, ``<entry>_<suffix>(bra, ket, *mid, batch, out, ws, ws_bytes, stream)``, over the
     batch in slices of at most MAX_BATCH samples: complex128 (B, *shape).  Each slice's float64 workspace is sized by
     ``<sizer>(n, batch, is_c128, bra is not ket)`` and comes from PyTorch's allocator (legal under capture)."""
-    lib = _lib.load()
-    fn = getattr(lib, f'{entry}_{_suffix(ket)}')
     n = _nqubit(ket)
     same = bra.data_ptr() == ket.data_ptr()
     out = torch.empty(ket.shape[0], *shape, 2, dtype=torch.float64, device=ket.device)
-    for lo in range(0, ket.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, ket.shape[0])
-        nbytes = getattr(lib, sizer)(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
+    for lo, hi in _slices(ket.shape[0]):
+        nbytes = getattr(_lib.load(), sizer)(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
-        rc = fn(_ptr(bra[lo:hi]), _ptr(ket[lo:hi]), *mid, hi - lo, _ptr(out[lo:hi]), _ptr(ws), nbytes, _stream(ket))
-        _lib.check(rc, entry)
+        _call(entry, ket, _ptr(bra, lo), _ptr(ket, lo), *mid, hi - lo, _ptr(out, lo), _ptr(ws), nbytes)
     return torch.view_as_complex(out)
 
 
@@ -725,12 +748,8 @@ def apply_wire_sum(state: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
         return _test_backend.apply_wire_sum(state, mats)
     m = torch.view_as_real(mats.to(device=state.device, dtype=torch.complex128).resolve_conj().resolve_neg().contiguous())
     out = torch.empty_like(state)
-    lib = _lib.load()
-    fn = getattr(lib, f'dq_apply_wire_sum_{_suffix(state)}')
-    for lo in range(0, state.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, state.shape[0])
-        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(m[lo:hi]), n, hi - lo, _stream(state))
-        _lib.check(rc, 'dq_apply_wire_sum')
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_wire_sum', state, _ptr(state, lo), _ptr(out, lo), _ptr(m, lo), n, hi - lo)
     return out
 
 
@@ -785,19 +804,13 @@ def sample_indices(state: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
             return _sample_indices_double(state, u)
     u = u.contiguous()
     out = torch.empty(u.shape, dtype=torch.int64, device=state.device)
-    lib = _lib.load()
-    fn = getattr(lib, f'dq_sample_{_suffix(state)}')
-    max_b = 65535                                            # (dq_sample_*'s limit on the batch)
-    for lo in range(0, state.shape[0], max_b):
-        hi = min(state.shape[0], lo + max_b)
-        nbytes = lib.dq_sample_ws_bytes(n, hi - lo, int(state.dtype == torch.complex128))
+    for lo, hi in _slices(state.shape[0], 65535):            # (dq_sample_*'s limit on the batch)
+        nbytes = _lib.load().dq_sample_ws_bytes(n, hi - lo, int(state.dtype == torch.complex128))
         if nbytes < 0:
             raise ValueError(f'sample_indices: bad shape (n={n}, batch={hi - lo})')
         ws = _sample_workspace(state, hi - lo, n, nbytes)
         pin_if_capturing(ws)
-        rc = fn(_ptr(state[lo:hi]), n, hi - lo, _ptr(u[lo:hi]), u.shape[1], _ptr(out[lo:hi]), _ptr(ws), nbytes,
-                _stream(state))
-        _lib.check(rc, 'dq_sample')
+        _call('dq_sample', state, _ptr(state, lo), n, hi - lo, _ptr(u, lo), u.shape[1], _ptr(out, lo), _ptr(ws), nbytes)
     return out
 
 
@@ -873,13 +886,7 @@ def _diag_table(table: torch.Tensor, like: torch.Tensor, dtype: torch.dtype, k: 
     if not ok:
         raise ValueError(f'{what}: a table over {k} bits has {d} entries' + (f', or ({like.shape[0]}, {d})' if batched else '')
                          + f'; got {tuple(table.shape)}')
-    if table.requires_grad:
-        raise ValueError(f'{what}: the table is a constant -- gradients with respect to its entries are not supported; '
-                         'detach() it')
-    table = table.to(device=like.device, dtype=dtype).resolve_conj().resolve_neg().contiguous()
-    if table.is_cuda and table.data_ptr() % 16:
-        table = table.clone()
-    return table
+    return _finish_table(table, like, dtype, what)
 
 
 def _sub_index(n: int, bits: Sequence[int], controls: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor]:
@@ -901,17 +908,13 @@ def apply_diag(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], con
     n, bits, controls = _diag_args(state, bits, controls, 'apply_diag')
     k = len(bits)
     diag = _diag_table(diag, state, state.dtype, k, 'apply_diag', True)
-    if out is None:
-        out = torch.empty_like(state)
+    out = _check_out(state, out, 'apply_diag')
     if not _use_hip(state):
         return _diag_double(lambda: _apply_diag_double(state, diag, n, bits, controls, out))
     stride = (1 << k) if (diag.ndim == 2 and diag.shape[0] > 1) else 0
-    fn = getattr(_lib.load(), f'dq_apply_diag_{_suffix(state)}')
-    for lo in range(0, state.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, state.shape[0])
-        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(diag[lo:hi] if stride else diag), stride, n, _lib.int_array(bits), k,
-                _lib.int_array(controls), len(controls), hi - lo, _stream(state))
-        _lib.check(rc, 'dq_apply_diag')
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_diag', state, _ptr(state, lo), _ptr(out, lo), _ptr(diag, lo if stride else 0), stride, n,
+              _lib.int_array(bits), k, _lib.int_array(controls), len(controls), hi - lo)
     return out
 
 
@@ -959,8 +962,7 @@ def apply_cost(state: torch.Tensor, cost: torch.Tensor, par: torch.Tensor, bits:
         raise ValueError(f'apply_cost: one parameter per sample, ({state.shape[0]},), expected; got {tuple(par.shape)}')
     if op == 'phase' and par.is_complex():
         raise ValueError('apply_cost: the phase parameter is real')
-    if out is None:
-        out = torch.empty_like(state)
+    out = _check_out(state, out, 'apply_cost')
     if not _use_hip(state):
         def double():
             sub, ok = _sub_index(n, bits, controls)
@@ -978,28 +980,22 @@ def apply_cost(state: torch.Tensor, cost: torch.Tensor, par: torch.Tensor, bits:
         p = par.to(device=state.device, dtype=torch.float64).contiguous()
     else:
         p = torch.view_as_real(par.to(device=state.device, dtype=torch.complex128).resolve_conj().resolve_neg().contiguous())
-    fn = getattr(_lib.load(), f'dq_apply_cost_{_suffix(state)}')
     code = _lib.COST_PHASE if op == 'phase' else _lib.COST_SCALE
     # complex128 phases of a small table: exp(-i t cost) once per table entry and sample -- the same kernel on a vector of
     # ones over the k table bits -- then the diagonal kernel, so that no double-precision sine and cosine is taken per
     # amplitude (measured: DESIGN.md section 4.8).  complex64 forms the phase in flight at every k: it is the faster there.
     via_table = (op == 'phase' and state.dtype == torch.complex128 and k <= PHASE_TABLE_MAX_BITS
                  and n >= max(k + PHASE_TABLE_MIN_REST, PHASE_TABLE_MIN_QUBITS))
-    for lo in range(0, state.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, state.shape[0])
+    for lo, hi in _slices(state.shape[0]):
         if via_table:
             table = torch.ones(hi - lo, 1 << k, dtype=state.dtype, device=state.device)
-            rc = fn(_ptr(table), _ptr(table), _ptr(cost), _ptr(p[lo:hi]), code, k, _lib.int_array(range(k - 1, -1, -1)), k,
-                    _lib.int_array([]), 0, hi - lo, _stream(state))
-            _lib.check(rc, 'dq_apply_cost')
-            rc = getattr(_lib.load(), f'dq_apply_diag_{_suffix(state)}')(
-                _ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(table), 1 << k, n, _lib.int_array(bits), k,
-                _lib.int_array(controls), len(controls), hi - lo, _stream(state))
-            _lib.check(rc, 'dq_apply_diag')
+            _call('dq_apply_cost', state, _ptr(table), _ptr(table), _ptr(cost), _ptr(p, lo), code, k,
+                  _lib.int_array(range(k - 1, -1, -1)), k, _lib.int_array([]), 0, hi - lo)
+            _call('dq_apply_diag', state, _ptr(state, lo), _ptr(out, lo), _ptr(table), 1 << k, n, _lib.int_array(bits), k,
+                  _lib.int_array(controls), len(controls), hi - lo)
             continue
-        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(cost), _ptr(p[lo:hi]), code, n, _lib.int_array(bits), k,
-                _lib.int_array(controls), len(controls), hi - lo, _stream(state))
-        _lib.check(rc, 'dq_apply_cost')
+        _call('dq_apply_cost', state, _ptr(state, lo), _ptr(out, lo), _ptr(cost), _ptr(p, lo), code, n,
+              _lib.int_array(bits), k, _lib.int_array(controls), len(controls), hi - lo)
     return out
 
 
@@ -1052,19 +1048,6 @@ def _pauli_coef(p, like: torch.Tensor, what: str) -> torch.Tensor:
     return p.resolve_conj().resolve_neg()
 
 
-def _pauli_out(state: torch.Tensor, out: torch.Tensor | None, what: str) -> torch.Tensor:
-    """``out`` checked: a contiguous tensor of the state's shape, dtype and device that is the state's own buffer or shares
-    no byte with it (a unit of work owns both ends of a pair, which makes the one safe, not a shifted overlap)."""
-    if out is None:
-        return torch.empty_like(state)
-    if out.shape != state.shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous tensor of the state's shape, dtype and device")
-    nbytes = state.numel() * state.element_size()
-    if out.data_ptr() != state.data_ptr() and abs(out.data_ptr() - state.data_ptr()) < nbytes:
-        raise ValueError(f'{what}: out overlaps the state without being the same buffer')
-    return out
-
-
 def _pauli_gather(n: int, xmask: int, zmask: int, controls: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Source index i ^ x, factor i^ny (-1)^popc((i ^ x) & z) and the control test for every i (CPU test double only)."""
     i = torch.arange(1 << n)
@@ -1091,7 +1074,7 @@ def apply_pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, control
         raise ValueError(f"apply_pauli_axpby: mode must be 'gate' or 'map', got {mode!r}")
     n, xmask, zmask, controls = _pauli_args(state, xmask, zmask, controls, 'apply_pauli_axpby')
     a, c = _pauli_coef(a, state, 'apply_pauli_axpby'), _pauli_coef(c, state, 'apply_pauli_axpby')
-    out = _pauli_out(state, out, 'apply_pauli_axpby')
+    out = _check_out(state, out, 'apply_pauli_axpby')
     if not _use_hip(state):
         def double():
             j, factor, ok = _pauli_gather(n, xmask, zmask, controls)
@@ -1106,12 +1089,9 @@ def apply_pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, control
 
 
 def _pauli_launch(state, out, xmask, zmask, coef, code, n, controls):
-    fn = getattr(_lib.load(), f'dq_apply_pauli_axpby_{_suffix(state)}')
-    for lo in range(0, state.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, state.shape[0])
-        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), xmask, zmask, _ptr(coef[lo:hi]), code, n, _lib.int_array(controls),
-                len(controls), hi - lo, _stream(state))
-        _lib.check(rc, 'dq_apply_pauli_axpby')
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_pauli_axpby', state, _ptr(state, lo), _ptr(out, lo), xmask, zmask, _ptr(coef, lo), code, n,
+              _lib.int_array(controls), len(controls), hi - lo)
     return out
 
 
@@ -1126,7 +1106,7 @@ def apply_pauli_rot(state: torch.Tensor, xmask: int, zmask: int, theta: torch.Te
     half = theta.to(device=state.device, dtype=torch.float64) * 0.5
     if not _use_hip(state):
         return apply_pauli_axpby(state, xmask, zmask, torch.cos(half), -1j * torch.sin(half), controls, 'gate', out)
-    out = _pauli_out(state, out, 'apply_pauli_rot')
+    out = _check_out(state, out, 'apply_pauli_rot')
     zero = torch.zeros_like(half)
     coef = torch.stack([torch.cos(half), zero, zero, -torch.sin(half)], dim=1)
     return _pauli_launch(state, out, xmask, zmask, coef, _lib.PAULI_GATE, n, controls)
@@ -1172,10 +1152,7 @@ def _perm_table(src: torch.Tensor, like: torch.Tensor, k: int, what: str) -> tor
         raise ValueError(f'{what}: the table must be an integer tensor')
     if src.shape != (1 << k,):
         raise ValueError(f'{what}: a table over {k} bits has {1 << k} entries; got {tuple(src.shape)}')
-    src = src.to(device=like.device, dtype=torch.int32).contiguous()
-    if src.is_cuda and src.data_ptr() % 16:
-        src = src.clone()
-    return src
+    return _finish_table(src, like, torch.int32, what)
 
 
 def apply_permutation(state: torch.Tensor, src: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = (),
@@ -1193,24 +1170,15 @@ def apply_permutation(state: torch.Tensor, src: torch.Tensor, bits: Sequence[int
         raise ValueError(f"apply_permutation: path must be 'auto', 'gather' or 'local', got {path!r}")
     _suffix(state)
     src = _perm_table(src, state, k, 'apply_permutation')
-    if out is None:
-        out = torch.empty_like(state)
-    else:
-        if out.shape != state.shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
-            raise ValueError("apply_permutation: out must be a contiguous tensor of the state's shape, dtype and device")
-        if abs(out.data_ptr() - state.data_ptr()) < state.numel() * state.element_size():
-            raise ValueError('apply_permutation: out overlaps the state (the permutation is out of place only)')
+    out = _check_out(state, out, 'apply_permutation', in_place=False)
     if path == 'local' and max(bits) >= permutation_local_bits(state.dtype):
         raise ValueError(f"apply_permutation: path='local' needs every table bit below "
                          f'{permutation_local_bits(state.dtype)}, got {bits}')
     if not _use_hip(state):
         return _diag_double(lambda: _apply_permutation_double(state, src, n, bits, controls, out))
-    fn = getattr(_lib.load(), f'dq_apply_permutation_{_suffix(state)}')
-    for lo in range(0, state.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, state.shape[0])
-        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(src), n, _lib.int_array(bits), k, _lib.int_array(controls),
-                len(controls), hi - lo, PERM_PATHS[path], _stream(state))
-        _lib.check(rc, 'dq_apply_permutation')
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_permutation', state, _ptr(state, lo), _ptr(out, lo), _ptr(src), n, _lib.int_array(bits), k,
+              _lib.int_array(controls), len(controls), hi - lo, PERM_PATHS[path])
     return out
 
 
@@ -1248,13 +1216,7 @@ def _mux_table(table: torch.Tensor, like: torch.Tensor, kind: str, k: int, what:
             raise ValueError(f"{what}: an 'ry' table over {k} select bits is real ({d}, 2), rows (c, s); got {table.dtype} "
                              f'{tuple(table.shape)}')
         dtype = torch.float64 if like.dtype == torch.complex128 else torch.float32
-    if table.requires_grad:
-        raise ValueError(f'{what}: the table is a constant -- gradients with respect to its entries are not supported; '
-                         'detach() it')
-    table = table.to(device=like.device, dtype=dtype).resolve_conj().resolve_neg().contiguous()
-    if table.is_cuda and table.data_ptr() % 16:
-        table = table.clone()
-    return table
+    return _finish_table(table, like, dtype, what)
 
 
 def apply_mux(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, bits: Sequence[int], controls: Sequence[int] = (),
@@ -1275,21 +1237,12 @@ def apply_mux(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, 
     k = len(bits)
     _suffix(state)
     table = _mux_table(table, state, kind, k, what)
-    if out is None:
-        out = torch.empty_like(state)
-    elif out is not state:
-        if out.shape != state.shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
-            raise ValueError(f"{what}: out must be a contiguous tensor of the state's shape, dtype and device")
-        if out.data_ptr() != state.data_ptr() and abs(out.data_ptr() - state.data_ptr()) < state.numel() * state.element_size():
-            raise ValueError(f'{what}: out overlaps the state without being the state')
+    out = _check_out(state, out, what)
     if not _use_hip(state):
         return _diag_double(lambda: _apply_mux_double(state, table, kind, n, target, bits, controls, bool(dagger), out))
-    fn = getattr(_lib.load(), f'dq_apply_mux_{_suffix(state)}')
-    for lo in range(0, state.shape[0], MAX_BATCH):
-        hi = min(lo + MAX_BATCH, state.shape[0])
-        rc = fn(_ptr(state[lo:hi]), _ptr(out[lo:hi]), _ptr(table), MUX_KINDS[kind], int(bool(dagger)), n, target,
-                _lib.int_array(bits), k, _lib.int_array(controls), len(controls), hi - lo, _stream(state))
-        _lib.check(rc, 'dq_apply_mux')
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_mux', state, _ptr(state, lo), _ptr(out, lo), _ptr(table), MUX_KINDS[kind], int(bool(dagger)), n,
+              target, _lib.int_array(bits), k, _lib.int_array(controls), len(controls), hi - lo)
     return out
 
 

@@ -204,17 +204,14 @@ template <typename T, int MODE>
 int apply_impl(const char* what, const void* in, void* out, const void* table, int64_t table_bstride, const double* par, int n,
                const int* bits, int k, const int* controls, int nc, int64_t batch, dq_stream_t stream) {
     constexpr bool C128 = sizeof(T) == 8;
-    if (!in || !out || !table || (MODE != MODE_DIAG && !par)) {
-        set_error("%s: null pointer", what);
+    if (int rc = check_states(what, in, out, 1, n, batch, sizeof(cx<T>), SAME_OR_DISJOINT)) return rc;
+    if (!table || misaligned(table) || (MODE != MODE_DIAG && (!par || (reinterpret_cast<uintptr_t>(par) & 7)))) {
+        set_error("%s: the table must be non-null and 16-byte aligned, the parameters non-null and 8-byte aligned", what);
         return DQ_ERR_ARG;
     }
     Gather g;
     bool ident;
     if (int rc = plan_gather(what, n, bits, k, controls, nc, batch, C128, &g, &ident)) return rc;
-    if (misaligned(in) || misaligned(out) || misaligned(table) || (reinterpret_cast<uintptr_t>(par) & 7)) {
-        set_error("%s: in, out and the table must be 16-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
     if (table_bstride != 0 && table_bstride != (int64_t)1 << k) {
         set_error("%s: table batch stride %lld, 0 (shared) or 2^k expected", what, (long long)table_bstride);
         return DQ_ERR_ARG;
@@ -249,18 +246,10 @@ int cross_impl(const void* bra, const void* ket, const void* cost, int n, const 
                int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
     constexpr bool C128 = sizeof(T) == 8;
     const char* what = "dq_cost_cross";
-    if (!bra || !ket || !cost || !out || !ws) {
-        set_error("%s: null pointer", what);
-        return DQ_ERR_ARG;
-    }
     Gather g;
     bool ident;
     if (int rc = plan_gather(what, n, bits, k, controls, nc, batch, C128, &g, &ident)) return rc;
-    if (misaligned(bra) || misaligned(ket) || misaligned(cost) || misaligned(ws) || (reinterpret_cast<uintptr_t>(out) & 7)) {
-        set_error("%s: bra, ket, cost and ws must be 16-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    if (int rc = check_cross_ws(what, ws_bytes, n, batch, C128)) return rc;
+    if (int rc = check_cross(what, bra, ket, cost, true, out, ws, ws_bytes, n, batch, C128)) return rc;
     const uint64_t nvec = vectors_of(n, C128);
     const unsigned nblk = blocks_of(nvec);
     const dim3 grid(nblk, (unsigned)batch);
@@ -305,8 +294,7 @@ extern "C" int dq_apply_cost_c128(const void* in, void* out, const void* cost, c
 
 extern "C" int64_t dq_cost_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross) {
     (void)cross;        // bra != ket reads twice as much and writes the same partial sums
-    if (n < 1 || n > 40 || batch < 1 || batch > 65535) return -1;
-    return dq::cross_ws_bytes(n, batch, is_c128 != 0);
+    return dq::cross_ws_bytes_or_refuse(n, batch, is_c128 != 0);
 }
 
 extern "C" int dq_cost_cross_c64(const void* bra, const void* ket, const void* cost, int n, const int* bits, int k,

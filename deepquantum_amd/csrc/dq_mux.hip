@@ -159,12 +159,9 @@ template <typename T>
 int plan_mux(const char* what, const void* in, const void* out, const void* table, int kind, int dagger, int n, int target,
              const int* bits, int k, const int* controls, int nc, int64_t batch, Mux* p, bool* inner) {
     constexpr bool C128 = sizeof(T) == 8;
-    if (!in || !out || !table) {
-        set_error("%s: null pointer", what);
-        return DQ_ERR_ARG;
-    }
-    if (n < 2 || n > 40) {
-        set_error("%s: n=%d out of range [2, 40]", what, n);
+    if (int rc = check_states(what, in, out, 2, n, batch, sizeof(cx<T>), SAME_OR_DISJOINT)) return rc;
+    if (!table || misaligned(table)) {
+        set_error("%s: the table must be non-null and 16-byte aligned", what);
         return DQ_ERR_ARG;
     }
     if (k < 1 || k > n - 1) {
@@ -192,17 +189,6 @@ int plan_mux(const char* what, const void* in, const void* out, const void* tabl
             return DQ_ERR_ARG;
         }
         (j < k ? pbits[j] : pctl[j - k]) = q > target ? q - 1 : q;
-    }
-    if (int rc = check_batch(what, batch)) return rc;
-    if (misaligned(in) || misaligned(out) || misaligned(table)) {
-        set_error("%s: in, out and the table must be 16-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    const uint64_t bytes = ((uint64_t)batch << n) * sizeof(cx<T>);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in), o = reinterpret_cast<uintptr_t>(out);
-    if (a != o && (a > o ? a - o : o - a) < bytes) {
-        set_error("%s: in and out overlap without being equal", what);
-        return DQ_ERR_ARG;
     }
     *inner = !C128 && target == 0;
     // a unit is 2^ST_UNIT_BITS items of one pair (complex128, INNER: the split plan_gather makes for complex128) or two

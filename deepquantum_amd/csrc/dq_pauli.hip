@@ -201,8 +201,9 @@ int axpby_impl(const void* in, void* out, uint64_t xmask, uint64_t zmask, const 
                int nc, int64_t batch, dq_stream_t stream) {
     constexpr bool C128 = sizeof(T) == 8;
     const char* what = "dq_apply_pauli_axpby";
-    if (!in || !out || !coef) {
-        set_error("%s: null pointer", what);
+    if (int rc = check_states(what, in, out, 1, n, batch, sizeof(cx<T>), SAME_OR_DISJOINT)) return rc;
+    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
+        set_error("%s: coef must be non-null and 8-byte aligned", what);
         return DQ_ERR_ARG;
     }
     if (mode != DQ_PAULI_GATE && mode != DQ_PAULI_MAP) {
@@ -211,10 +212,6 @@ int axpby_impl(const void* in, void* out, uint64_t xmask, uint64_t zmask, const 
     }
     Pauli p;
     if (int rc = plan_pauli(what, xmask, zmask, n, controls, nc, batch, C128, &p)) return rc;
-    if (misaligned(in) || misaligned(out) || (reinterpret_cast<uintptr_t>(coef) & 7)) {
-        set_error("%s: in and out must be 16-byte aligned, coef 8-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
     const uint64_t nvec = vectors_of(n, C128);
     const uint64_t items = p.vx ? nvec >> 1 : nvec;
     const dim3 grid(blocks_of(items), (unsigned)batch);
@@ -236,17 +233,9 @@ int cross_impl(const void* bra, const void* ket, uint64_t xmask, uint64_t zmask,
                double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
     constexpr bool C128 = sizeof(T) == 8;
     const char* what = "dq_pauli_cross";
-    if (!bra || !ket || !out || !ws) {
-        set_error("%s: null pointer", what);
-        return DQ_ERR_ARG;
-    }
     Pauli p;
     if (int rc = plan_pauli(what, xmask, zmask, n, controls, nc, batch, C128, &p)) return rc;
-    if (misaligned(bra) || misaligned(ket) || misaligned(ws) || (reinterpret_cast<uintptr_t>(out) & 7)) {
-        set_error("%s: bra, ket and ws must be 16-byte aligned, out 8-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    if (int rc = check_cross_ws(what, ws_bytes, n, batch, C128)) return rc;
+    if (int rc = check_cross(what, bra, ket, nullptr, false, out, ws, ws_bytes, n, batch, C128)) return rc;
     const uint64_t nvec = vectors_of(n, C128);
     const uint64_t items = p.vx ? nvec >> 1 : nvec;
     const unsigned nblk = blocks_of(items);             // (at most what the workspace was sized for)
@@ -280,8 +269,7 @@ extern "C" int dq_apply_pauli_axpby_c128(const void* in, void* out, uint64_t xma
 
 extern "C" int64_t dq_pauli_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross) {
     (void)cross;        // bra != ket reads twice as much and writes the same partial sums
-    if (n < 1 || n > 40 || batch < 1 || batch > 65535) return -1;
-    return dq::cross_ws_bytes(n, batch, is_c128 != 0);
+    return dq::cross_ws_bytes_or_refuse(n, batch, is_c128 != 0);
 }
 
 extern "C" int dq_pauli_cross_c64(const void* bra, const void* ket, uint64_t xmask, uint64_t zmask, int n, const int* controls,

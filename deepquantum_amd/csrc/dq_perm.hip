@@ -202,30 +202,17 @@ template <typename T>
 int plan_perm(const char* what, const void* in, const void* out, const uint32_t* table, int n, const int* bits, int k,
               const int* controls, int nc, int64_t batch, int path, Perm* p, bool* local) {
     constexpr bool C128 = sizeof(T) == 8;
-    if (!in || !out || !table) {
-        set_error("%s: null pointer", what);
-        return DQ_ERR_ARG;
-    }
-    if (n < 1 || n > 40) {
-        set_error("%s: n=%d out of range [1, 40]", what, n);
-        return DQ_ERR_ARG;
-    }
-    if (k < 1 || k > n || k > 31) {
+    if (k < 1 || k > n || k > 31) {                     // (first: its text names n, and at n = 40 most pairs of pointers overlap)
         set_error("%s: k=%d outside [1, min(n, 31)] (n=%d)", what, k, n);
+        return DQ_ERR_ARG;
+    }
+    if (int rc = check_states(what, in, out, 1, n, batch, sizeof(cx<T>), DISJOINT)) return rc;
+    if (!table || (reinterpret_cast<uintptr_t>(table) & 3)) {
+        set_error("%s: the table must be non-null and 4-byte aligned", what);
         return DQ_ERR_ARG;
     }
     bool ident;
     if (int rc = plan_gather(what, n, bits, k, controls, nc, batch, C128, &p->g, &ident)) return rc;
-    if (misaligned(in) || misaligned(out) || (reinterpret_cast<uintptr_t>(table) & 3)) {
-        set_error("%s: in and out must be 16-byte aligned, the table 4-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    const uint64_t bytes = ((uint64_t)batch << n) * sizeof(cx<T>);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in), o = reinterpret_cast<uintptr_t>(out);
-    if ((a > o ? a - o : o - a) < bytes) {
-        set_error("%s: in and out overlap (the permutation is out of place only)", what);
-        return DQ_ERR_ARG;
-    }
     if (path != DQ_PERM_AUTO && path != DQ_PERM_GATHER && path != DQ_PERM_LOCAL) {
         set_error("%s: path=%d is none of DQ_PERM_AUTO, DQ_PERM_GATHER, DQ_PERM_LOCAL", what, path);
         return DQ_ERR_ARG;

@@ -151,6 +151,37 @@ int check_batch(const char* what, int64_t batch) {
     return DQ_ERR_ARG;
 }
 
+// What a state-to-state primitive allows of its two buffers: a kernel whose lanes own what they read and write takes
+// in == out, one that reads where another lane writes (the permutation) does not; a shifted overlap is safe for nobody.
+enum Alias { SAME_OR_DISJOINT, DISJOINT };
+
+// in and out of a state-to-state primitive: non-null, 16-byte aligned, n in [nmin, 40], the batch, and the ranges
+// [in, in + batch * 2^n) and [out, ..) under `alias`
+int check_states(const char* what, const void* in, const void* out, int nmin, int n, int64_t batch, size_t amp_bytes,
+                 Alias alias) {
+    if (!in || !out) {
+        set_error("%s: null pointer", what);
+        return DQ_ERR_ARG;
+    }
+    if (misaligned(in) || misaligned(out)) {
+        set_error("%s: in and out must be 16-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    if (n < nmin || n > 40) {
+        set_error("%s: n=%d out of range [%d, 40]", what, n, nmin);
+        return DQ_ERR_ARG;
+    }
+    if (int rc = check_batch(what, batch)) return rc;
+    const uint64_t bytes = ((uint64_t)batch << n) * amp_bytes;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), o = reinterpret_cast<uintptr_t>(out);
+    if ((alias == DISJOINT || a != o) && (a > o ? a - o : o - a) < bytes) {
+        set_error(alias == DISJOINT ? "%s: in and out overlap (out of place only)" : "%s: in and out overlap without being equal",
+                  what);
+        return DQ_ERR_ARG;
+    }
+    return DQ_OK;
+}
+
 uint64_t control_mask(const int* controls, int nc) {
     uint64_t m = 0;
     for (int c = 0; c < nc; ++c) m |= 1ull << controls[c];
@@ -216,12 +247,34 @@ int64_t cross_ws_bytes(int n, int64_t batch, bool is_c128) {
     return batch * (int64_t)blocks_of(vectors_of(n, is_c128)) * 2 * (int64_t)sizeof(double);
 }
 
+// what the <what>_ws_bytes exports return: -1 outside the ranges of n and batch
+int64_t cross_ws_bytes_or_refuse(int n, int64_t batch, bool is_c128) {
+    if (n < 1 || n > 40 || batch < 1 || batch > 65535) return -1;
+    return cross_ws_bytes(n, batch, is_c128);
+}
+
 // `what` names the entry point; its sizing function is <what>_ws_bytes
 int check_cross_ws(const char* what, int64_t ws_bytes, int n, int64_t batch, bool is_c128) {
     const int64_t need = cross_ws_bytes(n, batch, is_c128);
     if (ws_bytes >= need) return DQ_OK;
     set_error("%s: workspace of %lld bytes, %lld needed (%s_ws_bytes)", what, (long long)ws_bytes, (long long)need, what);
     return DQ_ERR_ARG;
+}
+
+// The buffers of a cross reduction, once n and the batch are validated: bra, ket, the table (where the primitive has
+// one: `has_table`) and ws non-null and 16-byte aligned, out non-null and 8-byte aligned, ws large enough.
+int check_cross(const char* what, const void* bra, const void* ket, const void* table, bool has_table, const double* out,
+                const void* ws, int64_t ws_bytes, int n, int64_t batch, bool is_c128) {
+    if (!bra || !ket || (has_table && !table) || !out || !ws) {
+        set_error("%s: null pointer", what);
+        return DQ_ERR_ARG;
+    }
+    if (misaligned(bra) || misaligned(ket) || (has_table && misaligned(table)) || misaligned(ws) ||
+        (reinterpret_cast<uintptr_t>(out) & 7)) {
+        set_error("%s: bra, ket, the table and ws must be 16-byte aligned, out 8-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    return check_cross_ws(what, ws_bytes, n, batch, is_c128);
 }
 
 // out[b] = the sum of the nparts partial sums that the first kernel left in ws[b, :]

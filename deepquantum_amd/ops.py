@@ -500,6 +500,32 @@ def _fold(x: torch.Tensor, d: int | None, v: int) -> torch.Tensor:
     return x.reshape(v * x.shape[1], *x.shape[2:]).contiguous()
 
 
+def _vmap_states(cls, what: str, info, in_dims, args: tuple, folded: tuple = (), tables: tuple = ()):
+    """The ``vmap`` rule of a state-to-state Function ``cls``: the mapped dimension of the state (``args[0]``) and of the
+    per-sample arguments at ``folded`` goes into the batch dimension, the constant tables at ``tables`` must not be
+    mapped, and the result is unfolded again."""
+    for i in tables:
+        _unmapped_table(in_dims[i], what)
+    v = info.batch_size
+    args = list(args)
+    for i in (0, *folded):
+        args[i] = _fold(args[i], in_dims[i], v)
+    out = cls.apply(*args)
+    return out.reshape(v, -1, out.shape[-1]), 0
+
+
+def _vmap_cross(cls, what: str, info, in_dims, args: tuple, tables: tuple = ()):
+    """The ``vmap`` rule of a cross Function ``cls(bra, ket, ...)``: as :func:`_vmap_states`, and a bra that is the ket
+    mapped the same way stays the same tensor (one read of the state)."""
+    for i in tables:
+        _unmapped_table(in_dims[i], what)
+    v = info.batch_size
+    bra, ket = args[:2]
+    kf = _fold(ket, in_dims[1], v)
+    bf = kf if bra is ket and in_dims[0] == in_dims[1] else _fold(bra, in_dims[0], v)
+    return cls.apply(bf, kf, *args[2:]).reshape(v, -1), 0
+
+
 class _Rdm1Cross(torch.autograd.Function):
     """T[b, k, a, c] = sum_rest conj(bra[a on wire k, rest]) ket[c on wire k, rest]: complex128 (B, n, 2, 2), every wire
     at once (``dq_rdm1_cross_*``; bra and ket the same tensor: one read of the state per pass).  T is anti-linear in
@@ -706,11 +732,7 @@ class _CostPhase(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, state, cost, t, bits, controls):
-        _unmapped_table(in_dims[1], 'cost_phase')
-        v = info.batch_size
-        sf = _fold(state, in_dims[0], v)
-        out = _CostPhase.apply(sf, cost, _fold(t, in_dims[2], v), bits, controls)
-        return out.reshape(v, -1, out.shape[-1]), 0
+        return _vmap_states(_CostPhase, 'cost_phase', info, in_dims, (state, cost, t, bits, controls), folded=(2,), tables=(1,))
 
 
 class _CostCross(torch.autograd.Function):
@@ -750,13 +772,7 @@ class _CostCross(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, bra, ket, cost, bits, controls):
-        _unmapped_table(in_dims[2], 'cost_cross')
-        v = info.batch_size
-        same = bra is ket and in_dims[0] == in_dims[1]
-        kf = _fold(ket, in_dims[1], v)
-        bf = kf if same else _fold(bra, in_dims[0], v)
-        out = _CostCross.apply(bf, kf, cost, bits, controls)
-        return out.reshape(v, -1), 0
+        return _vmap_cross(_CostCross, 'cost_cross', info, in_dims, (bra, ket, cost, bits, controls), tables=(2,))
 
 
 class _CostScale(torch.autograd.Function):
@@ -797,11 +813,7 @@ class _CostScale(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, state, cost, s, bits, controls):
-        _unmapped_table(in_dims[1], 'cost_scale')
-        v = info.batch_size
-        sf = _fold(state, in_dims[0], v)
-        out = _CostScale.apply(sf, cost, _fold(s, in_dims[2], v), bits, controls)
-        return out.reshape(v, -1, out.shape[-1]), 0
+        return _vmap_states(_CostScale, 'cost_scale', info, in_dims, (state, cost, s, bits, controls), folded=(2,), tables=(1,))
 
 
 class _DiagMul(torch.autograd.Function):
@@ -831,13 +843,9 @@ class _DiagMul(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, state, diag, bits, controls):
-        _unmapped_table(in_dims[1], 'diag_mul')
-        v = info.batch_size
-        sf = _fold(state, in_dims[0], v)
-        if diag.ndim == 2 and diag.shape[0] > 1:
-            diag = diag.unsqueeze(0).expand(v, *diag.shape).reshape(-1, diag.shape[-1])
-        out = _DiagMul.apply(sf, diag, bits, controls)
-        return out.reshape(v, -1, out.shape[-1]), 0
+        if in_dims[1] is None and diag.ndim == 2 and diag.shape[0] > 1:         # one table per sample: per folded sample
+            diag = diag.unsqueeze(0).expand(info.batch_size, *diag.shape).reshape(-1, diag.shape[-1])
+        return _vmap_states(_DiagMul, 'diag_mul', info, in_dims, (state, diag, bits, controls), tables=(1,))
 
 
 def _flat_arg(x: torch.Tensor) -> torch.Tensor:
@@ -945,10 +953,7 @@ class _PauliAxpby(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, state, a, c, xmask, zmask, controls, mode):
-        v = info.batch_size
-        sf = _fold(state, in_dims[0], v)
-        out = _PauliAxpby.apply(sf, _fold(a, in_dims[1], v), _fold(c, in_dims[2], v), xmask, zmask, controls, mode)
-        return out.reshape(v, -1, out.shape[-1]), 0
+        return _vmap_states(_PauliAxpby, 'pauli_axpby', info, in_dims, (state, a, c, xmask, zmask, controls, mode), folded=(1, 2))
 
 
 class _PauliCross(torch.autograd.Function):
@@ -992,12 +997,7 @@ class _PauliCross(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, bra, ket, xmask, zmask, controls):
-        v = info.batch_size
-        same = bra is ket and in_dims[0] == in_dims[1]
-        kf = _fold(ket, in_dims[1], v)
-        bf = kf if same else _fold(bra, in_dims[0], v)
-        out = _PauliCross.apply(bf, kf, xmask, zmask, controls)
-        return out.reshape(v, -1), 0
+        return _vmap_cross(_PauliCross, 'pauli_cross', info, in_dims, (bra, ket, xmask, zmask, controls))
 
 
 class _PauliRot(torch.autograd.Function):
@@ -1041,10 +1041,7 @@ class _PauliRot(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, state, theta, xmask, zmask, controls):
-        v = info.batch_size
-        sf = _fold(state, in_dims[0], v)
-        out = _PauliRot.apply(sf, _fold(theta, in_dims[1], v), xmask, zmask, controls)
-        return out.reshape(v, -1, out.shape[-1]), 0
+        return _vmap_states(_PauliRot, 'pauli_rot', info, in_dims, (state, theta, xmask, zmask, controls), folded=(1,))
 
 
 def _pauli_masks(xmask: int, zmask: int, controls: Sequence[int]) -> tuple[int, int, tuple]:
@@ -1125,12 +1122,7 @@ class _PermuteBasis(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, state, perm, inv, bits, controls):
-        _unmapped_table(in_dims[1], 'permute_basis')
-        _unmapped_table(in_dims[2], 'permute_basis')
-        v = info.batch_size
-        sf = _fold(state, in_dims[0], v)
-        out = _PermuteBasis.apply(sf, perm, inv, bits, controls)
-        return out.reshape(v, -1, out.shape[-1]), 0
+        return _vmap_states(_PermuteBasis, 'permute_basis', info, in_dims, (state, perm, inv, bits, controls), tables=(1, 2))
 
 
 def invert_table(perm: torch.Tensor) -> torch.Tensor:
@@ -1188,11 +1180,8 @@ class _MuxApply(torch.autograd.Function):
 
     @staticmethod
     def vmap(info, in_dims, state, table, kind, target, bits, controls, dagger):
-        _unmapped_table(in_dims[1], 'mux_apply')
-        v = info.batch_size
-        sf = _fold(state, in_dims[0], v)
-        out = _MuxApply.apply(sf, table, kind, target, bits, controls, dagger)
-        return out.reshape(v, -1, out.shape[-1]), 0
+        return _vmap_states(_MuxApply, 'mux_apply', info, in_dims, (state, table, kind, target, bits, controls, dagger),
+                            tables=(1,))
 
 
 def mux_apply(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, bits: Sequence[int],

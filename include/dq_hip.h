@@ -568,11 +568,12 @@ int dq_sample_c128(const void* psi, int n, int64_t batch, const double* u, int64
  *    `bits`: HOST array of k distinct index-bit positions, bits[0] = the table index's most significant bit (as in
  *    dq_marginal_*); `controls` / `nc` as in dq_apply_gate_*: an amplitude whose control bits are not all 1 passes
  *    through unchanged (diag, PHASE) or is left out of the sum (cross).  1 <= k, k + nc <= n <= 40, 1 <= batch <= 65535; state
- *    and table pointers 16-byte aligned; in == out is allowed everywhere.  bits = n-1 .. 0 without controls streams the
- *    table beside the state (no gather).
+ *    and table pointers 16-byte aligned.  bits = n-1 .. 0 without controls streams the table beside the state (no
+ *    gather).
  * ------------------------------------------------------------------------------------------ */
 /* out[b, i] = diag[b * diag_batch_stride + sub(i)] * in[b, i]; diag: DEVICE complex in the state's precision, 2^k entries
- * per table; diag_batch_stride = 0 (one table for the batch) or 2^k. */
+ * per table; diag_batch_stride = 0 (one table for the batch) or 2^k.  in == out is allowed (a lane owns the vectors it
+ * reads and writes); any other overlap of [in, in + batch * 2^n) and [out, ..) is refused (DQ_ERR_ARG, "overlap"). */
 int dq_apply_diag_c64(const void* in, void* out, const void* diag, int64_t diag_batch_stride, int n, const int* bits, int k,
                       const int* controls, int nc, int64_t batch, dq_stream_t stream);
 int dq_apply_diag_c128(const void* in, void* out, const void* diag, int64_t diag_batch_stride, int n, const int* bits, int k,
@@ -586,7 +587,9 @@ int dq_apply_diag_c128(const void* in, void* out, const void* diag, int64_t diag
  *        fraction in the state's real precision (an angle of 1e4 rad formed in float is off by more than 1e-4).
  *   op = DQ_COST_SCALE: out[b, i] = s[b] * cost[sub(i)] * in[b, i], s = DEVICE double [batch][2] (re, im): the
  *        cotangent of dq_cost_cross_*, which leaves the amplitudes outside the controls out of its sum -- so here, and
- *        only here, they come out as 0 instead of passing through. */
+ *        only here, they come out as 0 instead of passing through.
+ * in == out is allowed (a lane owns the vectors it reads and writes); any other overlap is refused (DQ_ERR_ARG,
+ * "overlap"). */
 int dq_apply_cost_c64(const void* in, void* out, const void* cost, const double* t, int op, int n, const int* bits, int k,
                       const int* controls, int nc, int64_t batch, dq_stream_t stream);
 int dq_apply_cost_c128(const void* in, void* out, const void* cost, const double* t, int op, int n, const int* bits, int k,
@@ -619,7 +622,8 @@ int dq_cost_cross_c128(const void* bra, const void* ket, const void* cost, int n
  * [batch][4] = (Re a, Im a, Re c, Im c), rounded once to the state's real precision.
  *   mode = DQ_PAULI_GATE: the amplitudes outside the controls pass through bitwise.
  *   mode = DQ_PAULI_MAP:  they come out as 0 (the cotangent of dq_pauli_cross_*, which leaves them out).
- * in == out is allowed: one unit of work owns both ends of a pair i, i ^ xmask. */
+ * in == out is allowed (one unit of work owns both ends of a pair i, i ^ xmask); any other overlap is refused
+ * (DQ_ERR_ARG, "overlap"). */
 int dq_apply_pauli_axpby_c64(const void* in, void* out, uint64_t xmask, uint64_t zmask, const double* coef, int mode, int n,
                              const int* controls, int nc, int64_t batch, dq_stream_t stream);
 int dq_apply_pauli_axpby_c128(const void* in, void* out, uint64_t xmask, uint64_t zmask, const double* coef, int mode, int n,
