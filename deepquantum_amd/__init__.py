@@ -18,13 +18,13 @@ from .communication import (
 )
 from .ansatz import (
     HHL, Ansatz, ControlledMultiplier, ControlledUa, NumberEncoder, PhiAdder, PhiModularAdder,
-    QuantumConvolutionalNeuralNetwork, QuantumFourierTransform, QuantumPhaseEstimationSingleQubit, RandomCircuitG3, ShorCircuit, ShorCircuitFor15,
+    QuantumConvolutionalNeuralNetwork, QuantumFourierTransform, QuantumPhaseEstimationSingleQubit, RandomCircuitG3, ShorCircuit, ShorCircuitFor15, UCCSD,
 )
 from .channel import (
     AmplitudeDamping, BitFlip, Depolarizing, GeneralizedAmplitudeDamping, Pauli, PhaseDamping, PhaseFlip,
 )
 from .gate import (
-    CNOT, ArbitraryGate, Barrier, CombinedSingleGate, CostPhase, DiagonalGate, DoubleControlGate, DoubleGate, Fredkin, Hadamard,
+    CNOT, ArbitraryGate, Barrier, CombinedSingleGate, CostPhase, DiagonalGate, DoubleControlGate, DoubleGate, ExcitationGate, Fredkin, Hadamard,
     HamiltonianGate, Identity, ImaginarySwap, LatentGate, MultiplexedGate, MultiplexedRotation, ParametricDoubleGate, ParametricSingleGate, PauliEvolution, PauliRot, PauliX, PauliY,
     PauliZ, PermutationGate, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate,
     SingleGate, Swap, TDaggerGate, TGate, Toffoli, TripleGate, U3Gate, UAnyGate,

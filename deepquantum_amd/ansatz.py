@@ -397,6 +397,35 @@ class RandomCircuitG3(Ansatz):
                 self.t(where)
 
 
+class UCCSD(Ansatz):
+    """One Trotter step of unitary coupled cluster with singles and doubles on the Hartree-Fock reference: ``x`` on wires
+    ``0 .. nelectron - 1``, then every single excitation occupied ``i`` -> virtual ``a`` (lexicographic in ``(i, a)``), then
+    every double ``i < j`` -> ``a < b`` (lexicographic in ``(i, j, a, b)``), one parameter per excitation --
+    ``no nv + C(no, 2) C(nv, 2)`` of them -- each a stand-alone pass over its own subspace (:class:`ExcitationGate`).
+    ``inputs``: the angles in that order (fixed), or ``None`` for trainable ones.  ``fermionic=False``: qubit excitations."""
+
+    def __init__(self, nqubit: int, nelectron: int, inputs: Any = None, fermionic: bool = True) -> None:
+        if not 0 < nelectron < nqubit:
+            raise ValueError(f'UCCSD: nelectron={nelectron} must lie in (0, {nqubit})')
+        super().__init__(nqubit=nqubit, name='UCCSD')
+        occ, virt = range(nelectron), range(nelectron, nqubit)
+        self.singles = [[i, a] for i in occ for a in virt]
+        self.doubles = [[i, j, a, b] for i in occ for j in occ if i < j for a in virt for b in virt if a < b]
+        self.nparam = len(self.singles) + len(self.doubles)
+        if inputs is not None:
+            inputs = torch.as_tensor(inputs).reshape(-1)
+            if inputs.shape[0] != self.nparam:
+                raise ValueError(f'UCCSD: {self.nparam} angles expected, got {inputs.shape[0]}')
+        for w in occ:
+            self.x(w)
+        for k, wires in enumerate(self.singles + self.doubles):
+            theta = None if inputs is None else inputs[k]
+            if len(wires) == 2:
+                self.single_excitation(wires, inputs=theta, fermionic=fermionic)
+            else:
+                self.double_excitation(wires, inputs=theta, fermionic=fermionic)
+
+
 class ShorCircuit(Ansatz):
     """Order finding for ``a`` modulo the odd number ``mod``: ncount counting wires, the register (initialised
     to 1), then len(bin(mod)) ancillas (reference: ansatz.py:774-837)."""

@@ -1263,3 +1263,123 @@ def _apply_mux_double(state, table, kind, n, target, bits, controls, dagger, out
     row = m[i, t]                                       # (2^n, 2): the row of M that makes amplitude i
     out.copy_(torch.where(ok, row[:, 0] * x0 + row[:, 1] * x1, x).to(state.dtype))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Excitation gates that touch only their subspace (csrc/dq_excite.hip).  A spec is (xmask, amask, zmask, negate) or
+# (xmask, amask, zmask, negate, controls) over index bits: for every i0 with i0 & xmask == amask inside the controls,
+# i1 = i0 ^ xmask and sigma = (-1)^(negate + popc(i0 & zmask)): (K x)[i1] = sigma x[i0], (K x)[i0] = -sigma x[i1], 0 elsewhere
+def _excite_args(state: torch.Tensor, spec, what: str) -> tuple[int, int, int, int, int, list[int]]:
+    n = _nqubit(state)
+    if not isinstance(spec, (tuple, list)) or len(spec) not in (4, 5):
+        raise ValueError(f'{what}: a spec is (xmask, amask, zmask, negate[, controls]), got {spec!r}')
+    xmask, amask, zmask, negate = (int(v) for v in spec[:4])
+    controls = [int(c) for c in spec[4]] if len(spec) == 5 else []
+    if not state.is_contiguous():
+        raise ValueError(f'{what}: state must be contiguous')
+    _suffix(state)
+    if xmask <= 0 or amask < 0 or zmask < 0 or (xmask | zmask) >> n:
+        raise ValueError(f'{what}: xmask={xmask:#x} must lie in [1, 2**{n}), zmask={zmask:#x} in [0, 2**{n})')
+    if amask & ~xmask:
+        raise ValueError(f'{what}: amask={amask:#x} must be a subset of xmask={xmask:#x}')
+    if zmask & xmask:
+        raise ValueError(f'{what}: zmask={zmask:#x} and xmask={xmask:#x} share a bit: fold fixed bits into negate')
+    if negate not in (0, 1):
+        raise ValueError(f'{what}: negate must be 0 or 1, got {negate}')
+    if not _distinct_positions(controls, n):
+        raise ValueError(f'{what}: controls {controls} must be distinct positions in [0, {n})')
+    if any(((xmask | zmask) >> c) & 1 for c in controls):
+        raise ValueError(f'{what}: controls {controls} must be disjoint from xmask | zmask ({xmask | zmask:#x}): fold fixed '
+                         'bits into negate')
+    return n, xmask, amask, zmask, negate, controls
+
+
+def _excite_pairs(n: int, xmask: int, amask: int, zmask: int, negate: int, controls: Sequence[int]):
+    """i0, i1 and sigma of every pair (CPU test double only)."""
+    i = torch.arange(1 << n)
+    cmask = sum(1 << c for c in controls)
+    i0 = i[(i & (xmask | cmask)) == (amask | cmask)]
+    par = i0 & zmask
+    for sh in (32, 16, 8, 4, 2, 1):
+        par = par ^ (par >> sh)
+    sigma = (1 - 2 * ((par & 1) ^ negate)).to(torch.complex128)
+    return i0, i0 ^ xmask, sigma
+
+
+def apply_excite_axpby(state: torch.Tensor, spec, a, c, mode: str = 'gate', out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[b] = a[b] state[b] + c[b] K state[b] on the pairs of the excitation ``spec`` -- 2 / 2^(popc(xmask) + controls) of
+    the state -- (``dq_apply_excite_axpby_*``).  ``a``, ``c``: complex, one value or one per sample.  Outside the pairs:
+
+    * ``mode='gate'``: the amplitudes pass through bitwise (``a = cos t, c = sin t`` is ``exp(t K)``).
+    * ``mode='map'``: they come out as 0 (the cotangent of :func:`excite_cross`, which leaves them out).
+
+    What it costs.  ``out is state`` in ``'gate'`` mode is ONE sparse launch: a read and a write of the vectors that hold a
+    pair, nothing else.  Any other ``out`` (``None``: a new tensor) is filled first -- ``copy_`` of the state for ``'gate'``,
+    a full read and write; ``zero_()`` for ``'map'``, a full write -- and the sparse launch follows: out of place the gate
+    is no cheaper than one full pass.  ``out is state`` in ``'map'`` mode goes through a zeroed temporary and a copy back."""
+    what = 'apply_excite_axpby'
+    if mode not in ('gate', 'map'):
+        raise ValueError(f"{what}: mode must be 'gate' or 'map', got {mode!r}")
+    n, xmask, amask, zmask, negate, controls = _excite_args(state, spec, what)
+    a, c = _pauli_coef(a, state, what), _pauli_coef(c, state, what)
+    if out is None:
+        out = torch.empty_like(state)
+    else:
+        out = _check_out(state, out, what)
+    if out.data_ptr() == state.data_ptr():
+        if mode == 'map':
+            return out.copy_(apply_excite_axpby(state, spec, a, c, 'map'))
+    elif mode == 'gate':
+        out.copy_(state)
+    else:
+        out.zero_()
+    if not _use_hip(state):
+        def double():
+            i0, i1, sigma = _excite_pairs(n, xmask, amask, zmask, negate, controls)
+            x0, x1 = state[:, i0].to(torch.complex128), state[:, i1].to(torch.complex128)
+            out[:, i0] = (a.reshape(-1, 1) * x0 - c.reshape(-1, 1) * sigma * x1).to(state.dtype)
+            out[:, i1] = (a.reshape(-1, 1) * x1 + c.reshape(-1, 1) * sigma * x0).to(state.dtype)
+            return out
+
+        return _diag_double(double)
+    coef = torch.view_as_real(torch.stack([a, c], dim=1)).reshape(-1, 4).contiguous()
+    return _excite_launch(state, out, coef, _lib.EXCITE_GATE if mode == 'gate' else _lib.EXCITE_MAP,
+                          (xmask, amask, zmask, negate), n, controls)
+
+
+def _excite_launch(state, out, coef, code, masks, n, controls):
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_excite_axpby', state, _ptr(state, lo), _ptr(out, lo), _ptr(coef, lo), code, *masks, n,
+              _lib.int_array(controls), len(controls), hi - lo)
+    return out
+
+
+def apply_excite_rot(state: torch.Tensor, spec, theta: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """exp(theta K) state = (I + sin(theta) K + (1 - cos(theta)) K^2) state: :func:`apply_excite_axpby` in 'gate' mode with
+    a = cos(theta), c = sin(theta), formed in double from the real ``theta`` (B,), per sample.  ``out=state`` is the
+    sparse in-place gate; see :func:`apply_excite_axpby` for what any other ``out`` costs."""
+    if theta.is_complex() or theta.shape != (state.shape[0],):
+        raise ValueError(f'apply_excite_rot: one real angle per sample, ({state.shape[0]},), expected; got '
+                         f'{theta.dtype} {tuple(theta.shape)}')
+    theta = theta.to(device=state.device, dtype=torch.float64)
+    return apply_excite_axpby(state, spec, torch.cos(theta), torch.sin(theta), 'gate', out)
+
+
+def excite_cross(bra: torch.Tensor, ket: torch.Tensor, spec) -> torch.Tensor:
+    """out[b] = sum_i conj(bra[b, i]) (K ket[b])[i]: complex128 (B,), accumulated in double, bitwise reproducible, reading
+    only the pairs (``dq_excite_cross_*``).  ``bra`` and ``ket`` the same buffer: each pair is read once, and the real part
+    is 0 up to rounding (K is anti-Hermitian).  The workspace comes from PyTorch's allocator (legal under capture)."""
+    n, xmask, amask, zmask, negate, controls = _excite_args(ket, spec, 'excite_cross')
+    if bra.shape != ket.shape or bra.dtype != ket.dtype:
+        raise ValueError('excite_cross: bra/ket must be (batch, 2**n) tensors of one shape and dtype')
+    if not bra.is_contiguous():
+        raise ValueError('excite_cross: bra must be contiguous')
+    if not _use_hip(ket):
+        def double():
+            i0, i1, sigma = _excite_pairs(n, xmask, amask, zmask, negate, controls)
+            u, v = bra.to(torch.complex128).conj(), ket.to(torch.complex128)
+            return (sigma * (u[:, i1] * v[:, i0] - u[:, i0] * v[:, i1])).sum(dim=-1)
+
+        return _diag_double(double)
+    mid = (xmask, amask, zmask, negate, n, _lib.int_array(controls), len(controls))
+    return _cross_reduce('dq_excite_cross', 'dq_excite_cross_ws_bytes', bra, ket, mid)

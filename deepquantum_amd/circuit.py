@@ -26,7 +26,7 @@ from torch import nn
 
 from . import _functorch, executor, ops, qmath
 from .gate import (
-    CNOT, Barrier, CostPhase, DiagonalGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, MultiplexedGate, MultiplexedRotation, PauliEvolution,
+    CNOT, Barrier, CostPhase, DiagonalGate, ExcitationGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, MultiplexedGate, MultiplexedRotation, PauliEvolution,
     PauliRot, PauliX, PauliY, PauliZ, PermutationGate, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
     TDaggerGate, TGate, Toffoli, U3Gate, UAnyGate,
 )
@@ -152,7 +152,7 @@ class QubitCircuit(Operation):
 
     def _run_operators(self, flat: torch.Tensor, zero: bool = False) -> torch.Tensor:
         """All operators on a (B, 2**n) state: maximal stretches of gates go to the executor (fused passes),
-        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
+        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``, ``ExcitationGate``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
         density matrix alike: index 0 is 1, everything else 0)."""
         if self.den_mat:
             prims = []
@@ -850,6 +850,30 @@ class QubitCircuit(Operation):
         requires_grad = (not encode) and t is None
         self.add(PauliEvolution(hamiltonian=hamiltonian, t=t, nqubit=self.nqubit, steps=steps, order=order, name=name,
                                 den_mat=self.den_mat, requires_grad=requires_grad), encode=encode)
+
+    def excitation(self, create, annihilate, inputs=None, controls=None, fermionic=True, encode=False, name='excitation'):
+        """``exp(theta (E - E^dagger))`` for ``E = a^dagger_{create[0]} .. a_{annihilate[0]} ..`` (Jordan-Wigner over wire
+        numbers; ``fermionic=False``: the qubit excitation without the string), a rotation by the full angle ``theta`` that
+        touches only its subspace.  ``theta`` is trainable, given by ``inputs``, or fed from ``data`` with ``encode=True``:
+        see :class:`ExcitationGate`."""
+        requires_grad = (not encode) and inputs is None
+        self.add(ExcitationGate(create=create, annihilate=annihilate, nqubit=self.nqubit, inputs=inputs, controls=controls,
+                                fermionic=fermionic, requires_grad=requires_grad, name=name, den_mat=self.den_mat),
+                 encode=encode)
+
+    def single_excitation(self, wires, inputs=None, controls=None, fermionic=True, encode=False):
+        """The single excitation from wire ``p`` to wire ``q`` of ``wires=[p, q]``: ``create=[q], annihilate=[p]``."""
+        if len(wires) != 2:
+            raise ValueError(f'single_excitation: wires=[p, q] expected, got {wires}')
+        self.excitation([wires[1]], [wires[0]], inputs=inputs, controls=controls, fermionic=fermionic, encode=encode,
+                        name='single_excitation')
+
+    def double_excitation(self, wires, inputs=None, controls=None, fermionic=True, encode=False):
+        """The double excitation from wires ``p, q`` to ``r, s`` of ``wires=[p, q, r, s]``: ``create=[r, s], annihilate=[p, q]``."""
+        if len(wires) != 4:
+            raise ValueError(f'double_excitation: wires=[p, q, r, s] expected, got {wires}')
+        self.excitation(list(wires[2:]), list(wires[:2]), inputs=inputs, controls=controls, fermionic=fermionic, encode=encode,
+                        name='double_excitation')
 
     # layers
     def xlayer(self, wires=None):

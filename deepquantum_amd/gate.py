@@ -1423,6 +1423,92 @@ class PauliEvolution(_OneAngle, _FlatGate, ArbitraryGate):
         return f'terms={len(self.terms)}, steps={self.steps}, order={self.order}, ' + _OneAngle.extra_repr(self)
 
 
+def excitation_masks(nqubit: int, create, annihilate, fermionic: bool = True, controls=()) -> tuple[int, int, int, int]:
+    """``(xmask, amask, zmask, negate)`` over index bits (wire w is bit ``nqubit - 1 - w``) of ``K = E - E^dagger`` for
+    ``E = a^dagger_{create[0]} a^dagger_{create[1]} .. a_{annihilate[0]} a_{annihilate[1]} ..`` under the Jordan-Wigner
+    map over wire numbers, ``a_j = (prod_{l<j} Z_l) |0><1|_j``: for every index i0 with the annihilated wires occupied, the
+    created ones empty and the controls 1, ``i1 = i0 ^ xmask`` and ``<i1|E|i0> = (-1)^(negate + popc(i0 & zmask))``.
+    ``zmask`` holds the wires outside both lists below an odd number of listed wires; the sign of the listed wires
+    themselves is found by walking the operator product over one integer; a control inside the string is always 1 where
+    the gate acts, so its bit is folded into ``negate``.  ``fermionic=False``: no string and no sign, the qubit excitation."""
+    create, annihilate, controls = [int(w) for w in create], [int(w) for w in annihilate], [int(w) for w in controls]
+    listed = create + annihilate
+    if not create or not annihilate:
+        raise ValueError('excitation: create and annihilate each name at least one wire')
+    if len(set(listed + controls)) != len(listed + controls):
+        raise ValueError(f'excitation: a wire is repeated (create {create}, annihilate {annihilate}, controls {controls})')
+    if any(w < 0 or w >= nqubit for w in listed + controls):
+        raise ValueError(f'excitation: wires {listed + controls} outside the register of {nqubit} qubits')
+    bit = lambda w: 1 << (nqubit - 1 - w)  # noqa: E731
+    xmask = sum(bit(w) for w in listed)
+    amask = sum(bit(w) for w in annihilate)
+    if not fermionic:
+        return xmask, amask, 0, 0
+    occupied, negate = set(annihilate), 0
+    for j, w in enumerate(reversed(listed)):            # (the rightmost operator acts first)
+        negate ^= sum(1 for l in occupied if l < w) & 1
+        if j < len(annihilate):
+            occupied.remove(w)
+        else:
+            occupied.add(w)
+    zmask = 0
+    for l in range(nqubit):
+        if l not in listed and sum(1 for w in listed if w > l) & 1:
+            if l in controls:
+                negate ^= 1
+            else:
+                zmask |= bit(l)
+    return xmask, amask, zmask, negate
+
+
+class ExcitationGate(_OneAngle, _FlatGate, ArbitraryGate):
+    """``exp(theta (E - E^dagger))`` for the excitation ``E = a^dagger_{create[0]} a^dagger_{create[1]} .. a_{annihilate[0]}
+    a_{annihilate[1]} ..`` (Jordan-Wigner over wire numbers, ``|1>`` occupied): the gate of UCCSD and of every
+    particle-number-conserving ansatz, for any number of wires in the two lists.  It is a Givens rotation by the FULL angle
+    ``theta`` between the basis states with the annihilated wires occupied and the created ones empty and their partners
+    with the two lists swapped, with the sign of the Jordan-Wigner string; every other amplitude is untouched, and the
+    kernel reads and writes the rotated pairs only -- 1/2 of the state for a single, 1/8 for a double, half of that per
+    control (``dq_apply_excite_axpby_*``).  ``fermionic=False`` drops the string: the qubit excitation.
+
+    Conventions.  The qubit single ``create=[q], annihilate=[p]`` is exactly ``rbs(theta)`` on wires ``[p, q]``
+    (``ReconfigurableBeamSplitter``).  PennyLane's ``SingleExcitation(phi, wires=[p, q])`` / ``DoubleExcitation`` rotate by
+    HALF their parameter and carry no string: ``SingleExcitation(phi, [p, q])`` is the qubit excitation ``create=[p],
+    annihilate=[q], fermionic=False`` at ``theta = phi / 2`` (equally ``create=[q], annihilate=[p]`` at ``theta = -phi / 2``).
+
+    ``theta`` is trainable (``requires_grad=True``), fixed (``inputs``), or fed from the circuit's data (``encode=True``; a
+    batch of data gives one ``theta`` per sample)."""
+
+    _param_names = ('theta',)
+    get_matrix = None                                   # (no matrix: not one of the circuit's vectorised one-angle gates)
+
+    def __init__(self, create, annihilate, nqubit=1, inputs=None, controls=None, fermionic=True, requires_grad=False,
+                 name='ExcitationGate', den_mat=False, tsr_mode=False):
+        create = [create] if isinstance(create, int) else list(create)
+        annihilate = [annihilate] if isinstance(annihilate, int) else list(annihilate)
+        ctrl = [] if controls is None else [controls] if isinstance(controls, int) else list(controls)
+        excitation_masks(nqubit, create, annihilate, fermionic, ctrl)           # (the lists are checked there)
+        self.create, self.annihilate, self.fermionic = create, annihilate, bool(fermionic)
+        super().__init__(name=name, nqubit=nqubit, wires=create + annihilate, controls=controls, den_mat=den_mat,
+                         tsr_mode=tsr_mode)
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        self._one_angle(inputs, requires_grad)
+
+    def masks(self) -> tuple[int, int, int, int]:
+        """``(xmask, amask, zmask, negate)`` over index bits: see :func:`excitation_masks`."""
+        return excitation_masks(self.nqubit, self.create, self.annihilate, self.fermionic, self.controls)
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        return ops.excite_rot(x, (*self.masks(), self._bits(self.controls)), self._angle())
+
+    def extra_repr(self) -> str:
+        return (f'create={self.create}, annihilate={self.annihilate}, fermionic={self.fermionic}, '
+                + _OneAngle.extra_repr(self))
+
+
 class Reset(Gate):
     r"""Reset qubits to :math:`|0\rangle` (reference: gate.py:3027-3094).
 

@@ -1092,6 +1092,187 @@ def pauli_rot(state: torch.Tensor, xmask: int, zmask: int, theta, controls: Sequ
     return _PauliRot.apply(_flat_arg(state), theta, xmask, zmask, controls)
 
 
+# ---- excitation gates that touch only their subspace (csrc/dq_excite.hip) ------------------------------------------------
+# K = E - E^dagger over the pairs of a spec (xmask, amask, zmask, negate, controls): real, anti-symmetric, K^3 = -K, so
+# -K^2 is the projector onto the pairs.  Two operations closed under differentiation, and the rotation as a node of its
+# own on top of them:
+#     axpby(x; a, c)[i] = a x[i] + c (K x)[i] on the pairs   (elsewhere: x[i] in 'gate' mode, 0 in 'map' mode)
+#     cross(u, v)       = sum_i conj(u[i]) (K v)[i]
+#     rot(x; theta)     = axpby(x; cos(theta), sin(theta)) in 'gate' mode = exp(theta K) x
+class _ExciteAxpby(torch.autograd.Function):
+    """y = a x + c K x with a, c complex128 (B,): cotangents gx = axpby(gy; conj a, -conj c) in the same mode (K^T = -K),
+    gc = <K x, gy> = -cross(x, gy) and ga = the inner product over the pairs = -cross(x, K gy).  A tangent in a or c moves
+    the pairs only: a 'map' term."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, a: torch.Tensor, c: torch.Tensor, spec: tuple, mode: str) -> torch.Tensor:
+        return backend.apply_excite_axpby(_plain(state), spec, _plain(a), _plain(c), mode)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, a, c, ctx.spec, ctx.mode = inputs
+        ctx.save_for_backward(state, a, c)
+        ctx.save_for_forward(state, a, c)
+
+    @staticmethod
+    def jvp(ctx, state_t, a_t, c_t, *_):
+        _single_forward_level()
+        state, a, c = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = excite_axpby(state_t, ctx.spec, a, c, ctx.mode)
+        if a_t is not None or c_t is not None:
+            zero = torch.zeros_like(a)
+            term = excite_axpby(state, ctx.spec, zero if a_t is None else a_t, zero if c_t is None else c_t, 'map')
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, a, c = ctx.saved_tensors
+        gstate = ga = gc = None
+        if ctx.needs_input_grad[0]:
+            gstate = excite_axpby(gy, ctx.spec, a.conj(), -c.conj(), ctx.mode)
+        if ctx.needs_input_grad[1]:
+            kgy = excite_axpby(gy, ctx.spec, torch.zeros_like(a), torch.ones_like(a), 'map')
+            ga = (-excite_cross(state, kgy, ctx.spec)).to(a.dtype)
+        if ctx.needs_input_grad[2]:
+            gc = (-excite_cross(state, gy, ctx.spec)).to(c.dtype)
+        return gstate, ga, gc, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, a, c, spec, mode):
+        return _vmap_states(_ExciteAxpby, 'excite_axpby', info, in_dims, (state, a, c, spec, mode), folded=(1, 2))
+
+
+class _ExciteCross(torch.autograd.Function):
+    """z = sum_i conj(u_i) (K v)_i, complex128 (B,): anti-linear in u, linear in v; cotangents g_v = K^T u gz =
+    map(u; 0, -gz) and g_u = map(v; 0, conj(gz))."""
+
+    @staticmethod
+    def forward(bra: torch.Tensor, ket: torch.Tensor, spec: tuple) -> torch.Tensor:
+        pk = _plain(ket)
+        return backend.excite_cross(pk if bra is ket else _plain(bra), pk, spec)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        bra, ket, ctx.spec = inputs
+        ctx.save_for_backward(bra, ket)
+        ctx.save_for_forward(bra, ket)
+
+    @staticmethod
+    def jvp(ctx, bra_t, ket_t, *_):
+        _single_forward_level()
+        bra, ket = ctx.saved_tensors
+        out = None
+        if bra_t is not None:
+            out = excite_cross(bra_t, ket, ctx.spec)
+        if ket_t is not None:
+            term = excite_cross(bra, ket_t, ctx.spec)
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gz: torch.Tensor):
+        bra, ket = ctx.saved_tensors
+        gz = gz.to(torch.complex128)
+        zero = torch.zeros_like(gz)
+        gbra = gket = None
+        if ctx.needs_input_grad[0]:
+            gbra = excite_axpby(ket, ctx.spec, zero, gz.conj(), 'map')
+        if ctx.needs_input_grad[1]:
+            gket = excite_axpby(bra, ctx.spec, zero, -gz, 'map')
+        return gbra, gket, None
+
+    @staticmethod
+    def vmap(info, in_dims, bra, ket, spec):
+        return _vmap_cross(_ExciteCross, 'excite_cross', info, in_dims, (bra, ket, spec))
+
+
+class _ExciteRot(torch.autograd.Function):
+    """y = U x, U = exp(theta K), theta real (B,): cotangents gx = rot(gy, -theta) = U^T gy and gtheta = Re cross(gy, y)
+    (dy/dtheta = K y).  U commutes with K, so cross(gy, U x) = cross(U^T gy, x) = cross(gx, x): the cross takes the two
+    tensors the backward holds already -- one rotation and one cross per backward, both over the pairs only."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, theta: torch.Tensor, spec: tuple) -> torch.Tensor:
+        return backend.apply_excite_rot(_plain(state), spec, _plain(theta))
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, theta, ctx.spec = inputs
+        ctx.save_for_backward(state, theta)
+        ctx.save_for_forward(state, theta)
+
+    @staticmethod
+    def jvp(ctx, state_t, theta_t, *_):
+        _single_forward_level()
+        state, theta = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = excite_rot(state_t, ctx.spec, theta)
+        if theta_t is not None:
+            y = excite_rot(state, ctx.spec, theta)
+            rate = theta_t.to(torch.complex128)
+            term = excite_axpby(y, ctx.spec, torch.zeros_like(rate), rate, 'map')
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, theta = ctx.saved_tensors
+        gstate = excite_rot(gy, ctx.spec, -theta)
+        gtheta = None
+        if ctx.needs_input_grad[1]:
+            gtheta = excite_cross(gstate, state, ctx.spec).real.to(theta.dtype)
+        return (gstate if ctx.needs_input_grad[0] else None), gtheta, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, theta, spec):
+        return _vmap_states(_ExciteRot, 'excite_rot', info, in_dims, (state, theta, spec), folded=(1,))
+
+
+def _excite_spec(spec) -> tuple:
+    """(xmask, amask, zmask, negate, controls) with plain ints and a tuple of controls: hashable, and what the nodes keep."""
+    if not isinstance(spec, (tuple, list)) or len(spec) not in (4, 5):
+        raise ValueError(f'an excitation spec is (xmask, amask, zmask, negate[, controls]), got {spec!r}')
+    return (*(int(v) for v in spec[:4]), tuple(int(c) for c in spec[4]) if len(spec) == 5 else ())
+
+
+def excite_axpby(state: torch.Tensor, spec, a, c, mode: str = 'gate') -> torch.Tensor:
+    """Differentiable ``a x + c K x`` on the pairs of the excitation ``spec = (xmask, amask, zmask, negate[, controls])``
+    of a (B, 2**n) state (:func:`backend.apply_excite_axpby`); ``a``, ``c`` complex, one value or one per sample.
+    Amplitudes outside the pairs pass through (``mode='gate'``) or come out as 0 (``mode='map'``, the cotangent of
+    :func:`excite_cross`)."""
+    _no_legacy(state)
+    if mode not in ('gate', 'map'):
+        raise ValueError(f"excite_axpby: mode must be 'gate' or 'map', got {mode!r}")
+    a = _pauli_param(a, state, torch.complex128, 'excite_axpby')
+    c = _pauli_param(c, state, torch.complex128, 'excite_axpby')
+    return _ExciteAxpby.apply(_flat_arg(state), a, c, _excite_spec(spec), mode)
+
+
+def excite_cross(bra: torch.Tensor, ket: torch.Tensor, spec) -> torch.Tensor:
+    """Differentiable ``sum_i conj(bra_i) (K ket)_i`` of two (B, 2**n) states over the pairs of ``spec``: complex128 (B,).
+    Pass the same tensor twice to read each pair once (the real part is then 0 up to rounding)."""
+    _no_legacy(bra, ket)
+    if bra.dtype != ket.dtype:
+        raise ValueError('excite_cross: bra and ket must have one dtype')
+    same = bra is ket
+    ket = _flat_arg(ket)
+    bra = ket if same else _flat_arg(bra)
+    return _ExciteCross.apply(bra, ket, _excite_spec(spec))
+
+
+def excite_rot(state: torch.Tensor, spec, theta) -> torch.Tensor:
+    """Differentiable ``exp(theta K)`` -- a Givens rotation by the FULL angle theta in every pair of ``spec`` -- on a
+    (B, 2**n) state: ``theta`` real, one value or one per sample; cosine and sine are formed in double for both
+    precisions."""
+    _no_legacy(state)
+    theta = _pauli_param(theta, state, torch.float64, 'excite_rot')
+    return _ExciteRot.apply(_flat_arg(state), theta, _excite_spec(spec))
+
+
 # ---- basis-state permutations on any number of wires (csrc/dq_perm.hip) --------------------------------------------------
 # P |x> = |perm(x)> on the table bits, inside the controls: a real permutation matrix, so its adjoint is its inverse.  One
 # operation closed under differentiation: the backward and the jvp are the function itself.

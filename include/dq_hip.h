@@ -686,6 +686,44 @@ int dq_apply_mux_c64(const void* in, void* out, const void* table, int kind, int
 int dq_apply_mux_c128(const void* in, void* out, const void* table, int kind, int dagger, int n, int target, const int* bits,
                       int k, const int* controls, int nc, int64_t batch, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 12. Excitation gates -- Givens rotations between two bit patterns -- that touch only their subspace
+ *     (csrc/dq_excite.hip; added within ABI 30, presence is checked by symbol).  K = E - E^dagger for an excitation E
+ *     between the patterns `amask` and `xmask ^ amask` of the bits of `xmask`; exp(theta K) = I + sin(theta) K +
+ *     (1 - cos(theta)) K^2 is a = cos(theta), c = sin(theta) below.  For every i0 with i0 & xmask == amask and every
+ *     control bit 1, i1 = i0 ^ xmask and sigma = (-1)^(negate + popc(i0 & zmask)):
+ *         (K psi)[i1] = sigma * psi[i0]        (K psi)[i0] = -sigma * psi[i1]        (K psi)[i] = 0 elsewhere
+ *     xmask != 0 of any weight; amask a subset of xmask; zmask (the Jordan-Wigner string over the free bits) and the
+ *     controls disjoint from xmask and from each other -- a caller folds the zmask bits that fall on fixed bits into
+ *     `negate` (0 or 1).  1 <= n <= 40, 1 <= batch <= 65535; state pointers 16-byte aligned.  The pairs are
+ *     2 / 2^(popc(xmask) + nc) of the state, and the kernels read and write only the 16-byte vectors that hold an end
+ *     of a pair.
+ * ------------------------------------------------------------------------------------------ */
+#define DQ_EXCITE_GATE 0
+#define DQ_EXCITE_MAP 1
+/* out[b, i] = a[b] * in[b, i] + c[b] * (K in_b)[i] for i = i0, i1 of every pair; coef = DEVICE double [batch][4] =
+ * (Re a, Im a, Re c, Im c), rounded once to the state's real precision.  NOTHING ELSE OF `out` IS WRITTEN: with
+ * in == out that is the gate in place; with a disjoint `out` the caller fills the rest first (a copy of `in` for the gate,
+ * zeros for the cotangent map).  An amplitude that shares a 16-byte vector with an end of a pair without being one
+ * (complex64, bit 0 fixed) is copied bitwise from `in` (mode = DQ_EXCITE_GATE) or written as 0 (DQ_EXCITE_MAP).  Any
+ * overlap of in and out other than in == out is refused (DQ_ERR_ARG, "overlap"). */
+int dq_apply_excite_axpby_c64(const void* in, void* out, const double* coef, int mode, uint64_t xmask, uint64_t amask,
+                              uint64_t zmask, int negate, int n, const int* controls, int nc, int64_t batch, dq_stream_t stream);
+int dq_apply_excite_axpby_c128(const void* in, void* out, const double* coef, int mode, uint64_t xmask, uint64_t amask,
+                               uint64_t zmask, int negate, int n, const int* controls, int nc, int64_t batch, dq_stream_t stream);
+
+/* Bytes of device workspace dq_excite_cross_* needs (one partial sum per workgroup and sample: at most 32 KiB per
+ * sample, whatever the masks; `cross` != 0: bra != ket, the same amount); -1 on a bad argument. */
+int64_t dq_excite_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross);
+/* out[b] = sum_i conj(bra[b, i]) * (K ket_b)[i]: DEVICE double [batch][2] (re, im), fully overwritten, accumulated in
+ * double, reading only the pairs.  bra == ket reads each pair once (the real part is then 0 up to rounding: K is
+ * anti-Hermitian).  Workgroups write fixed-order partial sums into `ws` (at least dq_excite_cross_ws_bytes bytes,
+ * 16-byte aligned) and a second kernel adds them: no atomics, results are bitwise reproducible. */
+int dq_excite_cross_c64(const void* bra, const void* ket, uint64_t xmask, uint64_t amask, uint64_t zmask, int negate, int n,
+                        const int* controls, int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+int dq_excite_cross_c128(const void* bra, const void* ket, uint64_t xmask, uint64_t amask, uint64_t zmask, int negate, int n,
+                         const int* controls, int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
