@@ -866,6 +866,17 @@ def _distinct_positions(positions: Sequence[int], n: int) -> bool:
     return len(set(positions)) == len(positions) and not any(p < 0 or p >= n for p in positions)
 
 
+def _check_bra(bra: torch.Tensor, ket: torch.Tensor, what: str) -> None:
+    """The bra of a cross reduction of the streaming sections against its (checked) ket: one shape and dtype, contiguous
+    (the ket itself: nothing left to check)."""
+    if bra is ket:
+        return
+    if bra.shape != ket.shape or bra.dtype != ket.dtype:
+        raise ValueError(f'{what}: bra/ket must be (batch, 2**n) tensors of one shape and dtype')
+    if not bra.is_contiguous():
+        raise ValueError(f'{what}: bra must be contiguous')
+
+
 def _diag_args(state: torch.Tensor, bits: Sequence[int], controls: Sequence[int], what: str) -> tuple[int, list[int], list[int]]:
     n = _nqubit(state)
     bits, controls = [int(b) for b in bits], [int(c) for c in controls]
@@ -1006,10 +1017,7 @@ def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: S
     of the state, the expectation value <C>.  The workspace comes from PyTorch's allocator (legal under capture)."""
     n, bits, controls = _diag_args(ket, bits, controls, 'cost_cross')
     k = len(bits)
-    if bra.shape != ket.shape or bra.dtype != ket.dtype:
-        raise ValueError('cost_cross: bra/ket must be (batch, 2**n) tensors of one shape and dtype')
-    if not bra.is_contiguous():
-        raise ValueError('cost_cross: bra must be contiguous')
+    _check_bra(bra, ket, 'cost_cross')
     cost = _diag_table(cost, ket, ket.real.dtype, k, 'cost_cross', False)
     if not _use_hip(ket):
         def double():
@@ -1024,17 +1032,30 @@ def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: S
 
 # ---------------------------------------------------------------------------------------------------
 # Pauli strings on any number of wires (csrc/dq_pauli.hip): (P psi)[i] = i^ny (-1)^popc((i ^ x) & z) psi[i ^ x]
-def _pauli_args(state: torch.Tensor, xmask: int, zmask: int, controls: Sequence[int], what: str) -> tuple[int, int, int, list[int]]:
+def _support_args(state: torch.Tensor, controls: Sequence[int], support: int, named: str, what: str) -> tuple[int, list[int]]:
+    """What the Pauli and the excitation entry points ask alike, before their own mask checks: a contiguous state and
+    controls that are distinct positions of it outside the generator's mask ``support`` (``named``: what the message calls
+    it, with a place for the mask)."""
     n = _nqubit(state)
-    xmask, zmask, controls = int(xmask), int(zmask), [int(c) for c in controls]
+    controls = [int(c) for c in controls]
     if not state.is_contiguous():
         raise ValueError(f'{what}: state must be contiguous')
+    if controls:
+        if len(set(controls)) != len(controls) or min(controls) < 0 or max(controls) >= n:
+            raise ValueError(f'{what}: controls {controls} must be distinct positions in [0, {n})')
+        cmask = 0
+        for c in controls:
+            cmask |= 1 << c
+        if support & cmask:
+            raise ValueError(f'{what}: controls {controls} must be disjoint from {named.format(support)}')
+    return n, controls
+
+
+def _pauli_args(state: torch.Tensor, xmask: int, zmask: int, controls: Sequence[int], what: str) -> tuple[int, int, int, list[int]]:
+    xmask, zmask = int(xmask), int(zmask)
+    n, controls = _support_args(state, controls, xmask | zmask, 'the Pauli string ({:#x})', what)
     if xmask < 0 or zmask < 0 or (xmask | zmask) >> n:
         raise ValueError(f'{what}: xmask={xmask:#x} / zmask={zmask:#x} must lie in [0, 2**{n})')
-    if not _distinct_positions(controls, n):
-        raise ValueError(f'{what}: controls {controls} must be distinct positions in [0, {n})')
-    if any(((xmask | zmask) >> c) & 1 for c in controls):
-        raise ValueError(f'{what}: controls {controls} must be disjoint from the Pauli string ({xmask | zmask:#x})')
     return n, xmask, zmask, controls
 
 
@@ -1046,6 +1067,19 @@ def _pauli_coef(p, like: torch.Tensor, what: str) -> torch.Tensor:
     if p.shape[0] != like.shape[0]:
         raise ValueError(f'{what}: one coefficient, or one per sample ({like.shape[0]}), expected; got {p.shape[0]}')
     return p.resolve_conj().resolve_neg()
+
+
+def _axpby_coef(a: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """(B, 4) float64 rows (Re a, Im a, Re c, Im c): what the axpby kernels read."""
+    return torch.view_as_real(torch.stack([a, c], dim=1)).reshape(-1, 4).contiguous()
+
+
+def _real_angles(theta: torch.Tensor, state: torch.Tensor, what: str) -> torch.Tensor:
+    """One real angle per sample, as float64 on the state's device."""
+    if theta.is_complex() or theta.shape != (state.shape[0],):
+        raise ValueError(f'{what}: one real angle per sample, ({state.shape[0]},), expected; got '
+                         f'{theta.dtype} {tuple(theta.shape)}')
+    return theta.to(device=state.device, dtype=torch.float64)
 
 
 def _pauli_gather(n: int, xmask: int, zmask: int, controls: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -1084,8 +1118,7 @@ def apply_pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, control
             return out
 
         return _diag_double(double)
-    coef = torch.view_as_real(torch.stack([a, c], dim=1)).reshape(-1, 4).contiguous()
-    return _pauli_launch(state, out, xmask, zmask, coef, _lib.PAULI_GATE if mode == 'gate' else _lib.PAULI_MAP, n, controls)
+    return _pauli_launch(state, out, xmask, zmask, _axpby_coef(a, c), _lib.PAULI_GATE if mode == 'gate' else _lib.PAULI_MAP, n, controls)
 
 
 def _pauli_launch(state, out, xmask, zmask, coef, code, n, controls):
@@ -1100,10 +1133,7 @@ def apply_pauli_rot(state: torch.Tensor, xmask: int, zmask: int, theta: torch.Te
     """exp(-i theta/2 P) state: :func:`apply_pauli_axpby` in 'gate' mode with a = cos(theta/2), c = -i sin(theta/2), the
     four real coefficients formed in double from the real ``theta`` (B,) without a detour through complex tensors."""
     n, xmask, zmask, controls = _pauli_args(state, xmask, zmask, controls, 'apply_pauli_rot')
-    if theta.is_complex() or theta.shape != (state.shape[0],):
-        raise ValueError(f'apply_pauli_rot: one real angle per sample, ({state.shape[0]},), expected; got '
-                         f'{theta.dtype} {tuple(theta.shape)}')
-    half = theta.to(device=state.device, dtype=torch.float64) * 0.5
+    half = _real_angles(theta, state, 'apply_pauli_rot') * 0.5
     if not _use_hip(state):
         return apply_pauli_axpby(state, xmask, zmask, torch.cos(half), -1j * torch.sin(half), controls, 'gate', out)
     out = _check_out(state, out, 'apply_pauli_rot')
@@ -1118,10 +1148,7 @@ def pauli_cross(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, co
     the state.  ``xmask = zmask = 0``: the inner product over the controlled amplitudes.  The workspace comes from
     PyTorch's allocator (legal under capture)."""
     n, xmask, zmask, controls = _pauli_args(ket, xmask, zmask, controls, 'pauli_cross')
-    if bra.shape != ket.shape or bra.dtype != ket.dtype:
-        raise ValueError('pauli_cross: bra/ket must be (batch, 2**n) tensors of one shape and dtype')
-    if not bra.is_contiguous():
-        raise ValueError('pauli_cross: bra must be contiguous')
+    _check_bra(bra, ket, 'pauli_cross')
     if not _use_hip(ket):
         def double():
             j, factor, ok = _pauli_gather(n, xmask, zmask, controls)
@@ -1270,13 +1297,11 @@ def _apply_mux_double(state, table, kind, n, target, bits, controls, dagger, out
 # (xmask, amask, zmask, negate, controls) over index bits: for every i0 with i0 & xmask == amask inside the controls,
 # i1 = i0 ^ xmask and sigma = (-1)^(negate + popc(i0 & zmask)): (K x)[i1] = sigma x[i0], (K x)[i0] = -sigma x[i1], 0 elsewhere
 def _excite_args(state: torch.Tensor, spec, what: str) -> tuple[int, int, int, int, int, list[int]]:
-    n = _nqubit(state)
     if not isinstance(spec, (tuple, list)) or len(spec) not in (4, 5):
         raise ValueError(f'{what}: a spec is (xmask, amask, zmask, negate[, controls]), got {spec!r}')
     xmask, amask, zmask, negate = (int(v) for v in spec[:4])
-    controls = [int(c) for c in spec[4]] if len(spec) == 5 else []
-    if not state.is_contiguous():
-        raise ValueError(f'{what}: state must be contiguous')
+    n, controls = _support_args(state, spec[4] if len(spec) == 5 else (), xmask | zmask,
+                                'xmask | zmask ({:#x}): fold fixed bits into negate', what)
     _suffix(state)
     if xmask <= 0 or amask < 0 or zmask < 0 or (xmask | zmask) >> n:
         raise ValueError(f'{what}: xmask={xmask:#x} must lie in [1, 2**{n}), zmask={zmask:#x} in [0, 2**{n})')
@@ -1286,11 +1311,6 @@ def _excite_args(state: torch.Tensor, spec, what: str) -> tuple[int, int, int, i
         raise ValueError(f'{what}: zmask={zmask:#x} and xmask={xmask:#x} share a bit: fold fixed bits into negate')
     if negate not in (0, 1):
         raise ValueError(f'{what}: negate must be 0 or 1, got {negate}')
-    if not _distinct_positions(controls, n):
-        raise ValueError(f'{what}: controls {controls} must be distinct positions in [0, {n})')
-    if any(((xmask | zmask) >> c) & 1 for c in controls):
-        raise ValueError(f'{what}: controls {controls} must be disjoint from xmask | zmask ({xmask | zmask:#x}): fold fixed '
-                         'bits into negate')
     return n, xmask, amask, zmask, negate, controls
 
 
@@ -1342,8 +1362,7 @@ def apply_excite_axpby(state: torch.Tensor, spec, a, c, mode: str = 'gate', out:
             return out
 
         return _diag_double(double)
-    coef = torch.view_as_real(torch.stack([a, c], dim=1)).reshape(-1, 4).contiguous()
-    return _excite_launch(state, out, coef, _lib.EXCITE_GATE if mode == 'gate' else _lib.EXCITE_MAP,
+    return _excite_launch(state, out, _axpby_coef(a, c), _lib.EXCITE_GATE if mode == 'gate' else _lib.EXCITE_MAP,
                           (xmask, amask, zmask, negate), n, controls)
 
 
@@ -1358,10 +1377,7 @@ def apply_excite_rot(state: torch.Tensor, spec, theta: torch.Tensor, out: torch.
     """exp(theta K) state = (I + sin(theta) K + (1 - cos(theta)) K^2) state: :func:`apply_excite_axpby` in 'gate' mode with
     a = cos(theta), c = sin(theta), formed in double from the real ``theta`` (B,), per sample.  ``out=state`` is the
     sparse in-place gate; see :func:`apply_excite_axpby` for what any other ``out`` costs."""
-    if theta.is_complex() or theta.shape != (state.shape[0],):
-        raise ValueError(f'apply_excite_rot: one real angle per sample, ({state.shape[0]},), expected; got '
-                         f'{theta.dtype} {tuple(theta.shape)}')
-    theta = theta.to(device=state.device, dtype=torch.float64)
+    theta = _real_angles(theta, state, 'apply_excite_rot')
     return apply_excite_axpby(state, spec, torch.cos(theta), torch.sin(theta), 'gate', out)
 
 
@@ -1370,10 +1386,7 @@ def excite_cross(bra: torch.Tensor, ket: torch.Tensor, spec) -> torch.Tensor:
     only the pairs (``dq_excite_cross_*``).  ``bra`` and ``ket`` the same buffer: each pair is read once, and the real part
     is 0 up to rounding (K is anti-Hermitian).  The workspace comes from PyTorch's allocator (legal under capture)."""
     n, xmask, amask, zmask, negate, controls = _excite_args(ket, spec, 'excite_cross')
-    if bra.shape != ket.shape or bra.dtype != ket.dtype:
-        raise ValueError('excite_cross: bra/ket must be (batch, 2**n) tensors of one shape and dtype')
-    if not bra.is_contiguous():
-        raise ValueError('excite_cross: bra must be contiguous')
+    _check_bra(bra, ket, 'excite_cross')
     if not _use_hip(ket):
         def double():
             i0, i1, sigma = _excite_pairs(n, xmask, amask, zmask, negate, controls)

@@ -799,6 +799,8 @@ class HamiltonianGate(ArbitraryGate):
     Pauli letters each followed by its wire) or a dense tensor on ``wires`` / ``minmax``
     (reference: gate.py:2867-3024, matrix :2990-2994)."""
 
+    _complex_buffers = ('ham_tsr',)
+
     def __init__(self, hamiltonian, t=None, nqubit=1, wires=None, minmax=None, controls=None, name='HamiltonianGate',
                  den_mat=False, tsr_mode=False, requires_grad=False):
         self.nqubit = nqubit
@@ -813,15 +815,6 @@ class HamiltonianGate(ArbitraryGate):
         self.requires_grad = requires_grad
         self.register_buffer('ham_tsr', self._ham_matrix(hamiltonian))
         self.init_para([None, t])
-
-    def _apply(self, fn: Any, *args, **kwargs):
-        from .utils import complex_apply
-
-        held = {'ham_tsr': self._buffers.pop('ham_tsr')}
-        nn.Module._apply(self, fn, *args, **kwargs)
-        for key, value in complex_apply(fn, held).items():
-            self.register_buffer(key, value)
-        return self
 
     @staticmethod
     def _terms(ham: list) -> list[tuple[float, list[tuple[str, int]]]]:
@@ -913,9 +906,28 @@ class _FlatGate:
 
     _runs_flat = True
 
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        if kwargs.get('den_mat'):
+            self._refuse('den_mat=True (density matrices)')
+
     def _refuse(self, what: str):
         raise NotImplementedError(f'{type(self).__name__}: {what} is not supported (the gate runs as a stand-alone pass over '
                                   'a state vector on one device)')
+
+    @staticmethod
+    def _constant(t: torch.Tensor, name: str, noun: str, plural: bool = False) -> None:
+        """The gate's table carries no gradient: one that asks for it is refused by name."""
+        if t.requires_grad:
+            raise ValueError(f'{name}: {noun} are constants -- gradients with respect to them are not supported; detach() them'
+                             if plural else
+                             f'{name}: {noun} is a constant -- gradients with respect to its entries are not supported; '
+                             'detach() it')
+
+    def _mark_precision(self, device: torch.device) -> None:
+        """For a table that does not tell the circuit's precision -- integers, or angles that may be float64 in a complex64
+        circuit: a marker that follows ``.to()`` / ``.double()`` of the circuit, which ``_state_like`` reads instead."""
+        self.register_buffer('_like', torch.zeros((), device=device), persistent=False)
 
     def prims(self, decompose: bool = True) -> list[Prim]:
         self._refuse('a matrix primitive -- fused passes, DistributedQubitCircuit (sharded states) --')
@@ -937,8 +949,10 @@ class _FlatGate:
         return self.apply_flat(x.reshape(shape[0], -1)).reshape(shape)
 
     def _state_like(self) -> tuple[torch.dtype, torch.device]:
-        """Complex dtype and device of the states the gate's table belongs to."""
-        t = self._table()
+        """Complex dtype and device of the states the gate's table (or its precision marker) belongs to."""
+        t = getattr(self, '_like', None)
+        if t is None:
+            t = self._table()
         return (t.dtype if t.is_complex() else (torch.complex128 if t.dtype == torch.float64 else torch.complex64)), t.device
 
     def get_unitary(self) -> torch.Tensor:
@@ -954,17 +968,15 @@ class DiagonalGate(_FlatGate, ArbitraryGate):
     of the state for any k up to n (``dq_apply_diag_*``) -- a phase oracle over all wires, where a dense matrix has no
     route beyond 10.  The entries' moduli are checked to the 1e-4 that ``UAnyGate`` applies to its matrix."""
 
+    _complex_buffers = ('diag',)
+
     def __init__(self, diag, nqubit=1, wires=None, minmax=None, controls=None, name='DiagonalGate', den_mat=False,
                  tsr_mode=False):
         super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
                          tsr_mode=tsr_mode)
-        if den_mat:
-            self._refuse('den_mat=True (density matrices)')
         if not isinstance(diag, torch.Tensor):
             diag = torch.tensor(diag, dtype=torch.cfloat)
-        if diag.requires_grad:
-            raise ValueError('DiagonalGate: the table is a constant -- gradients with respect to its entries are not '
-                             'supported; detach() it')
+        self._constant(diag, 'DiagonalGate', 'the table')
         if not diag.is_complex():
             diag = diag.to(torch.cdouble if diag.dtype == torch.float64 else torch.cfloat)
         diag = diag.reshape(-1)
@@ -974,15 +986,6 @@ class DiagonalGate(_FlatGate, ArbitraryGate):
 
     def _table(self) -> torch.Tensor:
         return self.diag
-
-    def _apply(self, fn: Any, *args, **kwargs):
-        from .utils import complex_apply
-
-        held = {'diag': self._buffers.pop('diag')}
-        nn.Module._apply(self, fn, *args, **kwargs)
-        for key, value in complex_apply(fn, held).items():
-            self.register_buffer(key, value)
-        return self
 
     def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
         """(B, 2**n) -> (B, 2**n)."""
@@ -1004,8 +1007,6 @@ class PermutationGate(_FlatGate, ArbitraryGate):
                  tsr_mode=False):
         super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
                          tsr_mode=tsr_mode)
-        if den_mat:
-            self._refuse('den_mat=True (density matrices)')
         k = len(self.wires)
         if k > 31:
             raise ValueError(f'PermutationGate: at most 31 wires, got {k}')
@@ -1029,15 +1030,11 @@ class PermutationGate(_FlatGate, ArbitraryGate):
                              f'{int((inv < 0).nonzero()[0])}')
         self.register_buffer('perm', table.to(torch.int32))
         self.register_buffer('inv', inv.to(torch.int32))
-        # (integer tables have no precision: this marker follows `.to()` / `.double()` of the circuit for `_state_like`)
-        self.register_buffer('_like', torch.zeros((), device=table.device), persistent=False)
+        self._mark_precision(table.device)              # (integer tables have no precision)
 
     def tables(self) -> tuple[torch.Tensor, torch.Tensor]:
         """(perm, perm^-1) of the gate as it stands: ``inverse()`` swaps them."""
         return (self.inv, self.perm) if self.inv_mode else (self.perm, self.inv)
-
-    def _state_like(self) -> tuple[torch.dtype, torch.device]:
-        return (torch.complex128 if self._like.dtype == torch.float64 else torch.complex64), self.perm.device
 
     def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
         """(B, 2**n) -> (B, 2**n)."""
@@ -1067,18 +1064,16 @@ class MultiplexedGate(_FlatGate, ArbitraryGate):
     2^(k+1) multiply-adds per amplitude and has no route beyond 10 wires.  Every block is checked for unitarity to the
     1e-4 that ``UAnyGate`` applies to its matrix.  The table is a constant: it carries no gradient."""
 
+    _complex_buffers = ('unitaries',)
+
     def __init__(self, unitaries, nqubit=1, wires=None, minmax=None, controls=None, name='MultiplexedGate', den_mat=False,
                  tsr_mode=False):
         super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
                          tsr_mode=tsr_mode)
-        if den_mat:
-            self._refuse('den_mat=True (density matrices)')
         k = _mux_wires(self, 'MultiplexedGate')
         if not isinstance(unitaries, torch.Tensor):
             unitaries = torch.tensor(unitaries, dtype=torch.cfloat)
-        if unitaries.requires_grad:
-            raise ValueError('MultiplexedGate: the table is a constant -- gradients with respect to its entries are not '
-                             'supported; detach() it')
+        self._constant(unitaries, 'MultiplexedGate', 'the table')
         if not unitaries.is_complex():
             unitaries = unitaries.to(torch.cdouble if unitaries.dtype == torch.float64 else torch.cfloat)
         if unitaries.shape != (2**k, 2, 2):
@@ -1091,15 +1086,6 @@ class MultiplexedGate(_FlatGate, ArbitraryGate):
 
     def _table(self) -> torch.Tensor:
         return self.unitaries
-
-    def _apply(self, fn: Any, *args, **kwargs):
-        from .utils import complex_apply
-
-        held = {'unitaries': self._buffers.pop('unitaries')}
-        nn.Module._apply(self, fn, *args, **kwargs)
-        for key, value in complex_apply(fn, held).items():
-            self.register_buffer(key, value)
-        return self
 
     def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
         """(B, 2**n) -> (B, 2**n)."""
@@ -1128,27 +1114,19 @@ class MultiplexedRotation(_FlatGate, ArbitraryGate):
                  den_mat=False, tsr_mode=False):
         super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
                          tsr_mode=tsr_mode)
-        if den_mat:
-            self._refuse('den_mat=True (density matrices)')
         k = _mux_wires(self, 'MultiplexedRotation')
         if axis not in ('x', 'y', 'z'):
             raise ValueError(f"MultiplexedRotation: axis must be 'x', 'y' or 'z', got {axis!r}")
         self.axis = axis
         angles = _as_param_tensor(angles)
-        if angles.requires_grad:
-            raise ValueError('MultiplexedRotation: the angles are constants -- gradients with respect to them are not '
-                             'supported; detach() them')
+        self._constant(angles, 'MultiplexedRotation', 'the angles', plural=True)
         if angles.is_complex() or not angles.is_floating_point():
             angles = angles.real.to(torch.float) if angles.is_complex() else angles.to(torch.float)
         angles = angles.detach().reshape(-1)
         if angles.shape[0] != 2**k:
             raise ValueError(f'MultiplexedRotation: {k} select wires take {2**k} angles, got {angles.shape[0]}')
         self.register_buffer('angles', angles.contiguous())
-        # (the angles may be float64 in a complex64 circuit: this marker follows `.to()` / `.double()` for `_state_like`)
-        self.register_buffer('_like', torch.zeros((), device=angles.device), persistent=False)
-
-    def _state_like(self) -> tuple[torch.dtype, torch.device]:
-        return (torch.complex128 if self._like.dtype == torch.float64 else torch.complex64), self.angles.device
+        self._mark_precision(angles.device)             # (the angles may be float64 in a complex64 circuit)
 
     def table(self, dtype: torch.dtype) -> torch.Tensor:
         """The table of the gate as it stands for states of complex ``dtype``: 'y' (2^k, 2) real rows (c, s), 'x' complex
@@ -1190,76 +1168,9 @@ class MultiplexedRotation(_FlatGate, ArbitraryGate):
         return s if self.controls == [] else s + f', controls={self.controls}'
 
 
-class CostPhase(_FlatGate, ArbitraryGate):
-    """``exp(-i t diag(cost))`` with one parameter ``t`` and a classical cost table of 2^k real entries over ``wires`` /
-    ``minmax`` (``wires[0]`` the most significant bit of the entry index): a whole QAOA cost layer -- any cost, not only a
-    short Ising polynomial -- in one read and one write of the state (``dq_apply_cost_*``).  ``t`` is trainable
-    (``requires_grad=True``), fixed (``inputs``), or fed from the circuit's data (``encode=True``; a batch of data gives one
-    ``t`` per sample).  The table is a constant: it carries no gradient.  The kernels read it in the state's real
-    precision, so keep it in that precision (``.to()`` of the circuit converts it along) to spare a conversion per
-    forward."""
-
-    _param_names = ('t',)
-
-    def __init__(self, cost, nqubit=1, wires=None, minmax=None, inputs=None, controls=None, name='CostPhase',
-                 den_mat=False, tsr_mode=False, requires_grad=False):
-        super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
-                         tsr_mode=tsr_mode)
-        if den_mat:
-            self._refuse('den_mat=True (density matrices)')
-        if not isinstance(cost, torch.Tensor):
-            cost = torch.tensor(cost, dtype=torch.float)
-        if cost.requires_grad:
-            raise ValueError('CostPhase: the cost table is a constant -- gradients with respect to its entries are not '
-                             'supported; detach() it')
-        if cost.is_complex() or not cost.is_floating_point():
-            raise ValueError(f'CostPhase: the cost table must be real floating point, got {cost.dtype}')
-        cost = cost.reshape(-1)
-        assert cost.shape[0] == 2 ** len(self.wires), f'a cost on {len(self.wires)} wires has {2 ** len(self.wires)} entries'
-        self.register_buffer('cost', cost)
-        self.npara = 1
-        self.requires_grad = requires_grad
-        self.init_para(inputs)
-
-    def _table(self) -> torch.Tensor:
-        return self.cost
-
-    def inputs_to_tensor(self, inputs: Any = None) -> torch.Tensor:
-        while isinstance(inputs, list):
-            inputs = inputs[0]
-        if inputs is None:
-            return torch.rand(())
-        return _as_param_tensor(inputs)
-
-    def init_para(self, inputs: Any = None) -> None:
-        t = self.inputs_to_tensor(inputs)
-        if t.device != self.cost.device and not isinstance(t, nn.Parameter):
-            t = t.to(self.cost.device)
-        if self.requires_grad:
-            self.t = nn.Parameter(t)
-        else:
-            self.register_buffer('t', t)
-
-    def inverse(self) -> 'CostPhase':
-        return ArbitraryGate.inverse(self)          # (the copy shares t; `inv_mode` negates it where it is used)
-
-    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
-        """(B, 2**n) -> (B, 2**n)."""
-        from . import ops
-
-        t = -self.t if self.inv_mode else self.t
-        return ops.cost_phase(x, self.cost, t, self._bits(self.wires), self._bits(self.controls))
-
-    def extra_repr(self) -> str:
-        t = -self.t if self.inv_mode else self.t
-        val = t.item() if t.numel() == 1 else f'<batch of {t.numel()}>'
-        s = f'wires={self.wires}, t={val}'
-        return s if self.controls == [] else s + f', controls={self.controls}'
-
-
 class _OneAngle:
-    """One real parameter, trainable, fixed or encoded, of a gate that has no table: ``_state_like`` comes from the
-    parameter's device and precision (``.to()`` of the circuit converts it along)."""
+    """One real parameter, trainable, fixed or encoded, of a flat gate.  Where the gate has no table, ``_state_like`` comes
+    from the parameter's device and precision (``.to()`` of the circuit converts it along)."""
 
     def _one_angle(self, inputs: Any, requires_grad: bool) -> None:
         self.npara = 1
@@ -1304,6 +1215,54 @@ class _OneAngle:
         return s if self.controls == [] else s + f', controls={self.controls}'
 
 
+class CostPhase(_OneAngle, _FlatGate, ArbitraryGate):
+    """``exp(-i t diag(cost))`` with one parameter ``t`` and a classical cost table of 2^k real entries over ``wires`` /
+    ``minmax`` (``wires[0]`` the most significant bit of the entry index): a whole QAOA cost layer -- any cost, not only a
+    short Ising polynomial -- in one read and one write of the state (``dq_apply_cost_*``).  ``t`` is trainable
+    (``requires_grad=True``), fixed (``inputs``), or fed from the circuit's data (``encode=True``; a batch of data gives one
+    ``t`` per sample).  The table is a constant: it carries no gradient.  The kernels read it in the state's real
+    precision, so keep it in that precision (``.to()`` of the circuit converts it along) to spare a conversion per
+    forward."""
+
+    _param_names = ('t',)
+
+    def __init__(self, cost, nqubit=1, wires=None, minmax=None, inputs=None, controls=None, name='CostPhase',
+                 den_mat=False, tsr_mode=False, requires_grad=False):
+        super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
+                         tsr_mode=tsr_mode)
+        if not isinstance(cost, torch.Tensor):
+            cost = torch.tensor(cost, dtype=torch.float)
+        self._constant(cost, 'CostPhase', 'the cost table')
+        if cost.is_complex() or not cost.is_floating_point():
+            raise ValueError(f'CostPhase: the cost table must be real floating point, got {cost.dtype}')
+        cost = cost.reshape(-1)
+        assert cost.shape[0] == 2 ** len(self.wires), f'a cost on {len(self.wires)} wires has {2 ** len(self.wires)} entries'
+        self.register_buffer('cost', cost)
+        self._one_angle(inputs, requires_grad)
+
+    def _table(self) -> torch.Tensor:
+        return self.cost
+
+    _state_like = _FlatGate._state_like             # (the table tells the precision, not the parameter ...)
+
+    def init_para(self, inputs: Any = None) -> None:
+        # (... which, unlike `_OneAngle`'s, takes the precision of the values it is given: float64 data in a complex64
+        # circuit stay float64)
+        t = self.inputs_to_tensor(inputs)
+        if t.device != self.cost.device and not isinstance(t, nn.Parameter):
+            t = t.to(self.cost.device)
+        if self.requires_grad:
+            self.t = nn.Parameter(t)
+        else:
+            self.register_buffer('t', t)
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        return ops.cost_phase(x, self.cost, self._angle(), self._bits(self.wires), self._bits(self.controls))
+
+
 def _pauli_letters(pauli: str, what: str) -> str:
     if not isinstance(pauli, str) or any(ch not in 'xyzi' for ch in pauli.lower()):
         raise ValueError(f'{what}: a Pauli string is written with the letters x, y, z, i; got {pauli!r}')
@@ -1346,8 +1305,6 @@ class PauliRot(_OneAngle, _FlatGate, ArbitraryGate):
         self.pauli = ''.join(ch for ch in letters if ch != 'i')
         super().__init__(name=name, nqubit=nqubit, wires=[w for ch, w in zip(letters, wires) if ch != 'i'], controls=controls,
                          den_mat=den_mat, tsr_mode=tsr_mode)
-        if den_mat:
-            self._refuse('den_mat=True (density matrices)')
         self._one_angle(inputs, requires_grad)
 
     def masks(self) -> tuple[int, int]:
@@ -1394,8 +1351,6 @@ class PauliEvolution(_OneAngle, _FlatGate, ArbitraryGate):
         self.steps, self.order = steps, order
         super().__init__(name=name, nqubit=nqubit, wires=sorted({w for _, _, ws in self.terms for w in ws}), den_mat=den_mat,
                          tsr_mode=tsr_mode)
-        if den_mat:
-            self._refuse('den_mat=True (density matrices)')
         self._one_angle([t], requires_grad)
 
     def slice_sequence(self) -> list[tuple[int, float]]:
@@ -1490,8 +1445,6 @@ class ExcitationGate(_OneAngle, _FlatGate, ArbitraryGate):
         self.create, self.annihilate, self.fermionic = create, annihilate, bool(fermionic)
         super().__init__(name=name, nqubit=nqubit, wires=create + annihilate, controls=controls, den_mat=den_mat,
                          tsr_mode=tsr_mode)
-        if den_mat:
-            self._refuse('den_mat=True (density matrices)')
         self._one_angle(inputs, requires_grad)
 
     def masks(self) -> tuple[int, int, int, int]:

@@ -159,13 +159,14 @@ class Gate(Operation):
         self.nodes = self.wires
         self.nancilla = 1
 
+    #: complex buffers of the class besides ``matrix`` (a table, a Hamiltonian) that ``.to()`` must keep complex
+    _complex_buffers: tuple = ()
+
     def _apply(self, fn: Any, *args, **kwargs) -> 'Gate':
-        # .to(torch.double) must promote the complex64 matrix buffer to complex128 (utils.complex_apply)
-        if self.npara > 0:
-            return super()._apply(fn, *args, **kwargs)
-        held = {}
-        if 'matrix' in self._buffers and self._buffers['matrix'] is not None:
-            held['matrix'] = self._buffers.pop('matrix')
+        # .to(torch.double) must promote a complex64 buffer to complex128 (utils.complex_apply): the class's own complex
+        # buffers, and the matrix of a gate without parameters (a parametric gate forms its matrix again from its angle)
+        names = self._complex_buffers + (('matrix',) if self.npara == 0 else ())
+        held = {key: self._buffers.pop(key) for key in names if self._buffers.get(key) is not None}
         super()._apply(fn, *args, **kwargs)
         for key, value in complex_apply(fn, held).items():
             self.register_buffer(key, value)

@@ -14,7 +14,8 @@ gets from stock autograd (examples/benchmarks/gradient_benchmark.py:147-163) -- 
 
 from __future__ import annotations
 
-from typing import Sequence
+import dataclasses
+from typing import Callable, Sequence
 
 import torch
 
@@ -91,6 +92,18 @@ def _polar_scale(ref: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
         nd = torch.linalg.vector_norm(d.detach(), dim=-1, keepdim=True)
         ok = (nd > 0) & (nr > 0)
         return torch.where(ok, nr / torch.where(ok, nd, torch.ones_like(nd)), torch.ones_like(nd))
+
+
+def _jvp_two_slots(fn, x0, x1, t0, t1):
+    """The tangent of ``fn(x0, x1)`` for an ``fn`` that is linear (or anti-linear) in each of its two slots: the function
+    itself with one slot replaced by its tangent, ``fn(t0, x1) + fn(x0, t1)``; a tangent that is None is left out."""
+    out = None
+    if t0 is not None:
+        out = fn(t0, x1)
+    if t1 is not None:
+        term = fn(x0, t1)
+        out = term if out is None else out + term
+    return out
 
 
 class _ApplyGate(torch.autograd.Function):
@@ -206,13 +219,7 @@ class _GateGrad(torch.autograd.Function):
     def jvp(ctx, x_t, gy_t, _targets_t, _controls_t):
         _single_forward_level()
         x, gy = ctx.saved_tensors           # G is linear in gy and anti-linear in x
-        out = None
-        if gy_t is not None:
-            out = gate_grad(x, gy_t, ctx.targets, ctx.controls)
-        if x_t is not None:
-            term = gate_grad(x_t, gy, ctx.targets, ctx.controls)
-            out = term if out is None else out + term
-        return out
+        return _jvp_two_slots(lambda u, v: gate_grad(u, v, ctx.targets, ctx.controls), x, gy, x_t, gy_t)
 
     @staticmethod
     def backward(ctx, gg: torch.Tensor):
@@ -448,13 +455,7 @@ class _ScaleZSigns(torch.autograd.Function):
     def jvp(ctx, state_t, _zmasks_t, w_t):
         _single_forward_level()
         state, w = ctx.saved_tensors        # linear in psi and in w
-        out = None
-        if state_t is not None:
-            out = scale_z_signs(state_t, ctx.zmasks, w)
-        if w_t is not None:
-            term = scale_z_signs(state, ctx.zmasks, w_t)
-            out = term if out is None else out + term
-        return out
+        return _jvp_two_slots(lambda s, v: scale_z_signs(s, ctx.zmasks, v), state, w, state_t, w_t)
 
     @staticmethod
     def vmap(info, in_dims, state, zmasks, w):
@@ -549,13 +550,7 @@ class _Rdm1Cross(torch.autograd.Function):
     def jvp(ctx, bra_t, ket_t):
         _single_forward_level()
         bra, ket = ctx.saved_tensors
-        out = None
-        if bra_t is not None:
-            out = rdm1_cross(bra_t, ket)
-        if ket_t is not None:
-            term = rdm1_cross(bra, ket_t)
-            out = term if out is None else out + term
-        return out
+        return _jvp_two_slots(rdm1_cross, bra, ket, bra_t, ket_t)
 
     @staticmethod
     def backward(ctx, g: torch.Tensor):
@@ -596,13 +591,7 @@ class _WireSum(torch.autograd.Function):
     def jvp(ctx, state_t, mats_t):
         _single_forward_level()
         state, mats = ctx.saved_tensors
-        out = None
-        if state_t is not None:
-            out = wire_sum(state_t, mats)
-        if mats_t is not None:
-            term = wire_sum(state, mats_t)
-            out = term if out is None else out + term
-        return out
+        return _jvp_two_slots(wire_sum, state, mats, state_t, mats_t)
 
     @staticmethod
     def backward(ctx, g: torch.Tensor):
@@ -630,20 +619,25 @@ def _no_legacy(*ts: torch.Tensor) -> None:
                            'torch.func.jacrev / hessian')
 
 
+def _flat_arg(x: torch.Tensor) -> torch.Tensor:
+    return x if _is_batched(x) or x.is_contiguous() else x.contiguous()
+
+
+def _cross_pair(bra: torch.Tensor, ket: torch.Tensor, what: str = '') -> tuple[torch.Tensor, torch.Tensor]:
+    """What every public cross reduction does with its two states: no legacy vmap, one dtype (``what``: the function's
+    name in front of the message), both flat -- and a bra that is the ket stays the same tensor (one read of the state)."""
+    _no_legacy(bra, ket)
+    if bra.dtype != ket.dtype:
+        raise ValueError((what and what + ': ') + 'bra and ket must have one dtype')
+    same = bra is ket
+    ket = _flat_arg(ket)
+    return (ket if same else _flat_arg(bra)), ket
+
+
 def rdm1_cross(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
     """Differentiable one-body cross reduction of two (B, 2**n) states, complex128 (B, n, 2, 2), indexed by wire:
     ``rdm1_cross(psi, psi)[b, k].T`` is the reduced density matrix of wire k (pass the same tensor twice: one read)."""
-    _no_legacy(bra, ket)
-    if bra.dtype != ket.dtype:
-        raise ValueError('bra and ket must have one dtype')
-    same = bra is ket
-    if not _is_batched(ket) and not ket.is_contiguous():
-        ket = ket.contiguous()
-    if same:
-        bra = ket
-    elif not _is_batched(bra) and not bra.is_contiguous():
-        bra = bra.contiguous()
-    return _Rdm1Cross.apply(bra, ket)
+    return _Rdm1Cross.apply(*_cross_pair(bra, ket))
 
 
 def wire_sum(state: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
@@ -754,13 +748,7 @@ class _CostCross(torch.autograd.Function):
     def jvp(ctx, bra_t, ket_t, _cost_t, _bits_t, _controls_t):
         _single_forward_level()
         bra, ket, cost = ctx.saved_tensors
-        out = None
-        if bra_t is not None:
-            out = cost_cross(bra_t, ket, cost, ctx.bits, ctx.controls)
-        if ket_t is not None:
-            term = cost_cross(bra, ket_t, cost, ctx.bits, ctx.controls)
-            out = term if out is None else out + term
-        return out
+        return _jvp_two_slots(lambda u, v: cost_cross(u, v, cost, ctx.bits, ctx.controls), bra, ket, bra_t, ket_t)
 
     @staticmethod
     def backward(ctx, gz: torch.Tensor):
@@ -793,13 +781,7 @@ class _CostScale(torch.autograd.Function):
     def jvp(ctx, state_t, _cost_t, s_t, _bits_t, _controls_t):
         _single_forward_level()
         state, cost, s = ctx.saved_tensors
-        out = None
-        if state_t is not None:
-            out = cost_scale(state_t, cost, s, ctx.bits, ctx.controls)
-        if s_t is not None:
-            term = cost_scale(state, cost, s_t, ctx.bits, ctx.controls)
-            out = term if out is None else out + term
-        return out
+        return _jvp_two_slots(lambda x, v: cost_scale(x, cost, v, ctx.bits, ctx.controls), state, s, state_t, s_t)
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
@@ -848,10 +830,6 @@ class _DiagMul(torch.autograd.Function):
         return _vmap_states(_DiagMul, 'diag_mul', info, in_dims, (state, diag, bits, controls), tables=(1,))
 
 
-def _flat_arg(x: torch.Tensor) -> torch.Tensor:
-    return x if _is_batched(x) or x.is_contiguous() else x.contiguous()
-
-
 def _bit_args(bits: Sequence[int], controls: Sequence[int]) -> tuple[tuple, tuple]:
     return tuple(int(b) for b in bits), tuple(int(c) for c in controls)
 
@@ -872,14 +850,9 @@ def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: S
                controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable ``sum_i cost[sub(i)] conj(bra_i) ket_i`` of two (B, 2**n) states: complex128 (B,).  Pass the same
     tensor twice for ``<C>`` (one read of the state; the imaginary part is exactly 0)."""
-    _no_legacy(bra, ket)
+    bra, ket = _cross_pair(bra, ket, 'cost_cross')
     cost = _const_table(cost, 'cost_cross')
-    if bra.dtype != ket.dtype:
-        raise ValueError('cost_cross: bra and ket must have one dtype')
     bits, controls = _bit_args(bits, controls)
-    same = bra is ket
-    ket = _flat_arg(ket)
-    bra = ket if same else _flat_arg(bra)
     return _CostCross.apply(bra, ket, cost, bits, controls)
 
 
@@ -903,25 +876,57 @@ def diag_mul(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], contr
     return _DiagMul.apply(_flat_arg(state), diag, bits, controls)
 
 
-# ---- Pauli strings on any number of wires (csrc/dq_pauli.hip) -----------------------------------------------------------
-# P = (xmask, zmask) over index bits, a Y in both, Hermitian; (P x)[i] = i^ny (-1)^popc((i ^ xmask) & zmask) x[i ^ xmask].
-# Two operations closed under differentiation -- every backward and every jvp below is written with them -- so derivatives
-# of any order exist by construction, and the rotation as a node of its own on top of them:
-#     axpby(x; a, c)[i] = a x[i] + c (P x)[i]             (outside the controls: x[i] in 'gate' mode, 0 in 'map' mode)
-#     cross(u, v)       = sum_i conj(u[i]) (P v)[i]       (outside the controls: left out)
-#     rot(x; theta)     = axpby(x; cos(theta/2), -i sin(theta/2)) in 'gate' mode = exp(-i theta/2 P) x
-class _PauliAxpby(torch.autograd.Function):
-    """y = a x + c P x with a, c complex128 (B,): cotangents gx = axpby(gy; conj a, conj c) in the same mode,
-    ga = cross_I(x, gy), gc = cross_P(x, gy).  A tangent in a or c moves the controlled amplitudes only: a 'map' term."""
+# ---- a generator on its support: Pauli strings (csrc/dq_pauli.hip) and excitations (csrc/dq_excite.hip) -----------------
+# A family is a linear map G that acts on a support S of the index space -- the amplitudes inside the controls, or the
+# pairs of an excitation -- and is 0 elsewhere, with G^dagger = s G, s = +1 or -1.  A spec names one G of the family.  Two
+# operations closed under differentiation -- every backward and every jvp below is written with them -- so derivatives of
+# any order exist by construction, and the rotation as a node of its own on top of them:
+#     axpby(x; a, c)[i] = a x[i] + c (G x)[i] on S        (elsewhere: x[i] in 'gate' mode, 0 in 'map' mode)
+#     cross(u, v)       = sum_i conj(u[i]) (G v)[i]       (which is a sum over S)
+#     rot(x; theta)     = exp(r theta G) x = axpby(x; alpha(theta), beta(theta)) in 'gate' mode, theta real
+# The rules, for a, c, the cotangent gz of cross complex128 (B,) and theta real (B,):
+#     axpby:  gx = axpby(gy; conj a, s conj c) in the same mode;  gc = <G x, gy> = s cross(x, gy);  ga = the inner product
+#             <x, gy> over S, which the family says how to get (`inner`).  A tangent in a or c moves S only: a 'map' term.
+#     cross:  anti-linear in u, linear in v:  g_u = map(v; 0, conj gz),  g_v = G^dagger u gz = map(u; 0, s gz).
+#     rot:    y = U x with U^dagger = rot(-theta):  gx = rot(gy; -theta);  dy/dtheta = r G y on S and 0 elsewhere -- a 'map'
+#             term of y -- so gtheta = Re(conj(r) cross(gy, y)).  U is a function of G and commutes with it, so
+#             cross(gy, U x) = cross(U^dagger gy, x) = cross(gx, x): the cross takes the two tensors the backward holds
+#             already and y is not formed again -- one rotation and one cross per backward.
+# A family supplies, besides its name and its three backend functions, the four facts the rules leave open: s, `inner`,
+# r (`rate`, applied to the angle's tangent) and the read-out of gtheta (`gtheta`, in the family's own arithmetic).
+@dataclasses.dataclass(frozen=True, eq=False)
+class _Generator:
+    """What differs between the families.  The nodes take it as a non-tensor argument with the hashable spec, as ONE pair
+    ``gen = (family, spec)``: every positional argument of an ``autograd.Function`` costs about two microseconds per call
+    (its signature is bound anew each time), and a rotation forward plus backward is three such calls."""
+
+    name: str           # 'pauli' / 'excite': '<name>_axpby', '<name>_cross', '<name>_rot' in error and vmap messages
+    sign: int           # s: G^dagger = s G
+    axpby: str          # the names of the three functions of `backend`, looked up there at call time (tests wrap them)
+    cross: str
+    rot: str
+    spread: Callable    # spec -> (leading, trailing): backend.f(<states>, *leading, <parameters>, *trailing[, mode])
+    inner: Callable     # (gen, x, gy, like) -> <x, gy> over the support, complex128 (B,), like ``like``
+    rate: Callable      # theta_t -> r theta_t, complex128
+    gtheta: Callable    # cross(gx, x) -> gtheta, real
+
+    def adjoint(self, t: torch.Tensor) -> torch.Tensor:
+        """s t"""
+        return t if self.sign > 0 else -t
+
+
+class _GenAxpby(torch.autograd.Function):
+    """y = a x + c G x with a, c complex128 (B,): see the rules above."""
 
     @staticmethod
-    def forward(state: torch.Tensor, a: torch.Tensor, c: torch.Tensor, xmask: int, zmask: int, controls: tuple,
-                mode: str) -> torch.Tensor:
-        return backend.apply_pauli_axpby(_plain(state), xmask, zmask, _plain(a), _plain(c), controls, mode)
+    def forward(state: torch.Tensor, a: torch.Tensor, c: torch.Tensor, gen: tuple, mode: str) -> torch.Tensor:
+        fam, spec = gen
+        leading, trailing = fam.spread(spec)
+        return getattr(backend, fam.axpby)(_plain(state), *leading, _plain(a), _plain(c), *trailing, mode)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        state, a, c, ctx.xmask, ctx.zmask, ctx.controls, ctx.mode = inputs
+        state, a, c, ctx.gen, ctx.mode = inputs
         ctx.save_for_backward(state, a, c)
         ctx.save_for_forward(state, a, c)
 
@@ -931,43 +936,45 @@ class _PauliAxpby(torch.autograd.Function):
         state, a, c = ctx.saved_tensors
         out = None
         if state_t is not None:
-            out = pauli_axpby(state_t, ctx.xmask, ctx.zmask, a, c, ctx.controls, ctx.mode)
+            out = _gen_axpby(ctx.gen, state_t, a, c, ctx.mode)
         if a_t is not None or c_t is not None:
             zero = torch.zeros_like(a)
-            term = pauli_axpby(state, ctx.xmask, ctx.zmask, zero if a_t is None else a_t, zero if c_t is None else c_t,
-                               ctx.controls, 'map')
+            term = _gen_axpby(ctx.gen, state, zero if a_t is None else a_t, zero if c_t is None else c_t, 'map')
             out = term if out is None else out + term
         return out
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
+        gen = ctx.gen
+        fam = gen[0]
         state, a, c = ctx.saved_tensors
         gstate = ga = gc = None
         if ctx.needs_input_grad[0]:
-            gstate = pauli_axpby(gy, ctx.xmask, ctx.zmask, a.conj(), c.conj(), ctx.controls, ctx.mode)
+            gstate = _gen_axpby(gen, gy, a.conj(), fam.adjoint(c.conj()), ctx.mode)
         if ctx.needs_input_grad[1]:
-            ga = pauli_cross(state, gy, 0, 0, ctx.controls).to(a.dtype)
+            ga = fam.inner(gen, state, gy, a).to(a.dtype)
         if ctx.needs_input_grad[2]:
-            gc = pauli_cross(state, gy, ctx.xmask, ctx.zmask, ctx.controls).to(c.dtype)
-        return gstate, ga, gc, None, None, None, None
+            gc = fam.adjoint(_gen_cross(gen, state, gy)).to(c.dtype)
+        return gstate, ga, gc, None, None
 
     @staticmethod
-    def vmap(info, in_dims, state, a, c, xmask, zmask, controls, mode):
-        return _vmap_states(_PauliAxpby, 'pauli_axpby', info, in_dims, (state, a, c, xmask, zmask, controls, mode), folded=(1, 2))
+    def vmap(info, in_dims, state, a, c, gen, mode):
+        return _vmap_states(_GenAxpby, gen[0].name + '_axpby', info, in_dims, (state, a, c, gen, mode), folded=(1, 2))
 
 
-class _PauliCross(torch.autograd.Function):
-    """z = sum_i conj(u_i) (P v)_i, complex128 (B,): anti-linear in u, linear in v; cotangents g_v = map(u; 0, gz) and
-    g_u = map(v; 0, conj(gz))."""
+class _GenCross(torch.autograd.Function):
+    """z = sum_i conj(u_i) (G v)_i, complex128 (B,): see the rules above."""
 
     @staticmethod
-    def forward(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, controls: tuple) -> torch.Tensor:
+    def forward(bra: torch.Tensor, ket: torch.Tensor, gen: tuple) -> torch.Tensor:
+        fam, spec = gen
         pk = _plain(ket)
-        return backend.pauli_cross(pk if bra is ket else _plain(bra), pk, xmask, zmask, controls)
+        leading, trailing = fam.spread(spec)
+        return getattr(backend, fam.cross)(pk if bra is ket else _plain(bra), pk, *leading, *trailing)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        bra, ket, ctx.xmask, ctx.zmask, ctx.controls = inputs
+        bra, ket, ctx.gen = inputs
         ctx.save_for_backward(bra, ket)
         ctx.save_for_forward(bra, ket)
 
@@ -975,83 +982,131 @@ class _PauliCross(torch.autograd.Function):
     def jvp(ctx, bra_t, ket_t, *_):
         _single_forward_level()
         bra, ket = ctx.saved_tensors
-        out = None
-        if bra_t is not None:
-            out = pauli_cross(bra_t, ket, ctx.xmask, ctx.zmask, ctx.controls)
-        if ket_t is not None:
-            term = pauli_cross(bra, ket_t, ctx.xmask, ctx.zmask, ctx.controls)
-            out = term if out is None else out + term
-        return out
+        return _jvp_two_slots(lambda u, v: _gen_cross(ctx.gen, u, v), bra, ket, bra_t, ket_t)
 
     @staticmethod
     def backward(ctx, gz: torch.Tensor):
+        gen = ctx.gen
         bra, ket = ctx.saved_tensors
         gz = gz.to(torch.complex128)
         zero = torch.zeros_like(gz)
         gbra = gket = None
         if ctx.needs_input_grad[0]:
-            gbra = pauli_axpby(ket, ctx.xmask, ctx.zmask, zero, gz.conj(), ctx.controls, 'map')
+            gbra = _gen_axpby(gen, ket, zero, gz.conj(), 'map')
         if ctx.needs_input_grad[1]:
-            gket = pauli_axpby(bra, ctx.xmask, ctx.zmask, zero, gz, ctx.controls, 'map')
-        return gbra, gket, None, None, None
+            gket = _gen_axpby(gen, bra, zero, gen[0].adjoint(gz), 'map')
+        return gbra, gket, None
 
     @staticmethod
-    def vmap(info, in_dims, bra, ket, xmask, zmask, controls):
-        return _vmap_cross(_PauliCross, 'pauli_cross', info, in_dims, (bra, ket, xmask, zmask, controls))
+    def vmap(info, in_dims, bra, ket, gen):
+        return _vmap_cross(_GenCross, gen[0].name + '_cross', info, in_dims, (bra, ket, gen))
 
 
-class _PauliRot(torch.autograd.Function):
-    """y = U x, U = exp(-i theta/2 P), theta real (B,): cotangents gx = rot(gy, -theta) = U^dagger gy and gtheta =
-    1/2 Im cross_P(gy, y) (dy/dtheta = -(i/2) P y on the controlled amplitudes, 0 elsewhere -- which cross leaves out).  U
-    commutes with P, so cross_P(gy, U x) = cross_P(U^dagger gy, x) = cross_P(gx, x): the cross takes the two tensors the
-    backward holds already and y is not formed again -- one axpby and one cross per backward."""
+class _GenRot(torch.autograd.Function):
+    """y = exp(r theta G) x, theta real (B,): see the rules above -- one rotation and one cross per backward."""
 
     @staticmethod
-    def forward(state: torch.Tensor, theta: torch.Tensor, xmask: int, zmask: int, controls: tuple) -> torch.Tensor:
-        return backend.apply_pauli_rot(_plain(state), xmask, zmask, _plain(theta), controls)
+    def forward(state: torch.Tensor, theta: torch.Tensor, gen: tuple) -> torch.Tensor:
+        fam, spec = gen
+        leading, trailing = fam.spread(spec)
+        return getattr(backend, fam.rot)(_plain(state), *leading, _plain(theta), *trailing)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        state, theta, ctx.xmask, ctx.zmask, ctx.controls = inputs
+        state, theta, ctx.gen = inputs
         ctx.save_for_backward(state, theta)
         ctx.save_for_forward(state, theta)
 
     @staticmethod
     def jvp(ctx, state_t, theta_t, *_):
         _single_forward_level()
+        gen = ctx.gen
         state, theta = ctx.saved_tensors
         out = None
         if state_t is not None:
-            out = pauli_rot(state_t, ctx.xmask, ctx.zmask, theta, ctx.controls)
+            out = _gen_rot(gen, state_t, theta)
         if theta_t is not None:
-            y = pauli_rot(state, ctx.xmask, ctx.zmask, theta, ctx.controls)
-            half = -0.5j * theta_t.to(torch.complex128)
-            term = pauli_axpby(y, ctx.xmask, ctx.zmask, torch.zeros_like(half), half, ctx.controls, 'map')
+            y = _gen_rot(gen, state, theta)
+            rate = gen[0].rate(theta_t)
+            term = _gen_axpby(gen, y, torch.zeros_like(rate), rate, 'map')
             out = term if out is None else out + term
         return out
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
+        gen = ctx.gen
         state, theta = ctx.saved_tensors
-        gstate = pauli_rot(gy, ctx.xmask, ctx.zmask, -theta, ctx.controls)
+        gstate = _gen_rot(gen, gy, -theta)
         gtheta = None
         if ctx.needs_input_grad[1]:
-            gtheta = (0.5 * pauli_cross(gstate, state, ctx.xmask, ctx.zmask, ctx.controls).imag).to(theta.dtype)
-        return (gstate if ctx.needs_input_grad[0] else None), gtheta, None, None, None
+            gtheta = gen[0].gtheta(_gen_cross(gen, gstate, state)).to(theta.dtype)
+        return (gstate if ctx.needs_input_grad[0] else None), gtheta, None
 
     @staticmethod
-    def vmap(info, in_dims, state, theta, xmask, zmask, controls):
-        return _vmap_states(_PauliRot, 'pauli_rot', info, in_dims, (state, theta, xmask, zmask, controls), folded=(1,))
+    def vmap(info, in_dims, state, theta, gen):
+        return _vmap_states(_GenRot, gen[0].name + '_rot', info, in_dims, (state, theta, gen), folded=(1,))
+
+
+def _sample_param(p, state: torch.Tensor, dtype: torch.dtype, what: str) -> torch.Tensor:
+    if not isinstance(p, torch.Tensor):
+        p = torch.as_tensor(p, device=state.device)
+    return _per_sample(p, state.shape[-2], dtype, what)
+
+
+# (the three operations of a generator ``gen = (family, spec)``, the spec in the form the nodes keep: what the public
+# functions below and the rules above call)
+def _gen_axpby(gen: tuple, state: torch.Tensor, a, c, mode: str) -> torch.Tensor:
+    what = gen[0].name + '_axpby'
+    _no_legacy(state)
+    if mode not in ('gate', 'map'):
+        raise ValueError(f"{what}: mode must be 'gate' or 'map', got {mode!r}")
+    a = _sample_param(a, state, torch.complex128, what)
+    c = _sample_param(c, state, torch.complex128, what)
+    return _GenAxpby.apply(_flat_arg(state), a, c, gen, mode)
+
+
+def _gen_cross(gen: tuple, bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    return _GenCross.apply(*_cross_pair(bra, ket, gen[0].name + '_cross'), gen)
+
+
+def _gen_rot(gen: tuple, state: torch.Tensor, theta) -> torch.Tensor:
+    _no_legacy(state)
+    theta = _sample_param(theta, state, torch.float64, gen[0].name + '_rot')
+    return _GenRot.apply(_flat_arg(state), theta, gen)
+
+
+# Pauli strings: P = (xmask, zmask) over index bits, a Y in both, (P x)[i] = i^ny (-1)^popc((i ^ xmask) & zmask) x[i ^ xmask];
+# the support is the amplitudes inside the controls, and the spec is (xmask, zmask, controls).  P is Hermitian, the inner
+# product over the controls is the cross of the empty string, and rot = exp(-i theta/2 P) = axpby(cos(theta/2),
+# -i sin(theta/2)): r = -i/2, gtheta = 1/2 Im cross.
+_PAULI_STRINGS = _Generator(
+    name='pauli', sign=+1, axpby='apply_pauli_axpby', cross='pauli_cross', rot='apply_pauli_rot',
+    spread=lambda spec: (spec[:2], spec[2:]),
+    inner=lambda gen, x, gy, like: _gen_cross((gen[0], (0, 0, gen[1][2])), x, gy),
+    rate=lambda theta_t: -0.5j * theta_t.to(torch.complex128),
+    gtheta=lambda z: 0.5 * z.imag,
+)
+
+
+def _excite_inner(gen: tuple, x: torch.Tensor, gy: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    kgy = _gen_axpby(gen, gy, torch.zeros_like(like), torch.ones_like(like), 'map')
+    return -_gen_cross(gen, x, kgy)
+
+
+# Excitations: K = E - E^dagger over the pairs of a spec (xmask, amask, zmask, negate, controls), real and anti-symmetric;
+# the support is the pairs.  K^3 = -K, so -K^2 projects onto the pairs and the inner product over them is -cross(x, K gy),
+# one 'map' axpby more; rot = exp(theta K) = axpby(cos(theta), sin(theta)): r = 1, gtheta = Re cross.
+_EXCITATIONS = _Generator(
+    name='excite', sign=-1, axpby='apply_excite_axpby', cross='excite_cross', rot='apply_excite_rot',
+    spread=lambda spec: ((spec,), ()),
+    inner=_excite_inner,
+    rate=lambda theta_t: theta_t.to(torch.complex128),
+    gtheta=lambda z: z.real,
+)
 
 
 def _pauli_masks(xmask: int, zmask: int, controls: Sequence[int]) -> tuple[int, int, tuple]:
     return int(xmask), int(zmask), tuple(int(c) for c in controls)
-
-
-def _pauli_param(p, state: torch.Tensor, dtype: torch.dtype, what: str) -> torch.Tensor:
-    if not isinstance(p, torch.Tensor):
-        p = torch.as_tensor(p, device=state.device)
-    return _per_sample(p, state.shape[-2], dtype, what)
 
 
 def pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, controls: Sequence[int] = (),
@@ -1060,176 +1115,20 @@ def pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, controls: Seq
     sets its bit in both); ``a``, ``c`` complex, one value or one per sample.  Amplitudes outside the controls pass
     through (``mode='gate'``) or come out as 0 (``mode='map'``, the cotangent of :func:`pauli_cross`).  One read and one
     write of the state whatever the weight of P."""
-    _no_legacy(state)
-    if mode not in ('gate', 'map'):
-        raise ValueError(f"pauli_axpby: mode must be 'gate' or 'map', got {mode!r}")
-    xmask, zmask, controls = _pauli_masks(xmask, zmask, controls)
-    a = _pauli_param(a, state, torch.complex128, 'pauli_axpby')
-    c = _pauli_param(c, state, torch.complex128, 'pauli_axpby')
-    return _PauliAxpby.apply(_flat_arg(state), a, c, xmask, zmask, controls, mode)
+    return _gen_axpby((_PAULI_STRINGS, _pauli_masks(xmask, zmask, controls)), state, a, c, mode)
 
 
 def pauli_cross(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable ``sum_i conj(bra_i) (P ket)_i`` of two (B, 2**n) states over the amplitudes inside the controls:
     complex128 (B,).  Pass the same tensor twice for ``<P>`` (one read of the state); ``xmask = zmask = 0`` is the
     inner product."""
-    _no_legacy(bra, ket)
-    if bra.dtype != ket.dtype:
-        raise ValueError('pauli_cross: bra and ket must have one dtype')
-    xmask, zmask, controls = _pauli_masks(xmask, zmask, controls)
-    same = bra is ket
-    ket = _flat_arg(ket)
-    bra = ket if same else _flat_arg(bra)
-    return _PauliCross.apply(bra, ket, xmask, zmask, controls)
+    return _gen_cross((_PAULI_STRINGS, _pauli_masks(xmask, zmask, controls)), bra, ket)
 
 
 def pauli_rot(state: torch.Tensor, xmask: int, zmask: int, theta, controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable ``exp(-i theta/2 P)`` on a (B, 2**n) state: ``theta`` real, one value or one per sample; cosine and
     sine of ``theta / 2`` are formed in double for both precisions.  One read and one write of the state."""
-    _no_legacy(state)
-    xmask, zmask, controls = _pauli_masks(xmask, zmask, controls)
-    theta = _pauli_param(theta, state, torch.float64, 'pauli_rot')
-    return _PauliRot.apply(_flat_arg(state), theta, xmask, zmask, controls)
-
-
-# ---- excitation gates that touch only their subspace (csrc/dq_excite.hip) ------------------------------------------------
-# K = E - E^dagger over the pairs of a spec (xmask, amask, zmask, negate, controls): real, anti-symmetric, K^3 = -K, so
-# -K^2 is the projector onto the pairs.  Two operations closed under differentiation, and the rotation as a node of its
-# own on top of them:
-#     axpby(x; a, c)[i] = a x[i] + c (K x)[i] on the pairs   (elsewhere: x[i] in 'gate' mode, 0 in 'map' mode)
-#     cross(u, v)       = sum_i conj(u[i]) (K v)[i]
-#     rot(x; theta)     = axpby(x; cos(theta), sin(theta)) in 'gate' mode = exp(theta K) x
-class _ExciteAxpby(torch.autograd.Function):
-    """y = a x + c K x with a, c complex128 (B,): cotangents gx = axpby(gy; conj a, -conj c) in the same mode (K^T = -K),
-    gc = <K x, gy> = -cross(x, gy) and ga = the inner product over the pairs = -cross(x, K gy).  A tangent in a or c moves
-    the pairs only: a 'map' term."""
-
-    @staticmethod
-    def forward(state: torch.Tensor, a: torch.Tensor, c: torch.Tensor, spec: tuple, mode: str) -> torch.Tensor:
-        return backend.apply_excite_axpby(_plain(state), spec, _plain(a), _plain(c), mode)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        state, a, c, ctx.spec, ctx.mode = inputs
-        ctx.save_for_backward(state, a, c)
-        ctx.save_for_forward(state, a, c)
-
-    @staticmethod
-    def jvp(ctx, state_t, a_t, c_t, *_):
-        _single_forward_level()
-        state, a, c = ctx.saved_tensors
-        out = None
-        if state_t is not None:
-            out = excite_axpby(state_t, ctx.spec, a, c, ctx.mode)
-        if a_t is not None or c_t is not None:
-            zero = torch.zeros_like(a)
-            term = excite_axpby(state, ctx.spec, zero if a_t is None else a_t, zero if c_t is None else c_t, 'map')
-            out = term if out is None else out + term
-        return out
-
-    @staticmethod
-    def backward(ctx, gy: torch.Tensor):
-        state, a, c = ctx.saved_tensors
-        gstate = ga = gc = None
-        if ctx.needs_input_grad[0]:
-            gstate = excite_axpby(gy, ctx.spec, a.conj(), -c.conj(), ctx.mode)
-        if ctx.needs_input_grad[1]:
-            kgy = excite_axpby(gy, ctx.spec, torch.zeros_like(a), torch.ones_like(a), 'map')
-            ga = (-excite_cross(state, kgy, ctx.spec)).to(a.dtype)
-        if ctx.needs_input_grad[2]:
-            gc = (-excite_cross(state, gy, ctx.spec)).to(c.dtype)
-        return gstate, ga, gc, None, None
-
-    @staticmethod
-    def vmap(info, in_dims, state, a, c, spec, mode):
-        return _vmap_states(_ExciteAxpby, 'excite_axpby', info, in_dims, (state, a, c, spec, mode), folded=(1, 2))
-
-
-class _ExciteCross(torch.autograd.Function):
-    """z = sum_i conj(u_i) (K v)_i, complex128 (B,): anti-linear in u, linear in v; cotangents g_v = K^T u gz =
-    map(u; 0, -gz) and g_u = map(v; 0, conj(gz))."""
-
-    @staticmethod
-    def forward(bra: torch.Tensor, ket: torch.Tensor, spec: tuple) -> torch.Tensor:
-        pk = _plain(ket)
-        return backend.excite_cross(pk if bra is ket else _plain(bra), pk, spec)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        bra, ket, ctx.spec = inputs
-        ctx.save_for_backward(bra, ket)
-        ctx.save_for_forward(bra, ket)
-
-    @staticmethod
-    def jvp(ctx, bra_t, ket_t, *_):
-        _single_forward_level()
-        bra, ket = ctx.saved_tensors
-        out = None
-        if bra_t is not None:
-            out = excite_cross(bra_t, ket, ctx.spec)
-        if ket_t is not None:
-            term = excite_cross(bra, ket_t, ctx.spec)
-            out = term if out is None else out + term
-        return out
-
-    @staticmethod
-    def backward(ctx, gz: torch.Tensor):
-        bra, ket = ctx.saved_tensors
-        gz = gz.to(torch.complex128)
-        zero = torch.zeros_like(gz)
-        gbra = gket = None
-        if ctx.needs_input_grad[0]:
-            gbra = excite_axpby(ket, ctx.spec, zero, gz.conj(), 'map')
-        if ctx.needs_input_grad[1]:
-            gket = excite_axpby(bra, ctx.spec, zero, -gz, 'map')
-        return gbra, gket, None
-
-    @staticmethod
-    def vmap(info, in_dims, bra, ket, spec):
-        return _vmap_cross(_ExciteCross, 'excite_cross', info, in_dims, (bra, ket, spec))
-
-
-class _ExciteRot(torch.autograd.Function):
-    """y = U x, U = exp(theta K), theta real (B,): cotangents gx = rot(gy, -theta) = U^T gy and gtheta = Re cross(gy, y)
-    (dy/dtheta = K y).  U commutes with K, so cross(gy, U x) = cross(U^T gy, x) = cross(gx, x): the cross takes the two
-    tensors the backward holds already -- one rotation and one cross per backward, both over the pairs only."""
-
-    @staticmethod
-    def forward(state: torch.Tensor, theta: torch.Tensor, spec: tuple) -> torch.Tensor:
-        return backend.apply_excite_rot(_plain(state), spec, _plain(theta))
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        state, theta, ctx.spec = inputs
-        ctx.save_for_backward(state, theta)
-        ctx.save_for_forward(state, theta)
-
-    @staticmethod
-    def jvp(ctx, state_t, theta_t, *_):
-        _single_forward_level()
-        state, theta = ctx.saved_tensors
-        out = None
-        if state_t is not None:
-            out = excite_rot(state_t, ctx.spec, theta)
-        if theta_t is not None:
-            y = excite_rot(state, ctx.spec, theta)
-            rate = theta_t.to(torch.complex128)
-            term = excite_axpby(y, ctx.spec, torch.zeros_like(rate), rate, 'map')
-            out = term if out is None else out + term
-        return out
-
-    @staticmethod
-    def backward(ctx, gy: torch.Tensor):
-        state, theta = ctx.saved_tensors
-        gstate = excite_rot(gy, ctx.spec, -theta)
-        gtheta = None
-        if ctx.needs_input_grad[1]:
-            gtheta = excite_cross(gstate, state, ctx.spec).real.to(theta.dtype)
-        return (gstate if ctx.needs_input_grad[0] else None), gtheta, None
-
-    @staticmethod
-    def vmap(info, in_dims, state, theta, spec):
-        return _vmap_states(_ExciteRot, 'excite_rot', info, in_dims, (state, theta, spec), folded=(1,))
+    return _gen_rot((_PAULI_STRINGS, _pauli_masks(xmask, zmask, controls)), state, theta)
 
 
 def _excite_spec(spec) -> tuple:
@@ -1244,33 +1143,20 @@ def excite_axpby(state: torch.Tensor, spec, a, c, mode: str = 'gate') -> torch.T
     of a (B, 2**n) state (:func:`backend.apply_excite_axpby`); ``a``, ``c`` complex, one value or one per sample.
     Amplitudes outside the pairs pass through (``mode='gate'``) or come out as 0 (``mode='map'``, the cotangent of
     :func:`excite_cross`)."""
-    _no_legacy(state)
-    if mode not in ('gate', 'map'):
-        raise ValueError(f"excite_axpby: mode must be 'gate' or 'map', got {mode!r}")
-    a = _pauli_param(a, state, torch.complex128, 'excite_axpby')
-    c = _pauli_param(c, state, torch.complex128, 'excite_axpby')
-    return _ExciteAxpby.apply(_flat_arg(state), a, c, _excite_spec(spec), mode)
+    return _gen_axpby((_EXCITATIONS, _excite_spec(spec)), state, a, c, mode)
 
 
 def excite_cross(bra: torch.Tensor, ket: torch.Tensor, spec) -> torch.Tensor:
     """Differentiable ``sum_i conj(bra_i) (K ket)_i`` of two (B, 2**n) states over the pairs of ``spec``: complex128 (B,).
     Pass the same tensor twice to read each pair once (the real part is then 0 up to rounding)."""
-    _no_legacy(bra, ket)
-    if bra.dtype != ket.dtype:
-        raise ValueError('excite_cross: bra and ket must have one dtype')
-    same = bra is ket
-    ket = _flat_arg(ket)
-    bra = ket if same else _flat_arg(bra)
-    return _ExciteCross.apply(bra, ket, _excite_spec(spec))
+    return _gen_cross((_EXCITATIONS, _excite_spec(spec)), bra, ket)
 
 
 def excite_rot(state: torch.Tensor, spec, theta) -> torch.Tensor:
     """Differentiable ``exp(theta K)`` -- a Givens rotation by the FULL angle theta in every pair of ``spec`` -- on a
     (B, 2**n) state: ``theta`` real, one value or one per sample; cosine and sine are formed in double for both
     precisions."""
-    _no_legacy(state)
-    theta = _pauli_param(theta, state, torch.float64, 'excite_rot')
-    return _ExciteRot.apply(_flat_arg(state), theta, _excite_spec(spec))
+    return _gen_rot((_EXCITATIONS, _excite_spec(spec)), state, theta)
 
 
 # ---- basis-state permutations on any number of wires (csrc/dq_perm.hip) --------------------------------------------------

@@ -307,3 +307,31 @@ def test_the_circuit_itself_under_vmap_and_func_grad(cpu_backend):
 
     assert torch.allclose(torch.vmap(h)(ts), loop, atol=1e-13)
     gate.init_para(0.0)
+
+
+def test_to_double_and_back_keeps_the_complex_buffers_complex(cpu_backend):
+    """``.to(torch.double)`` promotes the complex buffer of a DiagonalGate, a MultiplexedGate and a HamiltonianGate to
+    complex128 with its imaginary part, so that the gate equals one built in double from the same numbers, and
+    ``.to(torch.float)`` brings it back to complex64."""
+    n = 3
+    g = torch.Generator().manual_seed(5)
+    phases = torch.exp(1j * torch.randn(1 << n, dtype=torch.float64, generator=g)).to(torch.complex64)
+    blocks = torch.linalg.qr(torch.randn(4, 2, 2, dtype=torch.complex128, generator=g))[0].to(torch.complex64)
+    ham = (0.5 * torch.from_numpy(np.kron([[0, 1], [1, 0]], [[0, -1j], [1j, 0]]))
+           - 0.75 * torch.from_numpy(np.kron([[0, -1j], [1j, 0]], [[1, 0], [0, -1]])))       # complex128, exact in complex64
+    cases = [
+        ('diag', lambda dt: dq.DiagonalGate(phases.to(dt), nqubit=n), phases, lambda gate: gate.get_unitary()),
+        ('unitaries', lambda dt: dq.MultiplexedGate(blocks.to(dt), nqubit=n, wires=[2, 0, 1]), blocks, lambda gate: gate.get_unitary()),
+        ('ham_tsr', lambda dt: dq.HamiltonianGate(ham.to(dt), t=torch.tensor(0.375, dtype=dt.to_real()), nqubit=n, wires=[0, 1]), ham,
+         lambda gate: gate.update_matrix()),
+    ]
+    for name, make, values, unitary in cases:
+        gate, want = make(torch.complex64), make(torch.complex128)
+        assert getattr(gate, name).dtype == torch.complex64 and getattr(want, name).dtype == torch.complex128
+        assert gate.to(torch.double) is gate
+        buf = getattr(gate, name)
+        assert buf.dtype == torch.complex128 and torch.equal(buf, values.to(torch.complex128)) and buf.imag.abs().max() > 0.1
+        assert unitary(gate).dtype == torch.complex128 and torch.equal(unitary(gate), unitary(want))
+        gate.to(torch.float)
+        assert getattr(gate, name).dtype == torch.complex64 and torch.equal(getattr(gate, name), values.to(torch.complex64))
+        assert unitary(gate).dtype == torch.complex64

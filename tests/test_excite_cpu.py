@@ -376,45 +376,6 @@ def test_refusals(cpu_backend):
         cir.qasm()
 
 
-def test_autograd_closure_through_the_stand_ins(cpu_backend):
-    """gradcheck / gradgradcheck at n = 4 of the operations that differentiate into one another, with a control, a
-    string bit and a per-sample angle."""
-    spec = (0b0101, 0b0100, 0b0010, 1, (3,))
-    x = tt(random_state(2, 4, 1)).requires_grad_()
-    y = tt(random_state(2, 4, 2)).requires_grad_()
-    a = torch.tensor([0.3 - 0.2j, 1.1j], dtype=torch.complex128, requires_grad=True)
-    c = torch.tensor([-0.6 + 0.1j, 0.4], dtype=torch.complex128, requires_grad=True)
-    th = torch.tensor([0.3, -3.8], dtype=torch.float64, requires_grad=True)
-    one = torch.tensor(0.45, dtype=torch.float64, requires_grad=True)
-    gc, ggc = torch.autograd.gradcheck, torch.autograd.gradgradcheck
-    for mode in ('gate', 'map'):
-        f = lambda s, p, q: ops.excite_axpby(s, spec, p, q, mode)  # noqa: E731
-        assert gc(f, (x, a, c))
-        assert ggc(f, (x, a, c))
-    assert gc(lambda u, v: ops.excite_cross(u, v, spec), (x, y))
-    assert ggc(lambda u, v: ops.excite_cross(u, v, spec), (x, y))
-    assert gc(lambda u: ops.excite_cross(u, u, spec), (x,))
-    assert gc(lambda s, p: ops.excite_rot(s, spec, p), (x, th))
-    assert ggc(lambda s, p: ops.excite_rot(s, spec, p), (x, th))
-    assert gc(lambda s, p: ops.excite_rot(s, spec[:4], p), (x, one))             # a shared angle: the sum of the samples' gradients
-    assert gc(lambda s, p: ops.excite_rot(s, spec, p), (x, th), check_forward_ad=True, check_backward_ad=False)
-    assert gc(lambda s, p, q: ops.excite_axpby(s, spec, p, q), (x, a, c), check_forward_ad=True, check_backward_ad=False)
-    assert gc(lambda u, v: ops.excite_cross(u, v, spec), (x, y), check_forward_ad=True, check_backward_ad=False)
-    # the backward of the rotation is the rotation back, exactly, and vmap folds into the batch
-    gy = tt(random_state(2, 4, 3))
-    (gx,) = torch.autograd.grad(ops.excite_rot(x, spec, th.detach()), x, gy)
-    assert torch.equal(gx, backend.apply_excite_rot(gy, spec, -th.detach()))
-    xs = tt(random_state(6, 4, 4)).reshape(3, 2, -1)
-    ths = torch.linspace(-1, 1, 6, dtype=torch.float64).reshape(3, 2)
-    want = backend.apply_excite_rot(xs.reshape(6, -1), spec, ths.reshape(-1))
-    assert torch.equal(torch.vmap(lambda s, p: ops.excite_rot(s, spec, p))(xs, ths).reshape(6, -1), want)
-    want = backend.excite_cross(xs.reshape(6, -1), xs.flip(0).reshape(6, -1).contiguous(), spec)
-    got = torch.vmap(lambda u, v: ops.excite_cross(u, v, spec))(xs, xs.flip(0))
-    assert torch.equal(got.reshape(-1), want)
-    g = torch.func.grad(lambda p: ops.excite_rot(x.detach(), spec, p)[:, 3].abs().pow(2).sum())(th.detach())
-    assert g.shape == (2,) and torch.isfinite(g).all()
-
-
 def test_rotation_backward_is_one_rotation_and_one_cross(cpu_backend, monkeypatch):
     calls = []
     for name in ('apply_excite_axpby', 'excite_cross'):

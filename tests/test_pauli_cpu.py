@@ -132,32 +132,6 @@ def test_backend_stand_ins_against_numpy(cpu_backend):
         backend.apply_pauli_rot(x, 1, 0, torch.zeros(3, dtype=torch.float64))
 
 
-def test_autograd_closure_through_the_stand_ins(cpu_backend):
-    """gradcheck / gradgradcheck at n = 3 of the operations that differentiate into one another, with a control, a Y and
-    a per-sample angle."""
-    n, xmask, zmask, controls = 3, 0b101, 0b100, (1,)
-    x = rand_state(2, n, 1).requires_grad_()
-    y = rand_state(2, n, 2).requires_grad_()
-    a = torch.tensor([0.3 - 0.2j, 1.1j], dtype=torch.complex128, requires_grad=True)
-    c = torch.tensor([-0.6 + 0.1j, 0.4], dtype=torch.complex128, requires_grad=True)
-    th = torch.tensor([0.3, -0.8], dtype=torch.float64, requires_grad=True)
-    one = torch.tensor(0.45, dtype=torch.float64, requires_grad=True)
-    gc, ggc = torch.autograd.gradcheck, torch.autograd.gradgradcheck
-    for mode in ('gate', 'map'):
-        f = lambda s, p, q: ops.pauli_axpby(s, xmask, zmask, p, q, controls, mode)  # noqa: E731
-        assert gc(f, (x, a, c))
-        assert ggc(f, (x, a, c))
-    assert gc(lambda u, v: ops.pauli_cross(u, v, xmask, zmask, controls), (x, y))
-    assert ggc(lambda u, v: ops.pauli_cross(u, v, xmask, zmask, controls), (x, y))
-    assert gc(lambda u: ops.pauli_cross(u, u, xmask, zmask), (x,))
-    assert gc(lambda s, p: ops.pauli_rot(s, xmask, zmask, p, controls), (x, th))
-    assert ggc(lambda s, p: ops.pauli_rot(s, xmask, zmask, p, controls), (x, th))
-    assert gc(lambda s, p: ops.pauli_rot(s, 0b011, 0b011, p), (x, one))         # a shared angle: the sum of the samples' gradients
-    assert gc(lambda s, p: ops.pauli_rot(s, xmask, zmask, p, controls), (x, th), check_forward_ad=True, check_backward_ad=False)
-    assert gc(lambda s, p, q: ops.pauli_axpby(s, xmask, zmask, p, q, controls), (x, a, c), check_forward_ad=True,
-              check_backward_ad=False)
-
-
 def test_one_parameter_gate_bookkeeping(cpu_backend):
     n = 3
     cir = dq.QubitCircuit(n)
