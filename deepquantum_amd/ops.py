@@ -68,6 +68,18 @@ def _plain(t: torch.Tensor) -> torch.Tensor:
     return t.resolve_conj().resolve_neg()
 
 
+def _kernel_arg(t: torch.Tensor) -> torch.Tensor:
+    """A state or a cotangent as the streaming kernels (diagonal, Pauli, excitation, permutation, multiplexer) read it:
+    :func:`_plain`, and 16-byte aligned.  Their entry points move 16-byte vectors and refuse any other pointer before a
+    launch; autograd produces such tensors on its own -- the backward of ``cat([h, y.reshape(-1)])`` hands the node that
+    made y a contiguous complex64 cotangent at element offset 1, 8 bytes off -- and nobody can ``clone()`` a cotangent, so a
+    misaligned tensor is copied here, as ``backend._finish_table`` copies a misaligned table.  Every forward of the
+    streaming nodes passes its states through this, and every backward, jvp and vmap rule is written with those nodes:
+    the one place.  Free (one pointer test) for what an allocator returns."""
+    t = _plain(t)
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 def _is_wrapped(t: torch.Tensor | None) -> bool:
     """True inside any ``torch.func`` transform (vmap, grad, vjp, jacrev, jvp ...): the tensor is a functorch wrapper -- no
     data pointer, and only the per-gate nodes (``setup_context`` style, with ``vmap`` and ``jvp`` rules) may see it.  Also
@@ -692,7 +704,7 @@ class _CostPhase(torch.autograd.Function):
 
     @staticmethod
     def forward(state: torch.Tensor, cost: torch.Tensor, t: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
-        return backend.apply_cost(_plain(state), cost, _plain(t), bits, controls, 'phase')
+        return backend.apply_cost(_kernel_arg(state), cost, _plain(t), bits, controls, 'phase')
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -735,8 +747,8 @@ class _CostCross(torch.autograd.Function):
 
     @staticmethod
     def forward(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
-        pk = _plain(ket)
-        return backend.cost_cross(pk if bra is ket else _plain(bra), pk, cost, bits, controls)
+        pk = _kernel_arg(ket)
+        return backend.cost_cross(pk if bra is ket else _kernel_arg(bra), pk, cost, bits, controls)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -769,7 +781,7 @@ class _CostScale(torch.autograd.Function):
 
     @staticmethod
     def forward(state: torch.Tensor, cost: torch.Tensor, s: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
-        return backend.apply_cost(_plain(state), cost, _plain(s), bits, controls, 'scale')
+        return backend.apply_cost(_kernel_arg(state), cost, _plain(s), bits, controls, 'scale')
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -804,7 +816,7 @@ class _DiagMul(torch.autograd.Function):
 
     @staticmethod
     def forward(state: torch.Tensor, diag: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
-        return backend.apply_diag(_plain(state), _plain(diag), bits, controls)
+        return backend.apply_diag(_kernel_arg(state), _plain(diag), bits, controls)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -838,7 +850,8 @@ def cost_phase(state: torch.Tensor, cost: torch.Tensor, t: torch.Tensor, bits: S
                controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable ``exp(-i t diag(cost))`` on a (B, 2**n) state: ``cost`` a constant real table (2^k,) over the index
     bits ``bits`` (``bits[0]`` = its most significant bit), ``t`` real, one value or one per sample.  One read and one
-    write of the state whatever k is."""
+    write of the state whatever k is.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     _no_legacy(state, t)
     cost = _const_table(cost, 'cost_phase')
     bits, controls = _bit_args(bits, controls)
@@ -849,7 +862,8 @@ def cost_phase(state: torch.Tensor, cost: torch.Tensor, t: torch.Tensor, bits: S
 def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: Sequence[int],
                controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable ``sum_i cost[sub(i)] conj(bra_i) ket_i`` of two (B, 2**n) states: complex128 (B,).  Pass the same
-    tensor twice for ``<C>`` (one read of the state; the imaginary part is exactly 0)."""
+    tensor twice for ``<C>`` (one read of the state; the imaginary part is exactly 0).
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     bra, ket = _cross_pair(bra, ket, 'cost_cross')
     cost = _const_table(cost, 'cost_cross')
     bits, controls = _bit_args(bits, controls)
@@ -859,7 +873,8 @@ def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: S
 def cost_scale(state: torch.Tensor, cost: torch.Tensor, s: torch.Tensor, bits: Sequence[int],
                controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable ``s diag(cost)`` on a (B, 2**n) state, ``s`` complex, one value or one per sample; amplitudes
-    outside the controls come out as 0 (the cotangent of :func:`cost_cross`)."""
+    outside the controls come out as 0 (the cotangent of :func:`cost_cross`).
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     _no_legacy(state, s)
     cost = _const_table(cost, 'cost_scale')
     bits, controls = _bit_args(bits, controls)
@@ -869,7 +884,8 @@ def cost_scale(state: torch.Tensor, cost: torch.Tensor, s: torch.Tensor, bits: S
 
 def diag_mul(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable (in the state) diagonal operator: ``diag`` a constant complex table (2^k,) or (B, 2^k) over the
-    index bits ``bits``; amplitudes outside the controls pass through."""
+    index bits ``bits``; amplitudes outside the controls pass through.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     _no_legacy(state)
     diag = _const_table(diag, 'diag_mul')
     bits, controls = _bit_args(bits, controls)
@@ -922,7 +938,7 @@ class _GenAxpby(torch.autograd.Function):
     def forward(state: torch.Tensor, a: torch.Tensor, c: torch.Tensor, gen: tuple, mode: str) -> torch.Tensor:
         fam, spec = gen
         leading, trailing = fam.spread(spec)
-        return getattr(backend, fam.axpby)(_plain(state), *leading, _plain(a), _plain(c), *trailing, mode)
+        return getattr(backend, fam.axpby)(_kernel_arg(state), *leading, _plain(a), _plain(c), *trailing, mode)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -968,9 +984,9 @@ class _GenCross(torch.autograd.Function):
     @staticmethod
     def forward(bra: torch.Tensor, ket: torch.Tensor, gen: tuple) -> torch.Tensor:
         fam, spec = gen
-        pk = _plain(ket)
+        pk = _kernel_arg(ket)
         leading, trailing = fam.spread(spec)
-        return getattr(backend, fam.cross)(pk if bra is ket else _plain(bra), pk, *leading, *trailing)
+        return getattr(backend, fam.cross)(pk if bra is ket else _kernel_arg(bra), pk, *leading, *trailing)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -1009,7 +1025,7 @@ class _GenRot(torch.autograd.Function):
     def forward(state: torch.Tensor, theta: torch.Tensor, gen: tuple) -> torch.Tensor:
         fam, spec = gen
         leading, trailing = fam.spread(spec)
-        return getattr(backend, fam.rot)(_plain(state), *leading, _plain(theta), *trailing)
+        return getattr(backend, fam.rot)(_kernel_arg(state), *leading, _plain(theta), *trailing)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -1114,20 +1130,23 @@ def pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, controls: Seq
     """Differentiable ``a x + c P x`` on a (B, 2**n) state for the Pauli string ``P = (xmask, zmask)`` over index bits (a Y
     sets its bit in both); ``a``, ``c`` complex, one value or one per sample.  Amplitudes outside the controls pass
     through (``mode='gate'``) or come out as 0 (``mode='map'``, the cotangent of :func:`pauli_cross`).  One read and one
-    write of the state whatever the weight of P."""
+    write of the state whatever the weight of P.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     return _gen_axpby((_PAULI_STRINGS, _pauli_masks(xmask, zmask, controls)), state, a, c, mode)
 
 
 def pauli_cross(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable ``sum_i conj(bra_i) (P ket)_i`` of two (B, 2**n) states over the amplitudes inside the controls:
     complex128 (B,).  Pass the same tensor twice for ``<P>`` (one read of the state); ``xmask = zmask = 0`` is the
-    inner product."""
+    inner product.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     return _gen_cross((_PAULI_STRINGS, _pauli_masks(xmask, zmask, controls)), bra, ket)
 
 
 def pauli_rot(state: torch.Tensor, xmask: int, zmask: int, theta, controls: Sequence[int] = ()) -> torch.Tensor:
     """Differentiable ``exp(-i theta/2 P)`` on a (B, 2**n) state: ``theta`` real, one value or one per sample; cosine and
-    sine of ``theta / 2`` are formed in double for both precisions.  One read and one write of the state."""
+    sine of ``theta / 2`` are formed in double for both precisions.  One read and one write of the state.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     return _gen_rot((_PAULI_STRINGS, _pauli_masks(xmask, zmask, controls)), state, theta)
 
 
@@ -1142,20 +1161,23 @@ def excite_axpby(state: torch.Tensor, spec, a, c, mode: str = 'gate') -> torch.T
     """Differentiable ``a x + c K x`` on the pairs of the excitation ``spec = (xmask, amask, zmask, negate[, controls])``
     of a (B, 2**n) state (:func:`backend.apply_excite_axpby`); ``a``, ``c`` complex, one value or one per sample.
     Amplitudes outside the pairs pass through (``mode='gate'``) or come out as 0 (``mode='map'``, the cotangent of
-    :func:`excite_cross`)."""
+    :func:`excite_cross`).
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     return _gen_axpby((_EXCITATIONS, _excite_spec(spec)), state, a, c, mode)
 
 
 def excite_cross(bra: torch.Tensor, ket: torch.Tensor, spec) -> torch.Tensor:
     """Differentiable ``sum_i conj(bra_i) (K ket)_i`` of two (B, 2**n) states over the pairs of ``spec``: complex128 (B,).
-    Pass the same tensor twice to read each pair once (the real part is then 0 up to rounding)."""
+    Pass the same tensor twice to read each pair once (the real part is then 0 up to rounding).
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     return _gen_cross((_EXCITATIONS, _excite_spec(spec)), bra, ket)
 
 
 def excite_rot(state: torch.Tensor, spec, theta) -> torch.Tensor:
     """Differentiable ``exp(theta K)`` -- a Givens rotation by the FULL angle theta in every pair of ``spec`` -- on a
     (B, 2**n) state: ``theta`` real, one value or one per sample; cosine and sine are formed in double for both
-    precisions."""
+    precisions.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     return _gen_rot((_EXCITATIONS, _excite_spec(spec)), state, theta)
 
 
@@ -1168,7 +1190,7 @@ class _PermuteBasis(torch.autograd.Function):
 
     @staticmethod
     def forward(state: torch.Tensor, perm: torch.Tensor, inv: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
-        return backend.apply_permutation(_plain(state), _plain(inv), bits, controls)
+        return backend.apply_permutation(_kernel_arg(state), _plain(inv), bits, controls)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -1204,7 +1226,8 @@ def permute_basis(state: torch.Tensor, perm: torch.Tensor, bits: Sequence[int], 
     """Differentiable (in the state) basis-state permutation ``|x> -> |perm(x)>`` on a (B, 2**n) state: ``perm`` a constant
     integer table of 2^k entries, a bijection of ``range(2^k)``, over the index bits ``bits`` (``bits[0]`` = its most
     significant bit); amplitudes outside the controls pass through.  One read and one write of the state, amplitudes
-    copied bit for bit.  ``inv``: perm^-1 where the caller holds it already (it is formed here otherwise)."""
+    copied bit for bit.  ``inv``: perm^-1 where the caller holds it already (it is formed here otherwise).
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     _no_legacy(state)
     for t in (perm, inv):
         if t is not None and (not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.ndim != 1):
@@ -1225,7 +1248,7 @@ class _MuxApply(torch.autograd.Function):
     @staticmethod
     def forward(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, bits: tuple, controls: tuple,
                 dagger: bool) -> torch.Tensor:
-        return backend.apply_mux(_plain(state), _plain(table), kind, target, bits, controls, dagger)
+        return backend.apply_mux(_kernel_arg(state), _plain(table), kind, target, bits, controls, dagger)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -1257,7 +1280,8 @@ def mux_apply(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, 
     ``bits`` (``bits[0]`` = the table index's most significant bit) its own 2x2 matrix on index bit ``target``; amplitudes
     outside the controls pass through.  ``kind='u'``: ``table`` a constant complex (2^k, 2, 2); ``kind='ry'``: a constant
     real (2^k, 2) of rows (c, s), M = [[c, -s], [s, c]].  ``dagger`` applies the conjugate transposes from the same table.
-    One read and one write of the state whatever k is."""
+    One read and one write of the state whatever k is.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     _no_legacy(state)
     table = _const_table(table, 'mux_apply')
     if kind not in ('u', 'ry'):

@@ -34,6 +34,7 @@ import pytest
 import torch
 
 from deepquantum_amd import backend
+from _diag_ref import diag_ref, on_mask, phase_ref, sub_index
 
 pytestmark = pytest.mark.gpu
 
@@ -51,20 +52,6 @@ GATHERED = {
 CONTROLS = {'ctrl_bit0': ((6, 5), (0,)), 'ctrl_top': ((6, 5), (NG - 1,)), 'straddle': ((6, 5), (1, NG - 1)),
             'straddle_low': ((3, 2), (1, 4))}
 WORST = {}
-
-
-def sub_index(n, bits):
-    i = np.arange(1 << n, dtype=np.int64)
-    k = len(bits)
-    s = np.zeros_like(i)
-    for j, p in enumerate(bits):
-        s |= ((i >> p) & 1) << (k - 1 - j)
-    return s
-
-
-def on_mask(n, controls):
-    cm = sum(1 << c for c in controls)
-    return (np.arange(1 << n, dtype=np.int64) & cm) == cm
 
 
 @functools.lru_cache(maxsize=None)
@@ -118,16 +105,6 @@ def parity(out, ref, dt, what):
 def bitwise_equal(a, b):
     return torch.equal(torch.view_as_real(a).view(torch.int32 if a.dtype == torch.complex64 else torch.int64),
                        torch.view_as_real(b).view(torch.int32 if b.dtype == torch.complex64 else torch.int64))
-
-
-def diag_ref(x, d, n, bits, controls=()):
-    f = d[..., sub_index(n, bits)]
-    return np.where(on_mask(n, controls), f * x, x)
-
-
-def phase_ref(x, c, t, n, bits, controls=()):
-    f = np.exp(-1j * np.asarray(t, dtype=np.float64)[:, None] * c[sub_index(n, bits)])
-    return np.where(on_mask(n, controls), f * x, x)
 
 
 def full(n):
