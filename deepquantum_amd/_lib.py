@@ -37,6 +37,7 @@ COST_PHASE, COST_SCALE = range(2)      # op of dq_apply_cost_*
 PAULI_GATE, PAULI_MAP = range(2)       # mode of dq_apply_pauli_axpby_*
 PERM_AUTO, PERM_GATHER, PERM_LOCAL = range(3)      # path of dq_apply_permutation_*
 MUX_U, MUX_RY = range(2)               # kind of dq_apply_mux_*
+MUX_AXES = {'i': 0, 'x': 1, 'y': 2, 'z': 3}        # axis of dq_mux_cross_*
 EXCITE_GATE, EXCITE_MAP = range(2)     # mode of dq_apply_excite_axpby_*
 
 
@@ -162,6 +163,8 @@ _SIGNATURES = {
     'dq_apply_permutation_{s}': (_i, [_vp, _vp, _vp, _i, _ip, _i, _ip, _i, _i64, _i, _vp]),
     'dq_permutation_local_bits': (_i, [_i]),
     'dq_apply_mux_{s}': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ip, _i, _ip, _i, _i64, _vp]),
+    'dq_mux_cross_ws_bytes': (_i64, [_i, _i64, _i, _i, _i]),
+    'dq_mux_cross_{s}': (_i, [_vp, _vp, _i, _i, _i, _ip, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),
     'dq_apply_excite_axpby_{s}': (_i, [_vp, _vp, _vp, _i, _u64, _u64, _u64, _i, _i, _ip, _i, _i64, _vp]),
     'dq_excite_cross_ws_bytes': (_i64, [_i, _i64, _i, _i]),
     'dq_excite_cross_{s}': (_i, [_vp, _vp, _u64, _u64, _u64, _i, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),

@@ -722,15 +722,16 @@ def rdm1_cross(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
     return _cross_reduce('dq_rdm1_cross', 'dq_rdm1_ws_bytes', bra, ket, (n,), (n, 2, 2))
 
 
-def _cross_reduce(entry: str, sizer: str, bra: torch.Tensor, ket: torch.Tensor, mid: tuple, shape: tuple[int, ...] = ()) -> torch.Tensor:
+def _cross_reduce(entry: str, sizer: str, bra: torch.Tensor, ket: torch.Tensor, mid: tuple, shape: tuple[int, ...] = (),
+                  sizer_args: tuple = ()) -> torch.Tensor:
     """A cross reduction of the library, ``<entry>_<suffix>(bra, ket, *mid, batch, out, ws, ws_bytes, stream)``, over the
     batch in slices of at most MAX_BATCH samples: complex128 (B, *shape).  Each slice's float64 workspace is sized by
-    ``<sizer>(n, batch, is_c128, bra is not ket)`` and comes from PyTorch's allocator (legal under capture)."""
+    ``<sizer>(n, batch, is_c128, bra is not ket, *sizer_args)`` and comes from PyTorch's allocator (legal under capture)."""
     n = _nqubit(ket)
     same = bra.data_ptr() == ket.data_ptr()
     out = torch.empty(ket.shape[0], *shape, 2, dtype=torch.float64, device=ket.device)
     for lo, hi in _slices(ket.shape[0]):
-        nbytes = getattr(_lib.load(), sizer)(n, hi - lo, int(ket.dtype == torch.complex128), int(not same))
+        nbytes = getattr(_lib.load(), sizer)(n, hi - lo, int(ket.dtype == torch.complex128), int(not same), *sizer_args)
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
         _call(entry, ket, _ptr(bra, lo), _ptr(ket, lo), *mid, hi - lo, _ptr(out, lo), _ptr(ws), nbytes)
     return torch.view_as_complex(out)
@@ -1290,6 +1291,122 @@ def _apply_mux_double(state, table, kind, n, target, bits, controls, dagger, out
     row = m[i, t]                                       # (2^n, 2): the row of M that makes amplitude i
     out.copy_(torch.where(ok, row[:, 0] * x0 + row[:, 1] * x1, x).to(state.dtype))
     return out
+
+
+def mux_cross(bra: torch.Tensor, ket: torch.Tensor, axis: str, target: int, bits: Sequence[int],
+              controls: Sequence[int] = ()) -> torch.Tensor:
+    """out[b, s] = sum over the amplitudes i with sub(i) = s whose ``controls`` are all 1 of conj(bra[b, i]) (G ket[b])[i],
+    G the one-qubit Pauli ``axis`` ('i', 'x', 'y', 'z') on index bit ``target`` and sub() over the k = len(bits) select
+    bits as in :func:`apply_mux`: complex128 (B, 2^k), accumulated in double, bitwise reproducible bin by bin, one read of
+    each state whatever k is (``dq_mux_cross_*``).  ``bra`` and ``ket`` the same buffer: one read of the state.  The
+    workspace comes from PyTorch's allocator (legal under capture)."""
+    what = 'mux_cross'
+    if axis not in _lib.MUX_AXES:
+        raise ValueError(f"{what}: axis must be 'i', 'x', 'y' or 'z', got {axis!r}")
+    n, bits, controls = _diag_args(ket, bits, controls, what)
+    target = int(target)
+    if not _distinct_positions(bits + controls + [target], n):
+        raise ValueError(f'{what}: target {target} / bits {bits} / controls {controls} must be distinct positions in [0, {n})')
+    k = len(bits)
+    _suffix(ket)
+    _check_bra(bra, ket, what)
+    if not _use_hip(ket):
+        return _diag_double(lambda: _mux_cross_double(bra, ket, axis, n, target, bits, controls))
+    mid = (_lib.MUX_AXES[axis], n, target, _lib.int_array(bits), k, _lib.int_array(controls), len(controls))
+    return _cross_reduce('dq_mux_cross', 'dq_mux_cross_ws_bytes', bra, ket, mid, (1 << k,), sizer_args=(k,))
+
+
+def _mux_coef(p, state: torch.Tensor, k: int, dtype: torch.dtype, what: str) -> torch.Tensor:
+    """One value per select value, shared by the batch (2^k,) / (1, 2^k) or per sample (B, 2^k): (1 or B, 2^k) in ``dtype``
+    on the state's device."""
+    p = torch.as_tensor(p, device=state.device)
+    if p.is_complex() and not dtype.is_complex:
+        raise ValueError(f'{what}: real angles expected, got {p.dtype}')
+    p = p.to(dtype)
+    if p.ndim == 1:
+        p = p.unsqueeze(0)
+    if p.ndim != 2 or p.shape[1] != 1 << k or p.shape[0] not in (1, state.shape[0]):
+        raise ValueError(f'{what}: {k} select bits take ({1 << k},) values, or ({state.shape[0]}, {1 << k}) for one row per '
+                         f'sample; got {tuple(p.shape)}')
+    return p.resolve_conj().resolve_neg()
+
+
+def _mux_launch(state: torch.Tensor, tables: torch.Tensor, kind: str, target: int, bits, controls) -> torch.Tensor:
+    """``apply_mux`` with one table for the batch (``tables.shape[0] == 1``: one launch) or one per sample (one launch per
+    sample: the route of second and higher derivatives, tested and not tuned)."""
+    if tables.shape[0] == 1:
+        return apply_mux(state, tables[0], kind, target, bits, controls)
+    out = torch.empty_like(state)
+    for b in range(state.shape[0]):
+        apply_mux(state[b:b + 1], tables[b], kind, target, bits, controls, out=out[b:b + 1])
+    return out
+
+
+def apply_mux_axpby(state: torch.Tensor, a, c, axis: str, target: int, bits: Sequence[int], controls: Sequence[int] = (),
+                    mode: str = 'gate') -> torch.Tensor:
+    """out[b, i] = a[b, sub(i)] state[b, i] + c[b, sub(i)] (G state[b])[i] on the amplitudes whose ``controls`` are all 1, G
+    the one-qubit Pauli ``axis`` ('i', 'x', 'y', 'z') on index bit ``target``; ``a``, ``c`` complex, (2^k,) for the batch or
+    (B, 2^k) per sample.  Runs on ``dq_apply_mux_*`` with the table of the blocks a[s] I + c[s] sigma.
+
+    * ``mode='gate'``: amplitudes outside the controls pass through.
+    * ``mode='map'``: they come out as 0 (the cotangent of :func:`mux_cross`, which leaves them out): the controls become
+      further select bits whose other entries are 0.
+
+    Per-sample coefficients run one launch per sample."""
+    what = 'apply_mux_axpby'
+    if mode not in ('gate', 'map'):
+        raise ValueError(f"{what}: mode must be 'gate' or 'map', got {mode!r}")
+    if axis not in _lib.MUX_AXES:
+        raise ValueError(f"{what}: axis must be 'i', 'x', 'y' or 'z', got {axis!r}")
+    _n, bits, controls = _diag_args(state, bits, controls, what)
+    k = len(bits)
+    a, c = _mux_coef(a, state, k, torch.complex128, what), _mux_coef(c, state, k, torch.complex128, what)
+    zero = torch.zeros_like(a + c)
+    if axis == 'i':
+        m = (a + c, zero, zero, a + c)
+    elif axis == 'x':
+        m = (a + zero, c + zero, c + zero, a + zero)
+    elif axis == 'y':
+        m = (a + zero, -1j * c + zero, 1j * c + zero, a + zero)
+    else:
+        m = (a + c, zero, zero, a - c)
+    m = torch.stack(m, dim=-1)                          # (1 or B, 2^k, 4)
+    if mode == 'map' and controls:
+        full = m.new_zeros(m.shape[0], 1 << k, 1 << len(controls), 4)
+        full[:, :, -1] = m
+        m, bits, controls = full, bits + controls, []
+    return _mux_launch(state, m.reshape(m.shape[0], -1, 2, 2).to(state.dtype), 'u', int(target), bits, controls)
+
+
+def apply_mux_rot(state: torch.Tensor, theta, axis: str, target: int, bits: Sequence[int],
+                  controls: Sequence[int] = ()) -> torch.Tensor:
+    """R_axis(theta[b, sub(i)]) on index bit ``target``, ``axis`` one of 'x', 'y', 'z': :func:`apply_mux_axpby` in 'gate'
+    mode with a = cos(theta/2), c = -i sin(theta/2), formed in double from the real ``theta`` -- (2^k,) or (B, 2^k); about
+    y the real ``DQ_MUX_RY`` table of rows (cos, sin)."""
+    what = 'apply_mux_rot'
+    if axis not in ('x', 'y', 'z'):
+        raise ValueError(f"{what}: axis must be 'x', 'y' or 'z', got {axis!r}")
+    _n, bits, controls = _diag_args(state, bits, controls, what)
+    half = _mux_coef(theta, state, len(bits), torch.float64, what) * 0.5
+    if axis != 'y':
+        return apply_mux_axpby(state, torch.cos(half), -1j * torch.sin(half), axis, target, bits, controls, 'gate')
+    return _mux_launch(state, torch.stack([torch.cos(half), torch.sin(half)], dim=-1), 'ry', int(target), bits, controls)
+
+
+def _mux_cross_double(bra, ket, axis, n, target, bits, controls):
+    sub, ok = _sub_index(n, bits, controls)
+    i = torch.arange(1 << n)
+    v = ket.to(torch.complex128)
+    t = (i >> target) & 1
+    if axis in 'xy':
+        v = v[:, i ^ (1 << target)]
+    if axis == 'y':
+        v = v * (1j * (2 * t - 1)).to(torch.complex128)             # (Y v)_0 = -i v_1, (Y v)_1 = i v_0
+    elif axis == 'z':
+        v = v * (1 - 2 * t).to(torch.complex128)
+    terms = torch.where(ok, bra.to(torch.complex128).conj() * v, torch.zeros((), dtype=torch.complex128))
+    out = torch.zeros(ket.shape[0], 1 << len(bits), dtype=torch.complex128)
+    return out.index_add_(1, sub, terms)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -785,21 +785,26 @@ class QubitCircuit(Operation):
         self.add(MultiplexedGate(unitaries=unitaries, nqubit=self.nqubit, wires=wires, controls=controls, name=name,
                                  den_mat=self.den_mat))
 
-    def ucr(self, axis, angles, wires, controls=None, name=None):
+    def ucr(self, axis, angles=None, wires=None, controls=None, name=None, requires_grad=False):
         """A multiplexed rotation: ``R_axis(angles[s])`` (``axis`` one of 'x', 'y', 'z') on the LAST wire of ``wires`` for
-        every value s of the k wires before it (``wires[0]`` = the most significant bit of s), 2^k fixed angles: see
+        every value s of the k wires before it (``wires[0]`` = the most significant bit of s), 2^k angles: fixed, or with
+        ``requires_grad=True`` one trainable parameter of 2^k entries (``angles=None``: random): see
         :class:`MultiplexedRotation`."""
+        if wires is None:
+            raise ValueError('ucr: wires lists at least one select wire and then the target')
+        if angles is None and not requires_grad:
+            raise ValueError('ucr: angles=None (random angles) needs requires_grad=True')
         self.add(MultiplexedRotation(axis=axis, angles=angles, nqubit=self.nqubit, wires=wires, controls=controls,
-                                     name=name or f'ucr{axis}', den_mat=self.den_mat))
+                                     name=name or f'ucr{axis}', den_mat=self.den_mat, requires_grad=requires_grad))
 
-    def ucrx(self, angles, wires, controls=None):
-        self.ucr('x', angles, wires, controls=controls)
+    def ucrx(self, angles=None, wires=None, controls=None, requires_grad=False):
+        self.ucr('x', angles, wires, controls=controls, requires_grad=requires_grad)
 
-    def ucry(self, angles, wires, controls=None):
-        self.ucr('y', angles, wires, controls=controls)
+    def ucry(self, angles=None, wires=None, controls=None, requires_grad=False):
+        self.ucr('y', angles, wires, controls=controls, requires_grad=requires_grad)
 
-    def ucrz(self, angles, wires, controls=None):
-        self.ucr('z', angles, wires, controls=controls)
+    def ucrz(self, angles=None, wires=None, controls=None, requires_grad=False):
+        self.ucr('z', angles, wires, controls=controls, requires_grad=requires_grad)
 
     def prepare_state(self, state, wires=None, controls=None):
         """Appends the gates that map ``|0..0>`` of ``wires`` (all by default) to the vector ``state`` of 2^k entries,

@@ -1,4 +1,4 @@
-// The core of the streaming primitives (dq_diag.hip, dq_pauli.hip, dq_perm.hip, dq_mux.hip): kernels that read a state once in
+// The core of the streaming primitives (dq_diag.hip, dq_pauli.hip, dq_perm.hip, dq_mux.hip, dq_muxgrad.hip): kernels that read a state once in
 // 16-byte vectors, do a little arithmetic per amplitude (or none) and either write the state back or reduce it to one
 // complex number per sample.
 // Each including file gets its own copy of what is here (the library is built without relocatable device code).
@@ -12,6 +12,7 @@
 // 4, .., 32), wave 0's first lane adds the four waves in order 0..3 and writes the workgroup's partial sum
 // (write_partial); cross_finish_kernel then adds the partial sums of a sample, strided by ST_THREADS over the lanes,
 // the same way.  No atomics, every sum in a fixed order: bitwise reproducible, and that promise lives here alone.
+// (dq_muxgrad.hip reduces per bin of select values, not per sample: its fixed orders are its own and stand in its header.)
 // The reductions of dq_reduce.hip (a __shfl_down tree from offset 32 downward: another order of additions, other
 // bits), dq_entangle.hip, dq_sample.hip and dq_rdm.hip (shaped by their own tiles) are deliberately not built on this.
 #pragma once
@@ -261,10 +262,10 @@ int check_cross_ws(const char* what, int64_t ws_bytes, int n, int64_t batch, boo
     return DQ_ERR_ARG;
 }
 
-// The buffers of a cross reduction, once n and the batch are validated: bra, ket, the table (where the primitive has
-// one: `has_table`) and ws non-null and 16-byte aligned, out non-null and 8-byte aligned, ws large enough.
-int check_cross(const char* what, const void* bra, const void* ket, const void* table, bool has_table, const double* out,
-                const void* ws, int64_t ws_bytes, int n, int64_t batch, bool is_c128) {
+// The pointers of a cross reduction: bra, ket, the table (where the primitive has one: `has_table`) and ws non-null and
+// 16-byte aligned, out non-null and 8-byte aligned.  (On its own for a primitive that sizes its workspace itself.)
+int check_cross_buffers(const char* what, const void* bra, const void* ket, const void* table, bool has_table, const double* out,
+                        const void* ws) {
     if (!bra || !ket || (has_table && !table) || !out || !ws) {
         set_error("%s: null pointer", what);
         return DQ_ERR_ARG;
@@ -274,6 +275,13 @@ int check_cross(const char* what, const void* bra, const void* ket, const void* 
         set_error("%s: bra, ket, the table and ws must be 16-byte aligned, out 8-byte aligned", what);
         return DQ_ERR_ARG;
     }
+    return DQ_OK;
+}
+
+// The buffers of a cross reduction, once n and the batch are validated: check_cross_buffers, and ws large enough.
+int check_cross(const char* what, const void* bra, const void* ket, const void* table, bool has_table, const double* out,
+                const void* ws, int64_t ws_bytes, int n, int64_t batch, bool is_c128) {
+    if (int rc = check_cross_buffers(what, bra, ket, table, has_table, out, ws)) return rc;
     return check_cross_ws(what, ws_bytes, n, batch, is_c128);
 }
 

@@ -1108,25 +1108,52 @@ class MultiplexedRotation(_FlatGate, ArbitraryGate):
     ``angles / 2`` are taken in the dtype of the angle buffer, on the host side; the tables made of them -- rows (c, s) for
     'y' (``DQ_MUX_RY``), 2x2 blocks for 'x' (``DQ_MUX_U``), phases over ``wires`` for 'z' (a diagonal operator:
     ``ops.diag_mul``, no multiplexer kernel) -- are formed once per precision and direction and kept.  The angles are
-    constants: they carry no gradient."""
+    constants: they carry no gradient -- unless ``requires_grad=True``: the 2^k angles are then one ``nn.Parameter``
+    (random when ``angles is None``), the gate runs ``ops.mux_rot`` -- the same kernels forward, one rotation and one binned
+    cross reduction (``dq_mux_cross_*``) backward, whatever k is -- and is differentiable to any order in the state and in
+    the angles."""
 
-    def __init__(self, axis, angles, nqubit=1, wires=None, minmax=None, controls=None, name='MultiplexedRotation',
-                 den_mat=False, tsr_mode=False):
+    def __init__(self, axis, angles=None, nqubit=1, wires=None, minmax=None, controls=None, name='MultiplexedRotation',
+                 den_mat=False, tsr_mode=False, requires_grad=False):
         super().__init__(name=name, nqubit=nqubit, wires=wires, minmax=minmax, controls=controls, den_mat=den_mat,
                          tsr_mode=tsr_mode)
         k = _mux_wires(self, 'MultiplexedRotation')
         if axis not in ('x', 'y', 'z'):
             raise ValueError(f"MultiplexedRotation: axis must be 'x', 'y' or 'z', got {axis!r}")
         self.axis = axis
+        self.requires_grad = bool(requires_grad)
+        if angles is None:
+            if not self.requires_grad:
+                raise ValueError('MultiplexedRotation: angles=None (random angles) needs requires_grad=True')
+            angles = torch.rand(2**k) * (4 * torch.pi)
         angles = _as_param_tensor(angles)
-        self._constant(angles, 'MultiplexedRotation', 'the angles', plural=True)
+        if not self.requires_grad:
+            self._constant(angles, 'MultiplexedRotation', 'the angles', plural=True)
         if angles.is_complex() or not angles.is_floating_point():
             angles = angles.real.to(torch.float) if angles.is_complex() else angles.to(torch.float)
         angles = angles.detach().reshape(-1)
         if angles.shape[0] != 2**k:
             raise ValueError(f'MultiplexedRotation: {k} select wires take {2**k} angles, got {angles.shape[0]}')
-        self.register_buffer('angles', angles.contiguous())
+        if self.requires_grad:
+            self.npara = 2**k
+            self.angles = nn.Parameter(angles.clone().contiguous())
+        else:
+            self.register_buffer('angles', angles.contiguous())
         self._mark_precision(angles.device)             # (the angles may be float64 in a complex64 circuit)
+
+    def init_para(self, inputs: Any = None) -> None:
+        """Trainable angles only (the pattern of ``_OneAngle``): new random angles, or ``inputs``, in the parameter's own
+        precision and on its device.  Constant angles stay as they are."""
+        if not self.requires_grad:
+            return
+        old = self.angles
+        if inputs is None:
+            value = torch.rand(old.shape[0]) * (4 * torch.pi)
+        else:
+            value = _as_param_tensor(inputs).detach().reshape(-1)
+            if value.shape[0] != old.shape[0]:
+                raise ValueError(f'MultiplexedRotation: {old.shape[0]} angles expected, got {value.shape[0]}')
+        self.angles = nn.Parameter(value.to(device=old.device, dtype=old.dtype))
 
     def table(self, dtype: torch.dtype) -> torch.Tensor:
         """The table of the gate as it stands for states of complex ``dtype``: 'y' (2^k, 2) real rows (c, s), 'x' complex
@@ -1156,6 +1183,10 @@ class MultiplexedRotation(_FlatGate, ArbitraryGate):
         """(B, 2**n) -> (B, 2**n)."""
         from . import ops
 
+        if self.requires_grad:                          # (the inverse shares the parameter and negates it here)
+            (target,) = self._bits(self.wires[-1:])
+            return ops.mux_rot(x, -self.angles if self.inv_mode else self.angles, self.axis, target,
+                               self._bits(self.wires[:-1]), self._bits(self.controls))
         t = self.table(x.dtype)
         if self.axis == 'z':
             return ops.diag_mul(x, t, self._bits(self.wires), self._bits(self.controls))

@@ -1288,3 +1288,241 @@ def mux_apply(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, 
         raise ValueError(f"mux_apply: kind must be 'u' or 'ry', got {kind!r}")
     bits, controls = _bit_args(bits, controls)
     return _MuxApply.apply(_flat_arg(state), table, kind, int(target), bits, controls, bool(dagger))
+
+
+# ---- trainable multiplexed rotations: per-select coefficients and angles (csrc/dq_mux.hip, csrc/dq_muxgrad.hip) ---------
+# G = the one-qubit Pauli sigma (I, X, Y, Z) on the target inside the controls, 0 elsewhere; bin s = the amplitudes with
+# sub(i) = s inside the controls.  G maps every bin to itself (the select bits, the controls and the target are disjoint)
+# and G^dagger = G.  The generator rules above, with one coefficient PER BIN instead of one per sample:
+#     axpby(x; a, c)[i] = a[sub i] x[i] + c[sub i] (G x)[i] inside the controls     (elsewhere: x[i] 'gate', 0 'map')
+#     cross(u, v)[b, s] = sum over bin s of conj(u[b, i]) (G v[b])[i]               complex128 (B, 2^k)
+#     rot(x; theta)     = axpby(x; cos(theta/2), -i sin(theta/2)) in 'gate' mode    sigma in {X, Y, Z}, theta real
+#     axpby:  gx = axpby(gy; conj a, conj c) in the same mode;  gc = cross_sigma(x, gy);  ga = cross_I(x, gy)
+#     cross:  g_u = map(v; 0, conj gz);  g_v = map(u; 0, gz)
+#     rot:    gx = rot(gy; -theta);  gtheta[b, s] = Im cross(gx, x)[b, s] / 2
+# These are three nodes of their own and not a third family of `_Generator`: its nodes keep a, c and theta as (B,), hand
+# them to `_vmap_states` as (B,) and reduce every cross to (B,); a parameter of shape (B, 2^k) changes each of those
+# lines, for the families that exist too.  A parameter is kept as (Bp, 2^k) with Bp = 1 (shared by the batch: one table,
+# one launch, and its gradient is the sum of the cross over the batch) or Bp = B (per sample: what the cotangents of
+# `cross` are, so from the second order on; one launch per sample, tested and not tuned).  The spec is
+# ``mux = (axis, target, bits, controls)``.
+def _mux_fit(z: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """A cross (B, 2^k) as the gradient of a parameter ``like`` of shape (1 or B, 2^k)."""
+    return z.sum(dim=0, keepdim=True) if like.shape[0] == 1 and z.shape[0] != 1 else z
+
+
+def _vmap_mux(cls, info, in_dims, args: tuple, params: tuple, nstates: int = 1):
+    """The ``vmap`` rule of the three nodes: the mapped dimension of the states goes into the batch dimension; a mapped
+    parameter becomes per sample, a shared one that is not mapped stays shared."""
+    v = info.batch_size
+    args = list(args)
+    same = nstates == 2 and args[0] is args[1] and in_dims[0] == in_dims[1]
+    for i in range(nstates):
+        args[i] = args[0] if (i == 1 and same) else _fold(args[i], in_dims[i], v)
+    b = args[0].shape[0] // v
+    for i in params:
+        p, d = args[i], in_dims[i]
+        if d is None and p.shape[0] == 1:
+            continue
+        p = p.movedim(d, 0) if d is not None else p.unsqueeze(0)
+        args[i] = p.expand(v, b, p.shape[-1]).reshape(v * b, p.shape[-1])
+    out = cls.apply(*args)
+    return out.reshape(v, -1, out.shape[-1]), 0
+
+
+class _MuxAxpby(torch.autograd.Function):
+    """y = a[sub] x + c[sub] G x with a, c complex128 (1 or B, 2^k): see the rules above."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, a: torch.Tensor, c: torch.Tensor, mux: tuple, mode: str) -> torch.Tensor:
+        return backend.apply_mux_axpby(_kernel_arg(state), _plain(a), _plain(c), *mux, mode)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, a, c, ctx.mux, ctx.mode = inputs
+        ctx.save_for_backward(state, a, c)
+        ctx.save_for_forward(state, a, c)
+
+    @staticmethod
+    def jvp(ctx, state_t, a_t, c_t, *_):
+        _single_forward_level()
+        state, a, c = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = _mux_axpby(ctx.mux, state_t, a, c, ctx.mode)
+        if a_t is not None or c_t is not None:
+            zero = torch.zeros_like(a)
+            term = _mux_axpby(ctx.mux, state, zero if a_t is None else a_t, zero if c_t is None else c_t, 'map')
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        mux = ctx.mux
+        state, a, c = ctx.saved_tensors
+        gstate = ga = gc = None
+        if ctx.needs_input_grad[0]:
+            gstate = _mux_axpby(mux, gy, a.conj(), c.conj(), ctx.mode)
+        if ctx.needs_input_grad[1]:
+            ga = _mux_fit(_mux_cross(('i', *mux[1:]), state, gy), a).to(a.dtype)
+        if ctx.needs_input_grad[2]:
+            gc = _mux_fit(_mux_cross(mux, state, gy), c).to(c.dtype)
+        return gstate, ga, gc, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, a, c, mux, mode):
+        return _vmap_mux(_MuxAxpby, info, in_dims, (state, a, c, mux, mode), params=(1, 2))
+
+
+class _MuxCross(torch.autograd.Function):
+    """z[b, s] = sum over bin s of conj(u_i) (G v)_i, complex128 (B, 2^k): see the rules above."""
+
+    @staticmethod
+    def forward(bra: torch.Tensor, ket: torch.Tensor, mux: tuple) -> torch.Tensor:
+        pk = _kernel_arg(ket)
+        return backend.mux_cross(pk if bra is ket else _kernel_arg(bra), pk, *mux)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        bra, ket, ctx.mux = inputs
+        ctx.save_for_backward(bra, ket)
+        ctx.save_for_forward(bra, ket)
+
+    @staticmethod
+    def jvp(ctx, bra_t, ket_t, *_):
+        _single_forward_level()
+        bra, ket = ctx.saved_tensors
+        return _jvp_two_slots(lambda u, v: _mux_cross(ctx.mux, u, v), bra, ket, bra_t, ket_t)
+
+    @staticmethod
+    def backward(ctx, gz: torch.Tensor):
+        mux = ctx.mux
+        bra, ket = ctx.saved_tensors
+        gz = gz.to(torch.complex128)
+        zero = torch.zeros_like(gz)
+        gbra = gket = None
+        if ctx.needs_input_grad[0]:
+            gbra = _mux_axpby(mux, ket, zero, gz.conj(), 'map')
+        if ctx.needs_input_grad[1]:
+            gket = _mux_axpby(mux, bra, zero, gz, 'map')
+        return gbra, gket, None
+
+    @staticmethod
+    def vmap(info, in_dims, bra, ket, mux):
+        return _vmap_mux(_MuxCross, info, in_dims, (bra, ket, mux), params=(), nstates=2)
+
+
+class _MuxRot(torch.autograd.Function):
+    """y = R_sigma(theta[sub]) x, theta real (1 or B, 2^k): see the rules above -- one rotation and one cross per backward."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, theta: torch.Tensor, mux: tuple) -> torch.Tensor:
+        return backend.apply_mux_rot(_kernel_arg(state), _plain(theta), *mux)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, theta, ctx.mux = inputs
+        ctx.save_for_backward(state, theta)
+        ctx.save_for_forward(state, theta)
+
+    @staticmethod
+    def jvp(ctx, state_t, theta_t, *_):
+        _single_forward_level()
+        mux = ctx.mux
+        state, theta = ctx.saved_tensors
+        out = None
+        if state_t is not None:
+            out = _mux_rot(mux, state_t, theta)
+        if theta_t is not None:
+            y = _mux_rot(mux, state, theta)
+            rate = -0.5j * theta_t.to(torch.complex128)
+            term = _mux_axpby(mux, y, torch.zeros_like(rate), rate, 'map')
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        mux = ctx.mux
+        state, theta = ctx.saved_tensors
+        gstate = _mux_rot(mux, gy, -theta)
+        gtheta = None
+        if ctx.needs_input_grad[1]:
+            gtheta = _mux_fit(0.5 * _mux_cross(mux, gstate, state).imag, theta).to(theta.dtype)
+        return (gstate if ctx.needs_input_grad[0] else None), gtheta, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, theta, mux):
+        return _vmap_mux(_MuxRot, info, in_dims, (state, theta, mux), params=(1,))
+
+
+def _mux_spec(axis: str, target: int, bits: Sequence[int], controls: Sequence[int], axes: str, what: str) -> tuple:
+    if axis not in tuple(axes):
+        raise ValueError(f'{what}: axis must be one of {", ".join(repr(ch) for ch in axes)}; got {axis!r}')
+    return (axis, int(target), *_bit_args(bits, controls))
+
+
+def _mux_param(p, state: torch.Tensor, mux: tuple, dtype: torch.dtype, what: str) -> torch.Tensor:
+    """(2^k,), (1, 2^k) or (B, 2^k) as (1 or B, 2^k) in ``dtype``, differentiably."""
+    if not isinstance(p, torch.Tensor):
+        p = torch.as_tensor(p, device=state.device)
+    if p.is_complex() and not dtype.is_complex:
+        raise ValueError(f'{what}: real angles expected, got {p.dtype}')
+    p = p.to(dtype)
+    if p.ndim == 1:
+        p = p.unsqueeze(0)
+    d = 1 << len(mux[2])
+    if p.ndim != 2 or p.shape[-1] != d or p.shape[-2] not in (1, state.shape[-2]):
+        raise ValueError(f'{what}: {len(mux[2])} select bits take ({d},) values, or ({state.shape[-2]}, {d}) for one row per '
+                         f'sample; got {tuple(p.shape)}')
+    return p
+
+
+def _mux_axpby(mux: tuple, state: torch.Tensor, a, c, mode: str) -> torch.Tensor:
+    _no_legacy(state)
+    if mode not in ('gate', 'map'):
+        raise ValueError(f"mux_axpby: mode must be 'gate' or 'map', got {mode!r}")
+    a = _mux_param(a, state, mux, torch.complex128, 'mux_axpby')
+    c = _mux_param(c, state, mux, torch.complex128, 'mux_axpby')
+    return _MuxAxpby.apply(_flat_arg(state), a, c, mux, mode)
+
+
+def _mux_cross(mux: tuple, bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    return _MuxCross.apply(*_cross_pair(bra, ket, 'mux_cross'), mux)
+
+
+def _mux_rot(mux: tuple, state: torch.Tensor, theta) -> torch.Tensor:
+    _no_legacy(state)
+    return _MuxRot.apply(_flat_arg(state), _mux_param(theta, state, mux, torch.float64, 'mux_rot'), mux)
+
+
+def mux_axpby(state: torch.Tensor, a, c, axis: str, target: int, bits: Sequence[int], controls: Sequence[int] = (),
+              mode: str = 'gate') -> torch.Tensor:
+    """Differentiable ``a[s] x + c[s] sigma x`` on a (B, 2**n) state: for every value s of the select bits ``bits``
+    (``bits[0]`` = the most significant bit of s) its own complex pair (a[s], c[s]) and the Pauli ``axis`` ('i', 'x', 'y',
+    'z') on index bit ``target``.  ``a``, ``c``: (2^k,) shared by the batch or (B, 2^k) per sample, differentiable to any
+    order like the state.  Amplitudes outside the controls pass through (``mode='gate'``) or come out as 0
+    (``mode='map'``, the cotangent of :func:`mux_cross`).  Shared coefficients are one read and one write of the state
+    whatever k is; per-sample coefficients -- they arise from the second derivative on -- run one launch per sample: that
+    route is tested, not tuned.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    return _mux_axpby(_mux_spec(axis, target, bits, controls, 'ixyz', 'mux_axpby'), state, a, c, mode)
+
+
+def mux_cross(bra: torch.Tensor, ket: torch.Tensor, axis: str, target: int, bits: Sequence[int],
+              controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable ``sum over sub(i) = s of conj(bra_i) (sigma ket)_i`` of two (B, 2**n) states inside the controls, one
+    number per sample and per value s of the select bits: complex128 (B, 2^k), one read of each state whatever k is,
+    bitwise reproducible.  Pass the same tensor twice for one read of the state.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    return _mux_cross(_mux_spec(axis, target, bits, controls, 'ixyz', 'mux_cross'), bra, ket)
+
+
+def mux_rot(state: torch.Tensor, theta, axis: str, target: int, bits: Sequence[int],
+            controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable multiplexed rotation ``R_axis(theta[s])`` (``axis`` 'x', 'y' or 'z') on index bit ``target`` of a
+    (B, 2**n) state for every value s of the select bits: ``theta`` real, (2^k,) shared by the batch or (B, 2^k) per
+    sample (one launch per sample: tested, not tuned); cosine and sine of ``theta / 2`` are formed in double for both
+    precisions.  One read and one write of the state forward; one rotation and one binned cross reduction backward,
+    whatever k is.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    return _mux_rot(_mux_spec(axis, target, bits, controls, 'xyz', 'mux_rot'), state, theta)

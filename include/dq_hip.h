@@ -686,6 +686,25 @@ int dq_apply_mux_c64(const void* in, void* out, const void* table, int kind, int
 int dq_apply_mux_c128(const void* in, void* out, const void* table, int kind, int dagger, int n, int target, const int* bits,
                       int k, const int* controls, int nc, int64_t batch, dq_stream_t stream);
 
+/* The binned cross reduction (csrc/dq_muxgrad.hip; added within ABI 30, presence is checked by symbol): what the gradient
+ * with respect to the 2^k angles of a multiplexed rotation is made of.  G = the one-qubit Pauli `axis` on bit `target`:
+ *     out[b, s] = sum over i with sub(i) = s and controls = 1 of conj(bra[b, i]) * (G ket_b)[i]
+ * DEVICE double [batch][2^k][2] (re, im), fully overwritten, accumulated in double.  bra == ket reads the state once.
+ * `bits`, `controls`, `target`, n, k and batch as for dq_apply_mux_*.  Workgroups write fixed-order partial sums per bin
+ * into `ws` (at least dq_mux_cross_ws_bytes bytes, 16-byte aligned) and a second kernel adds them: no atomics, results
+ * are bitwise reproducible bin by bin.  No address depends on data. */
+#define DQ_MUX_AXIS_I 0
+#define DQ_MUX_AXIS_X 1
+#define DQ_MUX_AXIS_Y 2
+#define DQ_MUX_AXIS_Z 3
+/* Bytes of device workspace dq_mux_cross_* needs for k select bits, wherever they lie (at most 8 MiB per sample, 16
+ * bytes where one workgroup owns every bin; `is_c128` and `cross` change nothing); -1 on a bad argument. */
+int64_t dq_mux_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross, int k);
+int dq_mux_cross_c64(const void* bra, const void* ket, int axis, int n, int target, const int* bits, int k, const int* controls,
+                     int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+int dq_mux_cross_c128(const void* bra, const void* ket, int axis, int n, int target, const int* bits, int k, const int* controls,
+                      int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 12. Excitation gates -- Givens rotations between two bit patterns -- that touch only their subspace
  *     (csrc/dq_excite.hip; added within ABI 30, presence is checked by symbol).  K = E - E^dagger for an excitation E

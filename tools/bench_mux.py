@@ -15,10 +15,16 @@
    matrix on 10 wires at n = 26 against ``cir.multiplexer`` with k = 9; ``prepare_state`` of a 2^20-entry vector on 20
    of 26 wires.
 
+3. The trainable rotations (``--cross-only`` runs these alone): ``dq_mux_cross_*``, the binned reduction behind the angle
+   gradients, at the same sizes against ``dq_pauli_cross_*`` with ``xmask = 1 << target`` on the same buffers -- k = 4 and
+   k = 10 with the selects low, high and across the unit, k = n - 1, ``bra is ket``, a high control -- and a forward plus
+   backward of a trainable ``ucry`` (k = 9, n = 26) against a forward plus backward of ``cir.pauli_rot('y')`` on the same
+   target.
+
 Every point: one warm-up call, then the median of ``reps`` calls between device events; the rows of a group, yardsticks
 included, take turns within every repetition.  The box is recorded first.
 
-usage: python tools/bench_mux.py [--quick] [--loop-only] [--out FILE]
+usage: python tools/bench_mux.py [--quick] [--loop-only] [--cross-only] [--out FILE]
 """
 import json
 import math
@@ -152,6 +158,77 @@ def kernels(rows, dtype, n, batch, reps):
     torch.cuda.empty_cache()
 
 
+def cross_kernels(rows, dtype, n, batch, reps):
+    """``dq_mux_cross_*`` (the binned reduction behind the angle gradients) against ``dq_pauli_cross_*`` with
+    ``xmask = 1 << target`` on the same buffers, which makes the same reads and returns one number per sample."""
+    esz = 8 if dtype == torch.complex64 else 16
+    p = 11 if dtype == torch.complex64 else 10
+    ket = torch.randn(batch, 1 << n, dtype=dtype, device='cuda')
+    bra = torch.randn(batch, 1 << n, dtype=dtype, device='cuda')
+    sbytes = ket.numel() * esz
+    t = 3
+    low = tuple(q for q in range(11, -1, -1) if q != t)
+    across = tuple(range(p + 6, p, -1)) + tuple(range(p - 1, p - 5, -1))
+    cases = {
+        # name: (bits, controls, bra is ket)
+        'cross k=4, selects low': (low[-4:], (), False),
+        'cross k=10, selects low': (low[:10], (), False),
+        'cross k=4, selects high': (tuple(range(n - 1, n - 5, -1)), (), False),
+        'cross k=10, selects high': (tuple(range(n - 1, n - 11, -1)), (), False),
+        'cross k=4, selects across the unit': (across[3:7], (), False),
+        'cross k=10, selects across the unit': (across, (), False),
+        'cross k=n-1': (tuple(q for q in range(n - 1, -1, -1) if q != t), (), False),
+        'cross k=4, selects low, bra is ket': (low[-4:], (), True),
+        'cross k=10, selects across the unit, bra is ket': (across, (), True),
+        'cross k=4, selects low, one high control': (low[-4:], (n - 1,), False),
+    }
+    yards = {(False, ()): 'pauli_cross xmask=1<<3 (yardstick)', (True, ()): 'pauli_cross xmask=1<<3, bra is ket (yardstick)',
+             (False, (n - 1,)): 'pauli_cross xmask=1<<3, one high control (yardstick)'}
+    fns = {name: (lambda s=same, c=controls: backend.pauli_cross(ket if s else bra, ket, 1 << t, 0, c))
+           for (same, controls), name in yards.items()}
+    for name, (bits, controls, same) in cases.items():
+        fns[name] = lambda b=bits, c=controls, s=same: backend.mux_cross(ket if s else bra, ket, 'y', t, b, c)
+    with torch.no_grad():
+        ts = timed_group(fns, reps)
+    moved = lambda same, controls: (1 if same else 2) * sbytes // (2 if controls else 1)  # noqa: E731
+    base = {key: row(rows, name, dtype, n, batch, ts[name], moved(*key)) for key, name in yards.items()}
+    for name, (bits, controls, same) in cases.items():
+        row(rows, name, dtype, n, batch, ts[name], moved(same, controls), {'time_over_pauli_cross': base[(same, controls)]})
+    del ket, bra
+    torch.cuda.empty_cache()
+
+
+def trainable_ucry(rows, n, k, reps):
+    """Forward plus backward of a trainable ``ucry`` with k select wires against a forward plus backward of
+    ``cir.pauli_rot('y')`` on the same target (one rotation and one cross), complex64, un-batched, from |0..0> behind a
+    layer of Hadamards."""
+    res = {}
+    for name in ("pauli_rot('y') forward + backward", f'trainable ucry k={k} forward + backward'):
+        cir = dq.QubitCircuit(n)
+        cir.hlayer()
+        if name.startswith('pauli'):
+            cir.pauli_rot('y', wires=[n - 3])
+        else:
+            cir.ucry(wires=list(range(k)) + [n - 3], requires_grad=True)
+        cir.observable(n - 3)
+        cir.to('cuda')
+
+        def step(c=cir):
+            c.zero_grad(set_to_none=True)
+            c()
+            c.expectation().sum().backward()
+
+        res[name] = (cir, step)
+    ts = timed_group({name: step for name, (_, step) in res.items()}, reps)
+    names = list(res)
+    circuit_row(rows, f'n = {n}: {names[0]}', res[names[0]][0], ts[names[0]])
+    circuit_row(rows, f'n = {n}: {names[1]}', res[names[1]][0], ts[names[1]],
+                {'time_over_pauli_rot': round(ts[names[1]][0] / ts[names[0]][0], 3)})
+    print(f'  x{ts[names[1]][0] / ts[names[0]][0]:.3f} pauli_rot', flush=True)
+    del res
+    torch.cuda.empty_cache()
+
+
 def circuit_row(rows, what, cir, t, extra=None):
     r = {'what': what, 'dtype': 'complex64', 'qubits': cir.nqubit, 'operators': len(cir.operators), 'ms': round(t[0], 3),
          'ms_min': round(t[1], 3), 'ms_max': round(t[2], 3)}
@@ -249,6 +326,7 @@ def prepare(rows, n, k, reps):
 def main():
     quick = '--quick' in sys.argv
     loop_only = '--loop-only' in sys.argv
+    cross_only = '--cross-only' in sys.argv
     out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
     assert torch.cuda.is_available(), 'bench_mux.py measures on the GPU: there is no fallback'
     prop = torch.cuda.get_device_properties(0)
@@ -257,14 +335,18 @@ def main():
            'host': platform.processor() or platform.machine()}
     print('box:', json.dumps(box), flush=True)
     rows = []
+    reps = 5 if quick else 11
+    points = ((torch.complex64, 22, 4), (torch.complex128, 21, 4)) if quick else ((torch.complex64, 28, 4), (torch.complex128, 27, 4))
     if not loop_only:
-        reps = 5 if quick else 11
-        points = ((torch.complex64, 22, 4), (torch.complex128, 21, 4)) if quick else ((torch.complex64, 28, 4), (torch.complex128, 27, 4))
+        for dtype, n, batch in points:
+            cross_kernels(rows, dtype, n, batch, reps)
+        trainable_ucry(rows, 16 if quick else 26, 9, 3 if quick else 7)
+    if not loop_only and not cross_only:
         for dtype, n, batch in points:
             kernels(rows, dtype, n, batch, reps)
         dense_against_multiplexer(rows, 16 if quick else 26, 9, 3 if quick else 7)
         prepare(rows, 16 if quick else 26, 10 if quick else 20, 3 if quick else 7)
-    for ncount in ((4, 6) if quick else (8, 10, 12)):
+    for ncount in () if cross_only else ((4, 6) if quick else (8, 10, 12)):
         hhl_rotation(rows, ncount, 3 if quick else 5, loop_only)
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
