@@ -34,7 +34,11 @@ from .layer import (
     U3Layer, XLayer, YLayer, ZLayer,
 )
 from .operation import Channel, Gate, Layer, Operation
-from .qmath import amplitude_encoding, expectation, expectation_cost, ising_cost, measure, meyer_wallach_measure, multi_kron, partial_trace
+from .pauli_sum import PauliSum
+from .qmath import (
+    amplitude_encoding, apply_pauli_sum, expectation, expectation_cost, expectation_pauli_sum, ising_cost, measure,
+    meyer_wallach_measure, multi_kron, partial_trace,
+)
 from .state import DistributedQubitState, QubitState
 from .utils import CapturedGraph, dtype_map
 from . import qasm3  # noqa: E402  (after the circuit classes it builds on)

@@ -168,6 +168,9 @@ _SIGNATURES = {
     'dq_apply_excite_axpby_{s}': (_i, [_vp, _vp, _vp, _i, _u64, _u64, _u64, _i, _i, _ip, _i, _i64, _vp]),
     'dq_excite_cross_ws_bytes': (_i64, [_i, _i64, _i, _i]),
     'dq_excite_cross_{s}': (_i, [_vp, _vp, _u64, _u64, _u64, _i, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),
+    'dq_apply_psum_axpby_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
+    'dq_psum_cross_ws_bytes': (_i64, [_i, _i64, _i, _i]),
+    'dq_psum_cross_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

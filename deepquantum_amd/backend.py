@@ -1513,3 +1513,112 @@ def excite_cross(bra: torch.Tensor, ket: torch.Tensor, spec) -> torch.Tensor:
         return _diag_double(double)
     mid = (xmask, amask, zmask, negate, n, _lib.int_array(controls), len(controls))
     return _cross_reduce('dq_excite_cross', 'dq_excite_cross_ws_bytes', bra, ket, mid)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Sums of Pauli strings (csrc/dq_psum.hip): H = sum_t h_t P_t, grouped by flip mask, the whole sum in one launch
+class PsumTable:
+    """The table of ``dq_apply_psum_axpby_*`` / ``dq_psum_cross_*`` for a register of ``nqubit`` wires, from host lists:
+    ``xmasks`` (G,), ``bounds`` (2G + 1,), ``zmasks`` (T,) and ``weights`` (T,) as include/dq_hip.h section 13 describes
+    them.  Checked here, once -- the kernels cannot -- kept as CPU tensors, and handed out per device by :meth:`on`
+    (cached; the first use on a device copies four small tensors, which a graph capture does not allow: run once before
+    capturing).  Pickles without the device copies."""
+
+    def __init__(self, nqubit: int, xmasks: Sequence[int], bounds: Sequence[int], zmasks: Sequence[int], weights: Sequence[float]):
+        n, g, t = int(nqubit), len(xmasks), len(zmasks)
+        if n < 1 or n > 40:
+            raise ValueError(f'PsumTable: nqubit={nqubit} out of range [1, 40]')
+        if g < 1 or t < 1 or len(bounds) != 2 * g + 1 or len(weights) != t:
+            raise ValueError(f'PsumTable: {g} groups, {len(bounds)} bounds, {t} masks and {len(weights)} weights do not fit '
+                             'together (at least one group and one term; 2G + 1 bounds)')
+        if any(int(m) < 0 or int(m) >> n for m in (*xmasks, *zmasks)):
+            raise ValueError(f'PsumTable: every mask must lie in [0, 2**{n})')
+        bounds = [int(b) for b in bounds]
+        if bounds[0] != 0 or bounds[-1] != t or any(lo > hi for lo, hi in zip(bounds, bounds[1:])):
+            raise ValueError(f'PsumTable: bounds must rise from 0 to the number of terms ({t}), got {bounds}')
+        self.nqubit, self.ngroups, self.nterms = n, g, t
+        self._host = (torch.tensor([int(m) for m in xmasks], dtype=torch.int64), torch.tensor(bounds, dtype=torch.int32),
+                      torch.tensor([int(m) for m in zmasks], dtype=torch.int64), torch.tensor(weights, dtype=torch.float64))
+        self._devices: dict = {}
+
+    def on(self, device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(xmasks, bounds, zmasks, weights) on ``device``."""
+        device = torch.device(device)
+        if device.type == 'cpu':
+            return self._host
+        hit = self._devices.get(device)
+        if hit is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('deepquantum_amd: the first use of a Pauli sum on a device copies its table there; run '
+                                   'the step once before capturing it (dq.CapturedGraph warms up by itself)')
+            hit = self._devices[device] = tuple(own(t.to(device)) for t in self._host)
+        pin_if_capturing(*hit)
+        return hit
+
+    def __getstate__(self):
+        return {**self.__dict__, '_devices': {}}
+
+
+def _psum_args(state: torch.Tensor, table: PsumTable, what: str) -> int:
+    n = _nqubit(state)
+    if not isinstance(table, PsumTable):
+        raise ValueError(f'{what}: the table must be a backend.PsumTable, got {type(table).__name__}')
+    if not state.is_contiguous():
+        raise ValueError(f'{what}: state must be contiguous')
+    if table.nqubit != n:
+        raise ValueError(f'{what}: the table is for {table.nqubit} qubits, the state has {n}')
+    return n
+
+
+def _psum_apply_double(x: torch.Tensor, table: PsumTable) -> torch.Tensor:
+    """H x in complex128, group by group (CPU test double only)."""
+    xmasks, bounds, zmasks, weights = (t.tolist() for t in table.on('cpu'))
+    j = torch.arange(x.shape[-1])
+    y = torch.zeros_like(x)
+    for g, xmask in enumerate(xmasks):
+        w = torch.zeros(x.shape[-1], dtype=torch.complex128)
+        for t in range(bounds[2 * g], bounds[2 * g + 2]):
+            par = j & zmasks[t]
+            for sh in (32, 16, 8, 4, 2, 1):
+                par = par ^ (par >> sh)
+            w += (weights[t] if t < bounds[2 * g + 1] else 1j * weights[t]) * (1 - 2 * (par & 1)).to(torch.complex128)
+        y += (w * x)[:, j ^ xmask]
+    return y
+
+
+def apply_psum_axpby(state: torch.Tensor, table: PsumTable, a, c, mode: str = 'gate', out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[b] = a[b] state[b] + c[b] H state[b] for the sum of Pauli strings H of ``table``, in one launch: G + 1 reads and
+    one write of the state for G groups, whatever the number of strings (``dq_apply_psum_axpby_*``).  ``a``, ``c``:
+    complex, one value or one per sample.  The support of H is the whole state, so ``mode`` -- 'gate' or 'map', as the
+    generator nodes of ``ops`` pass it -- changes nothing.  Out of place only: ``out`` must not overlap ``state``."""
+    what = 'apply_psum_axpby'
+    if mode not in ('gate', 'map'):
+        raise ValueError(f"{what}: mode must be 'gate' or 'map', got {mode!r}")
+    n = _psum_args(state, table, what)
+    a, c = _pauli_coef(a, state, what), _pauli_coef(c, state, what)
+    out = _check_out(state, out, what, in_place=False)
+    if not _use_hip(state):
+        def double():
+            x = state.to(torch.complex128)
+            return out.copy_((a.reshape(-1, 1) * x + c.reshape(-1, 1) * _psum_apply_double(x, table)).to(state.dtype))
+
+        return _diag_double(double)
+    coef = _axpby_coef(a, c)
+    ptrs = [_ptr(t) for t in table.on(state.device)]
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_psum_axpby', state, _ptr(state, lo), _ptr(out, lo), _ptr(coef, lo), *ptrs, table.ngroups, table.nterms,
+              n, hi - lo)
+    return out
+
+
+def psum_cross(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.Tensor:
+    """out[b] = sum_i conj(bra[b, i]) (H ket[b])[i] for the sum of Pauli strings H of ``table``, in one launch: complex128
+    (B,), bitwise reproducible (``dq_psum_cross_*``).  ``bra`` and ``ket`` the same buffer: G reads of the state for G
+    groups (one of them without a flip over 16-byte vectors), else G + 1.  The workspace comes from PyTorch's allocator
+    (legal under capture)."""
+    n = _psum_args(ket, table, 'psum_cross')
+    _check_bra(bra, ket, 'psum_cross')
+    if not _use_hip(ket):
+        return _diag_double(lambda: (bra.to(torch.complex128).conj() * _psum_apply_double(ket.to(torch.complex128), table)).sum(dim=-1))
+    mid = (*(_ptr(t) for t in table.on(ket.device)), table.ngroups, table.nterms, n)
+    return _cross_reduce('dq_psum_cross', 'dq_psum_cross_ws_bytes', bra, ket, mid)

@@ -400,6 +400,16 @@ class QubitCircuit(Operation):
             raise NotImplementedError('expectation_cost: den_mat=True (density matrices) is not supported')
         return qmath.expectation_cost(self.state, self.nqubit, cost, wires)
 
+    def expectation_pauli_sum(self, H) -> torch.Tensor:
+        """``Re <psi|H|psi>`` of the final state of the last forward for a sum of Pauli strings ``H`` -- a ``PauliSum`` or
+        the list form ``[[0.5, 'x0y1'], [-1, 'z3y1'], [0.25, '']]``: (B,) real, or 0-d for a single state, the whole sum
+        in one launch; see :func:`qmath.expectation_pauli_sum`."""
+        if self.state is None:
+            raise RuntimeError('expectation_pauli_sum: run the circuit first')
+        if self.den_mat:
+            raise NotImplementedError('expectation_pauli_sum: den_mat=True (density matrices) is not supported')
+        return qmath.expectation_pauli_sum(self.state, self.nqubit, H)
+
     def expectation(self, shots: int | None = None) -> torch.Tensor:
         """Expectation value of every registered observable, stacked on the last dimension
         (reference: circuit.py:381-428)."""
@@ -1040,6 +1050,9 @@ class DistributedQubitCircuit(QubitCircuit):
 
     def entanglement_entropy(self, wires: int | list[int], alpha: float = 1.0, base: float | None = None) -> torch.Tensor:
         raise NotImplementedError('entanglement_entropy: sharded states are not supported')
+
+    def expectation_pauli_sum(self, H) -> torch.Tensor:
+        raise NotImplementedError('expectation_pauli_sum: sharded states are not supported')
 
     def expectation(self, shots: int | None = None) -> torch.Tensor:
         from . import executor

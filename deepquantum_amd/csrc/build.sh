@@ -5,7 +5,7 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="${here}/../libdqhip.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-srcs=(dq_capi.hip dq_gate.hip dq_dense.hip dq_pass.hip dq_wave.hip dq_reduce.hip dq_dist.hip dq_plan.hip dq_entangle.hip dq_rdm.hip dq_sample.hip dq_diag.hip dq_pauli.hip dq_perm.hip dq_mux.hip dq_muxgrad.hip dq_excite.hip)
+srcs=(dq_capi.hip dq_gate.hip dq_dense.hip dq_pass.hip dq_wave.hip dq_reduce.hip dq_dist.hip dq_plan.hip dq_entangle.hip dq_rdm.hip dq_sample.hip dq_diag.hip dq_pauli.hip dq_perm.hip dq_mux.hip dq_muxgrad.hip dq_excite.hip dq_psum.hip)
 objs=()
 mkdir -p "${here}/build"
 # any header of this directory newer than object $1?

@@ -1,0 +1,301 @@
+// Sums of Pauli strings, H = sum_t h_t P_t with real h_t: a a-plus-c-H combination and a cross reduction, the whole
+// Hamiltonian in ONE launch each.
+//
+//     dq_apply_psum_axpby : out[b, i] = a[b] in[b, i] + c[b] (H in_b)[i]            (out of place only)
+//     dq_psum_cross       : out[b] = sum_i conj(bra[b, i]) (H ket_b)[i]
+//
+// The terms are grouped by flip mask.  For the group with mask x
+//     (G_x psi)[i] = w_x(i ^ x) psi[i ^ x],      w_x(j) = sum_{t in group} h_t i^{ny_t} (-1)^popc(j & z_t)
+// and every i^{ny_t} is real or imaginary, so w_x(j) = wr(j) + i wi(j) with two real signed sums.  The table (device
+// memory, built once per Hamiltonian by the caller) holds, for G groups and T terms,
+//     xmasks[G]; bounds[2G + 1]: the start of group g's real-weight terms, bounds[2g], of its imaginary-weight terms,
+//     bounds[2g + 1], and their end, bounds[2g + 2]; zmasks[T]; weights[T], the sign of i^{ny_t} folded in.
+//
+// Geometry.  That of dq_stream.hpp, in GATHER form: the item is an OUTPUT vector, never a pair.  For its ST_UNROLL output
+// vectors a lane walks the groups: it loads the partner vectors v ^ (x >> VB) (four loads in flight), swaps the elements
+// of a complex64 vector when bit 0 of x is set, sums wr and wi at the source index of each amplitude over the group's
+// terms, multiplies once per group and amplitude, and accumulates.  Nobody reads what another lane writes only because
+// in and out are disjoint.  The traffic is G + 1 reads of the state -- the group with no flip over vector indices reuses
+// the own vector -- and one write.
+//
+// The group and term loops are uniform over the workgroup: the table comes in through scalar loads.  A z mask is split
+// at the unit size: the part at or above it meets the unit's index, which is uniform -- a scalar parity folded into the
+// weight's sign -- and only the low 10 (complex128) or 11 (complex64) bits cost vector instructions, five per term and
+// amplitude (and, bit count, shift into the sign bit, xor, add).
+//
+// Safety.  Every x is masked with 2^n - 1 and every bound clamped to [0, T] in the kernel (scalar, once per group):
+// whatever the table holds, no load leaves the sample or the table.  A lane whose vector lies beyond a small sample
+// loads vector 0's partners and stores nothing.
+//
+// Reduction.  The sums over the terms are formed in the state's precision, the products and the sum over groups and
+// amplitudes in double; the rest is dq_stream.hpp's fixed-order scheme.
+#include "dq_stream.hpp"
+
+namespace dq {
+
+namespace {
+
+struct PsumTable {
+    const uint64_t* __restrict__ xmasks;
+    const int* __restrict__ bounds;
+    const uint64_t* __restrict__ zmasks;
+    const double* __restrict__ weights;
+    int ngroups, nterms;
+};
+
+__device__ __forceinline__ float flip_sign(float h, unsigned par) { return __uint_as_float(__float_as_uint(h) ^ (par << 31)); }
+__device__ __forceinline__ double flip_sign(double h, unsigned par) {
+    return __hiloint2double(__double2hiint(h) ^ (int)(par << 31), __double2loint(h));
+}
+
+// w[u][e] = sum over the terms [t0, t1) of weights[t] (-1)^popc(j & zmasks[t]) for the source indices j = (jhigh, jlow[u][e])
+template <typename T, int VEC>
+__device__ __forceinline__ void signed_sum(const PsumTable& tb, int t0, int t1, int sbits, uint64_t jhigh,
+                                           const unsigned (&jlow)[ST_UNROLL][VEC], T (&w)[ST_UNROLL][VEC]) {
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) w[u][e] = (T)0;
+    for (int t = t0; t < t1; ++t) {
+        const uint64_t z = tb.zmasks[t];
+        const unsigned zlow = (unsigned)z & ((1u << sbits) - 1u);
+        const T h = (T)flip_sign(tb.weights[t], (unsigned)__popcll(jhigh & (z >> sbits)));      // (uniform)
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) w[u][e] += flip_sign(h, (unsigned)__popc(jlow[u][e] & zlow));
+    }
+}
+
+// What a lane holds of group g: the partner vectors q and the weights wr + i wi at the source index of each amplitude.
+// `own`: the lane's own vectors of the same state, or nullptr where the caller has not loaded them.
+template <typename T, int VEC, typename Q>
+__device__ __forceinline__ void load_group(const PsumTable& tb, int g, int n, const Q* __restrict__ src, uint64_t unit,
+                                           const uint64_t (&vec)[ST_UNROLL], const Q* own, Q (&q)[ST_UNROLL], int& x0,
+                                           T (&wr)[ST_UNROLL][VEC], T (&wi)[ST_UNROLL][VEC]) {
+    constexpr int VB = VEC == 2 ? 1 : 0;
+    constexpr int sbits = ST_UNIT_BITS + VB;
+    const uint64_t x = tb.xmasks[g] & ((1ull << n) - 1ull);
+    const uint64_t vx = x >> VB;
+    x0 = (int)(x & (uint64_t)VB);
+    if (own != nullptr && vx == 0) {
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) q[u] = own[u];
+    } else {
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) q[u] = src[vec[u] ^ vx];
+    }
+    unsigned jlow[ST_UNROLL][VEC];
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+            jlow[u][e] = ((((unsigned)(u * ST_THREADS) + threadIdx.x) << VB | (unsigned)e) ^ (unsigned)x) & ((1u << sbits) - 1u);
+    const uint64_t jhigh = unit ^ (x >> sbits);
+    const int t0 = min(max(tb.bounds[2 * g], 0), tb.nterms), t1 = min(max(tb.bounds[2 * g + 1], 0), tb.nterms),
+              t2 = min(max(tb.bounds[2 * g + 2], 0), tb.nterms);
+    signed_sum<T, VEC>(tb, t0, t1, sbits, jhigh, jlow, wr);
+    signed_sum<T, VEC>(tb, t1, t2, sbits, jhigh, jlow, wi);
+}
+
+// The lane's vectors of unit `unit`; one that lies beyond the sample is replaced by vector 0 and marked in `live`.
+__device__ __forceinline__ unsigned unit_vectors(uint64_t unit, uint64_t nvec, uint64_t (&vec)[ST_UNROLL]) {
+    unsigned live = 0;
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u) {
+        const uint64_t v = (unit << ST_UNIT_BITS) + (uint64_t)(u * ST_THREADS) + threadIdx.x;
+        if (v < nvec) live |= 1u << u;
+        vec[u] = v < nvec ? v : 0;
+    }
+    return live;
+}
+
+template <typename T>
+__global__ __launch_bounds__(ST_THREADS) void psum_axpby_kernel(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
+                                                                const double* __restrict__ coef, PsumTable tb, int n,
+                                                                uint64_t nvec) {
+    using Q = typename Vec16<T>::type;
+    constexpr int VEC = 16 / (int)sizeof(cx<T>);
+    const uint64_t b = blockIdx.y;
+    const Q* src = reinterpret_cast<const Q*>(in + (b << n));
+    Q* dst = reinterpret_cast<Q*>(out + (b << n));
+    const cx<T> a = mk<T>((T)coef[4 * b], (T)coef[4 * b + 1]), c = mk<T>((T)coef[4 * b + 2], (T)coef[4 * b + 3]);
+    for (uint64_t unit = blockIdx.x; (unit << ST_UNIT_BITS) < nvec; unit += gridDim.x) {
+        uint64_t vec[ST_UNROLL];
+        const unsigned live = unit_vectors(unit, nvec, vec);
+        Q own[ST_UNROLL];
+        cx<T> acc[ST_UNROLL][VEC];
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            own[u] = src[vec[u]];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[u][e] = mk<T>((T)0, (T)0);
+        }
+        for (int g = 0; g < tb.ngroups; ++g) {
+            Q q[ST_UNROLL];
+            T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
+            int x0;
+            load_group<T, VEC, Q>(tb, g, n, src, unit, vec, own, q, x0, wr, wi);
+#pragma unroll
+            for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc[u][e] = cfma(mk<T>(wr[u][e], wi[u][e]), vec_get<T>(q[u], e ^ x0), acc[u][e]);
+        }
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            Q r;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) vec_set(r, e, cfma(c, acc[u][e], cmul(a, vec_get<T>(own[u], e))));
+            if (live >> u & 1u) dst[vec[u]] = r;
+        }
+    }
+}
+
+// ws[b, blockIdx.x] = this workgroup's part of sum_i conj(bra_i) (H ket)_i
+template <typename T, bool SAME>
+__global__ __launch_bounds__(ST_THREADS) void psum_cross_kernel(const cx<T>* __restrict__ bra, const cx<T>* __restrict__ ket,
+                                                                PsumTable tb, int n, uint64_t nvec, double* __restrict__ ws) {
+    using Q = typename Vec16<T>::type;
+    constexpr int VEC = 16 / (int)sizeof(cx<T>);
+    __shared__ double sh[ST_THREADS / 64][2];
+    const uint64_t b = blockIdx.y;
+    const Q* pb = reinterpret_cast<const Q*>(bra + (b << n));
+    const Q* pk = reinterpret_cast<const Q*>(ket + (b << n));
+    double re = 0.0, im = 0.0;
+    for (uint64_t unit = blockIdx.x; (unit << ST_UNIT_BITS) < nvec; unit += gridDim.x) {
+        uint64_t vec[ST_UNROLL];
+        const unsigned live = unit_vectors(unit, nvec, vec);
+        Q own[ST_UNROLL];                               // the bra's vectors: with SAME the ket's own as well
+        double2 hk[ST_UNROLL][VEC];                     // (H ket) at the lane's amplitudes
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            own[u] = pb[vec[u]];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) hk[u][e] = make_double2(0.0, 0.0);
+        }
+        for (int g = 0; g < tb.ngroups; ++g) {
+            Q q[ST_UNROLL];
+            T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
+            int x0;
+            load_group<T, VEC, Q>(tb, g, n, pk, unit, vec, SAME ? own : nullptr, q, x0, wr, wi);
+#pragma unroll
+            for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const cx<T> s = vec_get<T>(q[u], e ^ x0);
+                    hk[u][e] = cfma(make_double2((double)wr[u][e], (double)wi[u][e]), make_double2((double)s.x, (double)s.y),
+                                    hk[u][e]);
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                if (live >> u & 1u) {
+                    const cx<T> o = vec_get<T>(own[u], e);
+                    const double ar = (double)o.x, ai = (double)o.y;
+                    re = fma(ar, hk[u][e].x, fma(ai, hk[u][e].y, re));
+                    im = fma(ar, hk[u][e].y, fma(-ai, hk[u][e].x, im));
+                }
+            }
+    }
+    write_partial(re, im, sh, ws);
+}
+
+// The four arrays of the table: non-null, aligned to their element, at least one group and one term
+int check_table(const char* what, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks, const double* weights,
+                int ngroups, int nterms, PsumTable* tb) {
+    if (!xmasks || !bounds || !zmasks || !weights) {
+        set_error("%s: null table pointer", what);
+        return DQ_ERR_ARG;
+    }
+    if ((reinterpret_cast<uintptr_t>(xmasks) & 7) || (reinterpret_cast<uintptr_t>(zmasks) & 7) ||
+        (reinterpret_cast<uintptr_t>(weights) & 7) || (reinterpret_cast<uintptr_t>(bounds) & 3)) {
+        set_error("%s: xmasks, zmasks and weights must be 8-byte aligned, bounds 4-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    if (ngroups < 1) {
+        set_error("%s: ngroups=%d, at least one group is needed", what, ngroups);
+        return DQ_ERR_ARG;
+    }
+    if (nterms < 1) {
+        set_error("%s: nterms=%d, at least one term is needed", what, nterms);
+        return DQ_ERR_ARG;
+    }
+    *tb = PsumTable{xmasks, bounds, zmasks, weights, ngroups, nterms};
+    return DQ_OK;
+}
+
+template <typename T>
+int axpby_impl(const void* in, void* out, const double* coef, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks,
+               const double* weights, int ngroups, int nterms, int n, int64_t batch, dq_stream_t stream) {
+    constexpr bool C128 = sizeof(T) == 8;
+    const char* what = "dq_apply_psum_axpby";
+    if (int rc = check_states(what, in, out, 1, n, batch, sizeof(cx<T>), DISJOINT)) return rc;
+    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
+        set_error("%s: coef must be non-null and 8-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    PsumTable tb;
+    if (int rc = check_table(what, xmasks, bounds, zmasks, weights, ngroups, nterms, &tb)) return rc;
+    const uint64_t nvec = vectors_of(n, C128);
+    hipLaunchKernelGGL((psum_axpby_kernel<T>), dim3(blocks_of(nvec), (unsigned)batch), dim3(ST_THREADS), 0, as_stream(stream),
+                       static_cast<const cx<T>*>(in), static_cast<cx<T>*>(out), coef, tb, n, nvec);
+    return check_launch(what);
+}
+
+template <typename T>
+int cross_impl(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks,
+               const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws, int64_t ws_bytes,
+               dq_stream_t stream) {
+    constexpr bool C128 = sizeof(T) == 8;
+    const char* what = "dq_psum_cross";
+    if (n < 1 || n > 40) {
+        set_error("%s: n=%d out of range [1, 40]", what, n);
+        return DQ_ERR_ARG;
+    }
+    if (int rc = check_batch(what, batch)) return rc;
+    PsumTable tb;
+    if (int rc = check_table(what, xmasks, bounds, zmasks, weights, ngroups, nterms, &tb)) return rc;
+    if (int rc = check_cross(what, bra, ket, nullptr, false, out, ws, ws_bytes, n, batch, C128)) return rc;
+    const uint64_t nvec = vectors_of(n, C128);
+    const unsigned nblk = blocks_of(nvec);
+    const dim3 grid(nblk, (unsigned)batch);
+    const cx<T>* pb = static_cast<const cx<T>*>(bra);
+    const cx<T>* pk = static_cast<const cx<T>*>(ket);
+    double* part = static_cast<double*>(ws);
+    hipStream_t s = as_stream(stream);
+    if (bra == ket) hipLaunchKernelGGL((psum_cross_kernel<T, true>), grid, dim3(ST_THREADS), 0, s, pb, pk, tb, n, nvec, part);
+    else hipLaunchKernelGGL((psum_cross_kernel<T, false>), grid, dim3(ST_THREADS), 0, s, pb, pk, tb, n, nvec, part);
+    return finish_cross(what, part, nblk, batch, out, s);
+}
+
+}  // namespace
+}  // namespace dq
+
+extern "C" int dq_apply_psum_axpby_c64(const void* in, void* out, const double* coef, const uint64_t* xmasks, const int* bounds,
+                                       const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
+                                       int64_t batch, dq_stream_t stream) {
+    return dq::axpby_impl<float>(in, out, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, stream);
+}
+extern "C" int dq_apply_psum_axpby_c128(const void* in, void* out, const double* coef, const uint64_t* xmasks, const int* bounds,
+                                        const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
+                                        int64_t batch, dq_stream_t stream) {
+    return dq::axpby_impl<double>(in, out, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, stream);
+}
+
+extern "C" int64_t dq_psum_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross) {
+    (void)cross;        // bra != ket reads one vector more per item and writes the same partial sums
+    return dq::cross_ws_bytes_or_refuse(n, batch, is_c128 != 0);
+}
+
+extern "C" int dq_psum_cross_c64(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds,
+                                 const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n, int64_t batch,
+                                 double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
+    return dq::cross_impl<float>(bra, ket, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, out, ws, ws_bytes, stream);
+}
+extern "C" int dq_psum_cross_c128(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds,
+                                  const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n, int64_t batch,
+                                  double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
+    return dq::cross_impl<double>(bra, ket, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, out, ws, ws_bytes, stream);
+}

@@ -920,11 +920,11 @@ class _Generator:
     sign: int           # s: G^dagger = s G
     axpby: str          # the names of the three functions of `backend`, looked up there at call time (tests wrap them)
     cross: str
-    rot: str
+    rot: str | None     # (None, as `rate` and `gtheta`: a family without a rotation -- sums of Pauli strings)
     spread: Callable    # spec -> (leading, trailing): backend.f(<states>, *leading, <parameters>, *trailing[, mode])
     inner: Callable     # (gen, x, gy, like) -> <x, gy> over the support, complex128 (B,), like ``like``
-    rate: Callable      # theta_t -> r theta_t, complex128
-    gtheta: Callable    # cross(gx, x) -> gtheta, real
+    rate: Callable | None       # theta_t -> r theta_t, complex128
+    gtheta: Callable | None     # cross(gx, x) -> gtheta, real
 
     def adjoint(self, t: torch.Tensor) -> torch.Tensor:
         """s t"""
@@ -1119,6 +1119,39 @@ _EXCITATIONS = _Generator(
     rate=lambda theta_t: theta_t.to(torch.complex128),
     gtheta=lambda z: z.real,
 )
+
+
+# Sums of Pauli strings (csrc/dq_psum.hip): H = sum_t h_t P_t with real h_t is Hermitian and its support is the whole state --
+# 'gate' and 'map' coincide -- so the inner product is the cross of the empty Pauli string without controls.  The spec is
+# the `backend.PsumTable`.  No rotation: exp(-i t H) is not a combination of I and H.
+_PAULI_SUMS = _Generator(
+    name='psum', sign=+1, axpby='apply_psum_axpby', cross='psum_cross', rot=None,
+    spread=lambda spec: ((spec,), ()),
+    inner=lambda gen, x, gy, like: _gen_cross((_PAULI_STRINGS, (0, 0, ())), x, gy),
+    rate=None, gtheta=None,
+)
+
+
+def _psum_table(H, what: str) -> backend.PsumTable:
+    table = getattr(H, 'table', H)
+    if not isinstance(table, backend.PsumTable):
+        raise ValueError(f'{what}: H must be a PauliSum (or its backend.PsumTable), got {type(H).__name__}')
+    return table
+
+
+def psum_axpby(state: torch.Tensor, a, c, H) -> torch.Tensor:
+    """Differentiable ``a x + c H x`` on a (B, 2**n) state for the sum of Pauli strings ``H`` (a ``PauliSum``); ``a``, ``c``
+    complex, one value or one per sample.  One launch, G + 1 reads and one write of the state for G flip masks, whatever
+    the number of strings; the coefficients of H are constants.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    return _gen_axpby((_PAULI_SUMS, _psum_table(H, 'psum_axpby')), state, a, c, 'gate')
+
+
+def psum_cross(bra: torch.Tensor, ket: torch.Tensor, H) -> torch.Tensor:
+    """Differentiable ``sum_i conj(bra_i) (H ket)_i`` of two (B, 2**n) states for the sum of Pauli strings ``H`` (a
+    ``PauliSum``): complex128 (B,), one launch.  Pass the same tensor twice for ``<H>`` (the own vectors are read once).
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    return _gen_cross((_PAULI_SUMS, _psum_table(H, 'psum_cross')), bra, ket)
 
 
 def _pauli_masks(xmask: int, zmask: int, controls: Sequence[int]) -> tuple[int, int, tuple]:

@@ -541,6 +541,37 @@ def expectation_cost(state: torch.Tensor, nqubit: int, cost: torch.Tensor, wires
     return val.squeeze(0) if single else val
 
 
+def _pauli_sum(H: Any, nqubit: int, what: str):
+    from .pauli_sum import PauliSum
+
+    if not isinstance(H, PauliSum):
+        H = PauliSum(H, nqubit)
+    if H.nqubit != int(nqubit):
+        raise ValueError(f'{what}: the PauliSum is for {H.nqubit} qubits, the state has {int(nqubit)}')
+    return H
+
+
+def expectation_pauli_sum(state: torch.Tensor, nqubit: int, H: Any) -> torch.Tensor:
+    """``Re <psi|H|psi>`` for a sum of Pauli strings ``H`` -- a :class:`PauliSum`, or the list form it is built from,
+    ``[[0.5, 'x0y1'], [-1, 'z3y1'], [0.25, '']]`` (build the ``PauliSum`` once where the call repeats): (B,) real in the
+    state's precision, or 0-d for a single state.  ``state`` in the forms of :func:`reduced_density_matrix`.  One launch
+    for the whole sum, one read of the state per distinct flip mask, accumulated in double (``dq_psum_cross_*``);
+    differentiable to any order in the state (the coefficients are constants).  Not normalised."""
+    flat, single = _state_batch(state, nqubit, 'expectation_pauli_sum')
+    val = ops.psum_cross(flat, flat, _pauli_sum(H, nqubit, 'expectation_pauli_sum')).real.to(flat.real.dtype)
+    return val.squeeze(0) if single else val
+
+
+def apply_pauli_sum(state: torch.Tensor, nqubit: int, H: Any) -> torch.Tensor:
+    """``H|psi>`` for a sum of Pauli strings ``H`` (as in :func:`expectation_pauli_sum`), with the shape of ``state`` and
+    in its complex dtype: what variance, Krylov and imaginary-time steps are made of.  One launch for the whole sum
+    (``dq_apply_psum_axpby_*``); differentiable to any order in the state."""
+    flat, _ = _state_batch(state, nqubit, 'apply_pauli_sum')
+    zero = torch.zeros(flat.shape[0], dtype=torch.complex128, device=flat.device)      # (made on the device: legal under capture)
+    out = ops.psum_axpby(flat, zero, torch.ones_like(zero), _pauli_sum(H, nqubit, 'apply_pauli_sum'))
+    return out.reshape(state.shape)
+
+
 def ising_cost(nqubit: int, terms: list, dtype: torch.dtype | None = None, device: Any = None) -> torch.Tensor:
     """The table ``c[i] = sum_j w_j (-1)^popcount(i & zmask_j)`` over all ``nqubit`` wires of the Ising polynomial
     ``terms = [(weight, [wires...]), ...]`` (a term's sign is the product of Z eigenvalues of its wires in basis state i,

@@ -743,6 +743,47 @@ int dq_excite_cross_c64(const void* bra, const void* ket, uint64_t xmask, uint64
 int dq_excite_cross_c128(const void* bra, const void* ket, uint64_t xmask, uint64_t amask, uint64_t zmask, int negate, int n,
                          const int* controls, int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 13. Sums of Pauli strings (csrc/dq_psum.hip; added within ABI 30, presence is checked by symbol): H = sum_t h_t P_t
+ *     with real h_t and P_t = (x_t, z_t) as in section 9, the whole sum in ONE launch.  The terms are grouped by flip
+ *     mask; for the group with mask x
+ *         (G_x psi)[i] = w_x(i ^ x) psi[i ^ x],      w_x(j) = sum_{t in group} h_t i^{ny_t} (-1)^popc(j & z_t)
+ *     and H = sum_x G_x.  The table is four DEVICE arrays, shared by the batch, for `ngroups` groups and `nterms` terms:
+ *         xmasks[ngroups]        uint64, the flip mask of each group
+ *         bounds[2 ngroups + 1]  int32: group g's terms with a real i^{ny_t} are [bounds[2g], bounds[2g+1]), those with
+ *                                an imaginary one [bounds[2g+1], bounds[2g+2])
+ *         zmasks[nterms]         uint64
+ *         weights[nterms]        double: h_t with the sign of i^{ny_t} (real terms) or of i^{ny_t} / i (imaginary terms)
+ *     The kernels mask every xmask with 2^n - 1 and clamp every bound to [0, nterms]: a wrong table gives a wrong state
+ *     and never a load outside the sample or the table.  1 <= n <= 40, 1 <= batch <= 65535, ngroups >= 1, nterms >= 1;
+ *     state pointers 16-byte aligned, xmasks / zmasks / weights 8-byte and bounds 4-byte aligned.  The state is read
+ *     ngroups + 1 times (once less where a group has no flip over 16-byte vectors) whatever nterms is.
+ * ------------------------------------------------------------------------------------------ */
+/* out[b, i] = a[b] * in[b, i] + c[b] * (H in_b)[i]; coef = DEVICE double [batch][4] = (Re a, Im a, Re c, Im c), rounded
+ * once to the state's real precision.  OUT OF PLACE ONLY: [in, in + batch * 2^n) and [out, ..) must not overlap
+ * (DQ_ERR_ARG, "overlap"). */
+int dq_apply_psum_axpby_c64(const void* in, void* out, const double* coef, const uint64_t* xmasks, const int* bounds,
+                            const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n, int64_t batch,
+                            dq_stream_t stream);
+int dq_apply_psum_axpby_c128(const void* in, void* out, const double* coef, const uint64_t* xmasks, const int* bounds,
+                             const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n, int64_t batch,
+                             dq_stream_t stream);
+
+/* Bytes of device workspace dq_psum_cross_* needs (one partial sum per workgroup and sample: at most 32 KiB per sample,
+ * whatever the table; `cross` != 0: bra != ket, the same amount); -1 on a bad argument. */
+int64_t dq_psum_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross);
+/* out[b] = sum_i conj(bra[b, i]) * (H ket_b)[i]: DEVICE double [batch][2] (re, im), fully overwritten.  The sums over a
+ * group's terms are formed in the state's precision, everything after them in double.  bra == ket loads the own vector
+ * once and reuses it for the group without a flip.  Workgroups write fixed-order partial sums into `ws` (at least
+ * dq_psum_cross_ws_bytes bytes, 16-byte aligned) and a second kernel adds them: no atomics, results are bitwise
+ * reproducible. */
+int dq_psum_cross_c64(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks,
+                      const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws,
+                      int64_t ws_bytes, dq_stream_t stream);
+int dq_psum_cross_c128(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks,
+                       const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws,
+                       int64_t ws_bytes, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
