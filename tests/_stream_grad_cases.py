@@ -1,8 +1,9 @@
 """The case tables and the checks that test_stream_autograd_cpu.py (through the plain-torch stand-ins) and
 test_stream_autograd_gpu.py (through the HIP kernels) run alike: every streaming node of ``ops`` -- ``_CostPhase``,
 ``_CostCross``, ``_CostScale``, ``_DiagMul``, ``_GenAxpby`` / ``_GenCross`` / ``_GenRot`` for both generator families,
-``_PermuteBasis``, ``_MuxApply`` -- differentiated in reverse and in forward mode against the closed forms of
-tests/_stream_grad_ref.py.
+``_PermuteBasis``, ``_MuxApply``, ``_MuxAxpby`` / ``_MuxCross`` / ``_MuxRot`` (the trainable multiplexers, whose parameters
+are a row of 2^k values per sample or one shared row) -- differentiated in reverse and in forward mode against the closed
+forms of tests/_stream_grad_ref.py.
 
 The shapes come from the families' kernel tests (named behind each case): at n = 11 .. 15 a sample is more than one unit
 of work, so the backward, jvp and vmap rules run on the gathered, unit-crossing and batch-strided kernel paths.  The batch
@@ -13,7 +14,14 @@ Criteria (those of test_excite_gpu.py), TOL = 1e-4 (complex64) / 1e-10 (complex1
 TOL max|ref|; a reduction-shaped one (a parameter's gradient, a cross value's tangent) within TOL |u| |v|, the norms of
 the two tensors it reduces, per sample (summed where the parameter is shared); outside the support a 'gate'-mode gradient
 bit-identical to the cotangent and a 'map' / scale-mode one exactly 0.  References are formed from the amplitudes as
-stored -- rounded to the precision under test, then taken to complex128."""
+stored -- rounded to the precision under test, then taken to complex128.
+
+The trainable multiplexers reduce per bin (the amplitudes with one select value inside the controls), so their
+reduction-shaped results -- ga, gc, gtheta, the cross and its tangent, all (B, 2^k) -- are judged per bin: entry [b, s]
+within TOL |u restricted to bin s| |v restricted to bin s| (summed over b for a shared row).  A per-sample scale would be
+2^(k/2) times looser and would hide an error confined to one bin; `negative_controls` shows on reference tensors alone
+that the per-bin rule rejects reversed select bits, a shared gradient without its sum over the batch, a conjugation on
+the wrong factor and a gtheta formed with +theta."""
 
 import numpy as np
 import torch
@@ -84,10 +92,28 @@ MUX = {
     'wave6-bit0-control': ('ry', False, lambda p: 6, lambda p: (p + 1, 3), lambda p: (0, p + 2), 2),
     'top-bit0-free': ('u', True, lambda p: p + 2, lambda p: (p - 1, p - 2, p - 3), lambda p: (1,), 1),
 }
-FAMILIES = {'diag': DIAG, 'pauli': PAULI, 'excite': EXCITE, 'perm': PERM, 'mux': MUX}
+
+
+def every_other_position(p, target=5):
+    """All n - 1 positions of n = p + 3 but the target, in a seeded order: every bin is one pair."""
+    rest = [q for q in range(p + 3) if q != target]
+    return tuple(int(rest[j]) for j in np.random.default_rng(p).permutation(len(rest)))
+
+
+MUXGRAD = {
+    # test_muxgrad_gpu.PLACEMENTS at n = p + 3 (a sample is eight units): (axis, target, bits, controls) as functions of p,
+    # batch, shared row?
+    'bit0-target-run-across': ('x', lambda p: 0, lambda p: (p, p - 1, p - 2), lambda p: (), 2, True),   # c64: the pair inside a vector
+    # the ry table route, bit 0 a select, 'map' with k + nc = 7 table bits, one launch per sample
+    'selects-both-sides-2c': ('y', lambda p: 4, lambda p: (p + 2, 0, p + 1, p, 6), lambda p: (2, p - 1), 3, False),
+    'top-target-bit0-control': ('z', lambda p: p + 2, lambda p: (p + 1, 3, 1), lambda p: (0,), 2, True),
+    'wave-selects-identity': ('i', lambda p: 7, lambda p: (8, 9), lambda p: (5, p + 1), 1, True),
+    'every-pair-a-bin': ('y', lambda p: 5, every_other_position, lambda p: (), 2, True),              # k = n - 1
+}
+FAMILIES = {'diag': DIAG, 'pauli': PAULI, 'excite': EXCITE, 'perm': PERM, 'mux': MUX, 'muxgrad': MUXGRAD}
 #: the case of each family that also runs with other cotangent and state layouts, and under vmap
 LAYOUT_CASE = {'diag': 'straddle', 'pauli': 'ctrl_low', 'excite': 'n11-weight1-bit0-a1', 'perm': 'gather-bit0-control',
-               'mux': 'wave6-bit0-control'}
+               'mux': 'wave6-bit0-control', 'muxgrad': 'selects-both-sides-2c'}
 
 
 # ---- data ------------------------------------------------------------------------------------------------------------------
@@ -112,12 +138,17 @@ class Node:
     complex128 (``vjp`` returns the states' gradients and the parameters' per-sample rows), and what the criteria need:
     ``out`` ('state' or 'reduction'), ``pair(states)`` -- the two tensors a reduction-shaped output reduces --, ``ppairs(states,
     g)`` -- those of each parameter's gradient --, ``off`` (the indices outside the support) and ``off_kind`` ('same': the
-    gradient there is the cotangent bit for bit, 'zero': exactly 0)."""
+    gradient there is the cotangent bit for bit, 'zero': exactly 0).  A parameter is one value per sample, (B,), or -- with
+    ``bins``, a ``ref.MuxBins`` -- a row per sample, (B, 2^k); its reductions are then (B, 2^k) and judged bin by bin."""
 
     def __init__(self, name, call, states, params, fwd, vjp, jvp, out='state', pair=None, ppairs=None, off=None,
-                 off_kind='same'):
+                 off_kind='same', bins=None):
         self.name, self.call, self.states, self.params, self.fwd, self.vjp, self.jvp = name, call, states, params, fwd, vjp, jvp
-        self.out, self.pair, self.ppairs, self.off, self.off_kind = out, pair, ppairs, off, off_kind
+        self.out, self.pair, self.ppairs, self.off, self.off_kind, self.bins = out, pair, ppairs, off, off_kind, bins
+
+    def scale(self, u, v):
+        """|u| |v| of the two tensors a reduction reduces: per sample (B,), or per sample and bin (B, 2^k)."""
+        return norms(u) * norms(v) if self.bins is None else self.bins.norms(u) * self.bins.norms(v)
 
 
 def param_rows(values, batch, shared):
@@ -258,7 +289,59 @@ def mux_nodes(name, dt, rng):
                  off=~_diag_ref.on_mask(n, controls), off_kind='same')]
 
 
-BUILDERS = {'diag': diag_nodes, 'pauli': pauli_nodes, 'excite': excite_nodes, 'perm': perm_nodes, 'mux': mux_nodes}
+def muxgrad_spec(name, dt):
+    p = UNIT[dt]
+    axis, ftarget, fbits, fcontrols, batch, shared = MUXGRAD[name]
+    return p + 3, (axis, ftarget(p), fbits(p), fcontrols(p)), batch, shared
+
+
+def bin_rows(rng, batch, count, shared, real=False):
+    """A parameter of the binned nodes: seeded rows (batch, 2^k) -- equal rows for a shared one -- and ``shared``."""
+    v = rng.uniform(-6, 6, (batch, count)) if real else rng.standard_normal((batch, count)) + 1j * rng.standard_normal((batch, count))
+    return param_rows(v, batch, shared)
+
+
+def muxgrad_nodes(name, dt, rng):
+    n, mux, batch, shared = muxgrad_spec(name, dt)
+    axis = mux[0]
+    fam = ref.MuxBins(n, *mux)
+    tag = f'muxgrad {name} {dt}'
+    size = (batch, 1 << n)
+    x, u = gauss(rng, size, DTYPES[dt]), gauss(rng, size, DTYPES[dt])
+    a, c, th = (bin_rows(rng, batch, fam.count, shared, real) for real in (False, False, True))
+    off = ~fam.support()
+    nodes = []
+    for mode in ('gate', 'map'):
+        nodes.append(Node(
+            f'{tag} axpby {mode}', lambda s, p, mode=mode: ops.mux_axpby(s[0], p[0], p[1], *mux, mode), [x], [a, c],
+            fwd=lambda s, p, mode=mode: fam.axpby(s[0], p[0], p[1], mode),
+            vjp=lambda s, p, g, mode=mode: (lambda r: ([r[0]], [r[1], r[2]]))(ref.binned_axpby_vjp(fam, s[0], p[0], p[1], mode, g)),
+            jvp=lambda s, p, ds, dp, mode=mode: ref.binned_axpby_jvp(fam, s[0], p[0], p[1], mode, ds[0], dp[0], dp[1]),
+            ppairs=lambda s, g: [(s[0], g), (s[0], g)], off=off, off_kind='same' if mode == 'gate' else 'zero', bins=fam))
+    nodes.append(Node(
+        f'{tag} cross, two tensors', lambda s, p: ops.mux_cross(s[0], s[1], *mux), [u, x], [],
+        fwd=lambda s, p: fam.cross(s[0], s[1]),
+        vjp=lambda s, p, g: (list(ref.binned_cross_vjp(fam, s[0], s[1], g)), []),
+        jvp=lambda s, p, ds, dp: ref.binned_cross_jvp(fam, s[0], s[1], ds[0], ds[1]),
+        out='reduction', pair=lambda s: (s[0], s[1]), off=off, off_kind='zero', bins=fam))
+    nodes.append(Node(
+        f'{tag} cross, bra is ket', lambda s, p: ops.mux_cross(s[0], s[0], *mux), [x], [],
+        fwd=lambda s, p: fam.cross(s[0], s[0]),
+        vjp=lambda s, p, g: ([sum(ref.binned_cross_vjp(fam, s[0], s[0], g))], []),
+        jvp=lambda s, p, ds, dp: ref.binned_cross_jvp(fam, s[0], s[0], ds[0], ds[0]),
+        out='reduction', pair=lambda s: (s[0], s[0]), off=off, off_kind='zero', bins=fam))
+    if axis != 'i':
+        nodes.append(Node(
+            f'{tag} rot', lambda s, p: ops.mux_rot(s[0], p[0], *mux), [x], [th],
+            fwd=lambda s, p: fam.rot(s[0], p[0]),
+            vjp=lambda s, p, g: (lambda r: ([r[0]], [r[1]]))(ref.binned_rot_vjp(fam, s[0], p[0], g)),
+            jvp=lambda s, p, ds, dp: ref.binned_rot_jvp(fam, s[0], p[0], ds[0], dp[0]),
+            ppairs=lambda s, g: [(g, s[0])], off=off, off_kind='same', bins=fam))
+    return nodes
+
+
+BUILDERS = {'diag': diag_nodes, 'pauli': pauli_nodes, 'excite': excite_nodes, 'perm': perm_nodes, 'mux': mux_nodes,
+            'muxgrad': muxgrad_nodes}
 CASE_IDS = [(family, name) for family, cases in FAMILIES.items() for name in cases]
 
 
@@ -279,7 +362,8 @@ def close_state(got, want, dt, what):
 
 
 def close_reduction(got, want, scale, dt, what):
-    """``scale``: |u| |v| per sample, or their sum for a shared parameter."""
+    """``scale``: |u| |v| per sample (per sample and bin for the binned nodes), or their sum over the samples for a shared
+    parameter."""
     err = np.abs(host(got) - want)
     print(f'{what}: err / (tol * |u| |v|) = {(err / (TOL[dt] * scale)).max():.3e}')
     assert got.shape == want.shape and np.all(err <= TOL[dt] * scale), f'{what}: {err} against {TOL[dt]} * {scale}'
@@ -319,7 +403,8 @@ def device_inputs(node, device, state_layout='plain'):
 
 def cotangent(node, dt, device, rng, batch, size, layout='plain'):
     if node.out == 'reduction':
-        g = torch.from_numpy(rng.standard_normal(batch) + 1j * rng.standard_normal(batch)).to(device)
+        shape = batch if node.bins is None else (batch, node.bins.count)
+        g = torch.from_numpy(rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).to(device)
         return g, host(g)
     return laid_out(gauss(rng, (batch, size), DTYPES[dt])[0], layout, device)
 
@@ -333,7 +418,7 @@ def check_forward(node, dt, device, state_layout='plain'):
         close_state(got, want, dt, f'{node.name} forward, state {state_layout}')
     else:
         u, v = node.pair(xr)
-        close_reduction(got, want, norms(u) * norms(v), dt, f'{node.name} forward, state {state_layout}')
+        close_reduction(got, want, node.scale(u, v), dt, f'{node.name} forward, state {state_layout}')
 
 
 def check_vjp(node, dt, device, state_layout='plain', cot_layout='plain'):
@@ -356,9 +441,9 @@ def check_vjp(node, dt, device, state_layout='plain', cot_layout='plain'):
                 assert bitwise_equal(got[:, rest], g[:, rest]), f'{what}: outside the support the gradient is not the cotangent'
     if node.params:
         for k, (got, want, (u, v)) in enumerate(zip(grads[len(xs):], want_params, node.ppairs(xr, gr))):
-            scale = norms(u) * norms(v)
+            scale = node.scale(u, v)
             if node.params[k][1]:
-                want, scale = want.sum(), scale.sum()
+                want, scale = want.sum(0), scale.sum(0)         # (one value, or one row, for all samples)
             assert got.dtype == ps[k].dtype
             close_reduction(got, want if np.iscomplexobj(pr[k]) else np.real(want), scale, dt, f'{what}: gradient of parameter {k}')
 
@@ -369,7 +454,7 @@ def check_jvp(node, dt, device):
     dxs, dxr = zip(*(laid_out(gauss(rng, x.shape, DTYPES[dt])[0], 'plain', device) for x in xs))
     dps, dpr = [], []
     for p, (v, shared) in zip(ps, node.params):
-        d = rng.standard_normal(len(v)) + (1j * rng.standard_normal(len(v)) if np.iscomplexobj(v) else 0.0)
+        d = rng.standard_normal(v.shape) + (1j * rng.standard_normal(v.shape) if np.iscomplexobj(v) else 0.0)
         if shared:
             d[:] = d[0]
         dps.append(torch.tensor(d[0] if shared else d, device=device))
@@ -384,7 +469,7 @@ def check_jvp(node, dt, device):
     else:
         u, v = node.pair(xr)
         du, dv = node.pair(list(dxr))
-        close_reduction(got, want, norms(du) * norms(v) + norms(u) * norms(dv), dt, f'{node.name} jvp')
+        close_reduction(got, want, node.scale(du, v) + node.scale(u, dv), dt, f'{node.name} jvp')
 
 
 def check_layouts(node, dt, device):
@@ -398,38 +483,47 @@ def check_layouts(node, dt, device):
 
 
 def check_cat_loss(dt, device):
-    """loss = sum (w) |cat([h, y.reshape(-1)])|^2 with y = excite_rot(x) and y = cost_phase(x): the backward of ``cat`` hands
-    the node a contiguous cotangent at element offset 1, 2 w y -- plain (w = 1, the gradients are 2 x and 0: the
-    maps are unitary) and with a weight per element."""
+    """loss = sum (w) |cat([h, y.reshape(-1)])|^2 with y = excite_rot(x), y = cost_phase(x) and y = mux_rot(x) (a row of
+    angles per sample, its gradient judged per bin): the backward of ``cat`` hands the node a contiguous cotangent at
+    element offset 1, 2 w y -- plain (w = 1, the gradients are 2 x and 0: the maps are unitary) and with a weight per
+    element."""
     rng = np.random.default_rng(5)
     n, spec, batch, _ = EXCITE['n11-weight1-bit0-a1']
     fam = ref.Excitations(n, spec)
     tbits, controls = DIAG['straddle'][:2]
     where = (NG, tbits, controls)
     cost, cr = gauss(rng, 1 << len(tbits), DTYPES[dt].to_real())
+    per_sample = lambda u, v: norms(u) * norms(v)  # noqa: E731
+    nm, mux, mbatch, shared = muxgrad_spec(LAYOUT_CASE['muxgrad'], dt)
+    bins = ref.MuxBins(nm, *mux)
+    assert not shared                                   # (a row of angles per sample: the rows of gtheta are not summed)
     routes = (
-        ('excite_rot', n, lambda x, p: ops.excite_rot(x, spec, p), lambda x, p: fam.rot(x, p),
-         lambda x, p, g: ref.rot_vjp(fam, x, p, g)),
-        ('cost_phase', NG, lambda x, p: ops.cost_phase(x, cost.to(x.device), p, tbits, controls),
-         lambda x, p: _diag_ref.phase_ref(x, cr, p, *where), lambda x, p, g: ref.phase_vjp(x, cr, p, where, g)))
-    for name, nq, call, fwd, vjp in routes:
+        ('excite_rot', n, batch, THETAS[:batch], lambda x, p: ops.excite_rot(x, spec, p), lambda x, p: fam.rot(x, p),
+         lambda x, p, g: ref.rot_vjp(fam, x, p, g), per_sample),
+        ('cost_phase', NG, batch, THETAS[:batch], lambda x, p: ops.cost_phase(x, cost.to(x.device), p, tbits, controls),
+         lambda x, p: _diag_ref.phase_ref(x, cr, p, *where), lambda x, p, g: ref.phase_vjp(x, cr, p, where, g), per_sample),
+        ('mux_rot', nm, mbatch, bin_rows(np.random.default_rng(6), mbatch, bins.count, False, real=True)[0],
+         lambda x, p: ops.mux_rot(x, p, *mux),
+         bins.rot, lambda x, p, g: ref.binned_rot_vjp(bins, x, p, g), lambda u, v: bins.norms(u) * bins.norms(v)))
+    for name, nq, batch, thetas, call, fwd, vjp, scale in routes:
         x, xr = laid_out(gauss(rng, (batch, 1 << nq), DTYPES[dt])[0], 'plain', device)
-        th = torch.tensor(THETAS[:batch], device=device, requires_grad=True)
+        th = torch.tensor(thetas, device=device, requires_grad=True)
         h = torch.tensor([0.5 + 0.25j], dtype=DTYPES[dt], device=device)
         w, wr = gauss(rng, batch * (1 << nq) + 1, DTYPES[dt].to_real())
         for weighted in (False, True):
             x = x.detach().requires_grad_()
             sq = torch.cat([h, call(x, th).reshape(-1)]).abs().pow(2)
             gx, gth = torch.autograd.grad((sq * w.to(device)).sum() if weighted else sq.sum(), (x, th))
-            gy = 2.0 * (wr[1:].reshape(batch, -1) if weighted else 1.0) * fwd(xr, THETAS[:batch])
-            want_x, want_th = vjp(xr, THETAS[:batch], gy)
+            gy = 2.0 * (wr[1:].reshape(batch, -1) if weighted else 1.0) * fwd(xr, thetas)
+            want_x, want_th = vjp(xr, thetas, gy)
             what = f'{name} {dt} under cat' + (', weighted' if weighted else '')
             close_state(gx, want_x, dt, what + ': gradient of the state')
-            close_reduction(gth, want_th, norms(gy) * norms(xr), dt, what + ': gradient of the parameter')
+            close_reduction(gth, want_th, scale(gy, xr), dt, what + ': gradient of the parameter')
 
 
 def vmap_checks(family, dt, device):
-    """``torch.vmap`` over 3 x batch 2 equals the folded ``backend`` call bit for bit."""
+    """``torch.vmap`` over 3 x batch 2 equals the folded ``backend`` call bit for bit (for the trainable multiplexers with a
+    mapped and with an unmapped row of parameters)."""
     rng = np.random.default_rng(3)
     name = LAYOUT_CASE[family]
     same = lambda got, want: torch.equal(torch.view_as_real(got.reshape(want.shape)), torch.view_as_real(want))  # noqa: E731
@@ -471,6 +565,29 @@ def vmap_checks(family, dt, device):
         perm = torch.from_numpy(rng.permutation(1 << len(tbits)).astype(np.int64)).to(device)
         got = torch.vmap(lambda s: ops.permute_basis(s, perm, tbits, controls))(xs)
         assert same(got, backend.apply_permutation(xs.reshape(6, -1), ops.invert_table(perm), tbits, controls))
+    elif family == 'muxgrad':
+        n, mux, _, _ = muxgrad_spec(name, dt)
+        count = 1 << len(mux[2])
+        xs, flat = states(n), lambda t: t.reshape(6, -1)  # noqa: E731
+        other = xs.flip(0)
+        rows = torch.from_numpy(rng.uniform(-6, 6, (3, count))).to(device)
+        per_sample = rows.unsqueeze(1).expand(3, 2, count).reshape(6, count)   # row v of the map for its two samples
+        # a mapped row of angles becomes one row per sample (one launch each); an unmapped shared row stays one launch
+        got = torch.vmap(lambda s, t: ops.mux_rot(s, t, *mux))(xs, rows)
+        assert same(got, backend.apply_mux_rot(flat(xs), per_sample, *mux))
+        assert not same(got[1], backend.apply_mux_rot(xs[1], rows[0], *mux))          # (the rows differ: the order matters)
+        got = torch.vmap(lambda s: ops.mux_rot(s, rows[2], *mux))(xs)
+        assert same(got, backend.apply_mux_rot(flat(xs), rows[2], *mux))
+        cross = lambda u, v: ops.mux_cross(u, v, *mux)  # noqa: E731
+        assert same(torch.vmap(cross)(xs, other), backend.mux_cross(flat(xs), flat(other).contiguous(), *mux))
+        assert same(torch.vmap(lambda s: cross(s, s))(xs), backend.mux_cross(flat(xs), flat(xs), *mux))
+        # only `a` mapped: it becomes per sample, the unmapped `c` stays one shared row
+        a = torch.complex(rows, rows.flip(1))
+        c = torch.complex(rows[0].flip(0), rows[1]) / 6
+        for mode in ('gate', 'map'):
+            got = torch.vmap(lambda s, t, mode=mode: ops.mux_axpby(s, t, c, *mux, mode))(xs, a)
+            want = backend.apply_mux_axpby(flat(xs), a.unsqueeze(1).expand(3, 2, count).reshape(6, count), c, *mux, mode)
+            assert same(got, want)
     else:
         p = UNIT[dt]
         kind, dagger = MUX[name][:2]
@@ -480,3 +597,48 @@ def vmap_checks(family, dt, device):
         assert kind == 'ry'
         got = torch.vmap(lambda s: ops.mux_apply(s, table, kind, target, tbits, controls, dagger))(xs)
         assert same(got, backend.apply_mux(xs.reshape(6, -1), table, kind, target, tbits, controls, dagger))
+
+
+def negative_controls(dt):
+    """The per-bin criterion of the binned nodes on reference tensors alone (no node, no kernel): each bin-shaped result --
+    ga, gc, gtheta, the cross, its tangent -- passes as the closed forms give it and is rejected with (a) the bins indexed
+    with ``bits`` reversed, (b) a shared row's gradient taken from sample 0 instead of the sum over the batch, (c) the
+    conjugation on the wrong factor of the cross, (d) gtheta formed with rot(gy; +theta).  (b) is defined for the three
+    gradients of a row and (d) for gtheta only; (a) and (c) for all five."""
+    import pytest
+
+    n, batch, mux = 8, 2, ('y', 3, (6, 0, 4), (2,))
+    rng = np.random.default_rng(17)
+    fam, rev = ref.MuxBins(n, *mux), ref.MuxBins(n, mux[0], mux[1], mux[2][::-1], mux[3])
+    (_, x), (_, u), (_, gy), (_, dx), (_, du) = (gauss(rng, (batch, 1 << n), DTYPES[dt]) for _ in range(5))
+    a, c, th = (bin_rows(rng, batch, fam.count, True, real)[0] for real in (False, False, True))
+    pair = lambda f, p, q: f.norms(p) * f.norms(q)  # noqa: E731
+
+    def grads(f, sign=1.0):
+        _, ga, gc = ref.binned_axpby_vjp(f, x, a, c, 'gate', gy)
+        gx = f.rot(gy, -sign * th)
+        return ga, gc, 0.5 * f.cross(gx, x).imag
+
+    def swapped(f):                                     # conj(u) G v -> u conj(G v): G is Hermitian, so cross(v, u)
+        return f.cross(gy, x, 'i'), f.cross(gy, x), 0.5 * f.cross(x, f.rot(gy, -th)).imag
+
+    right = dict(zip(('ga', 'gc', 'gtheta'), grads(fam)))
+    scale = {'ga': pair(fam, x, gy).sum(0), 'gc': pair(fam, x, gy).sum(0), 'gtheta': pair(fam, gy, x).sum(0)}
+    wrong = {key: {'a': r.sum(0), 'b': right[key][0], 'c': w.sum(0)} for key, r, w in zip(right, grads(rev), swapped(fam))}
+    wrong['gtheta']['d'] = grads(fam, sign=-1.0)[2].sum(0)
+    right = {key: v.sum(0) for key, v in right.items()}
+    right['cross'], scale['cross'] = fam.cross(u, x), pair(fam, u, x)
+    wrong['cross'] = {'a': rev.cross(u, x), 'c': fam.cross(x, u)}
+    right['cross tangent'] = ref.binned_cross_jvp(fam, u, x, du, dx)
+    scale['cross tangent'] = pair(fam, du, x) + pair(fam, u, dx)
+    wrong['cross tangent'] = {'a': ref.binned_cross_jvp(rev, u, x, du, dx), 'c': ref.binned_cross_jvp(fam, x, u, dx, du)}
+    assert sorted(len(w) for w in wrong.values()) == [2, 2, 3, 3, 4]
+    for key, want in right.items():
+        close_reduction(torch.from_numpy(want), want, scale[key], dt, f'negative control {dt}: {key} as it is')
+        rounded = want.astype(np.complex64 if np.iscomplexobj(want) else np.float32)   # (a rounding of 6e-8 passes in both)
+        if dt == 'c64':
+            close_reduction(torch.from_numpy(rounded), want, scale[key], dt, f'negative control {dt}: {key} rounded to single')
+        for letter, bad in wrong[key].items():
+            with pytest.raises(AssertionError):
+                close_reduction(torch.from_numpy(np.ascontiguousarray(bad)), want, scale[key], dt,
+                                f'negative control {dt}: {key} with ({letter})')

@@ -1,5 +1,6 @@
 """Closed-form derivatives of the streaming operations, in numpy complex128, built from the forward references alone
-(tests/_diag_ref.py, _pauli_ref.py, _excite_ref.py, _perm_ref.py, _mux_ref.py): nothing here calls ``ops`` or ``backend``.
+(tests/_diag_ref.py, _pauli_ref.py, _excite_ref.py, _perm_ref.py, _mux_ref.py, _muxgrad_ref.py): nothing here calls ``ops`` or
+``backend``.
 
 Convention (PyTorch's): for a real loss L, dL = Re sum conj(g) d(input).  A linear map y = M x therefore has gx = M^+ gy,
 a complex parameter p of y = p w has gp = sum conj(w) gy, and a real one the real part of that.  Parameters are one value
@@ -20,6 +21,17 @@ The diagonal operations with a real table c over the controls' subspace `on`:
     scale(x; s) = s c x on `on`, 0 elsewhere:           gx = scale(gy; conj s);   gs = sum_on c conj(x) gy
     cross(a, b) = sum_on c conj(a) b:                   g_a = scale(b; conj gz);   g_b = scale(a; gz)
 
+The binned multiplexer operations (`MuxBins`): G the Pauli ``axis`` on ``target`` inside the controls (Hermitian, and it
+maps every bin -- the amplitudes with one select value inside the controls -- to itself); a parameter is a row of 2^k
+values per sample, (B, 2^k), and a cross is one number per sample and bin:
+
+    axpby(x; a, c)[i] = a[sub i] x[i] + c[sub i] (G x)[i] inside the controls; x ('gate') or 0 ('map') elsewhere
+        gx = axpby(gy; conj a, conj c), same mode;   ga = cross_I(x, gy);   gc = cross_axis(x, gy)
+    cross(u, v)[b, s] = sum over bin s of conj(u) (G v)
+        g_u = axpby(v; 0, conj gz, 'map');   g_v = axpby(u; 0, gz, 'map')
+    rot(x; theta) = axpby(x; cos(theta/2), -i sin(theta/2), 'gate')
+        gx = rot(gy; -theta);   gtheta = Im cross(gx, x) / 2
+
 A JVP is the sum of the same partials applied to the tangents; a parameter's tangent moves the support only (a 'map' /
 scale term)."""
 
@@ -28,6 +40,7 @@ import numpy as np
 import _diag_ref
 import _excite_ref
 import _mux_ref
+import _muxgrad_ref
 import _pauli_ref
 import _perm_ref
 
@@ -172,3 +185,57 @@ def mux_vjp(blocks, target, bits, controls, dagger, gy):
 
 def mux_jvp(blocks, target, bits, controls, dagger, dx):
     return _mux_ref.mux_ref(dx, blocks, target, bits, controls, dagger)
+
+
+# ---- the binned multiplexer operations: a parameter is (B, 2^k), a cross (B, 2^k) --------------------------------------
+class MuxBins:
+    """G = the Pauli ``axis`` on bit ``target`` inside the controls; bin s = the amplitudes inside the controls whose select
+    bits ``bits`` (``bits[0]`` the most significant) spell s."""
+
+    def __init__(self, n, axis, target, bits, controls=()):
+        self.n, self.axis, self.target, self.bits, self.controls = n, axis, target, tuple(bits), tuple(controls)
+        self.count = 1 << len(self.bits)
+
+    def support(self):
+        return _muxgrad_ref.inside(self.n, self.controls)
+
+    def axpby(self, x, a, c, mode='gate'):
+        return _muxgrad_ref.mux_axpby_ref(x, a, c, self.axis, self.target, self.bits, self.controls, mode)
+
+    def cross(self, u, v, axis=None):
+        return _muxgrad_ref.mux_cross_ref(u, v, axis or self.axis, self.target, self.bits, self.controls)
+
+    def rot(self, x, theta):
+        return _muxgrad_ref.mux_rot_ref(x, theta, self.axis, self.target, self.bits, self.controls)
+
+    def norms(self, a):
+        """|a restricted to bin s| for every sample and bin: (B, 2^k)."""
+        inside = np.where(self.support(), np.abs(np.asarray(a).astype(np.complex128)) ** 2, 0.0)
+        return np.sqrt(_muxgrad_ref.binned(inside, self.n, self.bits))
+
+
+def binned_axpby_vjp(fam, x, a, c, mode, gy):
+    return fam.axpby(gy, np.conj(a), np.conj(c), mode), fam.cross(x, gy, 'i'), fam.cross(x, gy)
+
+
+def binned_axpby_jvp(fam, x, a, c, mode, dx, da, dc):
+    return fam.axpby(dx, a, c, mode) + fam.axpby(x, da, dc, 'map')
+
+
+def binned_cross_vjp(fam, u, v, gz):
+    zero = np.zeros_like(gz)
+    return fam.axpby(v, zero, np.conj(gz), 'map'), fam.axpby(u, zero, gz, 'map')
+
+
+def binned_cross_jvp(fam, u, v, du, dv):
+    return fam.cross(du, v) + fam.cross(u, dv)
+
+
+def binned_rot_vjp(fam, x, theta, gy):
+    gx = fam.rot(gy, -np.asarray(theta))
+    return gx, 0.5 * fam.cross(gx, x).imag
+
+
+def binned_rot_jvp(fam, x, theta, dx, dtheta):
+    dtheta = np.asarray(dtheta)
+    return fam.rot(dx, theta) + fam.axpby(fam.rot(x, theta), np.zeros_like(dtheta), -0.5j * dtheta, 'map')

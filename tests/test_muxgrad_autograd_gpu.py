@@ -1,7 +1,9 @@
 """The autograd rules of ops.mux_axpby / mux_cross / mux_rot on the GPU: gradcheck and gradgradcheck in complex128 at a
 small n, the first derivatives of ``mux_rot`` in the state and in the angles at kernel-path shapes in both precisions
 against the closed forms  gx = rot(gy; -theta),  gtheta[b, s] = Im cross(gx, x)[b, s] / 2  evaluated by the numpy
-reference (tests/_muxgrad_ref.py), and the Hessian in the angles at k = 2 against the dense oracle.
+reference (tests/_muxgrad_ref.py), and the Hessian in the angles at k = 2 against the dense oracle.  The first derivatives of
+all three nodes at kernel-path shapes -- reverse and forward mode, ``vmap``, the layouts autograd hands a node, both
+precisions, judged bin by bin -- are the family 'muxgrad' of tests/_stream_grad_cases.py (test_stream_autograd_gpu.py).
 
 Kernel-path shapes (csrc/dq_muxgrad.hip): P = 10 + (1 for complex64 with target != 0) pair bits of a unit; n = P + 1 is one
 unit, n = P + 3 eight units, with selects and a control on both sides of the unit boundary."""

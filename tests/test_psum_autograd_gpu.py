@@ -2,9 +2,9 @@
 flip at bit 11 (above and inside a unit of complex64 vectors, above it for complex128) and one at bit 0 (inside a complex64
 vector), complex64 and complex128 -- against closed forms in numpy complex128 built from tests/_psum_ref.py alone.
 
-First derivatives: the checks of tests/_stream_grad_cases.py (reverse and forward mode) with the Pauli sums as a third
-family of tests/_stream_grad_ref.py.  Second derivatives: the rules in the comment above ``ops._Generator`` applied twice,
-written out below; a reduction through H is held to tol * |u| |v| sum_t |h_t|, the bound of |<u, H v>|."""
+First derivatives: the checks of tests/_stream_grad_cases.py (reverse and forward mode, and at n = 12 the state and cotangent
+layouts autograd hands a node) with the Pauli sums as a third family of tests/_stream_grad_ref.py.  Second derivatives: the
+rules in the comment above ``ops._Generator`` applied twice, written out below; a reduction through H is held to tol * |u| |v| sum_t |h_t|, the bound of |<u, H v>|."""
 
 import numpy as np
 import pytest
@@ -44,6 +44,17 @@ def test_vjp_and_jvp_against_the_closed_forms(n, dt):
         cases.check_forward(node, dt, DEVICE)
         cases.check_vjp(node, dt, DEVICE)
         cases.check_jvp(node, dt, DEVICE)
+
+
+@pytest.mark.parametrize('dt', ['c64', 'c128'])
+def test_cotangent_and_state_layouts(dt):
+    """The states at element offset 1 (a complex64 pointer at 8 mod 16) and an expanded, a strided and an offset cotangent."""
+    n = 12
+    fam, H, _ = family(n)
+    nodes = cases.generator_nodes(f'psum n={n} {dt}', fam, lambda s, a, c, mode: ops.psum_axpby(s, a, c, H),
+                                  lambda u, v: ops.psum_cross(u, v, H), None, 2, False, dt, np.random.default_rng(n))
+    for node in nodes[:-1]:
+        cases.check_layouts(node, dt, DEVICE)
 
 
 def dev(pair):

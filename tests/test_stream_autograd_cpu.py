@@ -1,7 +1,9 @@
 """The CPU twin of test_stream_autograd_gpu.py: the same case tables, checks and closed-form references
 (tests/_stream_grad_cases.py, tests/_stream_grad_ref.py) through the plain-torch stand-ins of ``backend`` under the CPU
 test double.  It validates the references, and the rules of the nodes as far as they do not depend on a kernel; the
-stand-ins do not care about alignment, so what ``ops`` hands a kernel is asserted on the helper itself."""
+stand-ins do not care about alignment, so what ``ops`` hands a kernel is asserted on the helper itself.  The trainable
+multiplexers (``_MuxAxpby`` / ``_MuxCross`` / ``_MuxRot``) are the family 'muxgrad' of the tables; the negative controls of
+their per-bin criterion need no node at all and run here."""
 
 import pytest
 import torch
@@ -17,6 +19,7 @@ DEVICE = 'cpu'
 @pytest.mark.parametrize('family,name', cases.CASE_IDS, ids=[f'{f}-{n}' for f, n in cases.CASE_IDS])
 def test_vjp_and_jvp_against_the_closed_forms(cpu_backend, family, name, dt):
     for node in cases.nodes_of(family, name, dt):
+        cases.check_forward(node, dt, DEVICE)
         cases.check_vjp(node, dt, DEVICE)
         cases.check_jvp(node, dt, DEVICE)
 
@@ -37,6 +40,11 @@ def test_cotangent_and_state_layouts(cpu_backend, family, dt):
 @pytest.mark.parametrize('dt', ['c64', 'c128'])
 def test_a_loss_over_cat_hands_the_node_a_cotangent_at_offset_1(cpu_backend, dt):
     cases.check_cat_loss(dt, DEVICE)
+
+
+@pytest.mark.parametrize('dt', ['c64', 'c128'])
+def test_the_per_bin_criterion_rejects_four_wrong_rules(dt):
+    cases.negative_controls(dt)
 
 
 def test_the_backward_of_cat_yields_a_contiguous_cotangent_at_offset_1():

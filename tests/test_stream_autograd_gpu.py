@@ -1,8 +1,9 @@
 """The derivatives of the streaming nodes of ``ops`` on the MI355X -- ``_CostPhase``, ``_CostCross``, ``_CostScale``,
 ``_DiagMul``, ``_GenAxpby`` / ``_GenCross`` / ``_GenRot`` for Pauli strings and for excitations, ``_PermuteBasis``,
-``_MuxApply`` -- at the shapes of the families' kernel tests, in complex64 and complex128: reverse mode, forward mode and
-``torch.vmap`` against the closed forms of tests/_stream_grad_ref.py (numpy complex128, built from the forward references
-alone).  The cases, the criteria and the checks are in tests/_stream_grad_cases.py, which test_stream_autograd_cpu.py runs
+``_MuxApply``, ``_MuxAxpby`` / ``_MuxCross`` / ``_MuxRot`` (the trainable multiplexers: a row of 2^k parameters, shared or one
+per sample, and reductions judged bin by bin) -- at the shapes of the families' kernel tests, in complex64 and
+complex128: the forward, reverse mode, forward mode and ``torch.vmap`` against the closed forms of
+tests/_stream_grad_ref.py (numpy complex128, built from the forward references alone).  The cases, the criteria and the checks are in tests/_stream_grad_cases.py, which test_stream_autograd_cpu.py runs
 through the plain-torch stand-ins as well.
 
 The layout cases hand the nodes what autograd hands them: an expanded cotangent, a strided one, one that is contiguous at
@@ -23,6 +24,7 @@ DEVICE = 'cuda'
 @pytest.mark.parametrize('family,name', cases.CASE_IDS, ids=[f'{f}-{n}' for f, n in cases.CASE_IDS])
 def test_vjp_and_jvp_against_the_closed_forms(family, name, dt):
     for node in cases.nodes_of(family, name, dt):
+        cases.check_forward(node, dt, DEVICE)
         cases.check_vjp(node, dt, DEVICE)
         cases.check_jvp(node, dt, DEVICE)
 
