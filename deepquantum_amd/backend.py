@@ -11,6 +11,7 @@ and is built on the oracle); the package itself never imports ``oracle/``.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Any, Sequence
 
 import torch
@@ -1537,6 +1538,13 @@ class PsumTable:
         if bounds[0] != 0 or bounds[-1] != t or any(lo > hi for lo, hi in zip(bounds, bounds[1:])):
             raise ValueError(f'PsumTable: bounds must rise from 0 to the number of terms ({t}), got {bounds}')
         self.nqubit, self.ngroups, self.nterms = n, g, t
+        # what the evolution needs of H (:func:`apply_psum_evolve`): the coefficient b of the empty string, and the sum of
+        # |h_t| over every other string -- each has norm 1, so the triangle inequality bounds ||H - b|| by it, rigorously
+        # (the sum rounded up, not to the nearest)
+        is_empty = [int(x) == 0 and int(zmasks[j]) == 0 for x, lo, hi in zip(xmasks, bounds[0::2], bounds[2::2]) for j in range(lo, hi)]
+        self.constant = math.fsum(float(w) for w, e in zip(weights, is_empty) if e)
+        rest = math.fsum(abs(float(w)) for w, e in zip(weights, is_empty) if not e)
+        self.norm_bound = math.nextafter(rest, math.inf) if rest > 0.0 else 0.0
         self._host = (torch.tensor([int(m) for m in xmasks], dtype=torch.int64), torch.tensor(bounds, dtype=torch.int32),
                       torch.tensor([int(m) for m in zmasks], dtype=torch.int64), torch.tensor(weights, dtype=torch.float64))
         self._devices: dict = {}
@@ -1557,6 +1565,16 @@ class PsumTable:
 
     def __getstate__(self):
         return {**self.__dict__, '_devices': {}}
+
+
+def _capturing(t: torch.Tensor) -> bool:
+    """Is the current stream capturing?  (Under the CPU test double there may be no device to ask: then it is not.)"""
+    if t.is_cuda:
+        return torch.cuda.is_current_stream_capturing()
+    try:
+        return bool(torch.cuda.is_current_stream_capturing())
+    except RuntimeError:
+        return False
 
 
 def _psum_args(state: torch.Tensor, table: PsumTable, what: str) -> int:
@@ -1622,3 +1640,159 @@ def psum_cross(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.
         return _diag_double(lambda: (bra.to(torch.complex128).conj() * _psum_apply_double(ket.to(torch.complex128), table)).sum(dim=-1))
     mid = (*(_ptr(t) for t in table.on(ket.device)), table.ngroups, table.nterms, n)
     return _cross_reduce('dq_psum_cross', 'dq_psum_cross_ws_bytes', bra, ket, mid)
+
+
+# ---- exp(-i t H) for a Pauli sum: a Chebyshev expansion, one launch per order --------------------------------------------
+# With b the coefficient of the empty string, a >= ||H - b|| (`PsumTable.norm_bound`: the sum of |h_t| over the other
+# strings -- every Pauli string has norm 1, so the triangle inequality makes it rigorous) and H' = (H - b) / a, whose
+# spectrum lies in [-1, 1],
+#     exp(-i t H) psi = e^{-i t b} [ J_0(z) phi_0 + 2 sum_{k >= 1} (-i)^k J_k(z) phi_k ],        z = a t,
+#     phi_0 = psi,  phi_1 = H' psi,  phi_{k+1} = 2 H' phi_k - phi_{k-1}
+# and |phi_k| <= |psi|, so the sum cut after order K is off by at most 2 sum_{k > K} |J_k(z)| |psi|: K is the smallest order
+# whose tail is below the caller's tolerance.
+def bessel_j(z: float, kmax: int | None = None) -> list[float]:
+    """``J_0(z) .. J_kmax(z)`` for ``z >= 0`` in float64 (``kmax=None``: up to the order the expansion can need, about
+    ``z + 10 z^(1/3) + 80``, beyond which every value is below 1e-40): Miller's backward recurrence
+    ``J_{k-1} = (2k / z) J_k - J_{k+1}`` from an even order 30 above the last one wanted, rescaled where it grows past
+    1e250, normalised by ``J_0 + 2 sum_k J_2k = 1``.  What it returns depends on ``z`` alone: ``kmax`` only cuts or pads."""
+    z = float(z)
+    if not (z >= 0.0 and math.isfinite(z)):
+        raise ValueError(f'bessel_j: z must be finite and >= 0, got {z}')
+    top = int(math.ceil(z + 10.0 * z ** (1.0 / 3.0))) + 80
+    if z == 0.0:
+        vals = [1.0] + [0.0] * top
+    else:
+        start = top + 30 + (top & 1)                    # (even)
+        vals = [0.0] * (start + 1)
+        hi, cur = 0.0, 1e-250                           # J_{k+1}, J_k up to the common factor
+        vals[start] = cur
+        for k in range(start, 0, -1):
+            hi, cur = cur, (2.0 * k / z) * cur - hi
+            vals[k - 1] = cur
+            if abs(cur) > 1e250:                        # (what was set far above underflows to 0: it is that small)
+                hi, cur = hi * 1e-250, cur * 1e-250
+                for m in range(k - 1, start + 1):
+                    vals[m] *= 1e-250
+        norm = vals[0] + 2.0 * math.fsum(vals[2::2])
+        vals = [v / norm for v in vals[:top + 1]]
+    if kmax is None:
+        return vals
+    return vals[:kmax + 1] + [0.0] * max(0, kmax - top)
+
+
+def _cheb_order(vals: list[float], tol: float) -> int:
+    """The smallest K with ``2 sum_{k > K} |J_k| < tol`` for the values of :func:`bessel_j` (which end where the rest is 0)."""
+    tail, k = 0.0, len(vals) - 1
+    while k > 0 and 2.0 * (tail + abs(vals[k])) < tol:
+        tail += abs(vals[k])
+        k -= 1
+    return k
+
+
+def chebyshev_order(z: float, tol: float) -> int:
+    """The order K at which the expansion of ``exp(-i z H')``, ``||H'|| <= 1``, is cut: the smallest with
+    ``2 sum_{k > K} |J_k(|z|)| < tol``; about ``|z|`` plus a few dozen."""
+    tol = float(tol)
+    if not (tol > 0.0 and math.isfinite(tol)):
+        raise ValueError(f'chebyshev_order: tol must be a positive number, got {tol}')
+    return _cheb_order(bessel_j(abs(float(z))), tol)
+
+
+def _evolve_plan(table: PsumTable, ts: list[float], tol: float):
+    """Per sample: the phase e^{-i t b} c_k of every order, c_0 = J_0, c_k = 2 (-i sgn t)^k J_k(a |t|) up to the sample's OWN
+    order K_b and exactly 0 above it -- a sample's result does not depend on who shares its batch -- and K = max K_b."""
+    a, b = table.norm_bound, table.constant
+    rows, memo = [], {}
+    for t in ts:
+        if t not in memo:
+            vals = bessel_j(a * abs(t))
+            kb = _cheb_order(vals, tol)
+            phase = complex(math.cos(t * b), -math.sin(t * b))
+            step = -1j if t >= 0 else 1j
+            memo[t] = [phase * ((1.0 if k == 0 else 2.0) * vals[k]) * step ** k for k in range(kb + 1)]
+        rows.append(memo[t])
+    order = max(len(r) for r in rows) - 1
+    return [r + [0j] * (order + 1 - len(r)) for r in rows], order
+
+
+def apply_psum_evolve(state: torch.Tensor, table: PsumTable, t, tol: float, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[b] = exp(-i t[b] H) state[b] for the sum of Pauli strings H of ``table``, to within ``tol`` |state[b]| in the
+    2-norm plus rounding: the Chebyshev expansion above, cut at ``chebyshev_order(norm_bound * max |t|, tol)``.  ``t``: real,
+    one value or one per sample; it is READ ON THE HOST (one device-to-host copy per call when it lives on a device),
+    because the number of launches depends on it -- so the call is refused under stream capture.  The coefficients of all
+    orders go to the device as one float64 tensor in one copy.
+
+    Launches: ``dq_apply_psum_axpby_*`` for phi_1, two elementwise operations to start the sum, then exactly one
+    ``dq_pauli_sum_cheb_step_*`` per order from 2 to K, each writing phi_{k+1} over phi_{k-1}.  Two state-sized work
+    buffers besides ``state`` (never written) and ``out`` (which must not overlap it).  A sample with ``t = 0`` comes back bit
+    for bit, and every sample comes out as it would alone."""
+    what = 'apply_psum_evolve'
+    n = _psum_args(state, table, what)
+    _suffix(state)
+    tol = float(tol)
+    if not (tol > 0.0 and math.isfinite(tol)):
+        raise ValueError(f'{what}: tol must be a positive number, got {tol}')
+    if _capturing(state):
+        raise RuntimeError(f'deepquantum_amd: {what} under stream capture: the number of launches depends on t, which is read '
+                           'on the host; capture the steps around it')
+    if not isinstance(t, torch.Tensor):                 # (a Python float is a double: not through the default float32)
+        t = torch.tensor(t, dtype=torch.complex128 if isinstance(t, complex) else torch.float64)
+    if t.is_complex():
+        raise ValueError(f'{what}: t must be real, got {t.dtype}')
+    ts = [float(v) for v in t.detach().reshape(-1).tolist()]
+    batch = state.shape[0]
+    if len(ts) == 1 and batch != 1:
+        ts = ts * batch
+    if len(ts) != batch:
+        raise ValueError(f'{what}: one t, or one per sample ({batch}), expected; got {len(ts)}')
+    if not all(math.isfinite(v) for v in ts):
+        raise ValueError(f'{what}: t is not finite')
+    out = _check_out(state, out, what, in_place=False)
+    coefs, order = _evolve_plan(table, ts, tol)
+    a, b = table.norm_bound, table.constant
+    hip = _use_hip(state)
+    if order == 0:                                      # (a t below the tolerance, or H a constant: a phase)
+        c0 = torch.tensor([r[0] for r in coefs], dtype=torch.complex128).to(device=state.device, dtype=state.dtype)
+        torch.mul(state, c0.reshape(-1, 1), out=out)
+    elif not hip:
+        def double():
+            x = state.to(torch.complex128)
+            c = torch.tensor(coefs, dtype=torch.complex128)             # (B, K + 1)
+            prev, cur = x, (_psum_apply_double(x, table) - b * x) / a
+            acc = c[:, 0:1] * prev + c[:, 1:2] * cur
+            for k in range(2, order + 1):
+                prev, cur = cur, (2.0 / a) * _psum_apply_double(cur, table) - (2.0 * b / a) * cur - prev
+                acc = acc + c[:, k:k + 1] * cur
+            return out.copy_(acc.to(state.dtype))
+
+        _diag_double(double)
+    else:
+        # ONE host tensor, one copy: [B][4] for phi_1 = -b/a psi + 1/a H psi, [B][2] c_0, [B][2] c_1, then [K - 1][B][5]
+        # rows (alpha, beta, gamma, Re c_k, Im c_k) = (2/a, -2b/a, -1, c_k) for the orders 2 .. K
+        flat = [v for _ in range(batch) for v in (-b / a, 0.0, 1.0 / a, 0.0)]
+        for k in (0, 1):
+            flat += [v for r in coefs for v in (r[k].real, r[k].imag)]
+        for k in range(2, order + 1):
+            flat += [v for r in coefs for v in (2.0 / a, -2.0 * b / a, -1.0, r[k].real, r[k].imag)]
+        dev = torch.tensor(flat, dtype=torch.float64).to(state.device)
+        first = dev[:4 * batch].reshape(batch, 4)
+        c01 = torch.view_as_complex(dev[4 * batch:8 * batch].reshape(2, batch, 2)).to(state.dtype)
+        steps = dev[8 * batch:].reshape(order - 1, batch, 5)
+        ptrs = [_ptr(x) for x in table.on(state.device)]
+        tail = (*ptrs, table.ngroups, table.nterms, n)
+        cur = torch.empty_like(state)
+        for lo, hi in _slices(batch):
+            _call('dq_apply_psum_axpby', state, _ptr(state, lo), _ptr(cur, lo), _ptr(first, lo), *tail, hi - lo)
+        torch.mul(state, c01[0].reshape(-1, 1), out=out)
+        out.addcmul_(cur, c01[1].reshape(-1, 1))
+        prev, nxt = state, (torch.empty_like(state) if order >= 2 else None)    # (order 2 must leave the input alone)
+        for k in range(2, order + 1):
+            for lo, hi in _slices(batch):
+                _call('dq_pauli_sum_cheb_step', state, _ptr(cur, lo), _ptr(prev, lo), _ptr(nxt, lo), _ptr(out, lo),
+                      _ptr(steps[k - 2], lo), *tail, hi - lo)
+            prev, cur = cur, nxt
+            nxt = prev                                  # (from the third order on, phi_{k+1} goes over phi_{k-1})
+    for s, v in enumerate(ts):
+        if v == 0.0:
+            out[s].copy_(state[s])
+    return out

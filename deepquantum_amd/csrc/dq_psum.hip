@@ -3,6 +3,10 @@
 //
 //     dq_apply_psum_axpby : out[b, i] = a[b] in[b, i] + c[b] (H in_b)[i]            (out of place only)
 //     dq_psum_cross       : out[b] = sum_i conj(bra[b, i]) (H ket_b)[i]
+//     dq_pauli_sum_cheb_step : next[b, i] = alpha[b] (H cur_b)[i] + beta[b] cur[b, i] + gamma[b] prev[b, i],
+//                              acc[b, i] += delta[b] next[b, i]                     (next may be prev)
+// The third is one order of the Chebyshev expansion of exp(-i t H) (backend.apply_psum_evolve): the gather of the first
+// over `cur`, with the recurrence's other two vectors and the running sum read and written at the lane's own vectors.
 //
 // The terms are grouped by flip mask.  For the group with mask x
 //     (G_x psi)[i] = w_x(i ^ x) psi[i ^ x],      w_x(j) = sum_{t in group} h_t i^{ny_t} (-1)^popc(j & z_t)
@@ -151,6 +155,75 @@ __global__ __launch_bounds__(ST_THREADS) void psum_axpby_kernel(const cx<T>* __r
     }
 }
 
+// One order of a Chebyshev recurrence in H and its running sum:
+//     next = alpha (H cur) + beta cur + gamma prev,      acc += delta next
+// The gather is psum_axpby_kernel's, over `cur` alone; prev, next and acc are touched at the lane's own vectors only, so
+// next may be prev (each lane has read its vectors of prev before it writes them).  The own vectors of prev and acc are
+// loaded AFTER the group loop: held across it they would be 32 more live registers (see profiles/evolve/resource_usage.txt).
+// SAME: next is prev, and prev is then read through `next` -- so that every pointer of either instantiation is __restrict__
+// in earnest.  Without that the compiler cannot tell the stores from the table and reads the table with vector loads in
+// the term loop instead of scalar ones: measured 1.4 to 1.9 times one psum_axpby launch where this form is at 0.97 to 1.20.
+// coef = [batch][5] doubles (alpha, beta, gamma, Re delta, Im delta), rounded once to the state's real precision.
+template <typename T, bool SAME>
+__global__ __launch_bounds__(ST_THREADS) void psum_cheb_step_kernel(const cx<T>* __restrict__ cur, const cx<T>* __restrict__ prev,
+                                                                    cx<T>* __restrict__ next, cx<T>* __restrict__ acc,
+                                                                    const double* __restrict__ coef, PsumTable tb, int n,
+                                                                    uint64_t nvec) {
+    using Q = typename Vec16<T>::type;
+    constexpr int VEC = 16 / (int)sizeof(cx<T>);
+    const uint64_t b = blockIdx.y;
+    const Q* src = reinterpret_cast<const Q*>(cur + (b << n));
+    Q* pnext = reinterpret_cast<Q*>(next + (b << n));
+    const Q* pprev = SAME ? pnext : reinterpret_cast<const Q*>(prev + (b << n));
+    Q* pacc = reinterpret_cast<Q*>(acc + (b << n));
+    const T alpha = (T)coef[5 * b], beta = (T)coef[5 * b + 1], gamma = (T)coef[5 * b + 2];
+    const cx<T> delta = mk<T>((T)coef[5 * b + 3], (T)coef[5 * b + 4]);
+    for (uint64_t unit = blockIdx.x; (unit << ST_UNIT_BITS) < nvec; unit += gridDim.x) {
+        uint64_t vec[ST_UNROLL];
+        const unsigned live = unit_vectors(unit, nvec, vec);
+        Q own[ST_UNROLL];
+        cx<T> h[ST_UNROLL][VEC];                        // (H cur) at the lane's amplitudes
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            own[u] = src[vec[u]];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) h[u][e] = mk<T>((T)0, (T)0);
+        }
+        for (int g = 0; g < tb.ngroups; ++g) {
+            Q q[ST_UNROLL];
+            T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
+            int x0;
+            load_group<T, VEC, Q>(tb, g, n, src, unit, vec, own, q, x0, wr, wi);
+#pragma unroll
+            for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) h[u][e] = cfma(mk<T>(wr[u][e], wi[u][e]), vec_get<T>(q[u], e ^ x0), h[u][e]);
+        }
+        Q p[ST_UNROLL], s[ST_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {           // (a lane beyond a small sample reads vector 0 and stores nothing)
+            p[u] = pprev[vec[u]];
+            s[u] = pacc[vec[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            Q r, t;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const cx<T> o = vec_get<T>(own[u], e), pv = vec_get<T>(p[u], e);
+                const cx<T> y = mk<T>(fma(gamma, pv.x, fma(beta, o.x, alpha * h[u][e].x)),
+                                      fma(gamma, pv.y, fma(beta, o.y, alpha * h[u][e].y)));
+                vec_set(r, e, y);
+                vec_set(t, e, cfma(delta, y, vec_get<T>(s[u], e)));
+            }
+            if (live >> u & 1u) {
+                pnext[vec[u]] = r;
+                pacc[vec[u]] = t;
+            }
+        }
+    }
+}
+
 // ws[b, blockIdx.x] = this workgroup's part of sum_i conj(bra_i) (H ket)_i
 template <typename T, bool SAME>
 __global__ __launch_bounds__(ST_THREADS) void psum_cross_kernel(const cx<T>* __restrict__ bra, const cx<T>* __restrict__ ket,
@@ -244,6 +317,50 @@ int axpby_impl(const void* in, void* out, const double* coef, const uint64_t* xm
     return check_launch(what);
 }
 
+// cur is only read and is gathered from: apart from everything that is written.  acc is read and written at own vectors
+// only but must be nobody else's; next may be prev, since each lane reads its vectors of prev before it writes them.
+template <typename T>
+int cheb_step_impl(const void* cur, const void* prev, void* next, void* acc, const double* coef, const uint64_t* xmasks,
+                   const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n, int64_t batch,
+                   dq_stream_t stream) {
+    constexpr bool C128 = sizeof(T) == 8;
+    const char* what = "dq_pauli_sum_cheb_step";
+    if (!cur || !prev || !next || !acc) {
+        set_error("%s: null pointer", what);
+        return DQ_ERR_ARG;
+    }
+    if (misaligned(cur) || misaligned(prev) || misaligned(next) || misaligned(acc)) {
+        set_error("%s: cur, prev, next and acc must be 16-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    if (n < 1 || n > 40) {
+        set_error("%s: n=%d out of range [1, 40]", what, n);
+        return DQ_ERR_ARG;
+    }
+    if (int rc = check_batch(what, batch)) return rc;
+    const uint64_t bytes = ((uint64_t)batch << n) * sizeof(cx<T>);
+    if (int rc = check_apart(what, "cur", cur, "next", next, bytes, DISJOINT)) return rc;
+    if (int rc = check_apart(what, "acc", acc, "cur", cur, bytes, DISJOINT)) return rc;
+    if (int rc = check_apart(what, "acc", acc, "prev", prev, bytes, DISJOINT)) return rc;
+    if (int rc = check_apart(what, "acc", acc, "next", next, bytes, DISJOINT)) return rc;
+    if (int rc = check_apart(what, "next", next, "prev", prev, bytes, SAME_OR_DISJOINT)) return rc;
+    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
+        set_error("%s: coef must be non-null and 8-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    PsumTable tb;
+    if (int rc = check_table(what, xmasks, bounds, zmasks, weights, ngroups, nterms, &tb)) return rc;
+    const uint64_t nvec = vectors_of(n, C128);
+    const dim3 grid(blocks_of(nvec), (unsigned)batch);
+    const cx<T>* pc = static_cast<const cx<T>*>(cur);
+    cx<T>* pn = static_cast<cx<T>*>(next);
+    cx<T>* pa = static_cast<cx<T>*>(acc);
+    hipStream_t s = as_stream(stream);
+    if (prev == next) hipLaunchKernelGGL((psum_cheb_step_kernel<T, true>), grid, dim3(ST_THREADS), 0, s, pc, nullptr, pn, pa, coef, tb, n, nvec);
+    else hipLaunchKernelGGL((psum_cheb_step_kernel<T, false>), grid, dim3(ST_THREADS), 0, s, pc, static_cast<const cx<T>*>(prev), pn, pa, coef, tb, n, nvec);
+    return check_launch(what);
+}
+
 template <typename T>
 int cross_impl(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks,
                const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws, int64_t ws_bytes,
@@ -282,6 +399,17 @@ extern "C" int dq_apply_psum_axpby_c128(const void* in, void* out, const double*
                                         const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
                                         int64_t batch, dq_stream_t stream) {
     return dq::axpby_impl<double>(in, out, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, stream);
+}
+
+extern "C" int dq_pauli_sum_cheb_step_c64(const void* cur, const void* prev, void* next, void* acc, const double* coef,
+                                     const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks, const double* weights,
+                                     int ngroups, int nterms, int n, int64_t batch, dq_stream_t stream) {
+    return dq::cheb_step_impl<float>(cur, prev, next, acc, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, stream);
+}
+extern "C" int dq_pauli_sum_cheb_step_c128(const void* cur, const void* prev, void* next, void* acc, const double* coef,
+                                      const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks, const double* weights,
+                                      int ngroups, int nterms, int n, int64_t batch, dq_stream_t stream) {
+    return dq::cheb_step_impl<double>(cur, prev, next, acc, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, stream);
 }
 
 extern "C" int64_t dq_psum_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross) {

@@ -156,6 +156,20 @@ int check_batch(const char* what, int64_t batch) {
 // in == out, one that reads where another lane writes (the permutation) does not; a shifted overlap is safe for nobody.
 enum Alias { SAME_OR_DISJOINT, DISJOINT };
 
+// Do two ranges of `bytes` bytes share a byte that `alias` does not let them share?
+bool clash(const void* p, const void* q, uint64_t bytes, Alias alias) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), o = reinterpret_cast<uintptr_t>(q);
+    return (alias == DISJOINT || a != o) && (a > o ? a - o : o - a) < bytes;
+}
+
+// Two named buffers of a primitive with more than two states (dq_psum.hip's Chebyshev step), each `bytes` long, under `alias`
+int check_apart(const char* what, const char* name_p, const void* p, const char* name_q, const void* q, uint64_t bytes,
+                Alias alias) {
+    if (!clash(p, q, bytes, alias)) return DQ_OK;
+    set_error(alias == DISJOINT ? "%s: %s and %s overlap" : "%s: %s and %s overlap without being equal", what, name_p, name_q);
+    return DQ_ERR_ARG;
+}
+
 // in and out of a state-to-state primitive: non-null, 16-byte aligned, n in [nmin, 40], the batch, and the ranges
 // [in, in + batch * 2^n) and [out, ..) under `alias`
 int check_states(const char* what, const void* in, const void* out, int nmin, int n, int64_t batch, size_t amp_bytes,
@@ -174,8 +188,7 @@ int check_states(const char* what, const void* in, const void* out, int nmin, in
     }
     if (int rc = check_batch(what, batch)) return rc;
     const uint64_t bytes = ((uint64_t)batch << n) * amp_bytes;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in), o = reinterpret_cast<uintptr_t>(out);
-    if ((alias == DISJOINT || a != o) && (a > o ? a - o : o - a) < bytes) {
+    if (clash(in, out, bytes, alias)) {
         set_error(alias == DISJOINT ? "%s: in and out overlap (out of place only)" : "%s: in and out overlap without being equal",
                   what);
         return DQ_ERR_ARG;

@@ -920,11 +920,12 @@ class _Generator:
     sign: int           # s: G^dagger = s G
     axpby: str          # the names of the three functions of `backend`, looked up there at call time (tests wrap them)
     cross: str
-    rot: str | None     # (None, as `rate` and `gtheta`: a family without a rotation -- sums of Pauli strings)
+    rot: str | None     # (None, as `rate` and `gtheta`: a family without a rotation)
     spread: Callable    # spec -> (leading, trailing): backend.f(<states>, *leading, <parameters>, *trailing[, mode])
     inner: Callable     # (gen, x, gy, like) -> <x, gy> over the support, complex128 (B,), like ``like``
     rate: Callable | None       # theta_t -> r theta_t, complex128
     gtheta: Callable | None     # cross(gx, x) -> gtheta, real
+    rot_tail: Callable = lambda spec: ()        # spec -> what `rot` alone takes after everything else (a tolerance)
 
     def adjoint(self, t: torch.Tensor) -> torch.Tensor:
         """s t"""
@@ -1025,7 +1026,7 @@ class _GenRot(torch.autograd.Function):
     def forward(state: torch.Tensor, theta: torch.Tensor, gen: tuple) -> torch.Tensor:
         fam, spec = gen
         leading, trailing = fam.spread(spec)
-        return getattr(backend, fam.rot)(_kernel_arg(state), *leading, _plain(theta), *trailing)
+        return getattr(backend, fam.rot)(_kernel_arg(state), *leading, _plain(theta), *trailing, *fam.rot_tail(spec))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -1123,12 +1124,16 @@ _EXCITATIONS = _Generator(
 
 # Sums of Pauli strings (csrc/dq_psum.hip): H = sum_t h_t P_t with real h_t is Hermitian and its support is the whole state --
 # 'gate' and 'map' coincide -- so the inner product is the cross of the empty Pauli string without controls.  The spec is
-# the `backend.PsumTable`.  No rotation: exp(-i t H) is not a combination of I and H.
+# (`backend.PsumTable`, tol): tol is the tolerance of the rotation and reaches `rot` alone (`rot_tail`).  exp(-i t H) is
+# not a combination of I and H, but it is a short sum of Chebyshev polynomials of H (`backend.apply_psum_evolve`), a
+# function of H that commutes with it as the rules ask: r = -i, gtheta = Re(-i cross) = Im cross.
 _PAULI_SUMS = _Generator(
-    name='psum', sign=+1, axpby='apply_psum_axpby', cross='psum_cross', rot=None,
-    spread=lambda spec: ((spec,), ()),
+    name='psum', sign=+1, axpby='apply_psum_axpby', cross='psum_cross', rot='apply_psum_evolve',
+    spread=lambda spec: ((spec[0],), ()),
     inner=lambda gen, x, gy, like: _gen_cross((_PAULI_STRINGS, (0, 0, ())), x, gy),
-    rate=None, gtheta=None,
+    rate=lambda t_t: -1j * t_t.to(torch.complex128),
+    gtheta=lambda z: z.imag,
+    rot_tail=lambda spec: (spec[1],),
 )
 
 
@@ -1144,14 +1149,31 @@ def psum_axpby(state: torch.Tensor, a, c, H) -> torch.Tensor:
     complex, one value or one per sample.  One launch, G + 1 reads and one write of the state for G flip masks, whatever
     the number of strings; the coefficients of H are constants.
     A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
-    return _gen_axpby((_PAULI_SUMS, _psum_table(H, 'psum_axpby')), state, a, c, 'gate')
+    return _gen_axpby((_PAULI_SUMS, (_psum_table(H, 'psum_axpby'), None)), state, a, c, 'gate')
 
 
 def psum_cross(bra: torch.Tensor, ket: torch.Tensor, H) -> torch.Tensor:
     """Differentiable ``sum_i conj(bra_i) (H ket)_i`` of two (B, 2**n) states for the sum of Pauli strings ``H`` (a
     ``PauliSum``): complex128 (B,), one launch.  Pass the same tensor twice for ``<H>`` (the own vectors are read once).
     A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
-    return _gen_cross((_PAULI_SUMS, _psum_table(H, 'psum_cross')), bra, ket)
+    return _gen_cross((_PAULI_SUMS, (_psum_table(H, 'psum_cross'), None)), bra, ket)
+
+
+def psum_evolve(state: torch.Tensor, t, H, tol: float | None = None) -> torch.Tensor:
+    """Differentiable ``exp(-i t H) x`` on a (B, 2**n) state for the sum of Pauli strings ``H`` (a ``PauliSum``), ``t`` real,
+    one value or one per sample: a Chebyshev expansion accurate to ``tol`` (default 1e-6 for complex64 states, 1e-12 for
+    complex128) uniformly in ``t`` -- no Trotter error -- in about ``norm_bound |t|`` plus a few dozen launches of one read
+    of the state per flip mask each (``backend.apply_psum_evolve``, which reads ``t`` on the host).  Differentiable to any
+    order in the state and in ``t``: the backward is one evolution by ``-t`` and one ``psum_cross``.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    if tol is None:
+        tol = 1e-12 if state.dtype == torch.complex128 else 1e-6
+    tol = float(tol)
+    if not (tol > 0.0 and tol < float('inf')):
+        raise ValueError(f'psum_evolve: tol must be a positive number, got {tol}')
+    if not isinstance(t, torch.Tensor):                 # (a Python float is a double: not through the default float32)
+        t = torch.tensor(t, dtype=torch.float64, device=state.device)
+    return _gen_rot((_PAULI_SUMS, (_psum_table(H, 'psum_evolve'), tol)), state, t)
 
 
 def _pauli_masks(xmask: int, zmask: int, controls: Sequence[int]) -> tuple[int, int, tuple]:

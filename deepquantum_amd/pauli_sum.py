@@ -8,7 +8,7 @@ from typing import Any
 import torch
 
 from . import backend
-from .gate import HamiltonianGate
+from .gate import ArbitraryGate, HamiltonianGate, _FlatGate, _OneAngle
 
 
 def _real_coefficient(h: Any, string: str) -> float:
@@ -79,9 +79,66 @@ class PauliSum:
     nterms = property(lambda self: self.table.nterms, doc='strings after merging')
     ngroups = property(lambda self: self.table.ngroups, doc='distinct flip masks')
 
+    norm_bound = property(lambda self: self.table.norm_bound,
+                          doc='the sum of |h_t| over the strings other than the empty one: a rigorous bound of ||H - constant|| '
+                              '(every Pauli string has norm 1: the triangle inequality)')
+    constant = property(lambda self: self.table.constant, doc='the coefficient of the empty string')
+
+    def chebyshev_order(self, t: float, tol: float) -> int:
+        """The number of orders -- launches, about -- that ``exp(-i t H)`` takes at tolerance ``tol``: the smallest K with
+        ``2 sum_{k > K} |J_k(norm_bound |t|)| < tol``."""
+        return backend.chebyshev_order(self.norm_bound * abs(float(t)), tol)
+
     def device_table(self, device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """(xmasks, bounds, zmasks, weights) on ``device``, cached per device."""
         return self.table.on(device)
 
     def __repr__(self) -> str:
         return f'PauliSum(nqubit={self.nqubit}, nterms={self.nterms}, ngroups={self.ngroups})'
+
+
+class PauliSumEvolution(_OneAngle, _FlatGate, ArbitraryGate):
+    """``exp(-i H t)`` for ``H = sum_j coef_j P_j`` given as ``HamiltonianGate`` takes it -- ``[[0.5, 'x0y1'], [-1, 'z3y1'],
+    [0.25, '']]``, real coefficients, wires anywhere in the register, the constant term included -- or as a
+    :class:`PauliSum`, with one parameter ``t``: a Chebyshev expansion in H, accurate to ``tol`` (default 1e-6 in a
+    complex64 circuit, 1e-12 in a complex128 one) whether or not the strings commute, on any number of wires
+    (``ops.psum_evolve``: about ``norm_bound * |t|`` plus a few dozen launches of one read of the state per flip mask).
+    :class:`PauliEvolution` is the Trotter product for the same list.  ``t`` is trainable (``requires_grad=True``), fixed
+    (``t=``), or fed from the circuit's data (``encode=True``; a batch of data gives one ``t`` per sample); it is read on the
+    host at every run, so a circuit with this gate cannot be captured into a graph."""
+
+    _param_names = ('t',)
+    get_matrix = None                                   # (no matrix: not one of the circuit's vectorised one-angle gates)
+
+    def __init__(self, hamiltonian, t=None, nqubit=1, tol=None, requires_grad=False, name='PauliSumEvolution', den_mat=False,
+                 tsr_mode=False):
+        if isinstance(hamiltonian, PauliSum):
+            if hamiltonian.nqubit != nqubit:
+                raise ValueError(f'PauliSumEvolution: the PauliSum is for {hamiltonian.nqubit} qubits, the gate for {nqubit}')
+            self.hamiltonian = hamiltonian
+        else:
+            if not isinstance(hamiltonian, list) or not hamiltonian:
+                raise ValueError("PauliSumEvolution: the Hamiltonian is a PauliSum or a list such as [[0.5, 'x0y1'], [0.25, '']]")
+            try:
+                self.hamiltonian = PauliSum(hamiltonian, nqubit)
+            except ValueError as exc:
+                raise ValueError(f'PauliSumEvolution: {exc}') from exc
+        if tol is not None and not (float(tol) > 0.0 and math.isfinite(float(tol))):
+            raise ValueError(f'PauliSumEvolution: tol must be a positive number, got {tol!r}')
+        self.tol = None if tol is None else float(tol)
+        n = self.hamiltonian.nqubit
+        support = 0
+        for _, xmask, zmask in self.hamiltonian.terms:
+            support |= xmask | zmask
+        wires = [w for w in range(n) if support >> (n - 1 - w) & 1] or [0]
+        super().__init__(name=name, nqubit=nqubit, wires=wires, den_mat=den_mat, tsr_mode=tsr_mode)
+        self._one_angle([t], requires_grad)
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        return ops.psum_evolve(x, self._angle(), self.hamiltonian, self.tol)
+
+    def extra_repr(self) -> str:
+        return f'terms={self.hamiltonian.nterms}, groups={self.hamiltonian.ngroups}, tol={self.tol}, ' + _OneAngle.extra_repr(self)

@@ -572,6 +572,26 @@ def apply_pauli_sum(state: torch.Tensor, nqubit: int, H: Any) -> torch.Tensor:
     return out.reshape(state.shape)
 
 
+def evolve_pauli_sum(state: torch.Tensor, H: Any, t: Any, nqubit: int | None = None, tol: float | None = None) -> torch.Tensor:
+    """``exp(-i t H)|psi>`` for a sum of Pauli strings ``H`` (as in :func:`expectation_pauli_sum`) and a real ``t``, one
+    value or one per sample, with the shape of ``state`` and in its complex dtype: a Chebyshev expansion in H, accurate to
+    ``tol`` (default 1e-6 for complex64, 1e-12 for complex128) for any ``t`` and any strings -- nothing has to commute --
+    in about ``H.norm_bound * |t|`` plus a few dozen launches (``ops.psum_evolve``).  ``t`` is read on the host, so the call
+    cannot be captured into a graph.  Differentiable to any order in the state and in ``t``.  ``nqubit`` may be left out
+    where ``H`` is a ``PauliSum``, or where the state is (2**n,) or (B, 2**n)."""
+    from .pauli_sum import PauliSum
+
+    if nqubit is None:
+        if isinstance(H, PauliSum):
+            nqubit = H.nqubit
+        elif state.ndim in (1, 2) and state.shape[-1] > 1:
+            nqubit = state.shape[-1].bit_length() - 1
+        else:
+            raise ValueError('evolve_pauli_sum: pass nqubit (the state is neither (2**n,) nor (B, 2**n), and H is a list)')
+    flat, _ = _state_batch(state, nqubit, 'evolve_pauli_sum')
+    return ops.psum_evolve(flat, t, _pauli_sum(H, nqubit, 'evolve_pauli_sum'), tol).reshape(state.shape)
+
+
 def ising_cost(nqubit: int, terms: list, dtype: torch.dtype | None = None, device: Any = None) -> torch.Tensor:
     """The table ``c[i] = sum_j w_j (-1)^popcount(i & zmask_j)`` over all ``nqubit`` wires of the Ising polynomial
     ``terms = [(weight, [wires...]), ...]`` (a term's sign is the product of Z eigenvalues of its wires in basis state i,

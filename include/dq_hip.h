@@ -784,6 +784,23 @@ int dq_psum_cross_c128(const void* bra, const void* ket, const uint64_t* xmasks,
                        const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws,
                        int64_t ws_bytes, dq_stream_t stream);
 
+/* One order of a Chebyshev recurrence in H and its running sum, in one launch:
+ *     next[b, i] = alpha[b] * (H cur_b)[i] + beta[b] * cur[b, i] + gamma[b] * prev[b, i]
+ *     acc[b, i] += delta[b] * next[b, i]
+ * coef = DEVICE double [batch][5] = (alpha, beta, gamma, Re delta, Im delta): alpha, beta, gamma real, delta complex,
+ * rounded once to the state's real precision; 8-byte aligned.  `cur` is only read (ngroups + 1 times, as above); prev,
+ * next and acc are read and written at each lane's own vectors, once each.  Which buffers may share memory, each being
+ * [p, p + batch * 2^n):
+ *     next == prev is allowed (phi_{k+1} written over phi_{k-1}); a shifted overlap of the two is not;
+ *     cur must be disjoint from next and from acc;  acc must be disjoint from cur, prev and next.
+ * Everything else is DQ_ERR_ARG, "<a> and <b> overlap".  prev is not written unless it is next. */
+int dq_pauli_sum_cheb_step_c64(const void* cur, const void* prev, void* next, void* acc, const double* coef, const uint64_t* xmasks,
+                          const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
+                          int64_t batch, dq_stream_t stream);
+int dq_pauli_sum_cheb_step_c128(const void* cur, const void* prev, void* next, void* acc, const double* coef, const uint64_t* xmasks,
+                           const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
+                           int64_t batch, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
