@@ -172,6 +172,8 @@ _SIGNATURES = {
     'dq_psum_cross_ws_bytes': (_i64, [_i, _i64, _i, _i]),
     'dq_psum_cross_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i64, _vp]),
     'dq_pauli_sum_cheb_step_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
+    'dq_pauli_sum_lanczos_step_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i64, _vp]),
+    'dq_lanczos_update_{s}': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Any, Sequence
+from typing import Any, NamedTuple, Sequence
 
 import torch
 
@@ -1698,10 +1698,26 @@ def chebyshev_order(z: float, tol: float) -> int:
     return _cheb_order(bessel_j(abs(float(z))), tol)
 
 
-def _evolve_plan(table: PsumTable, ts: list[float], tol: float):
+def _evolve_window(table: PsumTable, bounds, what: str) -> tuple[float, float]:
+    """(a, b) with the spectrum of H inside [b - a, b + a]: the rigorous ``(norm_bound, constant)`` of the table, or half the
+    width and the centre of the caller's ``bounds = (lo, hi)``."""
+    if bounds is None:
+        return table.norm_bound, table.constant
+    try:
+        lo, hi = (float(v) for v in bounds)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}: bounds must be (lo, hi), two real numbers, got {bounds!r}') from None
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError(f'{what}: bounds must be finite, got ({lo}, {hi})')
+    if lo >= hi:
+        raise ValueError(f'{what}: bounds must have lo < hi, got ({lo}, {hi})')
+    return (hi - lo) / 2.0, (hi + lo) / 2.0
+
+
+def _evolve_plan(table: PsumTable, ts: list[float], tol: float, window: tuple[float, float] | None = None):
     """Per sample: the phase e^{-i t b} c_k of every order, c_0 = J_0, c_k = 2 (-i sgn t)^k J_k(a |t|) up to the sample's OWN
     order K_b and exactly 0 above it -- a sample's result does not depend on who shares its batch -- and K = max K_b."""
-    a, b = table.norm_bound, table.constant
+    a, b = (table.norm_bound, table.constant) if window is None else window
     rows, memo = [], {}
     for t in ts:
         if t not in memo:
@@ -1715,7 +1731,8 @@ def _evolve_plan(table: PsumTable, ts: list[float], tol: float):
     return [r + [0j] * (order + 1 - len(r)) for r in rows], order
 
 
-def apply_psum_evolve(state: torch.Tensor, table: PsumTable, t, tol: float, out: torch.Tensor | None = None) -> torch.Tensor:
+def apply_psum_evolve(state: torch.Tensor, table: PsumTable, t, tol: float, out: torch.Tensor | None = None,
+                      bounds: tuple[float, float] | None = None) -> torch.Tensor:
     """out[b] = exp(-i t[b] H) state[b] for the sum of Pauli strings H of ``table``, to within ``tol`` |state[b]| in the
     2-norm plus rounding: the Chebyshev expansion above, cut at ``chebyshev_order(norm_bound * max |t|, tol)``.  ``t``: real,
     one value or one per sample; it is READ ON THE HOST (one device-to-host copy per call when it lives on a device),
@@ -1725,7 +1742,12 @@ def apply_psum_evolve(state: torch.Tensor, table: PsumTable, t, tol: float, out:
     Launches: ``dq_apply_psum_axpby_*`` for phi_1, two elementwise operations to start the sum, then exactly one
     ``dq_pauli_sum_cheb_step_*`` per order from 2 to K, each writing phi_{k+1} over phi_{k-1}.  Two state-sized work
     buffers besides ``state`` (never written) and ``out`` (which must not overlap it).  A sample with ``t = 0`` comes back bit
-    for bit, and every sample comes out as it would alone."""
+    for bit, and every sample comes out as it would alone.
+
+    ``bounds=(lo, hi)``: an interval that holds the spectrum of H, used in place of the rigorous ``constant -+ norm_bound`` --
+    half its width where ``norm_bound`` stands above and its centre in the phase -- so that the order follows the true width
+    (``PauliSum.spectral_bounds``).  The CALLER answers for it: outside the interval the expansion grows instead of
+    converging.  ``None``: today's path, the same launches and the same bits."""
     what = 'apply_psum_evolve'
     n = _psum_args(state, table, what)
     _suffix(state)
@@ -1748,8 +1770,9 @@ def apply_psum_evolve(state: torch.Tensor, table: PsumTable, t, tol: float, out:
     if not all(math.isfinite(v) for v in ts):
         raise ValueError(f'{what}: t is not finite')
     out = _check_out(state, out, what, in_place=False)
-    coefs, order = _evolve_plan(table, ts, tol)
-    a, b = table.norm_bound, table.constant
+    window = None if bounds is None else _evolve_window(table, bounds, what)
+    coefs, order = _evolve_plan(table, ts, tol, window)
+    a, b = (table.norm_bound, table.constant) if window is None else window
     hip = _use_hip(state)
     if order == 0:                                      # (a t below the tolerance, or H a constant: a phase)
         c0 = torch.tensor([r[0] for r in coefs], dtype=torch.complex128).to(device=state.device, dtype=state.dtype)
@@ -1796,3 +1819,249 @@ def apply_psum_evolve(state: torch.Tensor, table: PsumTable, t, tol: float, out:
         if v == 0.0:
             out[s].copy_(state[s])
     return out
+
+
+# ---- one extremal eigenpair of a Pauli sum: three-term Lanczos, two launches a step ----------------------------------------
+# With v_j the unit Lanczos vectors, step j is
+#     u = H v_j - beta_j v_{j-1}  (over v_{j-1}),    alpha_j = Re <v_j, u>                      dq_pauli_sum_lanczos_step_*
+#     w = u - alpha_j v_j  (in place),               beta_{j+1} = |w|,  Re <v_j, w> (the monitor)         dq_lanczos_update_*
+# and nothing is normalised in a pass of its own: the buffer of v_j holds x_j = s_j v_j with ONE known factor -- s_1 = |start|,
+# s_j = beta_j after that, since x_{j+1} is the w of step j as it stands -- and the host folds 1 / s_j into the coefficients of
+# the next launch: (1 / s_j, 0, -beta_j / s_{j-1}) for the first kernel, -alpha_j / s_j for the second.  The tridiagonal T_m of
+# the alpha and beta lives on the host in float64; its wanted eigenpair (theta, y) gives the residual |beta_{m+1} y_m|.
+class LanczosResult(NamedTuple):
+    """What :func:`psum_lanczos` returns, one entry per sample: ``value`` float64 (B,), ``vector`` (B, 2**n) in the start's
+    dtype and on its device or ``None``, ``residual`` float64 (B,) -- the estimate |beta_{m+1} y_m| --, ``steps`` int64 (B,),
+    ``converged`` bool (B,), and the records ``alphas`` / ``betas`` (lists of B lists: alpha_1 .. alpha_m, beta_2 ..
+    beta_{m+1}).  The small tensors live on the host."""
+    value: torch.Tensor
+    vector: torch.Tensor | None
+    residual: torch.Tensor
+    steps: torch.Tensor
+    converged: torch.Tensor
+    alphas: list
+    betas: list
+
+
+class _LanczosHip:
+    """The launches of one pass over a batch on the device: ``start`` (never written), two work buffers that take turns and,
+    for the pass that forms the Ritz vector, the sum."""
+
+    def __init__(self, table: PsumTable, start: torch.Tensor, n: int, acc: torch.Tensor | None):
+        self.start, self.n, self.acc, self.batch = start, n, acc, start.shape[0]
+        self.tail = (*(_ptr(x) for x in table.on(start.device)), table.ngroups, table.nterms, n)
+        self.out = torch.empty(self.batch, 2, dtype=torch.float64, device=start.device)
+        lib, c128 = _lib.load(), int(start.dtype == torch.complex128)
+        self.ws = []
+        for lo, hi in _slices(self.batch):
+            nbytes = lib.dq_psum_cross_ws_bytes(n, hi - lo, c128, 0)
+            self.ws.append((torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=start.device), nbytes))
+        # x_1 = start is copied into the first work buffer by the update kernel itself (0 + 1 * start), which leaves
+        # |start|^2 in the same fixed order as every other sum of the run: a sample's record does not depend on its batch
+        self.cur, self.prev, self.spare = start, torch.zeros_like(start), None
+        self.norm2 = [r[0] for r in self.update(self.prev, [[1.0, 0.0]] * self.batch, None, read=True)]
+
+    def coef(self, rows):
+        return rows if isinstance(rows, torch.Tensor) else torch.tensor(rows, dtype=torch.float64).to(self.start.device)
+
+    def step(self, rows, read=True):
+        """u over x_{j-1} (into a buffer of its own where x_{j-1} is the start); (Re <x_j, u>, |u|^2) per sample."""
+        if self.prev is self.start:
+            self.spare = nxt = torch.empty_like(self.start)
+        else:
+            nxt = self.prev
+        coef = self.coef(rows)
+        for (lo, hi), (ws, nbytes) in zip(_slices(self.batch), self.ws):
+            _call('dq_pauli_sum_lanczos_step', self.start, _ptr(self.cur, lo), _ptr(self.prev, lo), _ptr(nxt, lo), _ptr(coef, lo),
+                  *self.tail, hi - lo, _ptr(self.out, lo), _ptr(ws), nbytes)
+        self.w = nxt
+        return self.out.tolist() if read else None
+
+    def update(self, w, rows, acc, read=True):
+        coef = self.coef(rows)
+        for (lo, hi), (ws, nbytes) in zip(_slices(self.batch), self.ws):
+            _call('dq_lanczos_update', self.start, _ptr(self.cur, lo), _ptr(w, lo), _ptr(acc, lo) if acc is not None else _ptr(None),
+                  _ptr(coef, lo), self.n, hi - lo, _ptr(self.out, lo), _ptr(ws), nbytes)
+        return self.out.tolist() if read else None
+
+    def finish(self, rows, read=True):
+        """w = u + e x_j in place, the sum += d x_j; (|w|^2, Re <x_j, w>) per sample.  Then w is x_{j+1}."""
+        got = self.update(self.w, rows, self.acc, read)
+        self.cur, self.prev = self.w, self.cur
+        return got
+
+    def last(self, rows):
+        """The sum += d x_m for the samples whose last vector this is (e = 0: the other buffer stays as it is -- a scratch
+        one where the other buffer is the caller's start, which is never written)."""
+        self.update(torch.zeros_like(self.start) if self.prev is self.start else self.prev, rows, self.acc, read=False)
+
+
+class _LanczosDouble:
+    """The same recurrence in complex128 on the host, sample by sample (CPU test double only): every sum is taken over one
+    sample's own 1-D tensors, so that a sample's record does not depend on its batch."""
+
+    def __init__(self, table: PsumTable, start: torch.Tensor, n: int, acc: torch.Tensor | None):
+        self.table, self.acc, self.batch = table, acc, start.shape[0]
+        self.cur = [start[b].to(torch.complex128) for b in range(self.batch)]
+        self.prev = [torch.zeros_like(x) for x in self.cur]
+        self.norm2 = [float((x.real * x.real + x.imag * x.imag).sum()) for x in self.cur]
+
+    @staticmethod
+    def sums(x, y):
+        return float((x.real * y.real + x.imag * y.imag).sum()), float((y.real * y.real + y.imag * y.imag).sum())
+
+    def step(self, rows, read=True):
+        if isinstance(rows, torch.Tensor):
+            rows = rows.tolist()
+        self.w, out = [], []
+        for b, (alpha, beta, gamma) in enumerate(rows):
+            hx = _psum_apply_double(self.cur[b].reshape(1, -1), self.table)[0] if alpha != 0.0 else torch.zeros_like(self.cur[b])
+            u = alpha * hx + beta * self.cur[b] + gamma * self.prev[b]
+            self.w.append(u)
+            out.append(list(self.sums(self.cur[b], u)))
+        return out
+
+    def finish(self, rows, read=True):
+        if isinstance(rows, torch.Tensor):
+            rows = rows.tolist()
+        out = []
+        for b, (e, d) in enumerate(rows):
+            self.w[b] = self.w[b] + e * self.cur[b]
+            if self.acc is not None:
+                self.acc[b] += d * self.cur[b]
+            out.append(list(self.sums(self.cur[b], self.w[b]))[::-1])
+        self.cur, self.prev = self.w, self.cur
+        return out
+
+    def last(self, rows):
+        if isinstance(rows, torch.Tensor):
+            rows = rows.tolist()
+        for b, (_e, d) in enumerate(rows):
+            self.acc[b] += d * self.cur[b]
+
+
+def _ritz_pair(alphas: list[float], betas: list[float], highest: bool):
+    """The wanted eigenpair of T_m (alpha_1 .. alpha_m on the diagonal, beta_2 .. beta_m beside it), y_1 >= 0."""
+    m = len(alphas)
+    t = torch.diag(torch.tensor(alphas, dtype=torch.float64))
+    if m > 1:
+        off = torch.tensor(betas[:m - 1], dtype=torch.float64)
+        t = t + torch.diag(off, 1) + torch.diag(off, -1)
+    vals, vecs = torch.linalg.eigh(t)
+    k = m - 1 if highest else 0
+    y = vecs[:, k]
+    return float(vals[k]), (-y if float(y[0]) < 0 else y).tolist()
+
+
+def psum_lanczos(table: PsumTable, start: torch.Tensor, which: str = 'lowest', tol: float | None = None,
+                 max_steps: int | None = None, vector: bool = True) -> LanczosResult:
+    """ONE extremal eigenpair -- ``which='lowest'`` or ``'highest'`` -- of the sum of Pauli strings H of ``table``, per sample
+    of ``start`` (B, 2**n), complex64 or complex128, which is never written and need not be normalised: plain three-term
+    Lanczos, two launches a step (``dq_pauli_sum_lanczos_step_*``: G + 1 reads of the state for G groups and one write;
+    ``dq_lanczos_update_*``: two reads and a write), each leaving its two sums in the same launch, bitwise reproducible.
+
+    A sample stops at the first m with ``|beta_{m+1} y_m| <= tol * norm_bound`` (``tol``: 1e-6 for complex64, 1e-12 for
+    complex128 by default), on breakdown (``beta_{m+1} <= eps * norm_bound``: the Krylov space is exhausted, the pair exact) or
+    at ``max_steps`` (default ``min(1000, 4 * 2**n)``; then ``converged`` is False and the best pair so far comes back).  Every
+    sample stops at its OWN step, with coefficients that are exactly 0 after it, and comes out bit for bit as it would alone.
+    ``vector=True`` runs the recurrence a second time -- the same launches, the same bits -- and sums the unit Ritz vector
+    ``sum_j (y_j / s_j) x_j`` on the way: twice the launches, three state-sized work buffers besides ``start`` whatever m is.
+
+    The host reads one (B, 2) tensor of doubles per launch, so the call is refused under stream capture.
+
+    What this is not.  Not several eigenpairs, and no re-orthogonalisation: ghost copies of converged Ritz values appear in
+    T_m and do not disturb the extreme pair.  In a degenerate extremal eigenspace the value is right and the vector returned
+    depends on the start.  complex64 vectors stall near a residual of 1e-7 * norm_bound: a ``tol`` below that only runs to
+    ``max_steps``."""
+    what = 'psum_lanczos'
+    n = _psum_args(start, table, what)
+    _suffix(start)
+    if which not in ('lowest', 'highest'):
+        raise ValueError(f"{what}: which must be 'lowest' or 'highest', got {which!r}")
+    if tol is None:
+        tol = 1e-6 if start.dtype == torch.complex64 else 1e-12
+    tol = float(tol)
+    if not (tol > 0.0 and math.isfinite(tol)):
+        raise ValueError(f'{what}: tol must be a positive number, got {tol}')
+    if max_steps is None:
+        max_steps = min(1000, 4 << n)
+    if int(max_steps) != max_steps or max_steps < 1:
+        raise ValueError(f'{what}: max_steps must be a positive integer, got {max_steps!r}')
+    max_steps = int(max_steps)
+    if _capturing(start):
+        raise RuntimeError(f'deepquantum_amd: {what} under stream capture: the host reads two sums after every launch and decides '
+                           'when to stop; capture the steps around it')
+    batch, highest = start.shape[0], which == 'highest'
+    nb = table.norm_bound
+    eps = float(torch.finfo(torch.float32 if start.dtype == torch.complex64 else torch.float64).eps)
+    engine = _LanczosHip if _use_hip(start) else _LanczosDouble
+
+    def run():
+        first = engine(table, start, n, None)
+        s1 = []
+        for b, v in enumerate(first.norm2):
+            if not (v > 0.0 and math.isfinite(v)):
+                raise ValueError(f'{what}: the start vector of sample {b} is zero or not finite')
+            s1.append(math.sqrt(v))
+        if nb == 0.0:                                   # H is a constant: every vector is an eigenvector
+            zeros = torch.zeros(batch, dtype=torch.float64)
+            vec = None
+            if vector:
+                scale = torch.tensor([1.0 / s for s in s1], dtype=torch.float64).to(start.device).reshape(-1, 1)
+                vec = (start * scale).to(start.dtype)
+            return LanczosResult(torch.full((batch,), table.constant, dtype=torch.float64), vec, zeros, zeros.long(),
+                                 torch.ones(batch, dtype=torch.bool), [[] for _ in range(batch)], [[] for _ in range(batch)])
+        alphas, betas = [[] for _ in range(batch)], [[] for _ in range(batch)]
+        scales = [[s] for s in s1]                      # s_1 .. s_m of each sample
+        done: list = [None] * batch                     # (theta, y, residual, converged) once a sample has stopped
+        recs = []                                       # the coefficient rows of every launch, for the second pass
+        j = 0
+        while any(d is None for d in done):
+            j += 1
+            rows = [[0.0, 0.0, 0.0] if done[b] is not None else
+                    [1.0 / scales[b][-1], 0.0, -betas[b][-1] / scales[b][-2] if j > 1 else 0.0] for b in range(batch)]
+            got = first.step(rows)
+            for b in range(batch):
+                if done[b] is None:
+                    alphas[b].append(got[b][0] / scales[b][-1])
+            erows = [[0.0, 0.0] if done[b] is not None else [-alphas[b][-1] / scales[b][-1], 0.0] for b in range(batch)]
+            got = first.finish(erows)
+            recs.append((rows, erows))
+            for b in range(batch):
+                if done[b] is not None:
+                    continue
+                beta = math.sqrt(max(got[b][0], 0.0))
+                betas[b].append(beta)
+                theta, y = _ritz_pair(alphas[b], betas[b], highest)
+                res = abs(beta * y[-1])
+                if not math.isfinite(res):
+                    raise RuntimeError(f'{what}: the recurrence of sample {b} left the finite numbers at step {j}')
+                if res <= tol * nb or beta <= eps * nb or j >= max_steps:
+                    done[b] = (theta, y, res, res <= tol * nb or beta <= eps * nb)
+                else:
+                    scales[b].append(beta)
+        steps = [len(a) for a in alphas]
+        vec = None
+        if vector:
+            vec = torch.zeros_like(start) if engine is _LanczosHip else [torch.zeros(start.shape[-1], dtype=torch.complex128)
+                                                                         for _ in range(batch)]
+            again, top = engine(table, start, n, vec), max(steps)
+            weight = lambda b, k: float(done[b][1][k - 1]) / scales[b][k - 1] if k <= steps[b] else 0.0  # noqa: E731
+            # ONE host tensor, one copy: [top - 1][B][3] rows of the first kernel, then [top][B][2] rows of the second
+            flat = [v for k in range(1, top) for b in range(batch) for v in (recs[k - 1][0][b] if k < steps[b] else [0.0, 0.0, 0.0])]
+            flat += [v for k in range(1, top + 1) for b in range(batch)
+                     for v in (recs[k - 1][1][b][0] if k < steps[b] else 0.0, weight(b, k))]
+            dev = torch.tensor(flat, dtype=torch.float64).to(start.device)
+            arows = dev[:3 * batch * (top - 1)].reshape(top - 1, batch, 3)
+            erows = dev[3 * batch * (top - 1):].reshape(top, batch, 2)
+            for k in range(1, top):
+                again.step(arows[k - 1], read=False)
+                again.finish(erows[k - 1], read=False)
+            again.last(erows[top - 1])
+            if engine is _LanczosDouble:
+                vec = torch.stack(vec).to(start.dtype)
+        return LanczosResult(torch.tensor([d[0] for d in done], dtype=torch.float64), vec,
+                             torch.tensor([d[2] for d in done], dtype=torch.float64), torch.tensor(steps, dtype=torch.int64),
+                             torch.tensor([bool(d[3]) for d in done], dtype=torch.bool), alphas, betas)
+
+    return run() if engine is _LanczosHip else _diag_double(run)

@@ -866,15 +866,16 @@ class QubitCircuit(Operation):
         self.add(PauliEvolution(hamiltonian=hamiltonian, t=t, nqubit=self.nqubit, steps=steps, order=order, name=name,
                                 den_mat=self.den_mat, requires_grad=requires_grad), encode=encode)
 
-    def pauli_sum_evolution(self, hamiltonian, t=None, tol=None, encode=False, name='pauli_sum_evolution'):
+    def pauli_sum_evolution(self, hamiltonian, t=None, tol=None, encode=False, name='pauli_sum_evolution', bounds=None):
         """``exp(-i H t)`` for ``H`` a list such as ``[[0.5, 'x0y1'], [-1, 'z3y1'], [0.25, '']]`` or a ``PauliSum``, to the
         tolerance ``tol`` whether or not the strings commute (a Chebyshev expansion, no Trotter error), with one parameter
-        ``t`` -- trainable, given, or fed from ``data`` with ``encode=True``: see :class:`PauliSumEvolution`."""
+        ``t`` -- trainable, given, or fed from ``data`` with ``encode=True``: see :class:`PauliSumEvolution`.  ``bounds=(lo,
+        hi)``: an interval that holds the spectrum of H (``PauliSum.spectral_bounds``), for fewer orders."""
         from .pauli_sum import PauliSumEvolution
 
         requires_grad = (not encode) and t is None
         self.add(PauliSumEvolution(hamiltonian=hamiltonian, t=t, nqubit=self.nqubit, tol=tol, name=name, den_mat=self.den_mat,
-                                   requires_grad=requires_grad), encode=encode)
+                                   requires_grad=requires_grad, bounds=bounds), encode=encode)
 
     def excitation(self, create, annihilate, inputs=None, controls=None, fermionic=True, encode=False, name='excitation'):
         """``exp(theta (E - E^dagger))`` for ``E = a^dagger_{create[0]} .. a_{annihilate[0]} ..`` (Jordan-Wigner over wire

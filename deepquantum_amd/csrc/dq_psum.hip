@@ -5,8 +5,12 @@
 //     dq_psum_cross       : out[b] = sum_i conj(bra[b, i]) (H ket_b)[i]
 //     dq_pauli_sum_cheb_step : next[b, i] = alpha[b] (H cur_b)[i] + beta[b] cur[b, i] + gamma[b] prev[b, i],
 //                              acc[b, i] += delta[b] next[b, i]                     (next may be prev)
+//     dq_pauli_sum_lanczos_step : next as in the Chebyshev step (no acc),  out[b] = (Re <cur_b, next_b>, |next_b|^2)
+//     dq_lanczos_update      : w[b, i] += e[b] v[b, i],  acc[b, i] += d[b] v[b, i],  out[b] = (|w_b|^2, Re <v_b, w_b>)
 // The third is one order of the Chebyshev expansion of exp(-i t H) (backend.apply_psum_evolve): the gather of the first
 // over `cur`, with the recurrence's other two vectors and the running sum read and written at the lane's own vectors.
+// The last two are the two launches of a Lanczos step (backend.psum_lanczos): the third's gather and a plain stream,
+// each with the two sums the host needs, reduced in the same launch.
 //
 // The terms are grouped by flip mask.  For the group with mask x
 //     (G_x psi)[i] = w_x(i ^ x) psi[i ^ x],      w_x(j) = sum_{t in group} h_t i^{ny_t} (-1)^popc(j & z_t)
@@ -224,6 +228,126 @@ __global__ __launch_bounds__(ST_THREADS) void psum_cheb_step_kernel(const cx<T>*
     }
 }
 
+// One half of a Lanczos step in H, with the two sums the host needs of it:
+//     next = alpha (H cur) + beta cur + gamma prev,      ws[b, blockIdx.x] = this workgroup's part of
+//     ( sum_i Re conj(cur_i) next_i ,  sum_i |next_i|^2 )
+// psum_cheb_step_kernel without its running sum: the same gather over `cur`, prev loaded after the group loop, the same
+// SAME split (every pointer __restrict__ in earnest, see above).  The sums are taken over `next` AS STORED -- after the
+// rounding to the state's precision -- with products and sums in double, so the host's record describes the vectors that
+// exist.  A lane beyond a small sample stores nothing and adds nothing (`live`).
+// coef = [batch][3] doubles (alpha, beta, gamma), rounded once to the state's real precision.
+template <typename T, bool SAME>
+__global__ __launch_bounds__(ST_THREADS) void psum_lanczos_step_kernel(const cx<T>* __restrict__ cur, const cx<T>* __restrict__ prev,
+                                                                       cx<T>* __restrict__ next, const double* __restrict__ coef,
+                                                                       PsumTable tb, int n, uint64_t nvec, double* __restrict__ ws) {
+    using Q = typename Vec16<T>::type;
+    constexpr int VEC = 16 / (int)sizeof(cx<T>);
+    __shared__ double sh[ST_THREADS / 64][2];
+    const uint64_t b = blockIdx.y;
+    const Q* src = reinterpret_cast<const Q*>(cur + (b << n));
+    Q* pnext = reinterpret_cast<Q*>(next + (b << n));
+    const Q* pprev = SAME ? pnext : reinterpret_cast<const Q*>(prev + (b << n));
+    const T alpha = (T)coef[3 * b], beta = (T)coef[3 * b + 1], gamma = (T)coef[3 * b + 2];
+    double dot = 0.0, nrm = 0.0;
+    for (uint64_t unit = blockIdx.x; (unit << ST_UNIT_BITS) < nvec; unit += gridDim.x) {
+        uint64_t vec[ST_UNROLL];
+        const unsigned live = unit_vectors(unit, nvec, vec);
+        Q own[ST_UNROLL];
+        cx<T> h[ST_UNROLL][VEC];                        // (H cur) at the lane's amplitudes
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            own[u] = src[vec[u]];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) h[u][e] = mk<T>((T)0, (T)0);
+        }
+        for (int g = 0; g < tb.ngroups; ++g) {
+            Q q[ST_UNROLL];
+            T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
+            int x0;
+            load_group<T, VEC, Q>(tb, g, n, src, unit, vec, own, q, x0, wr, wi);
+#pragma unroll
+            for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) h[u][e] = cfma(mk<T>(wr[u][e], wi[u][e]), vec_get<T>(q[u], e ^ x0), h[u][e]);
+        }
+        Q p[ST_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) p[u] = pprev[vec[u]];      // (a lane beyond a small sample reads vector 0)
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            Q r;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const cx<T> o = vec_get<T>(own[u], e), pv = vec_get<T>(p[u], e);
+                const cx<T> y = mk<T>(fma(gamma, pv.x, fma(beta, o.x, alpha * h[u][e].x)),
+                                      fma(gamma, pv.y, fma(beta, o.y, alpha * h[u][e].y)));
+                vec_set(r, e, y);
+                if (live >> u & 1u) {
+                    const double yr = (double)y.x, yi = (double)y.y;
+                    dot = fma((double)o.x, yr, fma((double)o.y, yi, dot));
+                    nrm = fma(yr, yr, fma(yi, yi, nrm));
+                }
+            }
+            if (live >> u & 1u) pnext[vec[u]] = r;
+        }
+    }
+    write_partial(dot, nrm, sh, ws);
+}
+
+// The other half of a Lanczos step, a pure stream over the lane's own vectors (no gather):
+//     w += e v  (in place),      acc += d v  (HAS_ACC),      ws[b, blockIdx.x] = this workgroup's part of
+//     ( sum_i |w_i|^2 ,  sum_i Re conj(v_i) w_i )     over the updated w as stored
+// coef = [batch][2] doubles (e, d), real, rounded once to the state's real precision.  v, w and acc pairwise disjoint.
+template <typename T, bool HAS_ACC>
+__global__ __launch_bounds__(ST_THREADS) void lanczos_update_kernel(const cx<T>* __restrict__ v, cx<T>* __restrict__ w,
+                                                                    cx<T>* __restrict__ acc, const double* __restrict__ coef,
+                                                                    int n, uint64_t nvec, double* __restrict__ ws) {
+    using Q = typename Vec16<T>::type;
+    constexpr int VEC = 16 / (int)sizeof(cx<T>);
+    __shared__ double sh[ST_THREADS / 64][2];
+    const uint64_t b = blockIdx.y;
+    const Q* pv = reinterpret_cast<const Q*>(v + (b << n));
+    Q* pw = reinterpret_cast<Q*>(w + (b << n));
+    Q* pa = HAS_ACC ? reinterpret_cast<Q*>(acc + (b << n)) : nullptr;
+    const T ce = (T)coef[2 * b], cd = (T)coef[2 * b + 1];
+    double nrm = 0.0, dot = 0.0;
+    for (uint64_t unit = blockIdx.x; (unit << ST_UNIT_BITS) < nvec; unit += gridDim.x) {
+        uint64_t vec[ST_UNROLL];
+        const unsigned live = unit_vectors(unit, nvec, vec);
+        Q qv[ST_UNROLL], qw[ST_UNROLL], qa[ST_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            qv[u] = pv[vec[u]];
+            qw[u] = pw[vec[u]];
+            if (HAS_ACC) qa[u] = pa[vec[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) {
+            Q r, s;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const cx<T> x = vec_get<T>(qv[u], e), y0 = vec_get<T>(qw[u], e);
+                const cx<T> y = mk<T>(fma(ce, x.x, y0.x), fma(ce, x.y, y0.y));
+                vec_set(r, e, y);
+                if (HAS_ACC) {
+                    const cx<T> a0 = vec_get<T>(qa[u], e);
+                    vec_set(s, e, mk<T>(fma(cd, x.x, a0.x), fma(cd, x.y, a0.y)));
+                }
+                if (live >> u & 1u) {
+                    const double yr = (double)y.x, yi = (double)y.y;
+                    nrm = fma(yr, yr, fma(yi, yi, nrm));
+                    dot = fma((double)x.x, yr, fma((double)x.y, yi, dot));
+                }
+            }
+            if (live >> u & 1u) {
+                pw[vec[u]] = r;
+                if (HAS_ACC) pa[vec[u]] = s;
+            }
+        }
+    }
+    write_partial(nrm, dot, sh, ws);
+}
+
 // ws[b, blockIdx.x] = this workgroup's part of sum_i conj(bra_i) (H ket)_i
 template <typename T, bool SAME>
 __global__ __launch_bounds__(ST_THREADS) void psum_cross_kernel(const cx<T>* __restrict__ bra, const cx<T>* __restrict__ ket,
@@ -361,6 +485,109 @@ int cheb_step_impl(const void* cur, const void* prev, void* next, void* acc, con
     return check_launch(what);
 }
 
+// out and ws of a kernel that leaves two sums per sample: non-null, out 8-byte and ws 16-byte aligned, ws large enough
+// (check_cross's checks of the two, for entry points whose states are not a bra and a ket)
+int check_sums(const char* what, const double* out, const void* ws, int64_t ws_bytes, int n, int64_t batch, bool is_c128) {
+    if (!out || !ws) {
+        set_error("%s: null pointer (out, ws)", what);
+        return DQ_ERR_ARG;
+    }
+    if (misaligned(ws) || (reinterpret_cast<uintptr_t>(out) & 7)) {
+        set_error("%s: ws must be 16-byte aligned, out 8-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    const int64_t need = cross_ws_bytes(n, batch, is_c128);
+    if (ws_bytes < need) {
+        set_error("%s: workspace of %lld bytes, %lld needed (dq_psum_cross_ws_bytes)", what, (long long)ws_bytes, (long long)need);
+        return DQ_ERR_ARG;
+    }
+    return DQ_OK;
+}
+
+// cheb_step_impl's rules without acc: cur is gathered from and apart from next; next may be prev.
+template <typename T>
+int lanczos_step_impl(const void* cur, const void* prev, void* next, const double* coef, const uint64_t* xmasks, const int* bounds,
+                      const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out,
+                      void* ws, int64_t ws_bytes, dq_stream_t stream) {
+    constexpr bool C128 = sizeof(T) == 8;
+    const char* what = "dq_pauli_sum_lanczos_step";
+    if (!cur || !prev || !next) {
+        set_error("%s: null pointer", what);
+        return DQ_ERR_ARG;
+    }
+    if (misaligned(cur) || misaligned(prev) || misaligned(next)) {
+        set_error("%s: cur, prev and next must be 16-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    if (n < 1 || n > 40) {
+        set_error("%s: n=%d out of range [1, 40]", what, n);
+        return DQ_ERR_ARG;
+    }
+    if (int rc = check_batch(what, batch)) return rc;
+    const uint64_t bytes = ((uint64_t)batch << n) * sizeof(cx<T>);
+    if (int rc = check_apart(what, "cur", cur, "next", next, bytes, DISJOINT)) return rc;
+    if (int rc = check_apart(what, "next", next, "prev", prev, bytes, SAME_OR_DISJOINT)) return rc;
+    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
+        set_error("%s: coef must be non-null and 8-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    PsumTable tb;
+    if (int rc = check_table(what, xmasks, bounds, zmasks, weights, ngroups, nterms, &tb)) return rc;
+    if (int rc = check_sums(what, out, ws, ws_bytes, n, batch, C128)) return rc;
+    const uint64_t nvec = vectors_of(n, C128);
+    const unsigned nblk = blocks_of(nvec);
+    const dim3 grid(nblk, (unsigned)batch);
+    const cx<T>* pc = static_cast<const cx<T>*>(cur);
+    cx<T>* pn = static_cast<cx<T>*>(next);
+    double* part = static_cast<double*>(ws);
+    hipStream_t s = as_stream(stream);
+    if (prev == next) hipLaunchKernelGGL((psum_lanczos_step_kernel<T, true>), grid, dim3(ST_THREADS), 0, s, pc, nullptr, pn, coef, tb, n, nvec, part);
+    else hipLaunchKernelGGL((psum_lanczos_step_kernel<T, false>), grid, dim3(ST_THREADS), 0, s, pc, static_cast<const cx<T>*>(prev), pn, coef, tb, n, nvec, part);
+    return finish_cross(what, part, nblk, batch, out, s);
+}
+
+// v is only read, w and acc are read and written at each lane's own vectors: the three pairwise disjoint; acc may be null.
+template <typename T>
+int lanczos_update_impl(const void* v, void* w, void* acc, const double* coef, int n, int64_t batch, double* out, void* ws,
+                        int64_t ws_bytes, dq_stream_t stream) {
+    constexpr bool C128 = sizeof(T) == 8;
+    const char* what = "dq_lanczos_update";
+    if (!v || !w) {
+        set_error("%s: null pointer", what);
+        return DQ_ERR_ARG;
+    }
+    if (misaligned(v) || misaligned(w) || misaligned(acc)) {
+        set_error("%s: v, w and acc must be 16-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    if (n < 1 || n > 40) {
+        set_error("%s: n=%d out of range [1, 40]", what, n);
+        return DQ_ERR_ARG;
+    }
+    if (int rc = check_batch(what, batch)) return rc;
+    const uint64_t bytes = ((uint64_t)batch << n) * sizeof(cx<T>);
+    if (int rc = check_apart(what, "v", v, "w", w, bytes, DISJOINT)) return rc;
+    if (acc) {
+        if (int rc = check_apart(what, "acc", acc, "v", v, bytes, DISJOINT)) return rc;
+        if (int rc = check_apart(what, "acc", acc, "w", w, bytes, DISJOINT)) return rc;
+    }
+    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
+        set_error("%s: coef must be non-null and 8-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    if (int rc = check_sums(what, out, ws, ws_bytes, n, batch, C128)) return rc;
+    const uint64_t nvec = vectors_of(n, C128);
+    const unsigned nblk = blocks_of(nvec);
+    const dim3 grid(nblk, (unsigned)batch);
+    const cx<T>* pv = static_cast<const cx<T>*>(v);
+    cx<T>* pw = static_cast<cx<T>*>(w);
+    double* part = static_cast<double*>(ws);
+    hipStream_t s = as_stream(stream);
+    if (acc) hipLaunchKernelGGL((lanczos_update_kernel<T, true>), grid, dim3(ST_THREADS), 0, s, pv, pw, static_cast<cx<T>*>(acc), coef, n, nvec, part);
+    else hipLaunchKernelGGL((lanczos_update_kernel<T, false>), grid, dim3(ST_THREADS), 0, s, pv, pw, static_cast<cx<T>*>(nullptr), coef, n, nvec, part);
+    return finish_cross(what, part, nblk, batch, out, s);
+}
+
 template <typename T>
 int cross_impl(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks,
                const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws, int64_t ws_bytes,
@@ -410,6 +637,28 @@ extern "C" int dq_pauli_sum_cheb_step_c128(const void* cur, const void* prev, vo
                                       const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks, const double* weights,
                                       int ngroups, int nterms, int n, int64_t batch, dq_stream_t stream) {
     return dq::cheb_step_impl<double>(cur, prev, next, acc, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, stream);
+}
+
+extern "C" int dq_pauli_sum_lanczos_step_c64(const void* cur, const void* prev, void* next, const double* coef, const uint64_t* xmasks,
+                                             const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms,
+                                             int n, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
+    return dq::lanczos_step_impl<float>(cur, prev, next, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, out, ws,
+                                        ws_bytes, stream);
+}
+extern "C" int dq_pauli_sum_lanczos_step_c128(const void* cur, const void* prev, void* next, const double* coef, const uint64_t* xmasks,
+                                              const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms,
+                                              int n, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
+    return dq::lanczos_step_impl<double>(cur, prev, next, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, out, ws,
+                                         ws_bytes, stream);
+}
+
+extern "C" int dq_lanczos_update_c64(const void* v, void* w, void* acc, const double* coef, int n, int64_t batch, double* out,
+                                     void* ws, int64_t ws_bytes, dq_stream_t stream) {
+    return dq::lanczos_update_impl<float>(v, w, acc, coef, n, batch, out, ws, ws_bytes, stream);
+}
+extern "C" int dq_lanczos_update_c128(const void* v, void* w, void* acc, const double* coef, int n, int64_t batch, double* out,
+                                      void* ws, int64_t ws_bytes, dq_stream_t stream) {
+    return dq::lanczos_update_impl<double>(v, w, acc, coef, n, batch, out, ws, ws_bytes, stream);
 }
 
 extern "C" int64_t dq_psum_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross) {

@@ -1133,7 +1133,7 @@ _PAULI_SUMS = _Generator(
     inner=lambda gen, x, gy, like: _gen_cross((_PAULI_STRINGS, (0, 0, ())), x, gy),
     rate=lambda t_t: -1j * t_t.to(torch.complex128),
     gtheta=lambda z: z.imag,
-    rot_tail=lambda spec: (spec[1],),
+    rot_tail=lambda spec: (spec[1],) if len(spec) < 3 or spec[2] is None else (spec[1], None, spec[2]),     # (tol[, out, bounds])
 )
 
 
@@ -1159,12 +1159,14 @@ def psum_cross(bra: torch.Tensor, ket: torch.Tensor, H) -> torch.Tensor:
     return _gen_cross((_PAULI_SUMS, (_psum_table(H, 'psum_cross'), None)), bra, ket)
 
 
-def psum_evolve(state: torch.Tensor, t, H, tol: float | None = None) -> torch.Tensor:
+def psum_evolve(state: torch.Tensor, t, H, tol: float | None = None, bounds: tuple[float, float] | None = None) -> torch.Tensor:
     """Differentiable ``exp(-i t H) x`` on a (B, 2**n) state for the sum of Pauli strings ``H`` (a ``PauliSum``), ``t`` real,
     one value or one per sample: a Chebyshev expansion accurate to ``tol`` (default 1e-6 for complex64 states, 1e-12 for
     complex128) uniformly in ``t`` -- no Trotter error -- in about ``norm_bound |t|`` plus a few dozen launches of one read
     of the state per flip mask each (``backend.apply_psum_evolve``, which reads ``t`` on the host).  Differentiable to any
     order in the state and in ``t``: the backward is one evolution by ``-t`` and one ``psum_cross``.
+    ``bounds=(lo, hi)``: an interval that holds the spectrum of H (``PauliSum.spectral_bounds``), in place of the rigorous
+    and loose ``constant -+ norm_bound``: fewer orders; it travels with ``tol``, so the backward uses the same one.
     A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     if tol is None:
         tol = 1e-12 if state.dtype == torch.complex128 else 1e-6
@@ -1173,7 +1175,11 @@ def psum_evolve(state: torch.Tensor, t, H, tol: float | None = None) -> torch.Te
         raise ValueError(f'psum_evolve: tol must be a positive number, got {tol}')
     if not isinstance(t, torch.Tensor):                 # (a Python float is a double: not through the default float32)
         t = torch.tensor(t, dtype=torch.float64, device=state.device)
-    return _gen_rot((_PAULI_SUMS, (_psum_table(H, 'psum_evolve'), tol)), state, t)
+    table = _psum_table(H, 'psum_evolve')
+    if bounds is None:
+        return _gen_rot((_PAULI_SUMS, (table, tol)), state, t)
+    backend._evolve_window(table, bounds, 'psum_evolve')                           # (refused here, by name, once)
+    return _gen_rot((_PAULI_SUMS, (table, tol, (float(bounds[0]), float(bounds[1])))), state, t)
 
 
 def _pauli_masks(xmask: int, zmask: int, controls: Sequence[int]) -> tuple[int, int, tuple]:

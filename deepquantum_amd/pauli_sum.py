@@ -84,10 +84,55 @@ class PauliSum:
                               '(every Pauli string has norm 1: the triangle inequality)')
     constant = property(lambda self: self.table.constant, doc='the coefficient of the empty string')
 
-    def chebyshev_order(self, t: float, tol: float) -> int:
+    def chebyshev_order(self, t: float, tol: float, bounds: tuple[float, float] | None = None) -> int:
         """The number of orders -- launches, about -- that ``exp(-i t H)`` takes at tolerance ``tol``: the smallest K with
-        ``2 sum_{k > K} |J_k(norm_bound |t|)| < tol``."""
-        return backend.chebyshev_order(self.norm_bound * abs(float(t)), tol)
+        ``2 sum_{k > K} |J_k(norm_bound |t|)| < tol``; with ``bounds=(lo, hi)``, half their width in place of ``norm_bound``."""
+        a = self.norm_bound if bounds is None else backend._evolve_window(self.table, bounds, 'PauliSum.chebyshev_order')[0]
+        return backend.chebyshev_order(a * abs(float(t)), tol)
+
+    def spectral_bounds(self, tol: float = 1e-3, margin: float = 0.01, seed: int = 0, dtype: torch.dtype = torch.complex64,
+                        device: Any = None) -> tuple[float, float]:
+        """``(lo, hi)`` around the spectrum of H from two short Lanczos runs without vectors (:meth:`extremal`, lowest and
+        highest, to a residual of ``tol * norm_bound``): each Ritz value moved OUTWARD by its residual estimate plus ``margin``
+        times the width between the two, the result clipped into the rigorous ``[constant - norm_bound, constant + norm_bound]``.
+        Cached per argument set.  Made for ``bounds=`` of the evolution (``evolve_pauli_sum``, ``PauliSumEvolution``), whose
+        order then follows the true width of the spectrum and not the loose ``norm_bound``.
+
+        This is NOT a rigorous bound.  A small residual proves that an eigenvalue lies that close to the Ritz value, not that
+        it is the extreme one: a start vector with no weight on the extreme eigenvector never finds it (a Gaussian random
+        start has weight on everything, almost surely).  Why it is safe in practice all the same: a Ritz value that has
+        settled to ``tol`` misses the true edge by far less than the margin, and an eigenvalue a relative ``delta`` outside
+        the interval only makes the Chebyshev polynomial of order K grow like ``cosh(K sqrt(2 delta))`` -- for the delta
+        that can be left and the K of an evolution, a factor next to 1.  Where a proof is needed, leave ``bounds`` out."""
+        key = (float(tol), float(margin), int(seed), dtype, None if device is None else str(torch.device(device)))
+        cache = self.__dict__.setdefault('_spectral_bounds', {})
+        if key not in cache:
+            if not (float(margin) >= 0.0 and math.isfinite(float(margin))):
+                raise ValueError(f'PauliSum.spectral_bounds: margin must be a number >= 0, got {margin!r}')
+            rigorous = (self.constant - self.norm_bound, self.constant + self.norm_bound)
+            if self.norm_bound == 0.0:
+                cache[key] = rigorous
+            else:
+                kw = dict(tol=tol, vector=False, dtype=dtype, device=device, seed=seed)
+                low, high = self.extremal('lowest', **kw), self.extremal('highest', **kw)
+                width = float(high.value) - float(low.value)
+                lo = float(low.value) - float(low.residual) - float(margin) * width
+                hi = float(high.value) + float(high.residual) + float(margin) * width
+                cache[key] = (max(lo, rigorous[0]), min(hi, rigorous[1]))
+        return cache[key]
+
+    def extremal(self, which: str = 'lowest', **kw):
+        """The lowest or highest eigenvalue of H and its eigenvector by Lanczos steps on the device:
+        ``qmath.pauli_sum_extremal(self, which=which, **kw)``, which lists the keywords (``tol``, ``max_steps``, ``start``,
+        ``vector``, ``dtype``, ``device``, ``seed``) and what this is not: one pair only, a start-dependent vector in a
+        degenerate level, a complex64 residual that stalls near 1e-7 * norm_bound."""
+        from . import qmath
+
+        return qmath.pauli_sum_extremal(self, which=which, **kw)
+
+    def ground_state(self, **kw):
+        """The ground energy and ground state: ``self.extremal('lowest', **kw)``."""
+        return self.extremal('lowest', **kw)
 
     def device_table(self, device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """(xmasks, bounds, zmasks, weights) on ``device``, cached per device."""
@@ -105,13 +150,15 @@ class PauliSumEvolution(_OneAngle, _FlatGate, ArbitraryGate):
     (``ops.psum_evolve``: about ``norm_bound * |t|`` plus a few dozen launches of one read of the state per flip mask).
     :class:`PauliEvolution` is the Trotter product for the same list.  ``t`` is trainable (``requires_grad=True``), fixed
     (``t=``), or fed from the circuit's data (``encode=True``; a batch of data gives one ``t`` per sample); it is read on the
-    host at every run, so a circuit with this gate cannot be captured into a graph."""
+    host at every run, so a circuit with this gate cannot be captured into a graph.  ``bounds=(lo, hi)``: an interval that
+    holds the spectrum of H (``PauliSum.spectral_bounds``), in place of ``constant -+ norm_bound``: fewer orders, forward and
+    backward."""
 
     _param_names = ('t',)
     get_matrix = None                                   # (no matrix: not one of the circuit's vectorised one-angle gates)
 
     def __init__(self, hamiltonian, t=None, nqubit=1, tol=None, requires_grad=False, name='PauliSumEvolution', den_mat=False,
-                 tsr_mode=False):
+                 tsr_mode=False, bounds=None):
         if isinstance(hamiltonian, PauliSum):
             if hamiltonian.nqubit != nqubit:
                 raise ValueError(f'PauliSumEvolution: the PauliSum is for {hamiltonian.nqubit} qubits, the gate for {nqubit}')
@@ -126,6 +173,10 @@ class PauliSumEvolution(_OneAngle, _FlatGate, ArbitraryGate):
         if tol is not None and not (float(tol) > 0.0 and math.isfinite(float(tol))):
             raise ValueError(f'PauliSumEvolution: tol must be a positive number, got {tol!r}')
         self.tol = None if tol is None else float(tol)
+        if bounds is not None:
+            backend._evolve_window(self.hamiltonian.table, bounds, 'PauliSumEvolution')
+            bounds = (float(bounds[0]), float(bounds[1]))
+        self.bounds = bounds
         n = self.hamiltonian.nqubit
         support = 0
         for _, xmask, zmask in self.hamiltonian.terms:
@@ -138,7 +189,11 @@ class PauliSumEvolution(_OneAngle, _FlatGate, ArbitraryGate):
         """(B, 2**n) -> (B, 2**n)."""
         from . import ops
 
-        return ops.psum_evolve(x, self._angle(), self.hamiltonian, self.tol)
+        if self.bounds is None:
+            return ops.psum_evolve(x, self._angle(), self.hamiltonian, self.tol)
+        return ops.psum_evolve(x, self._angle(), self.hamiltonian, self.tol, self.bounds)
 
     def extra_repr(self) -> str:
-        return f'terms={self.hamiltonian.nterms}, groups={self.hamiltonian.ngroups}, tol={self.tol}, ' + _OneAngle.extra_repr(self)
+        bounds = '' if self.bounds is None else f'bounds={self.bounds}, '
+        return (f'terms={self.hamiltonian.nterms}, groups={self.hamiltonian.ngroups}, tol={self.tol}, ' + bounds
+                + _OneAngle.extra_repr(self))

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import math
 from collections import Counter
-from typing import TYPE_CHECKING, Any
+from typing import TYPE_CHECKING, Any, NamedTuple
 
 import torch
 from torch import nn
@@ -572,13 +572,16 @@ def apply_pauli_sum(state: torch.Tensor, nqubit: int, H: Any) -> torch.Tensor:
     return out.reshape(state.shape)
 
 
-def evolve_pauli_sum(state: torch.Tensor, H: Any, t: Any, nqubit: int | None = None, tol: float | None = None) -> torch.Tensor:
+def evolve_pauli_sum(state: torch.Tensor, H: Any, t: Any, nqubit: int | None = None, tol: float | None = None,
+                     bounds: tuple[float, float] | None = None) -> torch.Tensor:
     """``exp(-i t H)|psi>`` for a sum of Pauli strings ``H`` (as in :func:`expectation_pauli_sum`) and a real ``t``, one
     value or one per sample, with the shape of ``state`` and in its complex dtype: a Chebyshev expansion in H, accurate to
     ``tol`` (default 1e-6 for complex64, 1e-12 for complex128) for any ``t`` and any strings -- nothing has to commute --
     in about ``H.norm_bound * |t|`` plus a few dozen launches (``ops.psum_evolve``).  ``t`` is read on the host, so the call
     cannot be captured into a graph.  Differentiable to any order in the state and in ``t``.  ``nqubit`` may be left out
-    where ``H`` is a ``PauliSum``, or where the state is (2**n,) or (B, 2**n)."""
+    where ``H`` is a ``PauliSum``, or where the state is (2**n,) or (B, 2**n).  ``bounds=(lo, hi)``: an interval that holds
+    the spectrum of H, e.g. ``H.spectral_bounds()``, in place of the rigorous and loose ``constant -+ norm_bound``: about
+    as many launches fewer as the interval is narrower (``None``: today's path, bit for bit)."""
     from .pauli_sum import PauliSum
 
     if nqubit is None:
@@ -589,7 +592,65 @@ def evolve_pauli_sum(state: torch.Tensor, H: Any, t: Any, nqubit: int | None = N
         else:
             raise ValueError('evolve_pauli_sum: pass nqubit (the state is neither (2**n,) nor (B, 2**n), and H is a list)')
     flat, _ = _state_batch(state, nqubit, 'evolve_pauli_sum')
-    return ops.psum_evolve(flat, t, _pauli_sum(H, nqubit, 'evolve_pauli_sum'), tol).reshape(state.shape)
+    H = _pauli_sum(H, nqubit, 'evolve_pauli_sum')
+    if bounds is None:
+        return ops.psum_evolve(flat, t, H, tol).reshape(state.shape)
+    return ops.psum_evolve(flat, t, H, tol, bounds).reshape(state.shape)
+
+
+class ExtremalResult(NamedTuple):
+    """What :func:`pauli_sum_extremal` returns: ``value`` float64, ``vector`` (unit, in ``dtype``; ``None`` with
+    ``vector=False``), ``residual`` -- the Lanczos estimate of ``|H y - value y|`` --, ``steps`` and ``converged``; one entry
+    per start vector, (B,) and (B, 2**n), or 0-d and (2**n,) for a single start."""
+    value: torch.Tensor
+    vector: torch.Tensor | None
+    residual: torch.Tensor
+    steps: torch.Tensor
+    converged: torch.Tensor
+
+
+def pauli_sum_extremal(H: Any, nqubit: int | None = None, which: str = 'lowest', tol: float | None = None,
+                       max_steps: int | None = None, start: torch.Tensor | None = None, vector: bool = True,
+                       dtype: torch.dtype = torch.complex64, device: Any = None, seed: int = 0) -> ExtremalResult:
+    """The lowest (``which='lowest'``) or highest (``'highest'``) eigenvalue of a sum of Pauli strings ``H`` -- a
+    :class:`PauliSum` or the list form -- and its eigenvector: the exact ground energy and ground state a variational energy
+    is judged against, by Lanczos steps of two launches each on the device (:func:`backend.psum_lanczos`), to a residual of
+    ``tol * H.norm_bound`` (``tol``: 1e-6 for complex64, 1e-12 for complex128 by default).  ``start``: (2**n,) or (B, 2**n)
+    complex, never written, not necessarily normalised -- one eigenpair per start vector; ``None``: one Gaussian random vector
+    from ``seed`` in ``dtype`` on ``device`` (default: the GPU).  ``vector=False`` leaves the second pass out: half the launches.
+    The result is detached: the coefficients of a ``PauliSum`` carry no gradient, so neither does this.
+
+    What this is not.  Not several eigenpairs.  In a degenerate extremal eigenspace the value is right and the vector
+    returned depends on the start.  complex64 stalls near a residual of 1e-7 * norm_bound: ask complex128 for more.  The
+    host reads two numbers after every launch, so the call cannot be captured into a graph."""
+    from .pauli_sum import PauliSum
+
+    what = 'pauli_sum_extremal'
+    if nqubit is None:
+        if isinstance(H, PauliSum):
+            nqubit = H.nqubit
+        elif start is not None and start.ndim in (1, 2) and start.shape[-1] > 1:
+            nqubit = start.shape[-1].bit_length() - 1
+        else:
+            raise ValueError(f'{what}: pass nqubit (H is a list and there is no start vector to take it from)')
+    H = _pauli_sum(H, nqubit, what)
+    n = H.nqubit
+    single = start is None or start.ndim == 1
+    if start is None:
+        if dtype not in (torch.complex64, torch.complex128):
+            raise ValueError(f'{what}: dtype must be torch.complex64 or torch.complex128, got {dtype}')
+        device = torch.device('cuda' if device is None and backend.get_test_backend() is None else device or 'cpu')
+        g = torch.Generator().manual_seed(int(seed))
+        flat = torch.randn(1, 1 << n, dtype=torch.complex128, generator=g).to(device=device, dtype=dtype)
+    else:
+        if not isinstance(start, torch.Tensor) or start.ndim not in (1, 2) or start.shape[-1] != 1 << n:
+            raise ValueError(f'{what}: start must be a tensor of shape ({1 << n},) or (B, {1 << n})')
+        flat = start.detach().reshape(-1, 1 << n).contiguous()
+    got = backend.psum_lanczos(H.table, flat, which, tol, max_steps, vector)
+    vec = got.vector
+    if single:
+        return ExtremalResult(got.value[0], None if vec is None else vec[0], got.residual[0], got.steps[0], got.converged[0])
+    return ExtremalResult(got.value, vec, got.residual, got.steps, got.converged)
 
 
 def ising_cost(nqubit: int, terms: list, dtype: torch.dtype | None = None, device: Any = None) -> torch.Tensor:

@@ -801,6 +801,37 @@ int dq_pauli_sum_cheb_step_c128(const void* cur, const void* prev, void* next, v
                            const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
                            int64_t batch, dq_stream_t stream);
 
+/* The two launches of a three-term Lanczos step in H (added within ABI 30, presence is checked by symbol).  Both leave two
+ * real sums per sample in out = DEVICE double [batch][2], fully overwritten: products and sums in double over the values
+ * AS STORED (after rounding to the state's precision), workgroups' partial sums in a fixed order through `ws` (at least
+ * dq_psum_cross_ws_bytes(n, batch, is_c128, 0) bytes, 16-byte aligned) and a second kernel: no atomics, bitwise
+ * reproducible.  out 8-byte aligned.
+ *
+ * dq_pauli_sum_lanczos_step_*:
+ *     next[b, i] = alpha[b] * (H cur_b)[i] + beta[b] * cur[b, i] + gamma[b] * prev[b, i]
+ *     out[b]     = ( sum_i Re conj(cur[b, i]) next[b, i] ,  sum_i |next[b, i]|^2 )
+ * coef = DEVICE double [batch][3] = (alpha, beta, gamma), real, rounded once to the state's real precision; 8-byte
+ * aligned.  `cur` is only read (ngroups + 1 times, as above); prev is read and next written at each lane's own vectors.
+ * next == prev is allowed, a shifted overlap of the two is not; cur must be disjoint from next: everything else is
+ * DQ_ERR_ARG, "<a> and <b> overlap".  prev is never null (the first step passes zeros) and not written unless it is next. */
+int dq_pauli_sum_lanczos_step_c64(const void* cur, const void* prev, void* next, const double* coef, const uint64_t* xmasks,
+                                  const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
+                                  int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+int dq_pauli_sum_lanczos_step_c128(const void* cur, const void* prev, void* next, const double* coef, const uint64_t* xmasks,
+                                   const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
+                                   int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+/* dq_lanczos_update_*: a stream over the lane's own vectors, no table:
+ *     w[b, i]   += e[b] * v[b, i]                      (in place)
+ *     acc[b, i] += d[b] * v[b, i]                      (only when acc is non-null)
+ *     out[b]     = ( sum_i |w[b, i]|^2 ,  sum_i Re conj(v[b, i]) w[b, i] )       over the updated w
+ * coef = DEVICE double [batch][2] = (e, d), real, rounded once to the state's real precision; 8-byte aligned.  v is only
+ * read.  v, w and acc (where given) are 16-byte aligned and pairwise disjoint (DQ_ERR_ARG, "<a> and <b> overlap").
+ * 1 <= n <= 40, 1 <= batch <= 65535. */
+int dq_lanczos_update_c64(const void* v, void* w, void* acc, const double* coef, int n, int64_t batch, double* out, void* ws,
+                          int64_t ws_bytes, dq_stream_t stream);
+int dq_lanczos_update_c128(const void* v, void* w, void* acc, const double* coef, int n, int64_t batch, double* out, void* ws,
+                           int64_t ws_bytes, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
