@@ -1563,6 +1563,10 @@ class PsumTable:
         pin_if_capturing(*hit)
         return hit
 
+    def tail(self, device) -> tuple:
+        """What every entry point that takes the table takes of it, in order: its four pointers on ``device``, G, T and n."""
+        return (*(_ptr(t) for t in self.on(device)), self.ngroups, self.nterms, self.nqubit)
+
     def __getstate__(self):
         return {**self.__dict__, '_devices': {}}
 
@@ -1612,7 +1616,7 @@ def apply_psum_axpby(state: torch.Tensor, table: PsumTable, a, c, mode: str = 'g
     what = 'apply_psum_axpby'
     if mode not in ('gate', 'map'):
         raise ValueError(f"{what}: mode must be 'gate' or 'map', got {mode!r}")
-    n = _psum_args(state, table, what)
+    _psum_args(state, table, what)
     a, c = _pauli_coef(a, state, what), _pauli_coef(c, state, what)
     out = _check_out(state, out, what, in_place=False)
     if not _use_hip(state):
@@ -1622,10 +1626,9 @@ def apply_psum_axpby(state: torch.Tensor, table: PsumTable, a, c, mode: str = 'g
 
         return _diag_double(double)
     coef = _axpby_coef(a, c)
-    ptrs = [_ptr(t) for t in table.on(state.device)]
+    tail = table.tail(state.device)
     for lo, hi in _slices(state.shape[0]):
-        _call('dq_apply_psum_axpby', state, _ptr(state, lo), _ptr(out, lo), _ptr(coef, lo), *ptrs, table.ngroups, table.nterms,
-              n, hi - lo)
+        _call('dq_apply_psum_axpby', state, _ptr(state, lo), _ptr(out, lo), _ptr(coef, lo), *tail, hi - lo)
     return out
 
 
@@ -1634,12 +1637,11 @@ def psum_cross(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.
     (B,), bitwise reproducible (``dq_psum_cross_*``).  ``bra`` and ``ket`` the same buffer: G reads of the state for G
     groups (one of them without a flip over 16-byte vectors), else G + 1.  The workspace comes from PyTorch's allocator
     (legal under capture)."""
-    n = _psum_args(ket, table, 'psum_cross')
+    _psum_args(ket, table, 'psum_cross')
     _check_bra(bra, ket, 'psum_cross')
     if not _use_hip(ket):
         return _diag_double(lambda: (bra.to(torch.complex128).conj() * _psum_apply_double(ket.to(torch.complex128), table)).sum(dim=-1))
-    mid = (*(_ptr(t) for t in table.on(ket.device)), table.ngroups, table.nterms, n)
-    return _cross_reduce('dq_psum_cross', 'dq_psum_cross_ws_bytes', bra, ket, mid)
+    return _cross_reduce('dq_psum_cross', 'dq_psum_cross_ws_bytes', bra, ket, table.tail(ket.device))
 
 
 # ---- exp(-i t H) for a Pauli sum: a Chebyshev expansion, one launch per order --------------------------------------------
@@ -1801,8 +1803,7 @@ def apply_psum_evolve(state: torch.Tensor, table: PsumTable, t, tol: float, out:
         first = dev[:4 * batch].reshape(batch, 4)
         c01 = torch.view_as_complex(dev[4 * batch:8 * batch].reshape(2, batch, 2)).to(state.dtype)
         steps = dev[8 * batch:].reshape(order - 1, batch, 5)
-        ptrs = [_ptr(x) for x in table.on(state.device)]
-        tail = (*ptrs, table.ngroups, table.nterms, n)
+        tail = table.tail(state.device)
         cur = torch.empty_like(state)
         for lo, hi in _slices(batch):
             _call('dq_apply_psum_axpby', state, _ptr(state, lo), _ptr(cur, lo), _ptr(first, lo), *tail, hi - lo)
@@ -1849,7 +1850,7 @@ class _LanczosHip:
 
     def __init__(self, table: PsumTable, start: torch.Tensor, n: int, acc: torch.Tensor | None):
         self.start, self.n, self.acc, self.batch = start, n, acc, start.shape[0]
-        self.tail = (*(_ptr(x) for x in table.on(start.device)), table.ngroups, table.nterms, n)
+        self.tail = table.tail(start.device)
         self.out = torch.empty(self.batch, 2, dtype=torch.float64, device=start.device)
         lib, c128 = _lib.load(), int(start.dtype == torch.complex128)
         self.ws = []

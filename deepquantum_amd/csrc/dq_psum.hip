@@ -7,10 +7,16 @@
 //                              acc[b, i] += delta[b] next[b, i]                     (next may be prev)
 //     dq_pauli_sum_lanczos_step : next as in the Chebyshev step (no acc),  out[b] = (Re <cur_b, next_b>, |next_b|^2)
 //     dq_lanczos_update      : w[b, i] += e[b] v[b, i],  acc[b, i] += d[b] v[b, i],  out[b] = (|w_b|^2, Re <v_b, w_b>)
-// The third is one order of the Chebyshev expansion of exp(-i t H) (backend.apply_psum_evolve): the gather of the first
-// over `cur`, with the recurrence's other two vectors and the running sum read and written at the lane's own vectors.
-// The last two are the two launches of a Lanczos step (backend.psum_lanczos): the third's gather and a plain stream,
-// each with the two sums the host needs, reduced in the same launch.
+// The third is one order of the Chebyshev expansion of exp(-i t H) (backend.apply_psum_evolve), the last two are the two
+// launches of a Lanczos step (backend.psum_lanczos).
+//
+// What is written once.  The walk over the groups that applies H is one function, gather_h, templated on the
+// accumulator's complex type; psum_axpby_kernel, psum_cross_kernel (in double) and psum_lanczos_step_kernel call it.  The
+// third and the fourth entry point are the same three-term recurrence -- the gather over `cur`, the other two vectors read
+// and written at the lane's own vectors -- with a running sum, or with the two sums the host needs reduced in the same
+// launch.  They are two kernels all the same, and psum_cheb_step_kernel keeps a gather loop of its own: the shared forms
+// measured slower (see there).  The fifth is a plain stream with the same two sums.  On the host the two steps are one
+// function, step_impl.
 //
 // The terms are grouped by flip mask.  For the group with mask x
 //     (G_x psi)[i] = w_x(i ^ x) psi[i ^ x],      w_x(j) = sum_{t in group} h_t i^{ny_t} (-1)^popc(j & z_t)
@@ -76,17 +82,17 @@ __device__ __forceinline__ void signed_sum(const PsumTable& tb, int t0, int t1, 
 }
 
 // What a lane holds of group g: the partner vectors q and the weights wr + i wi at the source index of each amplitude.
-// `own`: the lane's own vectors of the same state, or nullptr where the caller has not loaded them.
-template <typename T, int VEC, typename Q>
+// OWN: `own` holds the lane's own vectors of the same state (else those of another state, which nothing here reads).
+template <typename T, int VEC, bool OWN, typename Q>
 __device__ __forceinline__ void load_group(const PsumTable& tb, int g, int n, const Q* __restrict__ src, uint64_t unit,
-                                           const uint64_t (&vec)[ST_UNROLL], const Q* own, Q (&q)[ST_UNROLL], int& x0,
+                                           const uint64_t (&vec)[ST_UNROLL], const Q (&own)[ST_UNROLL], Q (&q)[ST_UNROLL], int& x0,
                                            T (&wr)[ST_UNROLL][VEC], T (&wi)[ST_UNROLL][VEC]) {
     constexpr int VB = VEC == 2 ? 1 : 0;
     constexpr int sbits = ST_UNIT_BITS + VB;
     const uint64_t x = tb.xmasks[g] & ((1ull << n) - 1ull);
     const uint64_t vx = x >> VB;
     x0 = (int)(x & (uint64_t)VB);
-    if (own != nullptr && vx == 0) {
+    if (OWN && vx == 0) {
 #pragma unroll
         for (int u = 0; u < ST_UNROLL; ++u) q[u] = own[u];
     } else {
@@ -118,6 +124,44 @@ __device__ __forceinline__ unsigned unit_vectors(uint64_t unit, uint64_t nvec, u
     return live;
 }
 
+// A complex number in the accumulator's type A: itself, or (the cross reduction over a complex64 state) widened to double
+template <typename A, typename C>
+__device__ __forceinline__ A widen(C c) {
+    A r;
+    r.x = c.x;
+    r.y = c.y;
+    return r;
+}
+
+// THE gather: h[u][e] = (H src) at the lane's amplitudes of unit `unit`, summed over the groups in their order with one cfma
+// per group and amplitude, in A = cx<T>, or in double2 with both factors widened first.  OWN, `own`: as load_group has them.
+template <typename T, int VEC, bool OWN, typename Q, typename A>
+__device__ __forceinline__ void gather_h(const PsumTable& tb, int n, const Q* __restrict__ src, uint64_t unit,
+                                         const uint64_t (&vec)[ST_UNROLL], const Q (&own)[ST_UNROLL], A (&h)[ST_UNROLL][VEC]) {
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) h[u][e] = widen<A>(mk<T>((T)0, (T)0));
+    // The own vectors as VALUES, read before the loop.  This function is optimised on its own before it is inlined, and q
+    // is a local of it: with `own` read inside load_group's branch the compiler merges "q = own[u]" and "q = src[..]" into
+    // one load through a selected pointer -- a flat load, and the caller's own vectors in scratch memory (80 bytes a lane;
+    // profiles/psum_core/resource_usage.txt has both forms).
+    Q mine[ST_UNROLL];
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u) mine[u] = own[u];
+    for (int g = 0; g < tb.ngroups; ++g) {
+        Q q[ST_UNROLL];
+        T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
+        int x0;
+        load_group<T, VEC, OWN>(tb, g, n, src, unit, vec, mine, q, x0, wr, wi);
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e)
+                h[u][e] = cfma(widen<A>(mk<T>(wr[u][e], wi[u][e])), widen<A>(vec_get<T>(q[u], e ^ x0)), h[u][e]);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(ST_THREADS) void psum_axpby_kernel(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
                                                                 const double* __restrict__ coef, PsumTable tb, int n,
@@ -132,28 +176,15 @@ __global__ __launch_bounds__(ST_THREADS) void psum_axpby_kernel(const cx<T>* __r
         uint64_t vec[ST_UNROLL];
         const unsigned live = unit_vectors(unit, nvec, vec);
         Q own[ST_UNROLL];
-        cx<T> acc[ST_UNROLL][VEC];
 #pragma unroll
-        for (int u = 0; u < ST_UNROLL; ++u) {
-            own[u] = src[vec[u]];
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[u][e] = mk<T>((T)0, (T)0);
-        }
-        for (int g = 0; g < tb.ngroups; ++g) {
-            Q q[ST_UNROLL];
-            T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
-            int x0;
-            load_group<T, VEC, Q>(tb, g, n, src, unit, vec, own, q, x0, wr, wi);
-#pragma unroll
-            for (int u = 0; u < ST_UNROLL; ++u)
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) acc[u][e] = cfma(mk<T>(wr[u][e], wi[u][e]), vec_get<T>(q[u], e ^ x0), acc[u][e]);
-        }
+        for (int u = 0; u < ST_UNROLL; ++u) own[u] = src[vec[u]];
+        cx<T> h[ST_UNROLL][VEC];
+        gather_h<T, VEC, true>(tb, n, src, unit, vec, own, h);
 #pragma unroll
         for (int u = 0; u < ST_UNROLL; ++u) {
             Q r;
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) vec_set(r, e, cfma(c, acc[u][e], cmul(a, vec_get<T>(own[u], e))));
+            for (int e = 0; e < VEC; ++e) vec_set(r, e, cfma(c, h[u][e], cmul(a, vec_get<T>(own[u], e))));
             if (live >> u & 1u) dst[vec[u]] = r;
         }
     }
@@ -168,6 +199,11 @@ __global__ __launch_bounds__(ST_THREADS) void psum_axpby_kernel(const cx<T>* __r
 // in earnest.  Without that the compiler cannot tell the stores from the table and reads the table with vector loads in
 // the term loop instead of scalar ones: measured 1.4 to 1.9 times one psum_axpby launch where this form is at 0.97 to 1.20.
 // coef = [batch][5] doubles (alpha, beta, gamma, Re delta, Im delta), rounded once to the state's real precision.
+// This kernel keeps its OWN copy of gather_h's loop and of the recurrence that psum_lanczos_step_kernel has, on purpose.
+// Written as one kernel with the Lanczos step on gather_h, the tail chosen at compile time, it had the same registers and
+// the same term loop, and its complex128 SAME instantiation measured 0.6 to 1.6 per cent slower in every run where the
+// term loop bounds the time; on gather_h alone it compiles to that same code (profiles/psum_core/README.md, ab.txt).
+// Keep the two in step by hand.
 template <typename T, bool SAME>
 __global__ __launch_bounds__(ST_THREADS) void psum_cheb_step_kernel(const cx<T>* __restrict__ cur, const cx<T>* __restrict__ prev,
                                                                     cx<T>* __restrict__ next, cx<T>* __restrict__ acc,
@@ -197,7 +233,7 @@ __global__ __launch_bounds__(ST_THREADS) void psum_cheb_step_kernel(const cx<T>*
             Q q[ST_UNROLL];
             T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
             int x0;
-            load_group<T, VEC, Q>(tb, g, n, src, unit, vec, own, q, x0, wr, wi);
+            load_group<T, VEC, true>(tb, g, n, src, unit, vec, own, q, x0, wr, wi);
 #pragma unroll
             for (int u = 0; u < ST_UNROLL; ++u)
 #pragma unroll
@@ -231,7 +267,7 @@ __global__ __launch_bounds__(ST_THREADS) void psum_cheb_step_kernel(const cx<T>*
 // One half of a Lanczos step in H, with the two sums the host needs of it:
 //     next = alpha (H cur) + beta cur + gamma prev,      ws[b, blockIdx.x] = this workgroup's part of
 //     ( sum_i Re conj(cur_i) next_i ,  sum_i |next_i|^2 )
-// psum_cheb_step_kernel without its running sum: the same gather over `cur`, prev loaded after the group loop, the same
+// psum_cheb_step_kernel without its running sum: the same gather over `cur` (gather_h), prev loaded after the group loop, the same
 // SAME split (every pointer __restrict__ in earnest, see above).  The sums are taken over `next` AS STORED -- after the
 // rounding to the state's precision -- with products and sums in double, so the host's record describes the vectors that
 // exist.  A lane beyond a small sample stores nothing and adds nothing (`live`).
@@ -253,23 +289,10 @@ __global__ __launch_bounds__(ST_THREADS) void psum_lanczos_step_kernel(const cx<
         uint64_t vec[ST_UNROLL];
         const unsigned live = unit_vectors(unit, nvec, vec);
         Q own[ST_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ST_UNROLL; ++u) own[u] = src[vec[u]];
         cx<T> h[ST_UNROLL][VEC];                        // (H cur) at the lane's amplitudes
-#pragma unroll
-        for (int u = 0; u < ST_UNROLL; ++u) {
-            own[u] = src[vec[u]];
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) h[u][e] = mk<T>((T)0, (T)0);
-        }
-        for (int g = 0; g < tb.ngroups; ++g) {
-            Q q[ST_UNROLL];
-            T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
-            int x0;
-            load_group<T, VEC, Q>(tb, g, n, src, unit, vec, own, q, x0, wr, wi);
-#pragma unroll
-            for (int u = 0; u < ST_UNROLL; ++u)
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) h[u][e] = cfma(mk<T>(wr[u][e], wi[u][e]), vec_get<T>(q[u], e ^ x0), h[u][e]);
-        }
+        gather_h<T, VEC, true>(tb, n, src, unit, vec, own, h);
         Q p[ST_UNROLL];
 #pragma unroll
         for (int u = 0; u < ST_UNROLL; ++u) p[u] = pprev[vec[u]];      // (a lane beyond a small sample reads vector 0)
@@ -363,27 +386,10 @@ __global__ __launch_bounds__(ST_THREADS) void psum_cross_kernel(const cx<T>* __r
         uint64_t vec[ST_UNROLL];
         const unsigned live = unit_vectors(unit, nvec, vec);
         Q own[ST_UNROLL];                               // the bra's vectors: with SAME the ket's own as well
-        double2 hk[ST_UNROLL][VEC];                     // (H ket) at the lane's amplitudes
 #pragma unroll
-        for (int u = 0; u < ST_UNROLL; ++u) {
-            own[u] = pb[vec[u]];
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) hk[u][e] = make_double2(0.0, 0.0);
-        }
-        for (int g = 0; g < tb.ngroups; ++g) {
-            Q q[ST_UNROLL];
-            T wr[ST_UNROLL][VEC], wi[ST_UNROLL][VEC];
-            int x0;
-            load_group<T, VEC, Q>(tb, g, n, pk, unit, vec, SAME ? own : nullptr, q, x0, wr, wi);
-#pragma unroll
-            for (int u = 0; u < ST_UNROLL; ++u)
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const cx<T> s = vec_get<T>(q[u], e ^ x0);
-                    hk[u][e] = cfma(make_double2((double)wr[u][e], (double)wi[u][e]), make_double2((double)s.x, (double)s.y),
-                                    hk[u][e]);
-                }
-        }
+        for (int u = 0; u < ST_UNROLL; ++u) own[u] = pb[vec[u]];
+        double2 hk[ST_UNROLL][VEC];                     // (H ket) at the lane's amplitudes, in double
+        gather_h<T, VEC, SAME>(tb, n, pk, unit, vec, own, hk);
 #pragma unroll
         for (int u = 0; u < ST_UNROLL; ++u)
 #pragma unroll
@@ -429,10 +435,7 @@ int axpby_impl(const void* in, void* out, const double* coef, const uint64_t* xm
     constexpr bool C128 = sizeof(T) == 8;
     const char* what = "dq_apply_psum_axpby";
     if (int rc = check_states(what, in, out, 1, n, batch, sizeof(cx<T>), DISJOINT)) return rc;
-    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
-        set_error("%s: coef must be non-null and 8-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
+    if (int rc = check_coef(what, coef)) return rc;
     PsumTable tb;
     if (int rc = check_table(what, xmasks, bounds, zmasks, weights, ngroups, nterms, &tb)) return rc;
     const uint64_t nvec = vectors_of(n, C128);
@@ -441,109 +444,46 @@ int axpby_impl(const void* in, void* out, const double* coef, const uint64_t* xm
     return check_launch(what);
 }
 
-// cur is only read and is gathered from: apart from everything that is written.  acc is read and written at own vectors
-// only but must be nobody else's; next may be prev, since each lane reads its vectors of prev before it writes them.
-template <typename T>
-int cheb_step_impl(const void* cur, const void* prev, void* next, void* acc, const double* coef, const uint64_t* xmasks,
-                   const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n, int64_t batch,
-                   dq_stream_t stream) {
+// The Chebyshev step (SUMS false: out and ws unused) and the Lanczos step (SUMS true: no acc, which is null).  cur is only
+// read and is gathered from: apart from everything that is written.  acc is read and written at own vectors only but must
+// be nobody else's; next may be prev, since each lane reads its vectors of prev before it writes them.
+template <typename T, bool SUMS>
+int step_impl(const char* what, const void* cur, const void* prev, void* next, void* acc, const double* coef,
+              const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n,
+              int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
     constexpr bool C128 = sizeof(T) == 8;
-    const char* what = "dq_pauli_sum_cheb_step";
-    if (!cur || !prev || !next || !acc) {
-        set_error("%s: null pointer", what);
-        return DQ_ERR_ARG;
-    }
-    if (misaligned(cur) || misaligned(prev) || misaligned(next) || misaligned(acc)) {
-        set_error("%s: cur, prev, next and acc must be 16-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    if (n < 1 || n > 40) {
-        set_error("%s: n=%d out of range [1, 40]", what, n);
-        return DQ_ERR_ARG;
-    }
-    if (int rc = check_batch(what, batch)) return rc;
-    const uint64_t bytes = ((uint64_t)batch << n) * sizeof(cx<T>);
-    if (int rc = check_apart(what, "cur", cur, "next", next, bytes, DISJOINT)) return rc;
-    if (int rc = check_apart(what, "acc", acc, "cur", cur, bytes, DISJOINT)) return rc;
-    if (int rc = check_apart(what, "acc", acc, "prev", prev, bytes, DISJOINT)) return rc;
-    if (int rc = check_apart(what, "acc", acc, "next", next, bytes, DISJOINT)) return rc;
-    if (int rc = check_apart(what, "next", next, "prev", prev, bytes, SAME_OR_DISJOINT)) return rc;
-    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
-        set_error("%s: coef must be non-null and 8-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
+    enum { CUR, PREV, NEXT, ACC };
+    const StateBuf bufs[] = {{"cur", cur}, {"prev", prev}, {"next", next}, {"acc", acc}};
+    const ApartRule with_acc[] = {{CUR, NEXT, DISJOINT}, {ACC, CUR, DISJOINT}, {ACC, PREV, DISJOINT}, {ACC, NEXT, DISJOINT},
+                                  {NEXT, PREV, SAME_OR_DISJOINT}};
+    const ApartRule without[] = {{CUR, NEXT, DISJOINT}, {NEXT, PREV, SAME_OR_DISJOINT}};        // (the first three buffers only)
+    if (int rc = check_buffers(what, bufs, SUMS ? 3 : 4, SUMS ? without : with_acc, SUMS ? 2 : 5, 1, n, batch, sizeof(cx<T>)))
+        return rc;
+    if (int rc = check_coef(what, coef)) return rc;
     PsumTable tb;
     if (int rc = check_table(what, xmasks, bounds, zmasks, weights, ngroups, nterms, &tb)) return rc;
-    const uint64_t nvec = vectors_of(n, C128);
-    const dim3 grid(blocks_of(nvec), (unsigned)batch);
-    const cx<T>* pc = static_cast<const cx<T>*>(cur);
-    cx<T>* pn = static_cast<cx<T>*>(next);
-    cx<T>* pa = static_cast<cx<T>*>(acc);
-    hipStream_t s = as_stream(stream);
-    if (prev == next) hipLaunchKernelGGL((psum_cheb_step_kernel<T, true>), grid, dim3(ST_THREADS), 0, s, pc, nullptr, pn, pa, coef, tb, n, nvec);
-    else hipLaunchKernelGGL((psum_cheb_step_kernel<T, false>), grid, dim3(ST_THREADS), 0, s, pc, static_cast<const cx<T>*>(prev), pn, pa, coef, tb, n, nvec);
-    return check_launch(what);
-}
-
-// out and ws of a kernel that leaves two sums per sample: non-null, out 8-byte and ws 16-byte aligned, ws large enough
-// (check_cross's checks of the two, for entry points whose states are not a bra and a ket)
-int check_sums(const char* what, const double* out, const void* ws, int64_t ws_bytes, int n, int64_t batch, bool is_c128) {
-    if (!out || !ws) {
-        set_error("%s: null pointer (out, ws)", what);
-        return DQ_ERR_ARG;
+    if (SUMS) {
+        if (int rc = check_out_ws(what, out, ws)) return rc;
+        if (int rc = check_cross_ws(what, ws_bytes, n, batch, C128, "dq_psum_cross_ws_bytes")) return rc;
     }
-    if (misaligned(ws) || (reinterpret_cast<uintptr_t>(out) & 7)) {
-        set_error("%s: ws must be 16-byte aligned, out 8-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    const int64_t need = cross_ws_bytes(n, batch, is_c128);
-    if (ws_bytes < need) {
-        set_error("%s: workspace of %lld bytes, %lld needed (dq_psum_cross_ws_bytes)", what, (long long)ws_bytes, (long long)need);
-        return DQ_ERR_ARG;
-    }
-    return DQ_OK;
-}
-
-// cheb_step_impl's rules without acc: cur is gathered from and apart from next; next may be prev.
-template <typename T>
-int lanczos_step_impl(const void* cur, const void* prev, void* next, const double* coef, const uint64_t* xmasks, const int* bounds,
-                      const uint64_t* zmasks, const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out,
-                      void* ws, int64_t ws_bytes, dq_stream_t stream) {
-    constexpr bool C128 = sizeof(T) == 8;
-    const char* what = "dq_pauli_sum_lanczos_step";
-    if (!cur || !prev || !next) {
-        set_error("%s: null pointer", what);
-        return DQ_ERR_ARG;
-    }
-    if (misaligned(cur) || misaligned(prev) || misaligned(next)) {
-        set_error("%s: cur, prev and next must be 16-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    if (n < 1 || n > 40) {
-        set_error("%s: n=%d out of range [1, 40]", what, n);
-        return DQ_ERR_ARG;
-    }
-    if (int rc = check_batch(what, batch)) return rc;
-    const uint64_t bytes = ((uint64_t)batch << n) * sizeof(cx<T>);
-    if (int rc = check_apart(what, "cur", cur, "next", next, bytes, DISJOINT)) return rc;
-    if (int rc = check_apart(what, "next", next, "prev", prev, bytes, SAME_OR_DISJOINT)) return rc;
-    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
-        set_error("%s: coef must be non-null and 8-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    PsumTable tb;
-    if (int rc = check_table(what, xmasks, bounds, zmasks, weights, ngroups, nterms, &tb)) return rc;
-    if (int rc = check_sums(what, out, ws, ws_bytes, n, batch, C128)) return rc;
     const uint64_t nvec = vectors_of(n, C128);
     const unsigned nblk = blocks_of(nvec);
     const dim3 grid(nblk, (unsigned)batch);
     const cx<T>* pc = static_cast<const cx<T>*>(cur);
     cx<T>* pn = static_cast<cx<T>*>(next);
-    double* part = static_cast<double*>(ws);
+    const cx<T>* pp = prev == next ? nullptr : static_cast<const cx<T>*>(prev);     // (SAME: prev is read through next)
     hipStream_t s = as_stream(stream);
-    if (prev == next) hipLaunchKernelGGL((psum_lanczos_step_kernel<T, true>), grid, dim3(ST_THREADS), 0, s, pc, nullptr, pn, coef, tb, n, nvec, part);
-    else hipLaunchKernelGGL((psum_lanczos_step_kernel<T, false>), grid, dim3(ST_THREADS), 0, s, pc, static_cast<const cx<T>*>(prev), pn, coef, tb, n, nvec, part);
-    return finish_cross(what, part, nblk, batch, out, s);
+    if constexpr (SUMS) {
+        double* part = static_cast<double*>(ws);
+        if (prev == next) hipLaunchKernelGGL((psum_lanczos_step_kernel<T, true>), grid, dim3(ST_THREADS), 0, s, pc, pp, pn, coef, tb, n, nvec, part);
+        else hipLaunchKernelGGL((psum_lanczos_step_kernel<T, false>), grid, dim3(ST_THREADS), 0, s, pc, pp, pn, coef, tb, n, nvec, part);
+        return finish_cross(what, part, nblk, batch, out, s);
+    } else {
+        cx<T>* pa = static_cast<cx<T>*>(acc);
+        if (prev == next) hipLaunchKernelGGL((psum_cheb_step_kernel<T, true>), grid, dim3(ST_THREADS), 0, s, pc, pp, pn, pa, coef, tb, n, nvec);
+        else hipLaunchKernelGGL((psum_cheb_step_kernel<T, false>), grid, dim3(ST_THREADS), 0, s, pc, pp, pn, pa, coef, tb, n, nvec);
+        return check_launch(what);
+    }
 }
 
 // v is only read, w and acc are read and written at each lane's own vectors: the three pairwise disjoint; acc may be null.
@@ -552,30 +492,13 @@ int lanczos_update_impl(const void* v, void* w, void* acc, const double* coef, i
                         int64_t ws_bytes, dq_stream_t stream) {
     constexpr bool C128 = sizeof(T) == 8;
     const char* what = "dq_lanczos_update";
-    if (!v || !w) {
-        set_error("%s: null pointer", what);
-        return DQ_ERR_ARG;
-    }
-    if (misaligned(v) || misaligned(w) || misaligned(acc)) {
-        set_error("%s: v, w and acc must be 16-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    if (n < 1 || n > 40) {
-        set_error("%s: n=%d out of range [1, 40]", what, n);
-        return DQ_ERR_ARG;
-    }
-    if (int rc = check_batch(what, batch)) return rc;
-    const uint64_t bytes = ((uint64_t)batch << n) * sizeof(cx<T>);
-    if (int rc = check_apart(what, "v", v, "w", w, bytes, DISJOINT)) return rc;
-    if (acc) {
-        if (int rc = check_apart(what, "acc", acc, "v", v, bytes, DISJOINT)) return rc;
-        if (int rc = check_apart(what, "acc", acc, "w", w, bytes, DISJOINT)) return rc;
-    }
-    if (!coef || (reinterpret_cast<uintptr_t>(coef) & 7)) {
-        set_error("%s: coef must be non-null and 8-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    if (int rc = check_sums(what, out, ws, ws_bytes, n, batch, C128)) return rc;
+    enum { V, W, ACC };
+    const StateBuf bufs[] = {{"v", v}, {"w", w}, {"acc", acc, true}};
+    const ApartRule rules[] = {{V, W, DISJOINT}, {ACC, V, DISJOINT}, {ACC, W, DISJOINT}};
+    if (int rc = check_buffers(what, bufs, 3, rules, 3, 1, n, batch, sizeof(cx<T>))) return rc;
+    if (int rc = check_coef(what, coef)) return rc;
+    if (int rc = check_out_ws(what, out, ws)) return rc;
+    if (int rc = check_cross_ws(what, ws_bytes, n, batch, C128, "dq_psum_cross_ws_bytes")) return rc;
     const uint64_t nvec = vectors_of(n, C128);
     const unsigned nblk = blocks_of(nvec);
     const dim3 grid(nblk, (unsigned)batch);
@@ -631,25 +554,27 @@ extern "C" int dq_apply_psum_axpby_c128(const void* in, void* out, const double*
 extern "C" int dq_pauli_sum_cheb_step_c64(const void* cur, const void* prev, void* next, void* acc, const double* coef,
                                      const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks, const double* weights,
                                      int ngroups, int nterms, int n, int64_t batch, dq_stream_t stream) {
-    return dq::cheb_step_impl<float>(cur, prev, next, acc, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, stream);
+    return dq::step_impl<float, false>("dq_pauli_sum_cheb_step", cur, prev, next, acc, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n,
+                                       batch, nullptr, nullptr, 0, stream);
 }
 extern "C" int dq_pauli_sum_cheb_step_c128(const void* cur, const void* prev, void* next, void* acc, const double* coef,
                                       const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks, const double* weights,
                                       int ngroups, int nterms, int n, int64_t batch, dq_stream_t stream) {
-    return dq::cheb_step_impl<double>(cur, prev, next, acc, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, stream);
+    return dq::step_impl<double, false>("dq_pauli_sum_cheb_step", cur, prev, next, acc, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n,
+                                       batch, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int dq_pauli_sum_lanczos_step_c64(const void* cur, const void* prev, void* next, const double* coef, const uint64_t* xmasks,
                                              const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms,
                                              int n, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
-    return dq::lanczos_step_impl<float>(cur, prev, next, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, out, ws,
-                                        ws_bytes, stream);
+    return dq::step_impl<float, true>("dq_pauli_sum_lanczos_step", cur, prev, next, nullptr, coef, xmasks, bounds, zmasks, weights, ngroups,
+                                      nterms, n, batch, out, ws, ws_bytes, stream);
 }
 extern "C" int dq_pauli_sum_lanczos_step_c128(const void* cur, const void* prev, void* next, const double* coef, const uint64_t* xmasks,
                                               const int* bounds, const uint64_t* zmasks, const double* weights, int ngroups, int nterms,
                                               int n, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream) {
-    return dq::lanczos_step_impl<double>(cur, prev, next, coef, xmasks, bounds, zmasks, weights, ngroups, nterms, n, batch, out, ws,
-                                         ws_bytes, stream);
+    return dq::step_impl<double, true>("dq_pauli_sum_lanczos_step", cur, prev, next, nullptr, coef, xmasks, bounds, zmasks, weights, ngroups,
+                                      nterms, n, batch, out, ws, ws_bytes, stream);
 }
 
 extern "C" int dq_lanczos_update_c64(const void* v, void* w, void* acc, const double* coef, int n, int64_t batch, double* out,

@@ -16,6 +16,7 @@
 // The reductions of dq_reduce.hip (a __shfl_down tree from offset 32 downward: another order of additions, other
 // bits), dq_entangle.hip, dq_sample.hip and dq_rdm.hip (shaped by their own tiles) are deliberately not built on this.
 #pragma once
+#include <string.h>
 #include "dq_common.hpp"
 
 namespace dq {
@@ -162,24 +163,38 @@ bool clash(const void* p, const void* q, uint64_t bytes, Alias alias) {
     return (alias == DISJOINT || a != o) && (a > o ? a - o : o - a) < bytes;
 }
 
-// Two named buffers of a primitive with more than two states (dq_psum.hip's Chebyshev step), each `bytes` long, under `alias`
-int check_apart(const char* what, const char* name_p, const void* p, const char* name_q, const void* q, uint64_t bytes,
-                Alias alias) {
-    if (!clash(p, q, bytes, alias)) return DQ_OK;
-    set_error(alias == DISJOINT ? "%s: %s and %s overlap" : "%s: %s and %s overlap without being equal", what, name_p, name_q);
-    return DQ_ERR_ARG;
-}
+// One of the state buffers of a primitive, batch * 2^n amplitudes long; an `optional` one may be null
+struct StateBuf {
+    const char* name;
+    const void* p;
+    bool optional = false;
+};
 
-// in and out of a state-to-state primitive: non-null, 16-byte aligned, n in [nmin, 40], the batch, and the ranges
-// [in, in + batch * 2^n) and [out, ..) under `alias`
-int check_states(const char* what, const void* in, const void* out, int nmin, int n, int64_t batch, size_t amp_bytes,
-                 Alias alias) {
-    if (!in || !out) {
+// What two of them (indices into the primitive's list) may share
+struct ApartRule {
+    int p, q;
+    Alias alias;
+};
+
+// The state buffers of a primitive, in the order of the refusals: non-null (but for the optional ones), 16-byte aligned, n
+// in [nmin, 40], the batch, then the rules in their order, each over the ranges [p, p + batch * 2^n) (a rule with a null
+// buffer says nothing).  `tail` ends the message of a DISJOINT clash.
+int check_buffers(const char* what, const StateBuf* bufs, int nbufs, const ApartRule* rules, int nrules, int nmin, int n,
+                  int64_t batch, size_t amp_bytes, const char* tail = "") {
+    char names[128] = "";                               // "cur, prev, next and acc"
+    bool null = false, skew = false;
+    for (int i = 0; i < nbufs; ++i) {
+        null |= !bufs[i].p && !bufs[i].optional;
+        skew |= misaligned(bufs[i].p);
+        const size_t at = strlen(names);
+        snprintf(names + at, sizeof names - at, "%s%s", i == 0 ? "" : i == nbufs - 1 ? " and " : ", ", bufs[i].name);
+    }
+    if (null) {
         set_error("%s: null pointer", what);
         return DQ_ERR_ARG;
     }
-    if (misaligned(in) || misaligned(out)) {
-        set_error("%s: in and out must be 16-byte aligned", what);
+    if (skew) {
+        set_error("%s: %s must be 16-byte aligned", what, names);
         return DQ_ERR_ARG;
     }
     if (n < nmin || n > 40) {
@@ -188,12 +203,28 @@ int check_states(const char* what, const void* in, const void* out, int nmin, in
     }
     if (int rc = check_batch(what, batch)) return rc;
     const uint64_t bytes = ((uint64_t)batch << n) * amp_bytes;
-    if (clash(in, out, bytes, alias)) {
-        set_error(alias == DISJOINT ? "%s: in and out overlap (out of place only)" : "%s: in and out overlap without being equal",
-                  what);
+    for (int r = 0; r < nrules; ++r) {
+        const StateBuf &p = bufs[rules[r].p], &q = bufs[rules[r].q];
+        if (!p.p || !q.p || !clash(p.p, q.p, bytes, rules[r].alias)) continue;
+        set_error("%s: %s and %s overlap%s", what, p.name, q.name, rules[r].alias == DISJOINT ? tail : " without being equal");
         return DQ_ERR_ARG;
     }
     return DQ_OK;
+}
+
+// in and out of a state-to-state primitive: the two buffers of check_buffers under `alias`
+int check_states(const char* what, const void* in, const void* out, int nmin, int n, int64_t batch, size_t amp_bytes,
+                 Alias alias) {
+    const StateBuf bufs[] = {{"in", in}, {"out", out}};
+    const ApartRule rule{0, 1, alias};
+    return check_buffers(what, bufs, 2, &rule, 1, nmin, n, batch, amp_bytes, " (out of place only)");
+}
+
+// The coefficients of a launch, [batch][k] doubles on the device
+int check_coef(const char* what, const double* coef) {
+    if (coef && !(reinterpret_cast<uintptr_t>(coef) & 7)) return DQ_OK;
+    set_error("%s: coef must be non-null and 8-byte aligned", what);
+    return DQ_ERR_ARG;
 }
 
 uint64_t control_mask(const int* controls, int nc) {
@@ -267,12 +298,28 @@ int64_t cross_ws_bytes_or_refuse(int n, int64_t batch, bool is_c128) {
     return cross_ws_bytes(n, batch, is_c128);
 }
 
-// `what` names the entry point; its sizing function is <what>_ws_bytes
-int check_cross_ws(const char* what, int64_t ws_bytes, int n, int64_t batch, bool is_c128) {
+// `what` names the entry point; `sizer` the function that sizes its workspace, <what>_ws_bytes where none is given
+int check_cross_ws(const char* what, int64_t ws_bytes, int n, int64_t batch, bool is_c128, const char* sizer = nullptr) {
     const int64_t need = cross_ws_bytes(n, batch, is_c128);
     if (ws_bytes >= need) return DQ_OK;
-    set_error("%s: workspace of %lld bytes, %lld needed (%s_ws_bytes)", what, (long long)ws_bytes, (long long)need, what);
+    set_error("%s: workspace of %lld bytes, %lld needed (%s%s)", what, (long long)ws_bytes, (long long)need, sizer ? sizer : what,
+              sizer ? "" : "_ws_bytes");
     return DQ_ERR_ARG;
+}
+
+// out and ws of a kernel that leaves two sums per sample and whose states are not a bra and a ket (those go through
+// check_buffers): non-null, ws 16-byte and out 8-byte aligned -- check_cross_buffers's checks of the two; check_cross_ws
+// sizes ws for both.
+int check_out_ws(const char* what, const double* out, const void* ws) {
+    if (!out || !ws) {
+        set_error("%s: null pointer (out, ws)", what);
+        return DQ_ERR_ARG;
+    }
+    if (misaligned(ws) || (reinterpret_cast<uintptr_t>(out) & 7)) {
+        set_error("%s: ws must be 16-byte aligned, out 8-byte aligned", what);
+        return DQ_ERR_ARG;
+    }
+    return DQ_OK;
 }
 
 // The pointers of a cross reduction: bra, ket, the table (where the primitive has one: `has_table`) and ws non-null and
