@@ -34,7 +34,7 @@ from .layer import (
     U3Layer, XLayer, YLayer, ZLayer,
 )
 from .operation import Channel, Gate, Layer, Operation
-from .pauli_sum import PauliSum, PauliSumEvolution
+from .pauli_sum import PauliSum, PauliSumEvolution, SelectPauli
 from .qmath import (
     amplitude_encoding, apply_pauli_sum, evolve_pauli_sum, expectation, expectation_cost, expectation_pauli_sum, ising_cost, measure,
     meyer_wallach_measure, multi_kron, partial_trace, pauli_sum_extremal,

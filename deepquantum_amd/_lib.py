@@ -174,6 +174,8 @@ _SIGNATURES = {
     'dq_pauli_sum_cheb_step_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
     'dq_pauli_sum_lanczos_step_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i64, _vp]),
     'dq_lanczos_update_{s}': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _vp]),
+    'dq_apply_select_pauli_{s}': (_i, [_vp, _vp, _vp, _i, _ip, _i, _ip, _i, _i64, _vp]),
+    'dq_select_pauli_unit_bits': (_i, [_i]),
 }
 
 

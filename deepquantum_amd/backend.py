@@ -1224,6 +1224,112 @@ def _apply_permutation_double(state, src, n, bits, controls, out):
 
 
 # ---------------------------------------------------------------------------------------------------
+# SELECT over Pauli strings (csrc/dq_select.hip): out[b, i] = i^q (-1)^popc(j & z) in[b, j], j = i ^ x, with
+# (x, z, q) = table[sub(i)] read from the select bits of i and x confined to the bits that are neither select nor control
+SELECT_MAX_BITS = 31
+
+
+def select_pauli_unit_bits(dtype: torch.dtype) -> int:
+    """log2 of the amplitudes of a unit of the SELECT kernel: select bits at or above it are uniform over a workgroup."""
+    return _lib.load().dq_select_pauli_unit_bits(int(dtype == torch.complex128))
+
+
+class SelectTable:
+    """The two tables of ``dq_apply_select_pauli_*`` for ``sum_s |s><s| (x) i^q_s P_s`` on a register of ``nqubit`` wires,
+    from one ``(xmask, zmask, q)`` per value s of the select bits: masks over index bits as include/dq_hip.h section 14
+    describes them, ``q`` the power of i in front of the string, 2^k entries.  The kernel's entry holds the power of i in
+    front of ``X^x Z^z``: with ``ny = popc(x & z)`` Y factors that is ``q + ny`` for the operator and, P_s being Hermitian,
+    ``ny - q`` for its adjoint -- both tables are built here, once, as int64 tensors (2^k, 2) = (x | q << 62, z), kept on
+    the CPU and handed out per device by :meth:`on` (cached; the first use on a device copies them, which a graph capture
+    does not allow: run once before capturing).  Pickles without the device copies."""
+
+    def __init__(self, nqubit: int, entries: Sequence[tuple[int, int, int]]):
+        n, size = int(nqubit), len(entries)
+        if n < 1 or n > 40:
+            raise ValueError(f'SelectTable: nqubit={nqubit} out of range [1, 40]')
+        k = size.bit_length() - 1
+        if size < 2 or (1 << k) != size or k > SELECT_MAX_BITS:
+            raise ValueError(f'SelectTable: a table over k select bits has 2^k entries, 1 <= k <= {SELECT_MAX_BITS}; got {size}')
+        forward, dagger = [], []
+        for x, z, q in entries:
+            x, z, q = int(x), int(z), int(q)
+            if x < 0 or z < 0 or x >> n or z >> n:
+                raise ValueError(f'SelectTable: every mask must lie in [0, 2**{n})')
+            if q < 0 or q > 3:
+                raise ValueError(f'SelectTable: a phase is a power of i in 0..3, got {q}')
+            ny = bin(x & z).count('1')
+            forward.append((x | ((q + ny) % 4) << 62, z))
+            dagger.append((x | ((ny - q) % 4) << 62, z))
+        self.nqubit, self.k = n, k
+        signed = lambda rows: torch.tensor([[w - (1 << 64) if w >> 63 else w for w in row] for row in rows], dtype=torch.int64)
+        self._host = (signed(forward), signed(dagger))
+        self._devices: dict = {}
+
+    def on(self, device, dagger: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+        """(table, table of the adjoint) on ``device``; ``dagger``: the other way round."""
+        device = torch.device(device)
+        hit = self._host if device.type == 'cpu' else self._devices.get(device)
+        if hit is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('deepquantum_amd: the first use of a SELECT table on a device copies it there; run the '
+                                   'step once before capturing it (dq.CapturedGraph warms up by itself)')
+            hit = self._devices[device] = tuple(own(t.to(device)) for t in self._host)
+        pin_if_capturing(*hit)
+        return (hit[1], hit[0]) if dagger else hit
+
+    def __getstate__(self):
+        return {**self.__dict__, '_devices': {}}
+
+
+def _select_words(words: torch.Tensor, like: torch.Tensor, k: int, what: str) -> torch.Tensor:
+    """The table as int64 (2^k, 2) on the state's device, contiguous and 16-byte aligned.  Its entries are not looked at
+    here (no synchronisation): the kernel confines every flip mask to the free bits."""
+    if not isinstance(words, torch.Tensor) or words.dtype != torch.int64:
+        raise ValueError(f'{what}: the table must be an int64 tensor (SelectTable.on)')
+    if words.shape != (1 << k, 2):
+        raise ValueError(f'{what}: a table over {k} select bits has shape ({1 << k}, 2); got {tuple(words.shape)}')
+    return _finish_table(words, like, torch.int64, what)
+
+
+def apply_select_pauli(state: torch.Tensor, table_words: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = (),
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[b, i] = i^q (-1)^popc(j & z) state[b, j], j = i ^ x, with (x, z, q) = table[sub(i)], on the amplitudes whose
+    ``controls`` are all 1 (the others are copied): SELECT over the Pauli strings of ``table_words`` (one of
+    :meth:`SelectTable.on`) for k = len(bits) select bits, ``bits[0]`` the most significant bit of s -- one read and one
+    write of the state whatever the number of strings, exact (``dq_apply_select_pauli_*``).  Out of place only: ``out``
+    must not overlap ``state``."""
+    what = 'apply_select_pauli'
+    n, bits, controls = _diag_args(state, bits, controls, what)
+    k = len(bits)
+    if k > SELECT_MAX_BITS:
+        raise ValueError(f'{what}: at most {SELECT_MAX_BITS} select bits, got {k}')
+    _suffix(state)
+    words = _select_words(table_words, state, k, what)
+    out = _check_out(state, out, what, in_place=False)
+    if not _use_hip(state):
+        return _diag_double(lambda: _apply_select_pauli_double(state, words, n, bits, controls, out))
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_select_pauli', state, _ptr(state, lo), _ptr(out, lo), _ptr(words), n, _lib.int_array(bits), k,
+              _lib.int_array(controls), len(controls), hi - lo)
+    return out
+
+
+def _apply_select_pauli_double(state, words, n, bits, controls, out):
+    sub, ok = _sub_index(n, bits, controls)
+    i = torch.arange(1 << n)
+    free = ((1 << n) - 1) & ~sum(1 << p for p in [*bits, *controls])
+    w0, z = words[sub, 0], words[sub, 1]
+    j = i ^ (w0 & free)
+    par = torch.zeros_like(i)
+    for p in range(n):
+        par ^= ((j & z) >> p) & 1
+    q = torch.where(ok, ((w0 >> 62) + 2 * par) & 3, 0)
+    factor = torch.tensor([1, 1j, -1, -1j], dtype=state.dtype)[q]
+    out.copy_(state[:, torch.where(ok, j, i)] * factor)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # Multiplexed one-qubit gates on any number of select wires (csrc/dq_mux.hip): for every pair i0 (target bit 0),
 # i1 = i0 | 1 << target inside the controls, (out[i0], out[i1]) = M[sub(i0)] (in[i0], in[i1])
 MUX_KINDS = {'u': _lib.MUX_U, 'ry': _lib.MUX_RY}

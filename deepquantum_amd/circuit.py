@@ -15,6 +15,7 @@ QASM, drawing -- the corresponding entry points raise ``NotImplementedError``.
 
 from __future__ import annotations
 
+import math
 import weakref
 
 from copy import copy
@@ -152,7 +153,7 @@ class QubitCircuit(Operation):
 
     def _run_operators(self, flat: torch.Tensor, zero: bool = False) -> torch.Tensor:
         """All operators on a (B, 2**n) state: maximal stretches of gates go to the executor (fused passes),
-        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``, ``ExcitationGate``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
+        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``, ``ExcitationGate``, ``SelectPauli``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
         density matrix alike: index 0 is 1, everything else 0)."""
         if self.den_mat:
             prims = []
@@ -876,6 +877,61 @@ class QubitCircuit(Operation):
         requires_grad = (not encode) and t is None
         self.add(PauliSumEvolution(hamiltonian=hamiltonian, t=t, nqubit=self.nqubit, tol=tol, name=name, den_mat=self.den_mat,
                                    requires_grad=requires_grad, bounds=bounds), encode=encode)
+
+    def select_pauli(self, paulis, wires, system_wires=None, phases=None, controls=None):
+        """SELECT ``sum_s |s><s| (x) i^phases[s] P_s``: for every value s of the select wires ``wires`` (``wires[0]`` = the
+        most significant bit of s) the Pauli string ``paulis[s]`` on ``system_wires`` (``paulis``: a list of strings such as
+        ``['x0y2', '']``, or a ``PauliSum``, whose signs become the phases), in one pass: see :class:`SelectPauli`."""
+        from .pauli_sum import SelectPauli
+
+        self.add(SelectPauli(paulis=paulis, nqubit=self.nqubit, wires=wires, system_wires=system_wires, phases=phases,
+                             controls=controls, den_mat=self.den_mat))
+
+    def block_encode(self, H, wires, system_wires=None, controls=None) -> float:
+        """Appends the block encoding ``PREPARE^dagger SELECT PREPARE`` of ``H = sum_t h_t P_t`` (a ``PauliSum`` on
+        ``len(system_wires)`` wires, or its list form) with the select wires ``wires``, at least ``H.select_bits`` of them,
+        and returns ``lam = sum_t |h_t|``, the constant term included (``H.norm_bound + |H.constant|`` but for the upward
+        rounding of ``norm_bound``).  PREPARE is the ``ry`` / ``ucry`` sequence of :meth:`prepare_state` for the real vector
+        ``sqrt(|h_t| / lam)`` on the select wires, SELECT one :class:`SelectPauli` with the signs of the ``h_t`` -- the only
+        part under ``controls`` --, PREPARE^dagger the same rotations in reverse order with negated angles.  The circuit U so
+        appended is Hermitian and unitary, and ``(<0|_select (x) 1) U (|0>_select (x) 1) = H / lam``."""
+        from .pauli_sum import PauliSum, SelectPauli
+
+        wires = [wires] if isinstance(wires, int) else list(wires)
+        ctrl = [] if controls is None else [controls] if isinstance(controls, int) else list(controls)
+        if system_wires is None:
+            system_wires = [w for w in range(self.nqubit) if w not in wires and w not in ctrl]
+        if not isinstance(H, PauliSum):
+            try:
+                H = PauliSum(H, len(system_wires))
+            except ValueError as exc:
+                raise ValueError(f'block_encode: {exc}') from exc
+        if len(wires) < H.select_bits:
+            raise ValueError(f'block_encode: {H.nterms} strings need at least {H.select_bits} select wires, got {len(wires)}')
+        select = SelectPauli(paulis=H, nqubit=self.nqubit, wires=wires, system_wires=system_wires, controls=controls,
+                             den_mat=self.den_mat)
+        weights = [abs(h) for h, _, _ in H.terms]
+        lam = math.fsum(weights)
+        amplitude = torch.zeros(2 ** len(wires), dtype=torch.float64)
+        amplitude[:len(weights)] = torch.tensor(weights, dtype=torch.float64).div(lam).sqrt()
+        start = len(self.operators)
+        self.prepare_state(amplitude, wires=wires)
+        prepare = self.operators[start:]
+        self.add(select)
+        for op in reversed(prepare):
+            self.add(op.inverse())
+        return lam
+
+    def qubitization_walk(self, H, wires, system_wires=None) -> float:
+        """Appends the qubitization walk operator ``W = (2 |0><0| - 1)_select U`` of ``H``: :meth:`block_encode` and then the
+        reflection about ``|0..0>`` of the select wires, a diagonal ``[1, -1, .., -1]``.  Returns ``lam``: on an eigenvector
+        of H with eigenvalue E, ``<0, psi| W^j |0, psi> = cos(j arccos(E / lam))``."""
+        lam = self.block_encode(H, wires, system_wires=system_wires)
+        wires = [wires] if isinstance(wires, int) else list(wires)
+        reflection = -torch.ones(2 ** len(wires), dtype=torch.cfloat)
+        reflection[0] = 1
+        self.diagonal(reflection, wires=wires, name='qubitization_reflection')
+        return lam
 
     def excitation(self, create, annihilate, inputs=None, controls=None, fermionic=True, encode=False, name='excitation'):
         """``exp(theta (E - E^dagger))`` for ``E = a^dagger_{create[0]} .. a_{annihilate[0]} ..`` (Jordan-Wigner over wire

@@ -5,7 +5,7 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="${here}/../libdqhip.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-srcs=(dq_capi.hip dq_gate.hip dq_dense.hip dq_pass.hip dq_wave.hip dq_reduce.hip dq_dist.hip dq_plan.hip dq_entangle.hip dq_rdm.hip dq_sample.hip dq_diag.hip dq_pauli.hip dq_perm.hip dq_mux.hip dq_muxgrad.hip dq_excite.hip dq_psum.hip)
+srcs=(dq_capi.hip dq_gate.hip dq_dense.hip dq_pass.hip dq_wave.hip dq_reduce.hip dq_dist.hip dq_plan.hip dq_entangle.hip dq_rdm.hip dq_sample.hip dq_diag.hip dq_pauli.hip dq_perm.hip dq_mux.hip dq_muxgrad.hip dq_excite.hip dq_psum.hip dq_select.hip)
 objs=()
 mkdir -p "${here}/build"
 # any header of this directory newer than object $1?
@@ -17,6 +17,8 @@ for s in "${srcs[@]}"; do
   if newer_hpp "$o" || [[ ! -f "$o" || "${here}/$s" -nt "$o" || "${here}/../../include/dq_hip.h" -nt "$o" || ( "$s" == dq_wave.hip && ( "${here}/dq_wave_asm.inc" -nt "$o" || "${here}/dq_wave_asm64.inc" -nt "$o" || "${here}/dq_wave_valu.inc" -nt "$o" || "${here}/dq_wave_valu64.inc" -nt "$o" ) ) ]]; then
     if [[ "$s" == dq_wave.hip ]]; then
       "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -Wno-unused-value -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-uniform-regions -Rpass-analysis=kernel-resource-usage ${DQ_HIPCC_EXTRA:-} -c "${here}/$s" -o "$o" 2> "${here}/build/dq_wave.usage" &
+    elif [[ "$s" == dq_select.hip ]]; then
+      "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -Wno-unused-value -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-uniform-regions -Rpass-analysis=kernel-resource-usage ${DQ_HIPCC_EXTRA:-} -c "${here}/$s" -o "$o" 2> "${here}/build/dq_select.usage" &
     else
     "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -Wno-unused-value -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-uniform-regions ${DQ_HIPCC_EXTRA:-} -c "${here}/$s" -o "$o" &
     fi
@@ -25,7 +27,7 @@ for s in "${srcs[@]}"; do
 done
 for p in "${pids[@]:-}"; do
   if [[ -n "$p" ]] && ! wait "$p"; then
-    grep -B2 -A3 "error" "${here}/build/dq_wave.usage" 2>/dev/null | head -40 >&2
+    grep -h -B2 -A3 "error" "${here}/build/dq_wave.usage" "${here}/build/dq_select.usage" 2>/dev/null | head -40 >&2
     echo "build failed" >&2
     exit 1
   fi
@@ -36,6 +38,13 @@ if [[ -f "${here}/build/dq_wave.usage" ]]; then
   if grep -A8 "wave_pass_kernel" "${here}/build/dq_wave.usage" | grep -E "VGPRs: (169|1[7-9][0-9]|[2-9][0-9][0-9])|Spill: [1-9]" > /dev/null; then
     echo "dq_wave.hip: a wave_pass_kernel instantiation exceeds 168 VGPRs or spills (see build/dq_wave.usage)" >&2
     grep -E "Function Name|VGPRs:|Spill" "${here}/build/dq_wave.usage" | sed 's/.*remark: //' >&2
+    exit 1
+  fi
+fi
+# The SELECT kernels hold a unit's entries and vectors in registers: nothing of that may land in scratch memory.
+if [[ -f "${here}/build/dq_select.usage" ]]; then
+  if grep -E "ScratchSize \[bytes/lane\]: [1-9]|Spill: [1-9]" "${here}/build/dq_select.usage" > /dev/null; then
+    echo "dq_select.hip: a select_pauli_kernel instantiation spills or uses scratch memory (see build/dq_select.usage)" >&2
     exit 1
   fi
 fi

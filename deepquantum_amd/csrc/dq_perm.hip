@@ -66,21 +66,6 @@ __device__ __forceinline__ typename Vec16<T>::type vector_of(const typename Elem
     else return join_pair(q);
 }
 
-// the lane's vectors of a chunk as they are: all loads, then all stores
-template <typename Q> __device__ __forceinline__ void copy_chunk(const Q* own, Q* dst, uint64_t v0, uint64_t nvec) {
-    Q q[ST_UNROLL];
-#pragma unroll
-    for (int u = 0; u < ST_UNROLL; ++u) {
-        const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
-        q[u] = own[v < nvec ? v : nvec - 1];            // (no load is guarded, only the stores are)
-    }
-#pragma unroll
-    for (int u = 0; u < ST_UNROLL; ++u) {
-        const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
-        if (v < nvec) dst[v] = q[u];
-    }
-}
-
 template <typename T, bool WIDE>
 __global__ __launch_bounds__(ST_THREADS) void perm_gather_kernel(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
                                                                  const uint32_t* __restrict__ table, Perm p, int n,

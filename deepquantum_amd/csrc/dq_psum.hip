@@ -57,11 +57,6 @@ struct PsumTable {
     int ngroups, nterms;
 };
 
-__device__ __forceinline__ float flip_sign(float h, unsigned par) { return __uint_as_float(__float_as_uint(h) ^ (par << 31)); }
-__device__ __forceinline__ double flip_sign(double h, unsigned par) {
-    return __hiloint2double(__double2hiint(h) ^ (int)(par << 31), __double2loint(h));
-}
-
 // w[u][e] = sum over the terms [t0, t1) of weights[t] (-1)^popc(j & zmasks[t]) for the source indices j = (jhigh, jlow[u][e])
 template <typename T, int VEC>
 __device__ __forceinline__ void signed_sum(const PsumTable& tb, int t0, int t1, int sbits, uint64_t jhigh,

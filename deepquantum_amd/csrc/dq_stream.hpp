@@ -42,6 +42,12 @@ __device__ __forceinline__ void vec_set(float4& q, int e, float2 a) {
 }
 __device__ __forceinline__ void vec_set(double2& q, int, double2 a) { q = a; }
 
+// h with its sign flipped where par is 1: exact, bit for bit (dq_psum.hip, dq_select.hip)
+__device__ __forceinline__ float flip_sign(float h, unsigned par) { return __uint_as_float(__float_as_uint(h) ^ (par << 31)); }
+__device__ __forceinline__ double flip_sign(double h, unsigned par) {
+    return __hiloint2double(__double2hiint(h) ^ (int)(par << 31), __double2loint(h));
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
@@ -141,6 +147,22 @@ __device__ __forceinline__ uint64_t chunk_high(const Gather& g, int sbits, uint6
     uint64_t s = 0;
     for (int r = g.nlow; r < g.nruns; ++r) s |= ((chunk >> (g.src[r] - sbits)) & ((1ull << g.len[r]) - 1ull)) << g.dst[r];
     return s;
+}
+
+// the lane's vectors of a unit as they are: all loads, then all stores (dq_perm.hip, dq_select.hip: a unit outside the
+// high controls)
+template <typename Q> __device__ __forceinline__ void copy_chunk(const Q* own, Q* dst, uint64_t v0, uint64_t nvec) {
+    Q q[ST_UNROLL];
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u) {
+        const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
+        q[u] = own[v < nvec ? v : nvec - 1];            // (no load is guarded, only the stores are)
+    }
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u) {
+        const uint64_t v = v0 + (uint64_t)(u * ST_THREADS);
+        if (v < nvec) dst[v] = q[u];
+    }
 }
 
 // ---- host side ---------------------------------------------------------------------------------

@@ -1299,6 +1299,57 @@ def permute_basis(state: torch.Tensor, perm: torch.Tensor, bits: Sequence[int], 
     return _PermuteBasis.apply(_flat_arg(state), perm, inv, bits, controls)
 
 
+# ---- SELECT over Pauli strings (csrc/dq_select.hip) ------------------------------------------------------------------------
+# S = sum_s |s><s| (x) c_s P_s on the select bits and the wires its strings touch, inside the controls: linear in the state,
+# unitary, and its adjoint is the same map with every phase conjugated -- the other table of a backend.SelectTable.  One
+# operation closed under differentiation: the backward is the function itself with the two tables swapped, the jvp the
+# function itself.
+class _SelectPauli(torch.autograd.Function):
+    """y = S x from the table ``words``: linear in x, cotangent gx = S^dagger gy -- the same function from ``dagger``."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, words: torch.Tensor, dagger: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
+        return backend.apply_select_pauli(_kernel_arg(state), words, bits, controls)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _state, words, dagger, ctx.bits, ctx.controls = inputs
+        ctx.save_for_backward(words, dagger)
+        ctx.save_for_forward(words, dagger)
+
+    @staticmethod
+    def jvp(ctx, state_t, *_):
+        _single_forward_level()
+        words, dagger = ctx.saved_tensors
+        return _SelectPauli.apply(_flat_arg(state_t), words, dagger, ctx.bits, ctx.controls)
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        words, dagger = ctx.saved_tensors
+        return _SelectPauli.apply(_flat_arg(gy), dagger, words, ctx.bits, ctx.controls), None, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, words, dagger, bits, controls):
+        return _vmap_states(_SelectPauli, 'select_pauli', info, in_dims, (state, words, dagger, bits, controls), tables=(1, 2))
+
+
+def select_pauli(state: torch.Tensor, table: 'backend.SelectTable', bits: Sequence[int], controls: Sequence[int] = (),
+                 dagger: bool = False) -> torch.Tensor:
+    """Differentiable (in the state, to any order) SELECT ``sum_s |s><s| (x) c_s P_s`` on a (B, 2**n) state: ``table`` a
+    constant :class:`backend.SelectTable` of 2^k strings with their powers of i, read by the value s of the index bits
+    ``bits`` (``bits[0]`` = its most significant bit); amplitudes outside the controls pass through; ``dagger``: the
+    adjoint.  One read and one write of the state whatever the number of strings, exact.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    _no_legacy(state)
+    if not isinstance(table, backend.SelectTable):
+        raise ValueError(f'select_pauli: the table must be a backend.SelectTable, got {type(table).__name__}')
+    bits, controls = _bit_args(bits, controls)
+    if len(bits) != table.k:
+        raise ValueError(f'select_pauli: the table is over {table.k} select bits, got {len(bits)}')
+    words, other = table.on(state.device, dagger)
+    return _SelectPauli.apply(_flat_arg(state), words, other, bits, controls)
+
+
 # ---- multiplexed one-qubit gates on any number of select wires (csrc/dq_mux.hip) -----------------------------------------
 # M = sum_s |s><s| (x) M[s] on the select bits and the target, inside the controls: linear in the state, and its adjoint is
 # the same map with every entry daggered -- which the kernel applies from the same table.  One operation closed under

@@ -83,6 +83,8 @@ class PauliSum:
                           doc='the sum of |h_t| over the strings other than the empty one: a rigorous bound of ||H - constant|| '
                               '(every Pauli string has norm 1: the triangle inequality)')
     constant = property(lambda self: self.table.constant, doc='the coefficient of the empty string')
+    select_bits = property(lambda self: max(1, (self.nterms - 1).bit_length()),
+                           doc='the select wires a SELECT over the strings needs: ceil(log2 nterms), and 1 for a single string')
 
     def chebyshev_order(self, t: float, tol: float, bounds: tuple[float, float] | None = None) -> int:
         """The number of orders -- launches, about -- that ``exp(-i t H)`` takes at tolerance ``tol``: the smallest K with
@@ -197,3 +199,102 @@ class PauliSumEvolution(_OneAngle, _FlatGate, ArbitraryGate):
         bounds = '' if self.bounds is None else f'bounds={self.bounds}, '
         return (f'terms={self.hamiltonian.nterms}, groups={self.hamiltonian.ngroups}, tol={self.tol}, ' + bounds
                 + _OneAngle.extra_repr(self))
+
+
+def _select_wires(wires, what: str, noun: str) -> list[int]:
+    wires = [wires] if isinstance(wires, int) else list(wires)
+    if not all(isinstance(w, int) for w in wires):
+        raise ValueError(f'{what}: {noun} must be integers, got {wires}')
+    return wires
+
+
+class SelectPauli(_FlatGate, ArbitraryGate):
+    """SELECT of a linear combination of unitaries: ``sum_s |s><s| (x) c_s P_s`` -- for every value s of the k select
+    wires ``wires`` (``wires[0]`` the most significant bit of s) its own Pauli string ``P_s`` with a phase ``c_s = i^phases[s]``
+    on the system wires -- in one read and one write of the state whatever the number of strings, exact
+    (``dq_apply_select_pauli_*``), where a loop of controlled strings between X flips is one pass per string.
+
+    ``paulis``: at most 2^k strings in the factor notation of ``HamiltonianGate`` (``'x0y2'``, ``''`` for the identity), a
+    wire number w inside a string meaning ``system_wires[w]`` (default: every wire that is neither a select wire nor a
+    control, in rising order); missing entries up to 2^k are the identity.  Or a :class:`PauliSum` on ``len(system_wires)``
+    wires: its merged ``terms``, in their order, are the strings and the signs of the coefficients the phases (0 for
+    h > 0, 2 for h < 0) -- the magnitudes belong to PREPARE (``cir.block_encode``) and are ignored here.  The strings and
+    phases are constants."""
+
+    def __init__(self, paulis, nqubit=1, wires=None, system_wires=None, phases=None, controls=None, name='SelectPauli',
+                 den_mat=False):
+        what = 'SelectPauli'
+        n = int(nqubit)
+        if wires is None:
+            raise ValueError(f'{what}: wires lists the select wires, the most significant bit of s first')
+        wires = _select_wires(wires, what, 'the select wires')
+        controls = _select_wires([] if controls is None else controls, what, 'the controls')
+        k = len(wires)
+        if k < 1 or k > backend.SELECT_MAX_BITS:
+            raise ValueError(f'{what}: 1 to {backend.SELECT_MAX_BITS} select wires, got {k}')
+        taken = wires + controls
+        if len(set(taken)) != len(taken) or any(w < 0 or w >= n for w in taken):
+            raise ValueError(f'{what}: repeated wires, or wires outside [0, {n}): select wires {wires}, controls {controls}')
+        if system_wires is None:
+            system_wires = [w for w in range(n) if w not in taken]
+        else:
+            system_wires = _select_wires(system_wires, what, 'the system wires')
+            if len(set(system_wires)) != len(system_wires):
+                raise ValueError(f'{what}: repeated wires in system_wires {system_wires}')
+            if any(w < 0 or w >= n for w in system_wires):
+                raise ValueError(f'{what}: a system wire outside [0, {n}): {system_wires}')
+            if set(system_wires) & set(taken):
+                raise ValueError(f'{what}: system_wires {system_wires} touches a select or control wire '
+                                 f'(select wires {wires}, controls {controls})')
+        m = len(system_wires)
+        if isinstance(paulis, PauliSum):
+            if paulis.nqubit != m:
+                raise ValueError(f'{what}: the PauliSum is for {paulis.nqubit} qubits, the system register has {m} wires')
+            if phases is not None:
+                raise ValueError(f'{what}: the phases of a PauliSum are the signs of its coefficients; phases must be None')
+            # (a term's masks are over the PauliSum's own index bits: wire w of it is bit m - 1 - w)
+            strings = [[(('y' if x >> (m - 1 - w) & z >> (m - 1 - w) & 1 else 'x' if x >> (m - 1 - w) & 1 else 'z'), w)
+                        for w in range(m) if (x | z) >> (m - 1 - w) & 1] for _, x, z in paulis.terms]
+            phases = [0 if h > 0 else 2 for h, _, _ in paulis.terms]
+        else:
+            if not isinstance(paulis, (list, tuple)) or not all(isinstance(p, str) for p in paulis) or not paulis:
+                raise ValueError(f"{what}: paulis is a PauliSum or a non-empty list of strings such as ['x0y2', '']")
+            strings = [HamiltonianGate._terms([[1.0, p]])[0][1] for p in paulis]
+            for p, factors in zip(paulis, strings):
+                if ''.join(f'{a}{w}' for a, w in factors) != p.lower().replace(' ', ''):
+                    raise ValueError(f'{what}: {p!r} is not a string of factors such as x0y2')
+        if len(strings) > 2**k:
+            raise ValueError(f'{what}: too many strings for {k} select wires: {len(strings)} > {2**k}')
+        phases = [0] * len(strings) if phases is None else list(phases)
+        if len(phases) != len(strings):
+            raise ValueError(f'{what}: {len(phases)} phases for {len(strings)} strings')
+        if any(not isinstance(q, int) or q < 0 or q > 3 for q in phases):
+            raise ValueError(f'{what}: a phase is a power of i in 0..3, got {phases}')
+        entries = []
+        for factors in strings:
+            string = ''.join(f'{a}{w}' for a, w in factors)
+            ws = [w for _, w in factors]
+            if len(set(ws)) != len(ws):
+                raise ValueError(f'{what}: a wire is repeated in {string!r}')
+            if any(w >= m for w in ws):
+                raise ValueError(f'{what}: {string!r} has a wire outside the system register of {m} wires')
+            xmask = sum(1 << (n - 1 - system_wires[w]) for a, w in factors if a in 'xy')
+            zmask = sum(1 << (n - 1 - system_wires[w]) for a, w in factors if a in 'yz')
+            entries.append((xmask, zmask))
+        entries += [(0, 0)] * (2**k - len(entries))
+        phases += [0] * (2**k - len(phases))
+        super().__init__(name=name, nqubit=n, wires=wires, controls=controls, den_mat=den_mat)
+        self.system_wires = system_wires
+        self.nstrings = len(strings)
+        self.table = backend.SelectTable(n, [(x, z, q) for (x, z), q in zip(entries, phases)])
+        self._mark_precision(torch.device('cpu'))        # (integer tables have no precision)
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        return ops.select_pauli(x, self.table, self._bits(self.wires), self._bits(self.controls), dagger=self.inv_mode)
+
+    def extra_repr(self) -> str:
+        s = f'wires={self.wires}, strings={self.nstrings}'
+        return s if self.controls == [] else s + f', controls={self.controls}'

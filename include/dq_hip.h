@@ -832,6 +832,31 @@ int dq_lanczos_update_c64(const void* v, void* w, void* acc, const double* coef,
 int dq_lanczos_update_c128(const void* v, void* w, void* acc, const double* coef, int n, int64_t batch, double* out, void* ws,
                            int64_t ws_bytes, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 14. SELECT over Pauli strings (csrc/dq_select.hip; added within ABI 30, presence is checked by symbol): the operator
+ *     sum_s |s><s| (x) c_s P_s of a linear combination of unitaries -- for every value s of k select bits its own Pauli
+ *     string P_s = (x_s, z_s) as in section 9 with a phase c_s = i^q_s on the other wires -- in one read and one write of
+ *     the state whatever the number of strings.
+ *         sub(i) as in section 8; free = (2^n - 1) & ~(select bits | control bits)
+ *         s = sub(i),  (x, z, q) = table[s],  x &= free,  j = i ^ x
+ *         out[b, i] = i^q * (-1)^popc(j & z) * in[b, j]     where all control bits of i are 1, in[b, i] elsewhere
+ *     `table`: DEVICE table of 2^k entries of two uint64, shared by the batch, 16-byte aligned:
+ *         word0 = x | q << 62          (the flip mask over index bits; q in 0..3, the i^ny of the Y factors folded in)
+ *         word1 = z                    (the sign mask over index bits)
+ *     x is masked with `free` in the kernel: a wrong table gives a wrong state and never a load outside the sample, and an
+ *     amplitude and its source always share s and the controls.  The factor is applied by swapping re and im and flipping
+ *     sign bits: the result is exact, and an entry with x = z = q = 0 copies bit for bit.  `bits` / `controls` / `nc` as in
+ *     section 8.  1 <= n <= 40, 1 <= k <= min(n, 31), 1 <= batch <= 65535; state pointers 16-byte aligned.
+ *     OUT OF PLACE ONLY: [in, in + batch * 2^n) and [out, ..) must not overlap.
+ * ------------------------------------------------------------------------------------------ */
+int dq_apply_select_pauli_c64(const void* in, void* out, const uint64_t* table, int n, const int* bits, int k,
+                              const int* controls, int nc, int64_t batch, dq_stream_t stream);
+int dq_apply_select_pauli_c128(const void* in, void* out, const uint64_t* table, int n, const int* bits, int k,
+                               const int* controls, int nc, int64_t batch, dq_stream_t stream);
+/* log2 of the amplitudes of a unit of 1024 16-byte vectors: 11 (complex64) / 10 (complex128).  Select bits at or above it
+ * are uniform over a workgroup (the entry is read once per unit); below it every vector reads its own entry. */
+int dq_select_pauli_unit_bits(int is_c128);
+
 #ifdef __cplusplus
 }
 #endif
