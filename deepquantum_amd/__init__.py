@@ -36,8 +36,9 @@ from .layer import (
 from .operation import Channel, Gate, Layer, Operation
 from .pauli_sum import PauliSum, PauliSumEvolution, SelectPauli
 from .qmath import (
-    amplitude_encoding, apply_pauli_sum, evolve_pauli_sum, expectation, expectation_cost, expectation_pauli_sum, ising_cost, measure,
-    meyer_wallach_measure, multi_kron, partial_trace, pauli_sum_extremal,
+    amplitude_encoding, apply_pauli_sum, evolve_pauli_sum, expectation, expectation_cost, expectation_pauli_sum, fidelity_kernel,
+    gram_matrix, ising_cost, linear_combination, measure, meyer_wallach_measure, multi_kron, orthonormalize, partial_trace,
+    pauli_sum_extremal,
 )
 from .state import DistributedQubitState, QubitState
 from .utils import CapturedGraph, dtype_map

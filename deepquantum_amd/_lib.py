@@ -176,6 +176,10 @@ _SIGNATURES = {
     'dq_lanczos_update_{s}': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _vp]),
     'dq_apply_select_pauli_{s}': (_i, [_vp, _vp, _vp, _i, _ip, _i, _ip, _i, _i64, _vp]),
     'dq_select_pauli_unit_bits': (_i, [_i]),
+    'dq_gram_geometry': (_i, [_i, _ip, _ip, _ip, _ip, _ip, _ip]),
+    'dq_gram_ws_bytes': (_i64, [_i, _i64, _i64, _i]),
+    'dq_gram_{s}': (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp, _i64, _vp]),
+    'dq_combine_{s}': (_i, [_vp, _vp, _vp, _i, _i64, _i64, _vp]),
 }
 
 

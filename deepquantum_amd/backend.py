@@ -132,16 +132,21 @@ def _call(entry: str, t: torch.Tensor, *args) -> None:
     _lib.check(getattr(_lib.load(), f'{entry}_{_suffix(t)}')(*args, _stream(t)), entry)
 
 
-def _check_out(state: torch.Tensor, out: torch.Tensor | None, what: str, in_place: bool = True) -> torch.Tensor:
-    """``out`` checked (``None``: a new tensor): a contiguous tensor of the state's shape, dtype and device that shares no
-    byte with the state or, where ``in_place`` says that a unit of work owns what it reads and writes, is the state's own
-    buffer.  A shifted overlap is safe for nobody."""
+def _check_out(state: torch.Tensor, out: torch.Tensor | None, what: str, in_place: bool = True,
+               shape: tuple[int, ...] | None = None) -> torch.Tensor:
+    """``out`` checked (``None``: a new tensor): a contiguous tensor of the state's shape (or of ``shape``, where the
+    primitive's result has another number of rows), dtype and device that shares no byte with the state or, where
+    ``in_place`` says that a unit of work owns what it reads and writes, is the state's own buffer.  A shifted overlap is
+    safe for nobody."""
+    shape = tuple(state.shape) if shape is None else tuple(shape)
     if out is None:
-        return torch.empty_like(state)
-    if out.shape != state.shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous tensor of the state's shape, dtype and device")
-    apart = abs(out.data_ptr() - state.data_ptr())
-    if apart < state.nbytes and not (in_place and apart == 0):
+        return torch.empty_like(state) if shape == tuple(state.shape) else torch.empty(shape, dtype=state.dtype, device=state.device)
+    if tuple(out.shape) != shape or out.dtype != state.dtype or out.device != state.device or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous tensor of "
+                         + ("the state's shape" if shape == tuple(state.shape) else f'shape {shape}') + ", the state's dtype and device")
+    lo, hi = out.data_ptr(), state.data_ptr()
+    apart = abs(lo - hi)
+    if (lo < hi + state.nbytes and hi < lo + out.nbytes) and not (in_place and apart == 0 and out.nbytes == state.nbytes):
         raise ValueError(f'{what}: out overlaps the state '
                          + ('without being the same buffer' if in_place else '(out of place only)'))
     return out
@@ -2172,3 +2177,104 @@ def psum_lanczos(table: PsumTable, start: torch.Tensor, which: str = 'lowest', t
                              torch.tensor([bool(d[3]) for d in done], dtype=torch.bool), alphas, betas)
 
     return run() if engine is _LanczosHip else _diag_double(run)
+
+
+# ---- every sample against every sample (csrc/dq_gram.hip) ----------------------------------------------------------------
+#: rows of either operand per launch of `gram` (the workspace holds 32 x 32 partial sums per workgroup: 64 MiB at this size)
+#: and of the output of `combine`; the wrappers slice wider batches
+GRAM_MAX_ROWS = 2048
+
+
+class GramGeometry(NamedTuple):
+    """``dq_gram_geometry``: the rows of a tile; the real terms a float32 accumulator chains before it is added into a double
+    (0 for complex128: float64 throughout); the columns of a lane's segment, of a wave's share of a step and of a
+    workgroup's unit per iteration; the most workgroups a tile pair is spread over."""
+
+    tile_rows: int
+    chain: int
+    lane_cols: int
+    wave_cols: int
+    unit_cols: int
+    max_blocks: int
+
+
+def gram_geometry(dtype: torch.dtype) -> GramGeometry:
+    vals = [C.c_int() for _ in range(6)]
+    _lib.check(_lib.load().dq_gram_geometry(int(dtype == torch.complex128), *[C.byref(v) for v in vals]), 'dq_gram_geometry')
+    return GramGeometry(*[v.value for v in vals])
+
+
+def _gram_rows(t: torch.Tensor, name: str, what: str) -> int:
+    n = _nqubit(t)
+    _suffix(t)
+    if t.is_conj() or t.is_neg():                       # (what `_ptr` refuses, on the stand-in's route as well)
+        raise ValueError(f'{what}: {name} is a tensor with a pending conjugation / negation: resolve_conj() / resolve_neg() it first')
+    if not t.is_contiguous():
+        raise ValueError(f'{what}: {name} must be contiguous')
+    if t.shape[0] < 1:
+        raise ValueError(f'{what}: {name} has no rows')
+    if n == 0 and t.dtype == torch.complex64:
+        raise ValueError(f'{what}: a complex64 row needs at least two amplitudes (one 16-byte vector)')
+    return n
+
+
+def gram(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    """G[i, j] = sum_x conj(bra[i, x]) ket[j, x] for (M, 2^n) and (N, 2^n) states of one dtype: complex128 (M, N), on the
+    matrix cores (``dq_gram_*``).  Up to 32 x 32 rows every row is read once; beyond that rows are tiled and a row of
+    ``bra`` is read ceil(N / 32) times, a row of ``ket`` ceil(M / 32) times.  ``bra`` and ``ket`` the same buffer is the
+    self-Gram: half the tiles, exactly Hermitian, a real diagonal.  complex64 sums at most ``gram_geometry().chain`` real
+    terms in float32 before it continues in double.  Bitwise reproducible; an entry's bits depend on its two rows, n and the
+    number of tile pairs of the launch alone (one pair up to 32 x 32 rows: entry (i, j) of a 5 x 7 Gram is the 1 x 1 Gram
+    of those rows, bit for bit).  Batches beyond ``GRAM_MAX_ROWS`` rows are sliced here, so the self-Gram of a wider batch
+    is Hermitian within rounding only.  The workspace comes from PyTorch's allocator (legal under capture)."""
+    what = 'gram'
+    n = _gram_rows(ket, 'ket', what)
+    if bra is not ket:
+        if bra.ndim != 2 or bra.shape[1] != ket.shape[1] or bra.dtype != ket.dtype or bra.device != ket.device:
+            raise ValueError(f'{what}: bra/ket must be (rows, 2**n) tensors of one n, dtype and device, got {tuple(bra.shape)} '
+                             f'{bra.dtype} and {tuple(ket.shape)} {ket.dtype}')
+        _gram_rows(bra, 'bra', what)
+    if not _use_hip(ket):
+        def double():
+            g = bra.to(torch.complex128).conj() @ ket.to(torch.complex128).T
+            if bra.data_ptr() == ket.data_ptr() and bra.shape == ket.shape:      # the self-Gram, as the kernel leaves it
+                up = torch.triu(g, 1)
+                g = up + up.mH + torch.diag(g.diagonal().real).to(torch.complex128)
+            return g.resolve_conj()
+
+        return _diag_double(double)
+    M, N = bra.shape[0], ket.shape[0]
+    out = torch.empty(M, N, 2, dtype=torch.float64, device=ket.device)
+    whole = M <= GRAM_MAX_ROWS and N <= GRAM_MAX_ROWS
+    c128 = int(ket.dtype == torch.complex128)
+    for alo, ahi in _slices(M, GRAM_MAX_ROWS):
+        for blo, bhi in _slices(N, GRAM_MAX_ROWS):
+            nbytes = _lib.load().dq_gram_ws_bytes(n, ahi - alo, bhi - blo, c128)
+            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ket.device)
+            part = out if whole else torch.empty(ahi - alo, bhi - blo, 2, dtype=torch.float64, device=ket.device)
+            _call('dq_gram', ket, _ptr(bra, alo), _ptr(ket, blo), n, ahi - alo, bhi - blo, _ptr(part), _ptr(ws), nbytes)
+            if not whole:
+                out[alo:ahi, blo:bhi] = part
+    return torch.view_as_complex(out)
+
+
+def combine(states: torch.Tensor, coef: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[m, x] = sum_j coef[m, j] states[j, x] for (N, 2^n) states and a complex (M, N) ``coef``: (M, 2^n) in the states'
+    dtype, on the matrix cores (``dq_combine_*``).  ``coef`` is rounded once to the states' precision, the chain of an
+    output element is 2 N real terms in that precision.  Up to 32 output rows the states are read once and ``out`` written
+    once; beyond that output rows are tiled and the states read ceil(M / 32) times.  Out of place only: ``out`` must not
+    overlap ``states``."""
+    what = 'combine'
+    n = _gram_rows(states, 'states', what)
+    N = states.shape[0]
+    if not isinstance(coef, torch.Tensor) or coef.ndim != 2 or coef.shape[1] != N or coef.shape[0] < 1:
+        raise ValueError(f'{what}: coef must have shape (M, {N}) for {N} states, got '
+                         f'{tuple(coef.shape) if isinstance(coef, torch.Tensor) else type(coef).__name__}')
+    coef = _finish_table(coef, states, torch.complex128, what)
+    M = coef.shape[0]
+    out = _check_out(states, out, what, in_place=False, shape=(M, states.shape[1]))
+    if not _use_hip(states):
+        return _diag_double(lambda: out.copy_((coef @ states.to(torch.complex128)).to(states.dtype)))
+    for lo, hi in _slices(M, GRAM_MAX_ROWS):
+        _call('dq_combine', states, _ptr(states), _ptr(coef, lo), _ptr(out, lo), n, hi - lo, N)
+    return out

@@ -411,6 +411,30 @@ class QubitCircuit(Operation):
             raise NotImplementedError('expectation_pauli_sum: den_mat=True (density matrices) is not supported')
         return qmath.expectation_pauli_sum(self.state, self.nqubit, H)
 
+    def kernel_matrix(self, x1: torch.Tensor, x2: torch.Tensor | None = None) -> torch.Tensor:
+        """The fidelity kernel ``K[i, j] = |<phi(x1_i)|phi(x2_j)>|^2`` of the circuit as a feature map: the circuit runs on
+        the rows of ``x1`` (and of ``x2``) as encoder data, as ``forward`` with 2-D data does, and every final state meets
+        every other in one launch (:func:`qmath.fidelity_kernel`): real float64 (M, N).  ``x2=None``: the symmetric
+        ``K(x1, x1)`` from one run and half the reads.  Differentiable in the circuit's trainable parameters
+        (kernel-target alignment) and in the data."""
+        what = 'kernel_matrix'
+        if self.den_mat:
+            raise NotImplementedError(f'{what}: den_mat=True (density matrices) is not supported: the kernel is an overlap '
+                                      'of state vectors')
+        if self.ndata == 0:
+            raise ValueError(f'{what}: the circuit has no encoders (add gates with encode=True): every row would give one state')
+
+        def states(x):
+            if not isinstance(x, torch.Tensor) or x.ndim not in (1, 2):
+                raise ValueError(f'{what}: data must be a (rows, ndata) tensor')
+            out = self.forward(x.reshape(1, -1) if x.ndim == 1 else x)
+            if not isinstance(out, torch.Tensor):
+                raise NotImplementedError(f'{what}: the circuit returns a {type(out).__name__}, not a batch of state vectors')
+            return out.reshape(out.shape[0], -1)
+
+        a = states(x1)
+        return qmath.fidelity_kernel(a, None if x2 is None else states(x2))
+
     def expectation(self, shots: int | None = None) -> torch.Tensor:
         """Expectation value of every registered observable, stacked on the last dimension
         (reference: circuit.py:381-428)."""
@@ -1120,6 +1144,9 @@ class DistributedQubitCircuit(QubitCircuit):
 
     def expectation_pauli_sum(self, H) -> torch.Tensor:
         raise NotImplementedError('expectation_pauli_sum: sharded states are not supported')
+
+    def kernel_matrix(self, x1: torch.Tensor, x2: torch.Tensor | None = None) -> torch.Tensor:
+        raise NotImplementedError('kernel_matrix: sharded states are not supported')
 
     def expectation(self, shots: int | None = None) -> torch.Tensor:
         from . import executor

@@ -1638,3 +1638,121 @@ def mux_rot(state: torch.Tensor, theta, axis: str, target: int, bits: Sequence[i
     whatever k is.
     A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
     return _mux_rot(_mux_spec(axis, target, bits, controls, 'xyz', 'mux_rot'), state, theta)
+
+
+# ---- every sample against every sample (csrc/dq_gram.hip) ----------------------------------------------------------------
+# Two operations that close under differentiation -- every backward and every jvp below is written with the other one --
+# so derivatives of any order exist by construction.  In PyTorch's conjugate convention, with Gbar / Ybar the cotangents:
+#     G = gram(A, B)     = conj(A) B^T        Abar = combine(B, conj(Gbar))       Bbar = combine(A, Gbar^T)
+#     Y = combine(S, C)  = C S                Sbar = combine(Ybar, C^H)           Cbar = gram(S, Ybar)^T
+def _no_vmap(what: str):
+    raise RuntimeError(f'deepquantum_amd: {what} under torch.vmap is not supported: the node already works on all rows of a '
+                       'batch against all rows; call it on the whole batch instead of mapping over it')
+
+
+class _Gram(torch.autograd.Function):
+    """G[i, j] = sum_x conj(A[i, x]) B[j, x], complex128 (M, N): see the rules above."""
+
+    @staticmethod
+    def forward(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+        pk = _kernel_arg(ket)
+        return backend.gram(pk if bra is ket else _kernel_arg(bra), pk)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        bra, ket = inputs
+        ctx.save_for_backward(bra, ket)
+        ctx.save_for_forward(bra, ket)
+
+    @staticmethod
+    def jvp(ctx, bra_t, ket_t):
+        _single_forward_level()
+        bra, ket = ctx.saved_tensors
+        return _jvp_two_slots(gram, bra, ket, bra_t, ket_t)
+
+    @staticmethod
+    def backward(ctx, gg: torch.Tensor):
+        bra, ket = ctx.saved_tensors
+        gg = gg.to(torch.complex128)
+        gbra = gket = None
+        if ctx.needs_input_grad[0]:
+            gbra = combine(ket, gg.conj())
+        if ctx.needs_input_grad[1]:
+            gket = combine(bra, gg.transpose(0, 1))
+        return gbra, gket
+
+    @staticmethod
+    def vmap(info, in_dims, bra, ket):
+        _no_vmap('gram')
+
+
+class _Combine(torch.autograd.Function):
+    """Y[m, x] = sum_j C[m, j] S[j, x] with C complex128 (M, N): see the rules above."""
+
+    @staticmethod
+    def forward(states: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+        return backend.combine(_kernel_arg(states), _plain(coef).detach())
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        states, coef = inputs
+        ctx.save_for_backward(states, coef)
+        ctx.save_for_forward(states, coef)
+
+    @staticmethod
+    def jvp(ctx, states_t, coef_t):
+        _single_forward_level()
+        states, coef = ctx.saved_tensors
+        return _jvp_two_slots(combine, states, coef, states_t, coef_t)
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        states, coef = ctx.saved_tensors
+        gstates = gcoef = None
+        if ctx.needs_input_grad[0]:
+            gstates = combine(gy, coef.conj().transpose(0, 1))
+        if ctx.needs_input_grad[1]:
+            gcoef = gram(states, gy).transpose(0, 1).to(coef.dtype)
+        return gstates, gcoef
+
+    @staticmethod
+    def vmap(info, in_dims, states, coef):
+        _no_vmap('combine')
+
+
+def _rows_arg(x: torch.Tensor, what: str) -> torch.Tensor:
+    if _is_batched(x):
+        _no_vmap(what)
+    if not isinstance(x, torch.Tensor) or x.ndim != 2 or not x.is_complex():
+        raise ValueError(f'{what}: states must be complex (rows, 2**n) tensors')
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def gram(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    """Differentiable Gram matrix ``G[i, j] = <bra_i|ket_j>`` of (M, 2**n) and (N, 2**n) states, complex128 (M, N)
+    (``backend.gram``); pass the same tensor twice for the self-Gram (half the reads, exactly Hermitian).  Not under vmap.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    _no_legacy(bra, ket)
+    same = bra is ket
+    ket = _rows_arg(ket, 'gram')
+    bra = ket if same else _rows_arg(bra, 'gram')
+    if bra.dtype != ket.dtype:
+        raise ValueError('gram: bra and ket must have one dtype')
+    if bra.shape[1] != ket.shape[1]:
+        raise ValueError(f'gram: bra and ket must have one number of qubits, got rows of {bra.shape[1]} and {ket.shape[1]}')
+    return _Gram.apply(bra, ket)
+
+
+def combine(states: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """Differentiable linear combinations ``Y[m] = sum_j coef[m, j] states[j]`` of (N, 2**n) states for a complex (M, N)
+    ``coef``: (M, 2**n) in the states' dtype (``backend.combine``); gradients flow to both.  Not under vmap.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    _no_legacy(states, coef)
+    states = _rows_arg(states, 'combine')
+    if not isinstance(coef, torch.Tensor):
+        raise ValueError(f'combine: coef must be a tensor, got {type(coef).__name__}')
+    if _is_batched(coef):
+        _no_vmap('combine')
+    if coef.ndim != 2 or coef.shape[1] != states.shape[0]:
+        raise ValueError(f'combine: coef must have shape (M, {states.shape[0]}) for {states.shape[0]} states, got {tuple(coef.shape)}')
+    return _Combine.apply(states, coef.to(torch.complex128))

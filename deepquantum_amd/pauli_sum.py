@@ -136,6 +136,22 @@ class PauliSum:
         """The ground energy and ground state: ``self.extremal('lowest', **kw)``."""
         return self.extremal('lowest', **kw)
 
+    def subspace_matrices(self, states: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(Hs, S)`` for a handful of (M, 2**n) ``states`` V: the projected Hamiltonian ``Hs[i, j] = <v_i|H|v_j>`` and the
+        overlap matrix ``S[i, j] = <v_i|v_j>``, complex128 (M, M) -- what a generalised eigenproblem ``Hs c = E S c`` in
+        the span of V (subspace diagonalisation, several Ritz pairs of a Krylov basis) is made of.  ``H V`` is one
+        ``apply_psum_axpby`` launch, the two matrices one Gram launch each (``qmath.gram_matrix``); ``S`` is exactly
+        Hermitian, ``Hs`` Hermitian within rounding.  Differentiable in the states."""
+        from . import ops, qmath
+
+        v = qmath._gram_states(states, 'PauliSum.subspace_matrices')
+        if v.shape[1] != 1 << self.nqubit:
+            raise ValueError(f'PauliSum.subspace_matrices: the PauliSum is for {self.nqubit} qubits, the states have '
+                             f'{v.shape[1]} amplitudes')
+        zero = torch.zeros(v.shape[0], dtype=torch.complex128, device=v.device)
+        hv = ops.psum_axpby(v, zero, torch.ones_like(zero), self)
+        return ops.gram(v, hv), ops.gram(v, v)
+
     def device_table(self, device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """(xmasks, bounds, zmasks, weights) on ``device``, cached per device."""
         return self.table.on(device)

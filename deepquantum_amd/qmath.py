@@ -598,6 +598,79 @@ def evolve_pauli_sum(state: torch.Tensor, H: Any, t: Any, nqubit: int | None = N
     return ops.psum_evolve(flat, t, H, tol, bounds).reshape(state.shape)
 
 
+def _gram_states(state: torch.Tensor, what: str) -> torch.Tensor:
+    """A batch of state vectors -- (M, 2**n), (M, 2**n, 1), or a single (2**n, 1) / (2**n,) -- as the flat (M, 2**n)
+    tensor of :func:`_state_batch`, n taken from the shape."""
+    if not isinstance(state, torch.Tensor):
+        raise ValueError(f'{what}: states must be a tensor, got {type(state).__name__}')
+    single = state.ndim == 1 or (state.ndim == 2 and state.shape[-1] == 1)
+    dim = state.numel() if single else (state.shape[1] if state.ndim >= 2 else 0)
+    n = max(int(dim).bit_length() - 1, 0)
+    if state.ndim > 3 or dim != 1 << n or n < 1:
+        raise ValueError(f'{what}: states must have the shape (M, 2**n), (M, 2**n, 1) or (2**n, 1) with n >= 1; '
+                         f'got {tuple(state.shape)}')
+    return _state_batch(state, n, what)[0]
+
+
+def gram_matrix(a: torch.Tensor, b: torch.Tensor | None = None) -> torch.Tensor:
+    """The overlaps ``G[i, j] = <a_i|b_j>`` of every state of ``a`` with every state of ``b``: complex128 (M, N).  ``a`` and
+    ``b`` are (M, 2**n), (M, 2**n, 1) or a single (2**n, 1), of one dtype.  ``b=None`` is the self-Gram ``<a_i|a_j>``: half
+    the reads, exactly Hermitian, a real diagonal.  One launch on the matrix cores, every state read once up to 32 x 32
+    rows (``dq_gram_*``; the tiling beyond that: :func:`backend.gram`); complex64 sums at most a few hundred real terms in
+    float32, everything else in double.  Differentiable to any order in both batches; not under ``torch.vmap``."""
+    fa = _gram_states(a, 'gram_matrix')
+    return ops.gram(fa, fa if b is None else _gram_states(b, 'gram_matrix'))
+
+
+def fidelity_kernel(a: torch.Tensor, b: torch.Tensor | None = None) -> torch.Tensor:
+    """The fidelity kernel ``K[i, j] = |<a_i|b_j>|^2`` of quantum kernel methods: real float64 (M, N);
+    ``|gram_matrix(a, b)|^2``, symmetric with ``b=None``."""
+    g = gram_matrix(a, b)
+    return g.real * g.real + g.imag * g.imag
+
+
+def linear_combination(states: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """``out[m] = sum_j coef[m, j] states[j]`` for a complex (M, N) ``coef`` (a 1-D ``coef`` of N entries gives one
+    combination): (M, 2**n) in the states' dtype -- Ritz vectors, Gram-Schmidt, a classically summed LCU.  One read of the
+    states and one write of the result up to 32 combinations (``dq_combine_*``); ``coef`` is rounded once to the states'
+    precision.  Differentiable to any order in both; not under ``torch.vmap``."""
+    flat = _gram_states(states, 'linear_combination')
+    if not isinstance(coef, torch.Tensor):
+        coef = torch.as_tensor(coef)
+    if coef.ndim == 1:
+        coef = coef.unsqueeze(0)
+    return ops.combine(flat, coef.to(flat.device))
+
+
+def orthonormalize(states: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """An orthonormal basis ``Q`` of the span of the (M, 2**n) ``states`` and the lower-triangular complex128 (M, M) ``L``
+    with ``states = L Q`` (row m of ``states`` is ``sum_k L[m, k] Q[k]``): Cholesky-QR applied twice -- ``S = gram(V)``,
+    ``S = L1 L1^H``, ``V <- conj(inv(L1)) V`` (the rows are the vectors), then once more, ``L = conj(L1 L2)`` -- so that ``|gram(Q) - 1|`` is at rounding level of
+    the states' precision where one pass leaves ``cond(S)`` times that.  Two self-Grams and two combinations on the
+    device; the M x M matrices in complex128 through torch.  A numerically dependent batch -- a pivot of the Cholesky
+    factorisation below ``M * eps`` of the largest squared norm -- is refused by name of the pivot.  Differentiable."""
+    what = 'orthonormalize'
+    v = _gram_states(states, what)
+    m = v.shape[0]
+    eps = torch.finfo(v.real.dtype).eps
+    total = None
+    for sweep in range(2):
+        s = ops.gram(v, v).cpu()                        # (M x M: the factorisation runs on the host)
+        chol, info = torch.linalg.cholesky_ex(s)
+        floor = m * eps * float(s.detach().diagonal().real.max())
+        pivots = chol.detach().diagonal().real ** 2
+        low = torch.nonzero(~(pivots > floor)).flatten()
+        if int(info) != 0 or low.numel():
+            k = int(info) - 1 if int(info) != 0 else int(low[0])
+            raise ValueError(f'{what}: the states are numerically dependent: pivot {k} of the Cholesky factorisation of their '
+                             f'Gram matrix (pass {sweep + 1}) is not above {floor:.3e} -- state {k} lies in the span of the '
+                             'states before it')
+        eye = torch.eye(m, dtype=torch.complex128, device=chol.device)
+        v = ops.combine(v, torch.linalg.solve_triangular(chol, eye, upper=False).conj().to(v.device))
+        total = chol if total is None else total @ chol
+    return v, total.conj().resolve_conj().to(v.device)
+
+
 class ExtremalResult(NamedTuple):
     """What :func:`pauli_sum_extremal` returns: ``value`` float64, ``vector`` (unit, in ``dtype``; ``None`` with
     ``vector=False``), ``residual`` -- the Lanczos estimate of ``|H y - value y|`` --, ``steps`` and ``converged``; one entry

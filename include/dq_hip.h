@@ -857,6 +857,42 @@ int dq_apply_select_pauli_c128(const void* in, void* out, const uint64_t* table,
  * are uniform over a workgroup (the entry is read once per unit); below it every vector reads its own entry. */
 int dq_select_pauli_unit_bits(int is_c128);
 
+/* ------------------------------------------------------------------------------------------
+ * 15. Every sample against every sample (csrc/dq_gram.hip; added within ABI 30, presence is checked by symbol): the Gram
+ *     matrix of two batches of states and linear combinations of a batch, on the matrix cores with exact f32 / f64
+ *     products.  Rows are contiguous, 2^n amplitudes each; 1 <= n <= 40 for complex64, 0 <= n <= 40 for complex128 (a
+ *     row is at least one 16-byte vector); 1 <= rows <= 65535 * 32 on either side (a tile of 32 rows is a grid dimension),
+ *     and a Gram of at most 2^32 entries.
+ * ------------------------------------------------------------------------------------------ */
+/* The geometry of dq_gram_*: rows of a tile; `chain`, the number of real terms an f32 accumulator sums before it is added
+ * into a double (complex64; 0 for complex128, whose sums are f64 throughout); the columns (amplitudes) of a lane's segment,
+ * of a wave's share of a step and of a workgroup's unit per iteration; the most workgroups a tile pair is spread over. */
+int dq_gram_geometry(int is_c128, int* tile_rows, int* chain, int* lane_cols, int* wave_cols, int* unit_cols, int* max_blocks);
+/* Bytes of device workspace dq_gram_* needs (32 x 32 partial sums per workgroup); -1 on a bad argument. */
+int64_t dq_gram_ws_bytes(int n, int64_t rows_a, int64_t rows_b, int is_c128);
+/* out[i, j] = sum_x conj(a[i, x]) * b[j, x]: DEVICE double [rows_a][rows_b][2] (re, im), fully overwritten, 8-byte
+ * aligned; a, b and ws 16-byte aligned.  Up to 32 x 32 rows every row is read once; beyond that rows are tiled and a row
+ * of a is read ceil(rows_b / 32) times, a row of b ceil(rows_a / 32) times.  a == b with rows_a == rows_b is the
+ * self-Gram: tiles on and above the diagonal only, a diagonal tile's rows loaded once for both operands, the lower
+ * triangle written as the exact conjugate of the upper one and the diagonal's imaginary part as 0.  complex64: products
+ * and sums in f32 for at most `chain` real terms, everything after that in double; complex128: f64 throughout.
+ * Workgroups write fixed-order partial sums into `ws` (at least dq_gram_ws_bytes bytes) and a second kernel adds them: no
+ * atomics, results are bitwise reproducible, and an entry's bits depend on its two rows, n and the number of tile pairs
+ * alone.  a and b are only read and may share memory in any way; out and ws must overlap neither them nor each other
+ * (DQ_ERR_ARG, "out, ws and the states overlap"). */
+int dq_gram_c64(const void* a, const void* b, int n, int64_t rows_a, int64_t rows_b, double* out, void* ws, int64_t ws_bytes,
+                dq_stream_t stream);
+int dq_gram_c128(const void* a, const void* b, int n, int64_t rows_a, int64_t rows_b, double* out, void* ws, int64_t ws_bytes,
+                 dq_stream_t stream);
+/* out[m, x] = sum_j coef[m, j] * in[j, x]: in (rows_in, 2^n), out (rows_out, 2^n) in the states' dtype, both 16-byte
+ * aligned; coef = DEVICE complex128 [rows_out][rows_in] as (re, im) doubles, 16-byte aligned, rounded once to the states'
+ * real precision; products and sums on the matrix cores in that precision, 2 * rows_in real terms per output element.
+ * `in` is read ceil(rows_out / 32) times, `out` written once, whatever rows_in.
+ * OUT OF PLACE ONLY: [in, in + rows_in * 2^n) and [out, out + rows_out * 2^n) must not overlap ("in and out overlap"),
+ * nor may out and coef. */
+int dq_combine_c64(const void* in, const double* coef, void* out, int n, int64_t rows_out, int64_t rows_in, dq_stream_t stream);
+int dq_combine_c128(const void* in, const double* coef, void* out, int n, int64_t rows_out, int64_t rows_in, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
