@@ -118,6 +118,11 @@ _SIGNATURES = {
     'dq_dag_grow_step': (_i, [_vp, _u64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'dq_dag_plan': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     'dq_plan_pass_ms': (C.c_double, [C.c_double, C.c_double]),
+    'dq_dag_plan_many': (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    'dq_plan_threads': (_i, [_i]),
+    'dq_dag_plan_verify': (_i64, [_i, _vp]),
+    'dq_plan_pass_ms_trips': (C.c_double, [C.c_double, C.c_double, _i]),
+    'dq_wave_pass_cost_ctrl': (_i, [C.POINTER(DqFusedPass), _i, _u64, _vp, _vp]),
     'dq_wave_pass_cost': (_i, [C.POINTER(DqFusedPass), _i, _u64, _vp, _vp]),
     'dq_wave_handler_valu': (_i, [_i, _i]),
     'dq_wave_gate_valu': (_i, [_i, _i]),

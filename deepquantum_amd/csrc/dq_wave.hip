@@ -801,6 +801,52 @@ extern "C" int dq_wave_pass_cost(const DqFusedPass* pass, int n, uint64_t known_
     return DQ_ERR_ARG;
 }
 
+// The same count for the planner's second model (csrc/dq_plan.hip, dq_plan_pass_ms_trips).  *valu: a one-target gate or X
+// record with controls OUTSIDE the tile counts its instructions times the share of the tiles that execute its body -- a half
+// per control bit, 1 for a bit of `known_zero` (the same in every tile that runs); *trips: the layout changes among the records.
+namespace dq {
+template <class W>
+static int wave_pass_cost_ctrl(const DqFusedPass* pass, int n, uint64_t known_zero, const unsigned short* table, int nids,
+                               double* valu, int* trips) {
+    static thread_local WaveRec scratch[WAVE_EXT_REC];
+    WaveKernPass kp;
+    const int rc = wave_translate<W>(pass, n, &kp, known_zero, scratch, WAVE_EXT_REC);
+    if (rc) return rc;
+    double v = 0.0;
+    int nt = 0;
+    const unsigned nrec = kp.nrec_bytes / 32u;
+    for (unsigned r = 0; r < nrec; ++r) {
+        const uint32_t id = scratch[r].w[0];
+        double share = 1.0;
+        if (id < (uint32_t)W::ID_TRIP0) {
+            const uint64_t out = (uint64_t)scratch[r].w[2] | ((uint64_t)scratch[r].w[3] << 32);
+            share = 1.0 / (double)(1ull << __builtin_popcountll(out & ~known_zero));
+        }
+        if (id < (uint32_t)nids) v += share * (double)table[id];
+        if (id >= (uint32_t)W::ID_TRIP0 && id < (uint32_t)W::ID_SWAP) {
+            ++nt;
+            ++r;        // (a trip's second record holds addresses)
+        }
+    }
+    if (valu) *valu = v;
+    if (trips) *trips = nt;
+    return DQ_OK;
+}
+}  // namespace dq
+
+extern "C" int dq_wave_pass_cost_ctrl(const DqFusedPass* pass, int n, uint64_t known_zero, double* valu, int* trips) {
+    if (!pass) {
+        dq::set_error("dq_wave_pass_cost_ctrl: null pointer");
+        return DQ_ERR_ARG;
+    }
+    if (pass->m == 12 && pass->slots == 6)
+        return dq::wave_pass_cost_ctrl<dq::WaveC64>(pass, n, known_zero, dq::kWaveValu, DQ_WAVE_NIDS, valu, trips);
+    if (pass->m == 11 && pass->slots == 5)
+        return dq::wave_pass_cost_ctrl<dq::WaveC128>(pass, n, known_zero, dq::kWave64Valu, DQ_WAVE64_NIDS, valu, trips);
+    dq::set_error("dq_wave_pass_cost_ctrl: not a wave-tile pass (m = %d, %d slots)", pass->m, pass->slots);
+    return DQ_ERR_ARG;
+}
+
 // One entry of the generated table: VALU instructions of handler `id` (complex128: c128 != 0); -1 beyond the last id.
 extern "C" int dq_wave_handler_valu(int c128, int id) {
     if (id < 0 || id >= (c128 ? DQ_WAVE64_NIDS : DQ_WAVE_NIDS)) return -1;

@@ -65,6 +65,9 @@ CONFIG = {'fuse': True, 'min_low_c64': None, 'min_low_c128': None,
           'sweep_max_gates': 104,
           # pass planner (fusion._plan_tiles): beam width / tiles tried per state; 0 = first-come tiles, 1 = greedy
           'plan_width': None, 'plan_branch': None, 'plan_restarts': None,
+          # the settings of big states (make_plan: a wider beam for the priced searches, restarts) on a state of ANY size:
+          # True forces them on (tests of the wide search at sizes a test can afford), None = by size
+          'plan_wide': None,
           # permuted stores also re-label the contiguous low bits, so every pass picks all its tile qubits (None = on)
           'free_low': None,
           # out-of-place passes that write the next pass's qubits to cheap index bits (fusion._place_writes): needs a
@@ -181,6 +184,25 @@ def _steady(prims: Sequence[Prim]) -> dict | None:
     return e
 
 
+def _search_settings(geom: 'fusion.Geometry', amps: int) -> None:
+    """The pass planner's search for a plan that will run on ``amps`` amplitudes (batch included): from
+    ``CONFIG['plan_big_amps']`` on -- or with ``CONFIG['plan_wide']`` -- the settings of big states."""
+    if amps >= CONFIG['plan_big_amps'] or CONFIG['plan_wide']:
+        if CONFIG['plan_width'] is None:
+            geom.plan_width = 8
+        if CONFIG['plan_branch'] is None:
+            geom.plan_branch = 4
+        if CONFIG['plan_restarts'] is None:
+            geom.plan_restarts = 6
+        # the priced searches run a second time with a wider beam, in the same native call and on its threads; their
+        # cheapest plans JOIN the candidates of the beam of 8, so the choice is never dearer by the model than without them
+        # (DESIGN 4.0, round 8)
+        if CONFIG['plan_width'] is None:
+            geom.plan_price_width = 12
+        if CONFIG['plan_wide']:
+            geom.plan_min_bits = geom.plan_restart_bits = 0
+
+
 def make_plan(prims: Sequence[Prim], n: int, is128: bool, permute: bool = False,
               out_perm: Sequence[int] | None = None, amps: int = 0, steady: dict | None = None,
               final_free: tuple = (), pad_untouched: bool = False, known_zero: int | None = None) -> Plan:
@@ -193,19 +215,13 @@ def make_plan(prims: Sequence[Prim], n: int, is128: bool, permute: bool = False,
         # tile (n = 28, depth 40: 1120 gates + 420 reductions = 32 passes of at most 72, 23 of at most 104).  Such a pass
         # keeps its records in device memory (backend._device_records)
         geom.max_gates = CONFIG['sweep_max_gates']
-    if amps >= CONFIG['plan_big_amps']:
-        if CONFIG['plan_width'] is None:
-            geom.plan_width = 8
-        if CONFIG['plan_branch'] is None:
-            geom.plan_branch = 4
-        if CONFIG['plan_restarts'] is None:
-            geom.plan_restarts = 6
+    _search_settings(geom, amps)
     geom.permute_store = permute
     geom.final_free = tuple(final_free) if permute else ()
     geom.pad_last_with_untouched = bool(pad_untouched)
     geom.known_zero = known_zero
     head = (n, is128, geom.m, geom.slots, geom.min_low, geom.max_gates, geom.max_far, geom.far_bit, geom.plan_width,
-            geom.plan_branch, geom.plan_restarts, geom.free_low, permute, CONFIG['fuse'], None if out_perm is None else tuple(out_perm),
+            geom.plan_branch, geom.plan_restarts, geom.plan_price_width, geom.plan_min_bits, geom.free_low, permute, CONFIG['fuse'], None if out_perm is None else tuple(out_perm),
             geom.final_free, geom.pad_last_with_untouched, geom.known_zero)
     if steady is not None:
         plan = steady['plans'].get(head)

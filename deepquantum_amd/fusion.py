@@ -91,6 +91,8 @@ class Geometry:
     # the searches also run PRICED (beam states ranked by modelled time per retired gate, csrc/dq_plan.hip) and the schedule
     # with the lowest exact modelled time wins (`schedule`); False: the count-driven choice alone
     plan_priced: bool = True
+    plan_price_width: int = 0  # ... and AGAIN with a beam this wide, for more candidates (0: not)
+    plan_carry: int = 3       # ... of the priced plans of a beam width, the cheapest this many by the searches' own estimates are carried out
     far_bit: int = 19         # index bits >= far_bit are "far": every one gathered doubles the number of
     max_far: int | None = None  # distant address streams of a tile; None = no limit
     # positions (in the layout the LAST pass leaves, i.e. after ``final_perm``) whose qubits that pass keeps out of its tile
@@ -409,6 +411,35 @@ def _op_class(op: PrimOp) -> int:
     return 5 if op.controls else 1 + (op.mode if 0 <= op.mode <= 3 else 0)
 
 
+def _plan_params(dag: '_Dag', low: set[int], hcap: int, cap: int, width: int, branch: int, seed: int,
+                 far: tuple[int, int] | None, free_low: int, price: '_Price | None'):
+    """The DqPlanParams of one beam search (and the array its ``gate_valu`` points to, which the caller keeps alive)."""
+    import numpy as np
+
+    lib = dag.native()[0]
+    prm = _lib.DqPlanParams(low=_mask(low), known_zero=0, seed=seed, hcap=hcap, cap=cap, width=width, branch=branch,
+                       far_bit=far[0] if far else 64, max_far=far[1] if far else -1, free_low=free_low, priced=0,
+                       gate_valu=None, pass_valu=0.0, tiles_full=0.0, rate=0.0)
+    keep = None
+    if price is not None:
+        keep = getattr(dag, '_gate_valu', {}).get(price.c128)
+        per_class = [float(lib.dq_wave_gate_valu(int(price.c128), c)) for c in range(9)]
+        if keep is None:
+            keep = np.array([per_class[_op_class(op)] for op in dag.ops] or [0.0], dtype=np.float32)
+            dag._gate_valu = {**getattr(dag, '_gate_valu', {}), price.c128: keep}
+        prm.priced, prm.gate_valu = (2 if price.rate else 1), keep.ctypes.data
+        prm.rate = float(price.rate or 0.0)
+        prm.known_zero = ((1 << price.n) - 1) if price.known_zero is None else price.known_zero
+        prm.pass_valu = 3.0 * per_class[8]          # (a typical pass changes its layout three times)
+        prm.tiles_full = float(1 << max(price.n - price.m, 0))
+    return prm, keep
+
+
+def _tile_sets(masks) -> list:
+    none = (1 << 64) - 1
+    return [None if int(t) == none else {b for b in range(64) if (int(t) >> b) & 1} for t in masks]
+
+
 def _plan_tiles_native(dag: '_Dag', low: set[int], hcap: int, cap: int, width: int, branch: int, seed: int = 20250929,
                        far: tuple[int, int] | None = None, free_low: int = 0, price: '_Price | None' = None) -> list:
     """`_plan_tiles` as ONE native call (csrc/dq_plan.hip, dq_dag_plan): the same tile lists, seed for seed.  With ``price``
@@ -419,18 +450,7 @@ def _plan_tiles_native(dag: '_Dag', low: set[int], hcap: int, cap: int, width: i
     import numpy as np
 
     lib, h = dag.native()[:2]
-    prm = _lib.DqPlanParams(low=_mask(low), known_zero=0, seed=seed, hcap=hcap, cap=cap, width=width, branch=branch,
-                       far_bit=far[0] if far else 64, max_far=far[1] if far else -1, free_low=free_low, priced=0,
-                       gate_valu=None, pass_valu=0.0, tiles_full=0.0, rate=0.0)
-    keep = None
-    if price is not None:
-        per_class = [float(lib.dq_wave_gate_valu(int(price.c128), c)) for c in range(9)]
-        keep = np.array([per_class[_op_class(op)] for op in dag.ops] or [0.0], dtype=np.float32)
-        prm.priced, prm.gate_valu = (2 if price.rate else 1), keep.ctypes.data
-        prm.rate = float(price.rate or 0.0)
-        prm.known_zero = ((1 << price.n) - 1) if price.known_zero is None else price.known_zero
-        prm.pass_valu = 3.0 * per_class[8]          # (a typical pass changes its layout three times)
-        prm.tiles_full = float(1 << max(price.n - price.m, 0))
+    prm, _keep = _plan_params(dag, low, hcap, cap, width, branch, seed, far, free_low, price)
     indeg = np.ascontiguousarray(dag.indeg, dtype=np.int32)
     ready = np.array(dag.ready or [0], dtype=np.int32)
     out = np.empty(dag.n_ops + 1, dtype=np.uint64)
@@ -440,33 +460,74 @@ def _plan_tiles_native(dag: '_Dag', low: set[int], hcap: int, cap: int, width: i
         raise RuntimeError('dq_dag_plan failed: ' + lib.dq_last_error().decode())
     if price is not None:
         price.estimate = ms.value
-    none = (1 << 64) - 1
-    return [None if int(t) == none else {b for b in range(64) if (int(t) >> b) & 1} for t in out[:cnt]]
+    return _tile_sets(out[:cnt])
 
 
-def modelled_ms(steps: Sequence, n: int, known_zero: int | None = None, batch: int = 1) -> tuple[float, list]:
+def _plan_tiles_many(dag: '_Dag', low: set[int], hcap: int, cap: int, width, branch: int, seeds: Sequence[int],
+                     far: tuple[int, int] | None = None, free_low: int = 0, prices: Sequence | None = None) -> list:
+    """One beam search per entry of ``seeds`` (and of ``prices``: a `_Price` or None each; ``width``: one beam width for
+    all, or one per search) in ONE native call that shares them out among threads (csrc/dq_plan.hip, dq_dag_plan_many): the
+    plans of `_plan_tiles_native`, in the order of the seeds, whatever the number of threads."""
+    import numpy as np
+
+    lib, h = dag.native()[:2]
+    prices = list(prices) if prices is not None else [None] * len(seeds)
+    widths = [width] * len(seeds) if isinstance(width, int) else list(width)
+    made = [_plan_params(dag, low, hcap, cap, w_, branch, seed, far, free_low, price) for w_, seed, price in zip(widths, seeds, prices)]
+    prms = (_lib.DqPlanParams * len(made))(*[m_[0] for m_ in made])
+    indeg = np.ascontiguousarray(dag.indeg, dtype=np.int32)
+    ready = np.array(dag.ready or [0], dtype=np.int32)
+    room = dag.n_ops + 1
+    out = np.empty((len(made), room), dtype=np.uint64)
+    counts = np.zeros(len(made), dtype=np.int32)
+    ms = np.zeros(len(made), dtype=np.float64)
+    rc = lib.dq_dag_plan_many(h, prms, len(made), indeg.ctypes.data, ready.ctypes.data, len(dag.ready),
+                              out.ctypes.data, room, counts.ctypes.data, ms.ctypes.data)
+    if rc < 0:
+        raise RuntimeError('dq_dag_plan_many failed: ' + lib.dq_last_error().decode())
+    for k, price in enumerate(prices):
+        if price is not None:
+            price.estimate = float(ms[k])
+    return [_tile_sets(out[k, :counts[k]]) for k in range(len(made))]
+
+
+def modelled_ms(steps: Sequence, n: int, known_zero: int | None = None, batch: int = 1, trips: bool = False) -> tuple[float, list]:
     """The exact modelled time of a schedule run behind |0..0> (``known_zero``: behind a state with THESE index bits |0>):
     the pass-cost model (csrc/dq_plan.hip, dq_plan_pass_ms) over what the library itself says of every finished pass
     (dq_wave_pass_cost: VALU instructions per tile from the generated table, bytes moved under the pass's known-zero
     mask).  A gate that runs on its own counts one read and one write of the state.  Returns (milliseconds,
-    per-pass rows (valu, bytes, ms))."""
+    per-pass rows (valu, bytes, ms)).
+
+    ``trips``: the model the planner chooses by (dq_wave_pass_cost_ctrl, dq_plan_pass_ms_trips) -- a record with controls
+    outside the tile counts only in the share of the tiles that execute it, and every layout change among a pass's records
+    has its price; the rows are then (weighted valu, bytes, ms, layout changes)."""
     import ctypes as C
 
     lib = _lib.load()
     masks = zero_state_masks(steps, n, known_zero) or [0] * len(steps)
     total, rows = 0.0, []
     for st, kz in zip(steps, masks):
+        nt = None
         if isinstance(st, FusedStep):
             v, b = C.c_int64(0), C.c_double(0.0)
             rc = lib.dq_wave_pass_cost(C.byref(st.desc), n, kz, C.addressof(v), C.addressof(b))
             if rc < 0:
                 raise RuntimeError('dq_wave_pass_cost failed: ' + lib.dq_last_error().decode())
             row = (v.value, b.value * batch)
+            if trips:
+                w, t = C.c_double(0.0), C.c_int(0)
+                if lib.dq_wave_pass_cost_ctrl(C.byref(st.desc), n, kz, C.addressof(w), C.addressof(t)) < 0:
+                    raise RuntimeError('dq_wave_pass_cost_ctrl failed: ' + lib.dq_last_error().decode())
+                row, nt = (w.value, row[1]), t.value
         else:
             amp = 8 if any(isinstance(s_, FusedStep) and s_.c64 for s_ in steps) else 16
             row = (0, 2.0 * amp * (1 << n) * batch)
-        ms = lib.dq_plan_pass_ms(float(row[0]), float(row[1]))
-        rows.append(row + (ms,))
+        if nt is None:
+            ms = lib.dq_plan_pass_ms(float(row[0]), float(row[1]))
+            rows.append(row + ((ms, 0) if trips else (ms,)))
+        else:
+            ms = lib.dq_plan_pass_ms_trips(float(row[0]), float(row[1]), nt)
+            rows.append(row + (ms, nt))
         total += ms
     return total, rows
 
@@ -513,14 +574,14 @@ def schedule(ops: Sequence[PrimOp], n: int, geom: Geometry, fuse: bool = True,
     # (the priced searches run in ONE family of tiles, the last that is tried: with free low bits where those are allowed)
     free_family = bool(geom.free_low and geom.permute_store and several and (width > 1 or force))
     if width and several:
-        cand = _schedule(ops, n, geom, width, final_perm, pool=None if free_family else pool)
+        cand = _schedule(ops, n, geom, width, final_perm, pool=None if free_family else pool, batch=priced)
         if cost(cand) < cost(best):
             best = cand
     if free_family:
         # every pass picks ALL its tile qubits (the stores also re-label the contiguous low bits): fewer passes
         # when the circuit does not keep coming back to the same low qubits; None: it could not restore the
         # canonical order with its last pass, or a gate had to run on its own
-        cand = _schedule(ops, n, geom, max(width, 2), final_perm, free_low=True, pool=None if force else pool)
+        cand = _schedule(ops, n, geom, max(width, 2), final_perm, free_low=True, pool=None if force else pool, batch=priced)
         if cand is not None and (cost(cand) < cost(best) or force):
             best = cand
     if pool and not force:
@@ -529,15 +590,19 @@ def schedule(ops: Sequence[PrimOp], n: int, geom: Geometry, fuse: bool = True,
         # worse than the count-driven one by the model.  One plan serves the runs behind |0..0> (most: a circuit's default)
         # and the runs on any other state (a caller's state, the reverse sweep), so a candidate must be cheaper for the
         # first and no dearer for the second, where every pass moves the whole state
+        # The figures are those of the model with layout changes and controls outside the tile priced (``trips``); by the
+        # plain model (dq_plan_pass_ms over dq_wave_pass_cost) a candidate must be no dearer than the count-driven choice
         def price(steps):
-            return modelled_ms(steps, n, geom.known_zero)[0], modelled_ms(steps, n, 0)[0]
+            return modelled_ms(steps, n, geom.known_zero, trips=True)[0], modelled_ms(steps, n, 0, trips=True)[0]
 
-        best_ms = price(best)
+        # (every candidate is held against the COUNT-DRIVEN choice, so the outcome does not depend on their order)
+        base_ms = best_ms = price(best)
+        plain = modelled_ms(best, n, geom.known_zero)[0]
         for cand in pool:
             if cand is best or cand.applied_final_perm != best.applied_final_perm:
                 continue
             ms = price(cand)
-            if ms[0] < best_ms[0] * (1.0 - 1e-9) and ms[1] <= best_ms[1]:
+            if ms[0] < best_ms[0] * (1.0 - 1e-9) and ms[1] <= base_ms[1] and modelled_ms(cand, n, geom.known_zero)[0] <= plain:
                 best, best_ms = cand, ms
     return best
 
@@ -549,21 +614,26 @@ class Steps(list):
 
 
 def _schedule(ops: Sequence[PrimOp], n: int, geom: Geometry, width: int,
-              final_perm: Sequence[int] | None = None, free_low: bool = False, pool: list | None = None) -> 'Steps | None':
+              final_perm: Sequence[int] | None = None, free_low: bool = False, pool: list | None = None,
+              batch: bool = False) -> 'Steps | None':
     """The planner's restarts give several tile sequences: tried shortest first, the first that can be carried out wins
     (with free low bits a sequence may turn out infeasible -- `_schedule_planned` -- and the next one often is not).
 
     ``pool`` collects every schedule that could be carried out, and with it the searches are run a second time PRICED
     (`_plan_tiles_native`: beam states ranked by modelled time per retired gate) and their schedules join the pool:
-    `schedule` keeps the pool's cheapest by the exact model."""
+    `schedule` keeps the pool's cheapest by the exact model.  ``batch``: the restarts run in one native call that shares them
+    out among threads (`_plan_tiles_many`) instead of one call each; the plans are the same."""
     if not width:
         return _schedule_planned(ops, n, geom, width, final_perm, free_low, None)
     dag = _Dag(ops, n)
     L = geom.min_low
     restarts = geom.plan_restarts if width > 1 and n >= geom.plan_restart_bits else 1
     far = (geom.far_bit, geom.max_far) if geom.max_far is not None else None
-    plans = [_plan_tiles_native(dag, set(range(L)), geom.m - L, geom.max_gates, width, geom.plan_branch, 20250929 + r, far,
-                                free_low=L if free_low else 0) for r in range(restarts)]
+    search = (dag, set(range(L)), geom.m - L, geom.max_gates, width, geom.plan_branch)
+    if batch and width > 1:     # (all restarts in one native call, on several threads)
+        plans = _plan_tiles_many(*search, [20250929 + r for r in range(restarts)], far, free_low=L if free_low else 0)
+    else:
+        plans = [_plan_tiles_native(*search, 20250929 + r, far, free_low=L if free_low else 0) for r in range(restarts)]
     seen = []
     best = None
     for plan in sorted(plans, key=len):
@@ -587,23 +657,37 @@ def _schedule(ops: Sequence[PrimOp], n: int, geom: Geometry, width: int,
         # the same searches PRICED, twice as many seeds as restarts and two rankings each: by modelled time per retired
         # gate, and by the lead over the rate of the count-driven schedule in hand (its modelled time per gate).  A search
         # returns its own estimate of the plan's time, within about a millisecond of the exact figure on the headline;
-        # the three cheapest by that estimate are carried out
+        # the cheapest by that estimate are carried out (``geom.plan_carry`` of them).  With ``geom.plan_price_width`` the
+        # same searches run a second time with THAT beam width, and its cheapest are carried out as well: what a beam finds
+        # is erratic in its width, so the wider beam adds candidates and never replaces any.  One
+        # native call for all the searches
         rates = [None]
         if best is not None and ops:
             rates.append(modelled_ms(best[1], n, geom.known_zero)[0] / len(ops))
-        found = []
-        for rate in rates:
-            for r in range(2 * restarts):
-                price = _Price(n, geom.m, geom.vb == 0, geom.known_zero, rate)
-                plan = _plan_tiles_native(dag, set(range(L)), geom.m - L, geom.max_gates, width, geom.plan_branch, 20250929 + r,
-                                          far, free_low=L if free_low else 0, price=price)
-                if plan not in seen and all(plan != f_[1] for f_ in found):
+        widths = [width] + ([geom.plan_price_width] if geom.plan_price_width > 1 and geom.plan_price_width != width else [])
+        runs = [(w_, rate, 20250929 + r) for w_ in widths for rate in rates for r in range(2 * restarts)]
+        prices = [_Price(n, geom.m, geom.vb == 0, geom.known_zero, rate) for _w, rate, _seed in runs]
+        priced = _plan_tiles_many(*search[:4], [w_ for w_, _rate, _seed in runs], search[5], [seed for _w, _rate, seed in runs], far,
+                                  free_low=L if free_low else 0, prices=prices)
+        carried = []
+        bar = None
+        for w_ in widths:
+            found = []
+            for run, price, plan in zip(runs, prices, priced):
+                if run[0] == w_ and plan not in seen and all(plan != f_[1] for f_ in found):
                     found.append((price.estimate, plan))
-        found.sort(key=lambda f_: f_[0])
-        for _est, plan in found[:3]:
-            out = _schedule_planned(ops, n, geom, width, final_perm, free_low, list(plan))
-            if out is not None:
-                pool.append(out)
+            found.sort(key=lambda f_: f_[0])
+            for est, plan in found[:geom.plan_carry]:
+                # (carrying a plan out is what planning time goes to: of the wider beam only the plans whose estimate
+                # undercuts the best of the first beam)
+                if plan in carried or (bar is not None and est >= bar):
+                    continue
+                carried.append(plan)
+                out = _schedule_planned(ops, n, geom, width, final_perm, free_low, list(plan))
+                if out is not None:
+                    pool.append(out)
+            if bar is None and found:
+                bar = found[0][0]
     return None if best is None else best[1]
 
 

@@ -277,9 +277,25 @@ typedef struct DqPlanParams {
 } DqPlanParams;
 int dq_dag_plan(void* dag, const DqPlanParams* prm, const int* indeg, const int* ready, int nready, uint64_t* tiles_out,
                 int max_tiles, double* model_ms);
+/* Several beam searches in ONE call, shared out among threads (dq_plan_threads): search k takes prms[k] and writes its
+ * masks to tiles_out[k * max_tiles ..], how many to counts[k] and its estimate to model_ms[k] (may be NULL).  The searches
+ * are independent and each result has its own place, so the outcome is the same for any number of threads.  The DAG is only
+ * read.  Returns 0, or the status of the first search that failed (also when one ran out of memory). */
+int dq_dag_plan_many(void* dag, const DqPlanParams* prms, int nplans, const int* indeg,
+                     const int* ready, int nready, uint64_t* tiles_out, int max_tiles, int* counts, double* model_ms);
+/* Threads dq_dag_plan_many uses for `nplans` searches: min(hardware threads, 16, nplans); the environment variable
+ * DQ_PLAN_THREADS overrides the first two (1: one search after the other). */
+int dq_plan_threads(int nplans);
+/* Test hook.  The searches extend the dry run of a growing tile instead of repeating it; while enabled every count (and
+ * the front, where one is kept) is ALSO taken from scratch and compared.  Returns the mismatches so far and writes the
+ * comparisons made to *compared (may be NULL); enable != 0 then restarts both counts.  The switch and the counts are
+ * process-wide: searches of other threads that run meanwhile are compared and counted too. */
+int64_t dq_dag_plan_verify(int enable, int64_t* compared);
 /* The pass-cost model (constants and their sources: csrc/dq_plan.hip): milliseconds of a wave-tile pass that executes `valu`
  * VALU instructions per tile and moves `bytes_moved` bytes (all samples together). */
 double dq_plan_pass_ms(double valu, double bytes_moved);
+/* ... and with the term for `trips` layout changes among the pass's records (dq_wave_pass_cost_ctrl). */
+double dq_plan_pass_ms_trips(double valu, double bytes_moved, int trips);
 
 /* The deferred form of the uncontrolled Rx-like gates of a complex64 pass (DQ_MODE_RX above), in place, in the matrix
  * buffer the passes will read: for every sample b < batch and every k < count the block of four complex numbers at
@@ -305,6 +321,10 @@ int dq_wave_descriptor(const DqFusedPass* pass, int n, uint64_t known_zero, void
  * descriptor's zero-extension word: the tiles that run are written whole and read less what known-|0> bits inside the tile
  * leave unloaded.  Either may be NULL. */
 int dq_wave_pass_cost(const DqFusedPass* pass, int n, uint64_t known_zero, int64_t* valu, double* bytes_moved);
+/* No device needed: dq_wave_pass_cost's count with every one-target gate or X record whose controls lie OUTSIDE the tile
+ * weighted by the share of the tiles that execute its body (the kernel branches round it elsewhere): a half per control bit not in
+ * `known_zero`; *trips = the layout changes among the pass's records.  Either may be NULL. */
+int dq_wave_pass_cost_ctrl(const DqFusedPass* pass, int n, uint64_t known_zero, double* valu, int* trips);
 /* One entry of that table (tools/gen_wave_asm.py, gen_wave_asm64.py: handler_valu); -1 for an id the kernel does not have. */
 int dq_wave_handler_valu(int is_c128, int id);
 /* The planner's per-gate estimate: the table's entry for a gate of `opclass` on a middle slot -- 0 diagonal, 1 + mode a

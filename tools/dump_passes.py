@@ -32,10 +32,14 @@ for i, (s, (a, b, ng, _nb)) in enumerate(zip(steps, ev)):
         import _wave_emulator as emu
         g = emu.gen()
         kp = emu.descriptor(s.desc, n)
-        ids = [kp.rec[j][0] for j in range(kp.nrec_bytes // 32)]
+        # handler ids in walking order; the second record of a layout change holds addresses, no id
+        ids, j, nrec = [], 0, kp.nrec_bytes // 32
+        while j < nrec:
+            ids.append(kp.rec[j][0])
+            j += 2 if g.ID_TRIP0 <= ids[-1] < g.ID_SWAP else 1
         trips = [g.TRIP_MASKS[j - g.ID_TRIP] for j in ids if g.ID_TRIP <= j < g.ID_SWAP]
-        extra = (f' records {len(ids)} trips k={[bin(t).count("1") for t in trips]} lane-perm {ids.count(g.ID_TRIP0)} '
-                 f'swaps {sum(j >= g.ID_SWAP for j in ids)} read {sorted(s.desc.high_sorted[j] for j in range(s.desc.h))} '
+        extra = (f' records {nrec} trips k={[bin(t).count("1") for t in trips]} lane-perm {ids.count(g.ID_TRIP0)} '
+                 f'swaps {sum(g.ID_SWAP <= j < g.ID_DIAG1 for j in ids)} read {sorted(s.desc.high_sorted[j] for j in range(s.desc.h))} '
                  f'write-lanes {sorted(kp.store_lane_shift[j] - 3 for j in range(6))} write-slots {sorted(int(kp.store_off[j]).bit_length() - 4 for j in range(5))}')
     zm = plan._zero_masks[plan.steps.index(s)] if plan._zero_masks else 0
     if zm:      # a circuit started from its own |0..0> (executor.CONFIG['zero_state']): index bits still known to be zero
