@@ -185,6 +185,9 @@ _SIGNATURES = {
     'dq_gram_ws_bytes': (_i64, [_i, _i64, _i64, _i]),
     'dq_gram_{s}': (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp, _i64, _vp]),
     'dq_combine_{s}': (_i, [_vp, _vp, _vp, _i, _i64, _i64, _vp]),
+    'dq_apply_qft_{s}': (_i, [_vp, _vp, _i, _ip, _i, _i, _i64, _vp]),
+    'dq_qft_tile_bits': (_i, [_i]),
+    'dq_qft_passes': (_i, [_i, _ip, _i, _i]),
 }
 
 

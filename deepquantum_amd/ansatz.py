@@ -182,13 +182,20 @@ class NumberEncoder(Ansatz):
 
 class QuantumFourierTransform(Ansatz):
     """QFT on ``minmax``; ``reverse=True`` leaves out the final bit-reversal swaps, i.e. the phases come
-    out as x/2^n, ..., x/2 (reference: ansatz.py:565-618)."""
+    out as x/2^n, ..., x/2 (reference: ansatz.py:565-618).  ``native=True``: one :class:`QFTGate` -- FFT stages over
+    the state, three reads and writes for 28 wires -- in place of the m (m + 1) / 2 gates; state vectors only."""
 
     def __init__(self, nqubit: int, minmax=None, reverse: bool = False, init_state: Any = 'zeros', den_mat=False,
-                 mps=False, chi=None, show_barrier: bool = False) -> None:
+                 mps=False, chi=None, show_barrier: bool = False, native: bool = False) -> None:
         super().__init__(nqubit=nqubit, minmax=minmax, init_state=init_state, name='QuantumFourierTransform',
                          den_mat=den_mat, mps=mps, chi=chi)
         self.reverse = reverse
+        self.native = native
+        if native:
+            if show_barrier:
+                raise ValueError('QuantumFourierTransform: show_barrier needs the gate sequence, native=True has none')
+            self.qft(wires=list(self.wires), swaps=not reverse)
+            return
         _replay(self, _qft_steps(self.wires, swaps=not reverse, barrier=show_barrier))
 
 

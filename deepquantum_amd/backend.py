@@ -1335,6 +1335,84 @@ def _apply_select_pauli_double(state, words, n, bits, controls, out):
 
 
 # ---------------------------------------------------------------------------------------------------
+# The quantum Fourier transform on any list of index bits as FFT stages (csrc/dq_qft.hip): bits[0] the most significant
+# bit of the transformed number x, |x> -> 2^(-m/2) sum_y exp(+2 pi i x y / 2^m) |y> (``swaps``) or |rev(y)> (swap-free)
+def qft_tile_bits(dtype: torch.dtype) -> int:
+    """log2 of the amplitudes of a tile of the QFT kernel: 12 (complex64) / 11 (complex128)."""
+    return _lib.load().dq_qft_tile_bits(int(dtype == torch.complex128))
+
+
+def qft_passes(nqubit: int, bits: Sequence[int], dtype: torch.dtype = torch.complex64, swaps: bool = False) -> int:
+    """Reads and writes of the state that :func:`apply_qft` takes for this list of index bits: the stages of
+    ``dq_qft_passes``, and one ``permute_bits`` pass for the swap form of a list of more than one stage."""
+    bits = [int(b) for b in bits]
+    stages = _lib.load().dq_qft_passes(int(nqubit), _lib.int_array(bits), len(bits), int(dtype == torch.complex128))
+    if stages < 0:
+        raise ValueError(f'qft_passes: bits {bits} must be distinct positions in [0, {nqubit})')
+    return stages + int(bool(swaps) and stages > 1)
+
+
+def _qft_reversal(n: int, bits: Sequence[int]) -> list[int]:
+    """``src_of_dst`` of :func:`permute_bits` for the bit reversal over ``bits`` (an involution)."""
+    src = list(range(n))
+    for j, p in enumerate(bits):
+        src[p] = bits[len(bits) - 1 - j]
+    return src
+
+
+def apply_qft(state: torch.Tensor, bits: Sequence[int], inverse: bool = False, swaps: bool = False,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """The quantum Fourier transform of the number read from the index bits ``bits`` (``bits[0]`` its most significant bit)
+    of a (B, 2**n) state, the other bits riding along: ``|x> -> 2^(-m/2) sum_y exp(+2 pi i x y / 2^m) |y>`` with
+    ``swaps``, and with the bits of y reversed over the list without (the gate sequence less its final swaps);
+    ``inverse``: the adjoint of that.  ``qft_passes`` reads and writes of the state (``dq_apply_qft_*``): the swaps of a
+    one-stage list happen inside the kernel, those of a longer list in one ``permute_bits`` pass -- after the transform,
+    before its adjoint.  ``out`` may be ``state``."""
+    what = 'apply_qft'
+    n, bits, _ = _diag_args(state, bits, (), what)
+    m = len(bits)
+    _suffix(state)
+    out = _check_out(state, out, what)
+    if not _use_hip(state):
+        return _diag_double(lambda: _apply_qft_double(state, n, bits, inverse, swaps, out))
+    c128 = int(state.dtype == torch.complex128)
+    outside = bool(swaps) and _lib.load().dq_qft_passes(n, _lib.int_array(bits), m, c128) > 1
+    flags = int(bool(inverse)) | (2 if swaps and not outside else 0)
+    src = state
+    if outside and inverse:
+        src = permute_bits(state, _qft_reversal(n, bits))
+    dst = torch.empty_like(state) if outside and not inverse else out
+    for lo, hi in _slices(state.shape[0], 65535):
+        _call('dq_apply_qft', state, _ptr(src, lo), _ptr(dst, lo), n, _lib.int_array(bits), m, flags, hi - lo)
+    if outside and not inverse:
+        permute_bits(dst, _qft_reversal(n, bits), out=out)
+    return out
+
+
+def _apply_qft_double(state, n, bits, inverse, swaps, out):
+    m = len(bits)
+    rest = [p for p in range(n - 1, -1, -1) if p not in bits]
+    axis = lambda p: 1 + (n - 1 - p)                    # index bit p as an axis of the (B, 2, .., 2) view
+    x = state.to(torch.complex128).reshape(-1, *([2] * n))
+    order = [0] + [axis(p) for p in rest] + [axis(p) for p in bits]
+    x = x.permute(order).reshape(state.shape[0], 1 << (n - m), *([2] * m))
+    flip = lambda t: t.permute([0, 1] + list(range(m + 1, 1, -1)))
+    if not swaps and inverse:
+        x = flip(x)
+    x = x.reshape(state.shape[0], 1 << (n - m), 1 << m)
+    x = torch.fft.fft(x, dim=-1, norm='ortho') if inverse else torch.fft.ifft(x, dim=-1, norm='ortho')
+    x = x.reshape(state.shape[0], 1 << (n - m), *([2] * m))
+    if not swaps and not inverse:
+        x = flip(x)
+    x = x.reshape(state.shape[0], *([2] * n))
+    back = [0] * (n + 1)
+    for at, ax in enumerate(order):
+        back[ax] = at
+    out.copy_(x.permute(back).reshape(state.shape).to(state.dtype))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # Multiplexed one-qubit gates on any number of select wires (csrc/dq_mux.hip): for every pair i0 (target bit 0),
 # i1 = i0 | 1 << target inside the controls, (out[i0], out[i1]) = M[sub(i0)] (in[i0], in[i1])
 MUX_KINDS = {'u': _lib.MUX_U, 'ry': _lib.MUX_RY}

@@ -153,7 +153,7 @@ class QubitCircuit(Operation):
 
     def _run_operators(self, flat: torch.Tensor, zero: bool = False) -> torch.Tensor:
         """All operators on a (B, 2**n) state: maximal stretches of gates go to the executor (fused passes),
-        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``, ``ExcitationGate``, ``SelectPauli``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
+        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``, ``ExcitationGate``, ``SelectPauli``, ``QFTGate``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
         density matrix alike: index 0 is 1, everything else 0)."""
         if self.den_mat:
             prims = []
@@ -901,6 +901,15 @@ class QubitCircuit(Operation):
         requires_grad = (not encode) and t is None
         self.add(PauliSumEvolution(hamiltonian=hamiltonian, t=t, nqubit=self.nqubit, tol=tol, name=name, den_mat=self.den_mat,
                                    requires_grad=requires_grad, bounds=bounds), encode=encode)
+
+    def qft(self, wires=None, minmax=None, swaps=True, inverse=False):
+        """The quantum Fourier transform of the number read from ``wires`` (any distinct wires in any order, ``wires[0]``
+        the most significant bit; all wires by default) as FFT stages over the state, ``swaps=False`` without the final
+        bit reversal, ``inverse=True`` the adjoint: see :class:`QFTGate`."""
+        from .gate import QFTGate
+
+        gate = QFTGate(nqubit=self.nqubit, wires=wires, minmax=minmax, swaps=swaps, den_mat=self.den_mat)
+        self.add(gate.inverse() if inverse else gate)
 
     def select_pauli(self, paulis, wires, system_wires=None, phases=None, controls=None):
         """SELECT ``sum_s |s><s| (x) i^phases[s] P_s``: for every value s of the select wires ``wires`` (``wires[0]`` = the

@@ -1048,6 +1048,31 @@ class PermutationGate(_FlatGate, ArbitraryGate):
         return s if self.controls == [] else s + f', controls={self.controls}'
 
 
+class QFTGate(_FlatGate, ArbitraryGate):
+    """The quantum Fourier transform of the number read from ``wires`` / ``minmax`` (any distinct wires in any order,
+    ``wires[0]`` the most significant bit): ``|x> -> 2^(-m/2) sum_y exp(2 pi i x y / 2^m) |y>``, the unitary of
+    ``QuantumFourierTransform`` on those wires; ``swaps=False`` leaves out the final bit reversal (its ``reverse=True``).
+    It runs as FFT stages over the state -- ``backend.qft_passes`` reads and writes, three for 28 wires -- where the gate
+    sequence has m (m + 1) / 2 gates (``dq_apply_qft_*``)."""
+
+    def __init__(self, nqubit=1, wires=None, minmax=None, swaps=True, name='QFTGate', den_mat=False, tsr_mode=False):
+        if isinstance(wires, (list, tuple)) and len(set(wires)) != len(wires):
+            raise ValueError(f'QFTGate: repeated wires in {list(wires)}')
+        super().__init__(name=name, nqubit=nqubit, wires=None if wires is None else list(wires), minmax=minmax, controls=None,
+                         den_mat=den_mat, tsr_mode=tsr_mode)
+        self.swaps = bool(swaps)
+        self._mark_precision(torch.device('cpu'))       # (no table: the marker tells get_unitary the precision)
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import ops
+
+        return ops.qft(x, self._bits(self.wires), inverse=self.inv_mode, swaps=self.swaps)
+
+    def extra_repr(self) -> str:
+        return f'wires={self.wires}, swaps={self.swaps}'
+
+
 def _mux_wires(gate: 'ArbitraryGate', name: str) -> int:
     """k of a multiplexer on ``gate.wires`` = k select wires, most significant first, then the target."""
     k = len(gate.wires) - 1

@@ -1350,6 +1350,45 @@ def select_pauli(state: torch.Tensor, table: 'backend.SelectTable', bits: Sequen
     return _SelectPauli.apply(_flat_arg(state), words, other, bits, controls)
 
 
+# ---- the quantum Fourier transform on any list of index bits (csrc/dq_qft.hip) ----------------------------------------------
+# F is unitary and linear in the state: one operation closed under differentiation -- the backward is the function itself
+# with ``inverse`` toggled, the jvp the function itself.
+class _Qft(torch.autograd.Function):
+    """y = F x (``inverse``: F^+ x): linear in x, cotangent gx = F^+ gy."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, bits: tuple, inverse: bool, swaps: bool) -> torch.Tensor:
+        return backend.apply_qft(_kernel_arg(state), bits, inverse, swaps)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _state, ctx.bits, ctx.inverse, ctx.swaps = inputs
+
+    @staticmethod
+    def jvp(ctx, state_t, *_):
+        _single_forward_level()
+        return _Qft.apply(_flat_arg(state_t), ctx.bits, ctx.inverse, ctx.swaps)
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        return _Qft.apply(_flat_arg(gy), ctx.bits, not ctx.inverse, ctx.swaps), None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, bits, inverse, swaps):
+        return _vmap_states(_Qft, 'qft', info, in_dims, (state, bits, inverse, swaps))
+
+
+def qft(state: torch.Tensor, bits: Sequence[int], inverse: bool = False, swaps: bool = True) -> torch.Tensor:
+    """Differentiable (in the state, to any order) quantum Fourier transform of the number read from the index bits
+    ``bits`` (``bits[0]`` = its most significant bit) of a (B, 2**n) state: ``|x> -> 2^(-m/2) sum_y exp(2 pi i x y / 2^m) |y>``;
+    ``swaps=False``: the bits of y reversed over the list (the gate sequence less its final swaps); ``inverse``: the
+    adjoint.  ``backend.qft_passes`` reads and writes of the state, where the gate sequence has m (m + 1) / 2 gates.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    _no_legacy(state)
+    bits, _ = _bit_args(bits, ())
+    return _Qft.apply(_flat_arg(state), bits, bool(inverse), bool(swaps))
+
+
 # ---- multiplexed one-qubit gates on any number of select wires (csrc/dq_mux.hip) -----------------------------------------
 # M = sum_s |s><s| (x) M[s] on the select bits and the target, inside the controls: linear in the state, and its adjoint is
 # the same map with every entry daggered -- which the kernel applies from the same table.  One operation closed under

@@ -913,6 +913,28 @@ int dq_gram_c128(const void* a, const void* b, int n, int64_t rows_a, int64_t ro
 int dq_combine_c64(const void* in, const double* coef, void* out, int n, int64_t rows_out, int64_t rows_in, dq_stream_t stream);
 int dq_combine_c128(const void* in, const double* coef, void* out, int n, int64_t rows_out, int64_t rows_in, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 16. The quantum Fourier transform on any list of wires as FFT stages (csrc/dq_qft.hip; added within ABI 30, presence
+ *     is checked by symbol).  bits[0..m) are distinct index-bit positions, bits[0] the most significant bit of the
+ *     transformed number x.  The swap-free transform is the gate sequence (Hadamard on wire i, then controlled phases
+ *     pi / 2^d from wire i + d) without its final swaps:
+ *         |x>  ->  2^(-m/2) sum_y exp(+2 pi i x y / 2^m) |rev(y)>       rev: the m bits reversed over the list
+ *     and the other index bits ride along.  It runs as dq_qft_passes stages, each one read and one write of the state:
+ *     a workgroup owns a tile of 2^min(T, n) amplitudes, T = dq_qft_tile_bits -- a group of consecutive wires of the
+ *     list plus the index bits of a 128-byte line the group misses -- transforms it in LDS and applies the phases
+ *     exp(2 pi i (A B mod 2^s) / 2^s) that tie the group to the later wires, the exponent reduced in integers.
+ *     `inverse`: 0 the transform, 1 its adjoint, | 2 the swap form (|y> in place of |rev(y)>, the adjoint of that with
+ *     1) -- inside the kernel and for lists of one stage only (DQ_ERR_ARG otherwise: permute the bits in a pass of
+ *     dq_permute_bits_*).  in == out is allowed (a stage reads and writes its own tile); with in != out the first stage
+ *     goes in -> out and the others run on out.  1 <= m <= n <= 40, 1 <= batch <= 65535; pointers 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int dq_apply_qft_c64(const void* in, void* out, int n, const int* bits, int m, int inverse, int64_t batch, dq_stream_t stream);
+int dq_apply_qft_c128(const void* in, void* out, int n, const int* bits, int m, int inverse, int64_t batch, dq_stream_t stream);
+/* log2 of the amplitudes of a tile: 12 (complex64) / 11 (complex128). */
+int dq_qft_tile_bits(int is_c128);
+/* The number of stages dq_apply_qft_* runs for this list; -1 on a bad argument (repeated or out-of-range bits). */
+int dq_qft_passes(int n, const int* bits, int m, int is_c128);
+
 #ifdef __cplusplus
 }
 #endif
