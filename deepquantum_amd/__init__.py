@@ -38,7 +38,7 @@ from .pauli_sum import PauliSum, PauliSumEvolution, SelectPauli
 from .qmath import (
     amplitude_encoding, apply_pauli_sum, evolve_pauli_sum, expectation, expectation_cost, expectation_pauli_sum, fidelity_kernel,
     gram_matrix, ising_cost, linear_combination, measure, meyer_wallach_measure, multi_kron, orthonormalize, partial_trace,
-    pauli_sum_extremal,
+    pauli_pool_gradients, pauli_sum_extremal, pauli_term_expectations, pauli_term_overlaps,
 )
 from .state import DistributedQubitState, QubitState
 from .utils import CapturedGraph, dtype_map

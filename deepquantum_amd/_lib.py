@@ -188,6 +188,9 @@ _SIGNATURES = {
     'dq_apply_qft_{s}': (_i, [_vp, _vp, _i, _ip, _i, _i, _i64, _vp]),
     'dq_qft_tile_bits': (_i, [_i]),
     'dq_qft_passes': (_i, [_i, _ip, _i, _i]),
+    'dq_pauli_terms_max': (_i, []),
+    'dq_pauli_terms_ws_bytes': (_i64, [_i, _i64, _i, _i, _i]),
+    'dq_pauli_terms_cross_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

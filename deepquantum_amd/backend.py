@@ -1833,6 +1833,77 @@ def psum_cross(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.
     return _cross_reduce('dq_psum_cross', 'dq_psum_cross_ws_bytes', bra, ket, table.tail(ket.device))
 
 
+# ---- every string of the sum on its own (csrc/dq_terms.hip) ---------------------------------------------------------------
+def pauli_terms_max() -> int:
+    """The most terms ``dq_pauli_terms_cross_*`` takes in one launch."""
+    return int(_lib.load().dq_pauli_terms_max())
+
+
+def _terms_pieces(table: PsumTable, cap: int) -> list[tuple[PsumTable, torch.Tensor]]:
+    """``table`` cut into tables of at most ``cap`` terms each, in term order -- whole groups where they fit, a group above
+    the cap cut into groups with its flip mask -- and with each the factors ``sign(h_t)`` of its terms, float64: the table's
+    sign bit times the sign of ``i^ny`` that ``PauliSum`` folded into the weight.  Cached per cap."""
+    cache = table.__dict__.setdefault('_pieces', {})
+    if cap not in cache:
+        xmasks, bounds, zmasks, weights = (t.tolist() for t in table.on('cpu'))
+        runs = []                                       # (flip mask, first term, start of the imaginary class, end), <= cap terms
+        for g, x in enumerate(xmasks):
+            for lo in range(bounds[2 * g], bounds[2 * g + 2], cap):
+                hi = min(lo + cap, bounds[2 * g + 2])
+                runs.append((x, lo, min(max(bounds[2 * g + 1], lo), hi), hi))
+        pieces, cur = [], []
+        for run in runs + [None]:
+            if cur and (run is None or run[3] - cur[0][1] > cap):
+                lo, hi = cur[0][1], cur[-1][3]
+                flat = [0] + [t - lo for r in cur for t in r[2:]]
+                sign = [math.copysign(1.0, weights[t]) * (-1.0 if bin(r[0] & zmasks[t]).count('1') & 2 else 1.0)
+                        for r in cur for t in range(r[1], r[3])]
+                pieces.append((PsumTable(table.nqubit, [r[0] for r in cur], flat, zmasks[lo:hi], weights[lo:hi]),
+                               torch.tensor(sign, dtype=torch.float64)))
+                cur = []
+            cur.append(run)
+        cache[cap] = pieces
+    return cache[cap]
+
+
+def _terms_double(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.Tensor:
+    """What ``dq_pauli_terms_cross_*`` leaves for ``table``, in complex128 (CPU test double only)."""
+    xmasks, bounds, zmasks, weights = (t.tolist() for t in table.on('cpu'))
+    u, v = bra.to(torch.complex128).conj(), ket.to(torch.complex128)
+    i = torch.arange(v.shape[-1])
+    out = torch.empty(v.shape[0], table.nterms, dtype=torch.complex128)
+    for g, x in enumerate(xmasks):
+        p = u * v[:, i ^ x]
+        for t in range(bounds[2 * g], bounds[2 * g + 2]):
+            par = (i ^ x) & zmasks[t]
+            for sh in (32, 16, 8, 4, 2, 1):
+                par = par ^ (par >> sh)
+            c = math.copysign(1.0, weights[t]) * (1j if t >= bounds[2 * g + 1] else 1.0)
+            out[:, t] = c * (p * (1 - 2 * (par & 1)).to(torch.complex128)).sum(dim=-1)
+    return out
+
+
+def pauli_terms_cross(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.Tensor:
+    """out[b, t] = <bra[b]| P_t |ket[b]> for every string of ``table``, in table order (the order of ``PauliSum.terms``):
+    complex128 (B, T), bitwise reproducible, one launch per ``pauli_terms_max()`` terms (``dq_pauli_terms_cross_*``) where
+    a loop over the strings is T of them.  The states are read once per flip mask plus one, as :func:`psum_cross` reads
+    them.  The coefficients of the table do not enter: the kernel reads their sign bits only and that sign is taken out
+    again here, exactly.  The first call for a table copies a few small tensors to the device (not under graph capture)."""
+    what = 'pauli_terms_cross'
+    _psum_args(ket, table, what)
+    _check_bra(bra, ket, what)
+    parts = []
+    for piece, sign in _terms_pieces(table, pauli_terms_max()):
+        if not _use_hip(ket):
+            val = _diag_double(lambda: _terms_double(bra, ket, piece))
+        else:
+            val = _cross_reduce('dq_pauli_terms_cross', 'dq_pauli_terms_ws_bytes', bra, ket, piece.tail(ket.device),
+                                shape=(piece.nterms,), sizer_args=(piece.nterms,))
+        parts.append(val * sign.to(val.device))
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+
 # ---- exp(-i t H) for a Pauli sum: a Chebyshev expansion, one launch per order --------------------------------------------
 # With b the coefficient of the empty string, a >= ||H - b|| (`PsumTable.norm_bound`: the sum of |h_t| over the other
 # strings -- every Pauli string has norm 1, so the triangle inequality makes it rigorous) and H' = (H - b) / a, whose

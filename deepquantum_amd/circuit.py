@@ -411,6 +411,26 @@ class QubitCircuit(Operation):
             raise NotImplementedError('expectation_pauli_sum: den_mat=True (density matrices) is not supported')
         return qmath.expectation_pauli_sum(self.state, self.nqubit, H)
 
+    def expectation_pauli_terms(self, H) -> torch.Tensor:
+        """``<psi|P_t|psi>`` of the final state of the last forward for every string of ``H`` (a ``PauliSum`` or its list
+        form), in the order of ``PauliSum.terms``: float64 (B, T), or (T,) for a single state, in one launch; see
+        :func:`qmath.pauli_term_expectations`.  Not differentiable: under grad mode a state with a graph is refused."""
+        if self.state is None:
+            raise RuntimeError('expectation_pauli_terms: run the circuit first')
+        if self.den_mat:
+            raise NotImplementedError('expectation_pauli_terms: den_mat=True (density matrices) is not supported')
+        return qmath.pauli_term_expectations(self.state, self.nqubit, H)
+
+    def pauli_pool_gradients(self, H, pool) -> torch.Tensor:
+        """``d<H>/d theta_k`` at 0 for ``exp(-i theta_k / 2 P_k)`` appended behind the final state of the last forward, for
+        every string ``P_k`` of ``pool`` (a list of strings or a ``PauliSum``): float64 (B, K), or (K,) for a single
+        state; see :func:`qmath.pauli_pool_gradients`.  Not differentiable."""
+        if self.state is None:
+            raise RuntimeError('pauli_pool_gradients: run the circuit first')
+        if self.den_mat:
+            raise NotImplementedError('pauli_pool_gradients: den_mat=True (density matrices) is not supported')
+        return qmath.pauli_pool_gradients(self.state, self.nqubit, H, pool)
+
     def kernel_matrix(self, x1: torch.Tensor, x2: torch.Tensor | None = None) -> torch.Tensor:
         """The fidelity kernel ``K[i, j] = |<phi(x1_i)|phi(x2_j)>|^2`` of the circuit as a feature map: the circuit runs on
         the rows of ``x1`` (and of ``x2``) as encoder data, as ``forward`` with 2-D data does, and every final state meets
@@ -1153,6 +1173,12 @@ class DistributedQubitCircuit(QubitCircuit):
 
     def expectation_pauli_sum(self, H) -> torch.Tensor:
         raise NotImplementedError('expectation_pauli_sum: sharded states are not supported')
+
+    def expectation_pauli_terms(self, H) -> torch.Tensor:
+        raise NotImplementedError('expectation_pauli_terms: sharded states are not supported')
+
+    def pauli_pool_gradients(self, H, pool) -> torch.Tensor:
+        raise NotImplementedError('pauli_pool_gradients: sharded states are not supported')
 
     def kernel_matrix(self, x1: torch.Tensor, x2: torch.Tensor | None = None) -> torch.Tensor:
         raise NotImplementedError('kernel_matrix: sharded states are not supported')

@@ -43,19 +43,11 @@
 //
 // Reduction.  The sums over the terms are formed in the state's precision, the products and the sum over groups and
 // amplitudes in double; the rest is dq_stream.hpp's fixed-order scheme.
-#include "dq_stream.hpp"
+#include "dq_psum_table.hpp"
 
 namespace dq {
 
 namespace {
-
-struct PsumTable {
-    const uint64_t* __restrict__ xmasks;
-    const int* __restrict__ bounds;
-    const uint64_t* __restrict__ zmasks;
-    const double* __restrict__ weights;
-    int ngroups, nterms;
-};
 
 // w[u][e] = sum over the terms [t0, t1) of weights[t] (-1)^popc(j & zmasks[t]) for the source indices j = (jhigh, jlow[u][e])
 template <typename T, int VEC>
@@ -105,18 +97,6 @@ __device__ __forceinline__ void load_group(const PsumTable& tb, int g, int n, co
               t2 = min(max(tb.bounds[2 * g + 2], 0), tb.nterms);
     signed_sum<T, VEC>(tb, t0, t1, sbits, jhigh, jlow, wr);
     signed_sum<T, VEC>(tb, t1, t2, sbits, jhigh, jlow, wi);
-}
-
-// The lane's vectors of unit `unit`; one that lies beyond the sample is replaced by vector 0 and marked in `live`.
-__device__ __forceinline__ unsigned unit_vectors(uint64_t unit, uint64_t nvec, uint64_t (&vec)[ST_UNROLL]) {
-    unsigned live = 0;
-#pragma unroll
-    for (int u = 0; u < ST_UNROLL; ++u) {
-        const uint64_t v = (unit << ST_UNIT_BITS) + (uint64_t)(u * ST_THREADS) + threadIdx.x;
-        if (v < nvec) live |= 1u << u;
-        vec[u] = v < nvec ? v : 0;
-    }
-    return live;
 }
 
 // A complex number in the accumulator's type A: itself, or (the cross reduction over a complex64 state) widened to double
@@ -398,30 +378,6 @@ __global__ __launch_bounds__(ST_THREADS) void psum_cross_kernel(const cx<T>* __r
             }
     }
     write_partial(re, im, sh, ws);
-}
-
-// The four arrays of the table: non-null, aligned to their element, at least one group and one term
-int check_table(const char* what, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks, const double* weights,
-                int ngroups, int nterms, PsumTable* tb) {
-    if (!xmasks || !bounds || !zmasks || !weights) {
-        set_error("%s: null table pointer", what);
-        return DQ_ERR_ARG;
-    }
-    if ((reinterpret_cast<uintptr_t>(xmasks) & 7) || (reinterpret_cast<uintptr_t>(zmasks) & 7) ||
-        (reinterpret_cast<uintptr_t>(weights) & 7) || (reinterpret_cast<uintptr_t>(bounds) & 3)) {
-        set_error("%s: xmasks, zmasks and weights must be 8-byte aligned, bounds 4-byte aligned", what);
-        return DQ_ERR_ARG;
-    }
-    if (ngroups < 1) {
-        set_error("%s: ngroups=%d, at least one group is needed", what, ngroups);
-        return DQ_ERR_ARG;
-    }
-    if (nterms < 1) {
-        set_error("%s: nterms=%d, at least one term is needed", what, nterms);
-        return DQ_ERR_ARG;
-    }
-    *tb = PsumTable{xmasks, bounds, zmasks, weights, ngroups, nterms};
-    return DQ_OK;
 }
 
 template <typename T>

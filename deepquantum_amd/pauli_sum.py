@@ -152,6 +152,28 @@ class PauliSum:
         hv = ops.psum_axpby(v, zero, torch.ones_like(zero), self)
         return ops.gram(v, hv), ops.gram(v, v)
 
+    @classmethod
+    def from_strings(cls, strings, nqubit: int) -> tuple['PauliSum', list[int]]:
+        """A pool of strings such as ``['x0y1', 'y0x1', 'z2']`` as a ``PauliSum`` with every coefficient 1, and for each
+        string of the list the index of its term in ``terms`` (merging and grouping reorder them; a string listed twice
+        points at one term)."""
+        if not isinstance(strings, (list, tuple)) or not strings or not all(isinstance(p, str) for p in strings):
+            raise ValueError("PauliSum.from_strings: a non-empty list of strings such as ['x0y1', 'z2'] is needed")
+        n = int(nqubit)
+        pool = cls([[1.0, p] for p in dict.fromkeys(strings)], n)
+        at = {(x, z): t for t, (_, x, z) in enumerate(pool.terms)}
+        order = []
+        for _, factors in HamiltonianGate._terms([[1.0, p] for p in strings]):
+            order.append(at[sum(1 << (n - 1 - w) for p, w in factors if p in 'xy'), sum(1 << (n - 1 - w) for p, w in factors if p in 'yz')])
+        return pool, order
+
+    def term_expectations(self, state: torch.Tensor) -> torch.Tensor:
+        """``<psi|P_t|psi>`` for every string, in the order of ``terms``: ``qmath.pauli_term_expectations(state, nqubit,
+        self)`` -- float64 (B, T), one launch, not differentiable."""
+        from . import qmath
+
+        return qmath.pauli_term_expectations(state, self.nqubit, self)
+
     def device_table(self, device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """(xmasks, bounds, zmasks, weights) on ``device``, cached per device."""
         return self.table.on(device)

@@ -562,6 +562,60 @@ def expectation_pauli_sum(state: torch.Tensor, nqubit: int, H: Any) -> torch.Ten
     return val.squeeze(0) if single else val
 
 
+def _terms_flat(state: torch.Tensor, nqubit: int, what: str) -> tuple[torch.Tensor, bool]:
+    """:func:`_state_batch` for the per-string functions, which build no graph: a state that asks for one is refused."""
+    if isinstance(state, torch.Tensor) and state.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f'{what}: not differentiable -- the per-string values carry no gradient; '
+                                  'expectation_pauli_sum is the differentiable route (or call this under torch.no_grad())')
+    flat, single = _state_batch(state, nqubit, what)
+    flat = flat.detach().resolve_conj().resolve_neg().contiguous()
+    return (flat.clone() if flat.data_ptr() % 16 else flat), single
+
+
+def pauli_term_overlaps(bra: torch.Tensor, ket: torch.Tensor, nqubit: int, H: Any) -> torch.Tensor:
+    """``<bra|P_t|ket>`` for every string of ``H`` (as in :func:`expectation_pauli_sum`) without its coefficient, in the
+    order of ``H.terms``: complex128 (B, T), or (T,) for single states.  One launch for up to
+    ``backend.pauli_terms_max()`` strings, one read of the states per distinct flip mask plus one
+    (``dq_pauli_terms_cross_*``), where a loop over the strings reads them once per string.  Not differentiable."""
+    what = 'pauli_term_overlaps'
+    u, single = _terms_flat(bra, nqubit, what)
+    v = u if ket is bra else _terms_flat(ket, nqubit, what)[0]
+    if v.shape != u.shape or v.dtype != u.dtype or v.device != u.device:
+        raise ValueError(f'{what}: bra and ket must be states of one shape, dtype and device')
+    val = backend.pauli_terms_cross(u, v, _pauli_sum(H, nqubit, what).table)
+    return val.squeeze(0) if single else val
+
+
+def pauli_term_expectations(state: torch.Tensor, nqubit: int, H: Any) -> torch.Tensor:
+    """``<psi|P_t|psi>`` for every string of ``H``, in the order of ``H.terms``: float64 (B, T), or (T,) for a single state --
+    the gradient of ``<H>`` in the coefficients, and what the shot-noise variance ``sum_t h_t^2 (1 - <P_t>^2) / shots`` is
+    made of.  See :func:`pauli_term_overlaps`.  Not normalised; not differentiable."""
+    flat, single = _terms_flat(state, nqubit, 'pauli_term_expectations')
+    val = backend.pauli_terms_cross(flat, flat, _pauli_sum(H, nqubit, 'pauli_term_expectations').table).real
+    return val.squeeze(0) if single else val
+
+
+def pauli_pool_gradients(state: torch.Tensor, nqubit: int, H: Any, pool: Any) -> torch.Tensor:
+    """The operator-selection step of ADAPT-VQE: entry k is ``d<H>/d theta_k`` at ``theta_k = 0`` for ``exp(-i theta_k / 2
+    P_k)`` appended to the circuit that made ``state``, ``Im <H psi|P_k|psi>``, for every string of ``pool`` -- a list of
+    strings such as ``['x0y1', 'y0x1']``, in its order, or a :class:`PauliSum`, in the order of its ``terms``; coefficients
+    count as 1.  float64 (B, K), or (K,) for a single state.  One ``apply_pauli_sum`` and one launch per
+    ``backend.pauli_terms_max()`` strings.  Not differentiable."""
+    from .pauli_sum import PauliSum
+
+    what = 'pauli_pool_gradients'
+    flat, single = _terms_flat(state, nqubit, what)
+    order = None
+    if not isinstance(pool, PauliSum):
+        pool, order = PauliSum.from_strings(pool, nqubit)
+    with torch.no_grad():
+        hpsi = apply_pauli_sum(flat, nqubit, _pauli_sum(H, nqubit, what))
+    val = backend.pauli_terms_cross(hpsi, flat, _pauli_sum(pool, nqubit, what).table).imag
+    if order is not None:
+        val = val[:, torch.tensor(order, device=val.device)]
+    return val.squeeze(0) if single else val
+
+
 def apply_pauli_sum(state: torch.Tensor, nqubit: int, H: Any) -> torch.Tensor:
     """``H|psi>`` for a sum of Pauli strings ``H`` (as in :func:`expectation_pauli_sum`), with the shape of ``state`` and
     in its complex dtype: what variance, Krylov and imaginary-time steps are made of.  One launch for the whole sum

@@ -935,6 +935,34 @@ int dq_qft_tile_bits(int is_c128);
 /* The number of stages dq_apply_qft_* runs for this list; -1 on a bad argument (repeated or out-of-range bits). */
 int dq_qft_passes(int n, const int* bits, int m, int is_c128);
 
+/* ------------------------------------------------------------------------------------------
+ * 17. Every string of a sum of Pauli strings on its own (csrc/dq_terms.hip; added within ABI 30, presence is checked by
+ *     symbol): for the table of section 13, in ONE launch and in table order,
+ *         out[b, t] = s_t * c_t * sum_i conj(bra[b, i]) * (-1)^popc((i ^ x_t) & z_t) * ket[b, i ^ x_t]
+ *     with c_t = 1 for a term of the real class and i for one of the imaginary class, and s_t the SIGN BIT of weights[t]:
+ *     the magnitude of a weight is not read.  (With the table of a Hamiltonian, out[b, t] = sign(h_t) <bra_b|P_t|ket_b>.)
+ *     A workgroup takes the Walsh-Hadamard transform of a unit's products conj(bra[j]) ket[j ^ x] once per group and
+ *     reads each term's value out of it; the states are read ngroups + 1 times as in section 13, whatever nterms is.
+ *     The same masking and clamping as in section 13.  1 <= n <= 40, 1 <= batch <= 65535, ngroups >= 1,
+ *     1 <= nterms <= dq_pauli_terms_max(); bra, ket, ws and out 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+/* The most terms of a launch (the per-term accumulators of a workgroup live in LDS): 1024.  A longer table is cut into
+ * tables of whole groups, a longer group into several groups with the same flip mask. */
+int dq_pauli_terms_max(void);
+/* Bytes of device workspace dq_pauli_terms_cross_* needs: batch * min(units, 1024) * nterms * 16, a unit being 1024
+ * 16-byte vectors -- at most nterms / 1024 of the ket's own size (`cross` != 0: bra != ket, the same amount); -1 on a bad
+ * argument. */
+int64_t dq_pauli_terms_ws_bytes(int n, int64_t batch, int is_c128, int cross, int nterms);
+/* out = DEVICE double [batch][nterms][2] (re, im), fully overwritten.  Products and sums in double.  Workgroups write
+ * their per-term partial sums into `ws` and a second kernel adds them in index order: no atomics, bitwise reproducible,
+ * and a sample's bits do not depend on the rest of the batch.  bra == ket loads the own vectors once. */
+int dq_pauli_terms_cross_c64(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks,
+                             const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws,
+                             int64_t ws_bytes, dq_stream_t stream);
+int dq_pauli_terms_cross_c128(const void* bra, const void* ket, const uint64_t* xmasks, const int* bounds, const uint64_t* zmasks,
+                              const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws,
+                              int64_t ws_bytes, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
