@@ -39,6 +39,8 @@ PERM_AUTO, PERM_GATHER, PERM_LOCAL = range(3)      # path of dq_apply_permutatio
 MUX_U, MUX_RY = range(2)               # kind of dq_apply_mux_*
 MUX_AXES = {'i': 0, 'x': 1, 'y': 2, 'z': 3}        # axis of dq_mux_cross_*
 EXCITE_GATE, EXCITE_MAP = range(2)     # mode of dq_apply_excite_axpby_*
+COLLAPSE_FULL, COLLAPSE_DROP = range(2)        # layout of dq_apply_collapse_*
+COLLAPSE_MAX_BITS = 20                 # measured wires of one dq_measure_draw / dq_apply_collapse_*
 
 
 class DqFusedGate(C.Structure):
@@ -98,6 +100,13 @@ class DqPlanParams(C.Structure):
                 ('hcap', C.c_int32), ('cap', C.c_int32), ('width', C.c_int32), ('branch', C.c_int32),
                 ('far_bit', C.c_int32), ('max_far', C.c_int32), ('free_low', C.c_int32), ('priced', C.c_int32),
                 ('gate_valu', C.c_void_p), ('pass_valu', C.c_double), ('tiles_full', C.c_double), ('rate', C.c_double)]
+
+
+class DqCollapseRec(C.Structure):
+    """include/dq_hip.h, DqCollapseRec: what dq_measure_draw writes and dq_apply_collapse_* reads, per sample."""
+
+    _fields_ = [('outcome', C.c_int64), ('xmask', C.c_uint64), ('zmask', C.c_uint64), ('scale', C.c_double),
+                ('prob', C.c_double)]
 
 
 _vp, _i, _i64, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64
@@ -191,6 +200,9 @@ _SIGNATURES = {
     'dq_pauli_terms_max': (_i, []),
     'dq_pauli_terms_ws_bytes': (_i64, [_i, _i64, _i, _i, _i]),
     'dq_pauli_terms_cross_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i64, _vp]),
+    'dq_collapse_rec_layout': (_i, [_ip, _i]),
+    'dq_measure_draw': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
+    'dq_apply_collapse_{s}': (_i, [_vp, _vp, _vp, _i, _ip, _i, _i, _i, _i, _i64, _vp]),
 }
 
 

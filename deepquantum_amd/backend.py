@@ -2427,3 +2427,191 @@ def combine(states: torch.Tensor, coef: torch.Tensor, out: torch.Tensor | None =
     for lo, hi in _slices(M, GRAM_MAX_ROWS):
         _call('dq_combine', states, _ptr(states), _ptr(coef, lo), _ptr(out, lo), n, hi - lo, N)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Mid-circuit measurement (csrc/dq_collapse.hip): the draw of one outcome per sample from its marginal table and the
+# collapse X^x Z^z P_o onto it, every sample by its own record, in one pass over the output.
+COLLAPSE_MAX_BITS = _lib.COLLAPSE_MAX_BITS
+
+
+class CollapseRec:
+    """One ``DqCollapseRec`` per sample as the collapse kernel reads it on the device: ``data`` is int64 (B, 5) --
+    outcome, xmask, zmask and the bits of the float64 scale and prob -- and ``has_x`` says whether an x table went into
+    it (only without one may a FULL collapse run in place).  The fields are views: nothing is copied to the host."""
+
+    def __init__(self, data: torch.Tensor, has_x: bool):
+        self.data, self.has_x = data, bool(has_x)
+
+    outcome = property(lambda self: self.data[:, 0])
+    xmask = property(lambda self: self.data[:, 1])
+    zmask = property(lambda self: self.data[:, 2])
+    scale = property(lambda self: self.data[:, 3].view(torch.float64))
+    prob = property(lambda self: self.data[:, 4].view(torch.float64))
+
+
+def collapse_rec(outcome: torch.Tensor, scale: torch.Tensor, xmask: torch.Tensor | None = None,
+                 zmask: torch.Tensor | None = None, prob: torch.Tensor | None = None) -> CollapseRec:
+    """The records of explicit per-sample values: int64 (B,) ``outcome`` (and masks over the n index bits), real (B,)
+    ``scale``."""
+    b = outcome.shape[0]
+    if outcome.ndim != 1 or outcome.dtype != torch.int64 or any(
+            t is not None and (t.shape != (b,) or t.device != outcome.device) for t in (scale, xmask, zmask, prob)):
+        raise ValueError('collapse_rec: outcome must be int64 (B,), scale / xmask / zmask / prob (B,) on its device')
+    data = torch.zeros(b, 5, dtype=torch.int64, device=outcome.device)
+    rec = CollapseRec(data, xmask is not None)
+    data[:, 0] = outcome
+    if xmask is not None:
+        data[:, 1] = xmask
+    if zmask is not None:
+        data[:, 2] = zmask
+    rec.scale.copy_(scale.detach())
+    if prob is not None:
+        rec.prob.copy_(prob.detach())
+    return rec
+
+
+def _mask_table(t: torch.Tensor | None, like: torch.Tensor, k: int, name: str) -> torch.Tensor | None:
+    if t is None:
+        return None
+    if t.shape != (1 << k,) or t.dtype != torch.int64:
+        raise ValueError(f'measure_draw: {name} must be int64 ({1 << k},) masks over the index bits, got {t.dtype} {tuple(t.shape)}')
+    return t.to(like.device).contiguous()
+
+
+def measure_draw(probs: torch.Tensor, u: torch.Tensor | None, forced: torch.Tensor | None = None, fx: torch.Tensor | None = None,
+                 fz: torch.Tensor | None = None) -> CollapseRec:
+    """One record per sample from its marginal table (``dq_measure_draw``; no host synchronisation).  ``probs``: float64
+    (B, 2^k) as :func:`marginal` returns it, not necessarily normalised; ``u``: float64 (B,) in [0, 1); ``forced``: int64
+    (B,), an entry < 0 draws, any other post-selects; ``fx`` / ``fz``: int64 (2^k,) masks of the correction by outcome.
+    The outcome is the smallest o with ``C(o) > u T`` (C the running sum, T the total); one of probability 0 is never
+    drawn.  ``scale = probs[o]^(-1/2)`` and ``prob = probs[o] / T``; a forced outcome of probability 0 gives
+    ``scale = prob = 0``: a zero state, no error.  ``u=None`` is allowed where ``forced`` is given."""
+    what = 'measure_draw'
+    if probs.ndim != 2 or probs.dtype != torch.float64 or probs.shape[0] < 1:
+        raise ValueError(f'{what}: probs must be float64 (B, 2**k), got {probs.dtype} {tuple(probs.shape)}')
+    b, d = probs.shape
+    k = d.bit_length() - 1
+    if (1 << k) != d or k < 1 or k > COLLAPSE_MAX_BITS:
+        raise ValueError(f'{what}: {d} outcomes: 2**k with 1 <= k <= {COLLAPSE_MAX_BITS} is needed (all wires of a large '
+                         'register are measured with sample())')
+    if u is None and forced is None:
+        raise ValueError(f'{what}: u or forced is needed')
+    for name, t, dt in (('u', u, torch.float64), ('forced', forced, torch.int64)):
+        if t is not None and (t.shape != (b,) or t.dtype != dt or t.device != probs.device):
+            raise ValueError(f'{what}: {name} must be {dt} ({b},) on the device of probs, got {t.dtype} {tuple(t.shape)} on {t.device}')
+    fx, fz = _mask_table(fx, probs, k, 'fx'), _mask_table(fz, probs, k, 'fz')
+    probs = probs.contiguous()
+    u = None if u is None else u.contiguous()
+    forced = None if forced is None else forced.contiguous()
+    rec = CollapseRec(torch.zeros(b, 5, dtype=torch.int64, device=probs.device), fx is not None)
+    if not _use_hip(probs):
+        return _diag_double(lambda: _measure_draw_double(probs, u, forced, fx, fz, rec))
+    for lo, hi in _slices(b, 65535):                         # (one workgroup per sample)
+        rc = _lib.load().dq_measure_draw(_ptr(probs, lo), _ptr(u, lo), _ptr(forced, lo), _ptr(fx), _ptr(fz), k, hi - lo,
+                                         _ptr(rec.data, lo), _stream(probs))
+        _lib.check(rc, 'dq_measure_draw')
+    return rec
+
+
+def _measure_draw_double(probs, u, forced, fx, fz, rec):
+    draw = _sample_indices_double(probs, (torch.zeros_like(probs[:, 0]) if u is None else u)[:, None])[:, 0]
+    want = torch.full_like(draw, -1) if forced is None else forced
+    o = torch.where(want >= 0, want & (probs.shape[1] - 1), draw)
+    po = torch.gather(probs, 1, o[:, None])[:, 0]
+    total = probs.sum(-1)
+    live = (po > 0) & (total > 0) & (want < probs.shape[1])
+    one = torch.ones_like(po)
+    rec.data[:, 0] = o
+    if fx is not None:
+        rec.data[:, 1] = fx[o]
+    if fz is not None:
+        rec.data[:, 2] = fz[o]
+    rec.scale.copy_(torch.where(live, torch.where(live, po, one) ** -0.5, 0 * one))
+    rec.prob.copy_(torch.where(live, po / torch.where(total > 0, total, one), 0 * one))
+    return rec
+
+
+def collapse(state: torch.Tensor, bits: Sequence[int], rec: CollapseRec, layout: str = 'full', transpose: bool = False,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+    """``X^x Z^z P_o``, scaled, every sample b by its own ``rec`` = (o, x, z, s), in one write of the output and 1 / 2^k of
+    a read (``dq_apply_collapse_*``).  ``bits[0]`` is the most significant bit of the outcome, as in :func:`marginal`;
+    ``sigma(i) = (-1)^popcount(i & z)``: Z acts first, then X, no phase -- a Y is both bits set.
+
+    ``layout='full'``: ``out[b, j] = s sigma(j ^ x) state[b, j ^ x]`` where the measured bits of ``j ^ x`` spell o, else 0.
+    ``layout='drop'``: the measured bits are squeezed out, (B, 2^n) -> (B, 2^(n-k)); the bits of x on measured wires are
+    ignored; at least one wire must stay.  ``transpose``: the transpose of the same real-entried map -- for ``'drop'``
+    the expansion (B, 2^(n-k)) -> (B, 2^n) with zeros outside the kept slice.  Signs are exact and the scale is one
+    multiplication in the state's precision.  ``out`` may be ``state`` only for ``'full'`` with a ``rec`` made without
+    an x table."""
+    what = 'collapse'
+    if layout not in ('full', 'drop'):
+        raise ValueError(f"{what}: layout must be 'full' or 'drop', got {layout!r}")
+    if not isinstance(rec, CollapseRec):
+        raise ValueError(f'{what}: rec must be a backend.CollapseRec, got {type(rec).__name__}')
+    bits = [int(b) for b in bits]
+    k = len(bits)
+    expand = layout == 'drop' and bool(transpose)
+    n = _nqubit(state) + (k if expand else 0)
+    if not state.is_contiguous():
+        raise ValueError(f'{what}: state must be contiguous')
+    if k < 1 or k > COLLAPSE_MAX_BITS:
+        raise ValueError(f'{what}: {k} measured bits: 1 to {COLLAPSE_MAX_BITS} are supported (all wires of a large register are '
+                         'measured with sample())')
+    if not _distinct_positions(bits, n):
+        raise ValueError(f'{what}: bits {bits} must be distinct positions in [0, {n})')
+    if layout == 'drop' and k == n:
+        raise ValueError(f"{what}: layout='drop' of all {n} wires leaves no state")
+    batch = state.shape[0]
+    if rec.data.shape != (batch, 5) or rec.data.device != state.device:
+        raise ValueError(f'{what}: rec holds {rec.data.shape[0]} records on {rec.data.device}, the state {batch} samples on {state.device}')
+    nout = n - k if layout == 'drop' and not transpose else n
+    out = _check_out(state, out, what, in_place=layout == 'full' and not rec.has_x, shape=(batch, 1 << nout))
+    if not _use_hip(state):
+        _suffix(state)
+        return _diag_double(lambda: _collapse_double(state, n, bits, rec, layout, bool(transpose), out))
+    code = _lib.COLLAPSE_FULL if layout == 'full' else _lib.COLLAPSE_DROP
+    for lo, hi in _slices(batch):
+        _call('dq_apply_collapse', state, _ptr(state, lo), _ptr(out, lo), _ptr(rec.data, lo), n, _lib.int_array(bits), k, code,
+              int(bool(transpose)), int(rec.has_x), hi - lo)
+    return out
+
+
+def _bit_parity(v: torch.Tensor) -> torch.Tensor:
+    for sh in (32, 16, 8, 4, 2, 1):
+        v = v ^ (v >> sh)
+    return v & 1
+
+
+def _collapse_double(state, n, bits, rec, layout, transpose, out):
+    """The four maps of ``collapse`` as they are defined, in complex128 torch (CPU test double only)."""
+    k = len(bits)
+    kept = [p for p in range(n - 1, -1, -1) if p not in bits]           # ext(): the kept positions, high to low
+    full = (1 << n) - 1
+    meas = sum(1 << p for p in bits)
+    o, s = rec.outcome[:, None], rec.scale[:, None]
+    x = (rec.xmask[:, None] & full) if rec.has_x else torch.zeros_like(o)
+    z = rec.zmask[:, None] & full
+    idx = torch.arange(1 << n, device=state.device)[None]
+
+    def sub(i, positions):
+        r = torch.zeros_like(i)
+        for j, p in enumerate(positions):
+            r |= ((i >> p) & 1) << (len(positions) - 1 - j)
+        return r
+
+    wide = state.to(torch.complex128)
+    if layout == 'full':
+        src = idx ^ x
+        at = idx if transpose else src                                  # the index of the input basis that P and Z see
+        val = torch.where(sub(at, bits) == o, (1 - 2 * _bit_parity(at & z)) * s * torch.gather(wide, 1, src), 0)
+    elif transpose:
+        val = torch.where(sub(idx, bits) == o, (1 - 2 * _bit_parity(idx & z)) * s * torch.gather(wide, 1, sub(idx ^ x, kept)), 0)
+    else:
+        keep = sub(idx, bits) == o                                      # (B, 2^n): 2^(n-k) kept indices per sample, ascending
+        i = idx.expand(state.shape[0], -1)[keep].reshape(state.shape[0], -1)
+        t = sub(i ^ (x & ~meas), kept)
+        val = torch.zeros(state.shape[0], 1 << (n - k), dtype=torch.complex128, device=state.device)
+        val.scatter_(1, t, (1 - 2 * _bit_parity(i & z)) * s * torch.gather(wide, 1, i))
+    out.copy_(val.to(state.dtype))
+    return out

@@ -27,7 +27,7 @@ from torch import nn
 
 from . import _functorch, executor, ops, qmath
 from .gate import (
-    CNOT, Barrier, CostPhase, DiagonalGate, ExcitationGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, MultiplexedGate, MultiplexedRotation, PauliEvolution,
+    CNOT, Barrier, CostPhase, DiagonalGate, ExcitationGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, Measure, MultiplexedGate, MultiplexedRotation, PauliEvolution,
     PauliRot, PauliX, PauliY, PauliZ, PermutationGate, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
     TDaggerGate, TGate, Toffoli, U3Gate, UAnyGate,
 )
@@ -153,7 +153,7 @@ class QubitCircuit(Operation):
 
     def _run_operators(self, flat: torch.Tensor, zero: bool = False) -> torch.Tensor:
         """All operators on a (B, 2**n) state: maximal stretches of gates go to the executor (fused passes),
-        the operations that run through ``apply_flat`` (``Reset``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``, ``ExcitationGate``, ``SelectPauli``, ``QFTGate``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
+        the operations that run through ``apply_flat`` (``Reset``, ``Measure``, ``DiagonalGate``, ``CostPhase``, ``PauliRot``, ``PauliEvolution``, ``PermutationGate``, ``MultiplexedGate``, ``MultiplexedRotation``, ``ExcitationGate``, ``SelectPauli``, ``QFTGate``) run between them.  ``zero``: ``flat`` is |0..0> (vec |0..0><0..0| of a
         density matrix alike: index 0 is 1, everything else 0)."""
         if self.den_mat:
             prims = []
@@ -1052,6 +1052,26 @@ class QubitCircuit(Operation):
         """Add a reset operation (reference: circuit.py:1603-1607)."""
         assert not self.den_mat and not self.mps, 'Currently NOT supported'
         self.add(Reset(nqubit=self.nqubit, wires=wires, postselect=postselect))
+
+    def mid_measure(self, wires=None, postselect=None, reset=False, correct=None, generator=None):
+        """Measure ``wires`` in the middle of the circuit, every sample of a batch on its own, and apply the Pauli
+        correction ``correct`` assigns to the outcome (:class:`Measure`); ``reset=True`` returns the measured wires to |0>.
+        After a forward, :attr:`outcomes` and :attr:`outcome_probs` hold what was seen."""
+        if self.den_mat or self.mps:
+            Measure._refuse('den_mat=True (density matrices)' if self.den_mat else 'MPS (matrix product states)')
+        self.add(Measure(nqubit=self.nqubit, wires=wires, postselect=postselect, reset=reset, correct=correct,
+                         generator=generator))
+
+    @property
+    def outcomes(self) -> list:
+        """Per :class:`Measure` of the circuit, in circuit order: the int64 (B,) device tensor of the outcomes of the last
+        forward (``None`` before one)."""
+        return [op.outcome for op in self.operators if isinstance(op, Measure)]
+
+    @property
+    def outcome_probs(self) -> list:
+        """Per :class:`Measure`, in circuit order: the float64 (B,) device tensor of the probabilities its outcomes had."""
+        return [op.outcome_prob for op in self.operators if isinstance(op, Measure)]
 
     # explicitly out of scope -----------------------------------------------------------------------
     def _out_of_scope(self, *a, **k):

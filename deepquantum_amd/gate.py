@@ -1583,6 +1583,95 @@ class Reset(Gate):
         raise NotImplementedError('Reset is not unitary')
 
 
+class Measure(Gate):
+    r"""Mid-circuit measurement of ``wires`` in the computational basis with Pauli feed-forward.
+
+    Every sample of the batch draws its own outcome from its marginal distribution, is projected on it and renormalised,
+    and gets the correction that ``correct`` assigns to that outcome -- all on the device, in one pass over the state
+    (``qmath.collapse_tables`` has the spelling of ``correct``; the operator applied is exactly :math:`X^x Z^z`, Z first,
+    no phase: a ``'y'`` acts as :math:`XZ = -iY`).  ``reset=True`` also flips the measured wires back to
+    :math:`|0..0\rangle`.  ``postselect`` -- an int or a bit string over the wires in ascending order -- forces the
+    outcome; one of probability 0 leaves a zero state.  After a forward, ``outcome`` (int64) and ``outcome_prob`` (float64)
+    hold one value per sample as device tensors.  The gate depends on the state, so a circuit runs it between two fused
+    stretches, as it runs ``Reset``.  The uniforms come from ``torch.rand`` on the state's device (``generator``)."""
+
+    _state_dependent = True
+
+    def __init__(self, nqubit=1, wires=None, postselect=None, reset=False, correct=None, generator=None, den_mat=False,
+                 tsr_mode=False):
+        from . import qmath
+
+        if den_mat:
+            self._refuse('den_mat=True (density matrices)')
+        if wires is None:
+            wires = list(range(nqubit))
+        wires = sorted(qmath._wire_list(wires, nqubit, 'Measure'))
+        super().__init__(name='Measure', nqubit=nqubit, wires=wires, tsr_mode=tsr_mode)
+        self.postselect = None if postselect is None else qmath._outcome_key(postselect, len(wires), 'Measure')
+        self.reset, self.generator = bool(reset), generator
+        self.fx, self.fz = qmath.collapse_tables(nqubit, wires, correct, reset, 'Measure')
+        self.outcome = self.outcome_prob = None
+        self._tables: dict = {}
+
+    @staticmethod
+    def _refuse(what: str):
+        raise NotImplementedError(f'Measure: {what} is not supported (a mid-circuit measurement collapses a state vector on '
+                                  'one device, sample by sample)')
+
+    def _device_tables(self, device: torch.device):
+        if device not in self._tables:
+            self._tables[device] = tuple(None if t is None else torch.tensor(t, dtype=torch.int64, device=device)
+                                         for t in (self.fx, self.fz))
+        return self._tables[device]
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import qmath
+
+        if not x.is_contiguous():
+            x = x.contiguous()
+        forced = None
+        if self.postselect is not None:
+            forced = torch.full((x.shape[0],), self.postselect, dtype=torch.int64, device=x.device)
+        fx, fz = self._device_tables(x.device)
+        out, self.outcome, self.outcome_prob = qmath._collapse_flat(x, self.nqubit, self.wires, forced, self.generator, False,
+                                                                    fx, fz)
+        return out
+
+    def op_state(self, x: torch.Tensor) -> torch.Tensor:
+        shape = x.shape
+        return self.apply_flat(x.reshape(shape[0], -1)).reshape(shape)
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d['_tables'], d['outcome'], d['outcome_prob'] = {}, None, None
+        return d
+
+    def prims(self, decompose: bool = True) -> list[Prim]:
+        self._refuse('a matrix primitive -- get_unitary(), fused passes, DistributedQubitCircuit (sharded states) --')
+
+    def dm_prims(self, decompose: bool = True) -> list[Prim]:
+        self._refuse('den_mat=True (density matrices)')
+
+    def op_den_mat(self, x: torch.Tensor) -> torch.Tensor:
+        self._refuse('den_mat=True (density matrices)')
+
+    def op_dist_state(self, x):
+        self._refuse('DistributedQubitCircuit (a sharded state)')
+
+    def op_mps(self, x):
+        self._refuse('MPS (matrix product states)')
+
+    def inverse(self):
+        self._refuse('inverse() (a measurement is not invertible)')
+
+    def get_unitary(self) -> torch.Tensor:
+        self._refuse('get_unitary() (a measurement is not unitary)')
+
+    def extra_repr(self) -> str:
+        return f'wires={self.wires}, postselect={self.postselect}, reset={self.reset}'
+
+
 class Barrier(Gate):
     """No-op separator (reference: gate.py:3097-3126)."""
 

@@ -1795,3 +1795,70 @@ def combine(states: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
     if coef.ndim != 2 or coef.shape[1] != states.shape[0]:
         raise ValueError(f'combine: coef must have shape (M, {states.shape[0]}) for {states.shape[0]} states, got {tuple(coef.shape)}')
     return _Combine.apply(states, coef.to(torch.complex128))
+
+
+# ---- mid-circuit measurement: the collapse onto per-sample outcomes (csrc/dq_collapse.hip) ---------------------------------
+# y_b = s_b X^x_b Z^z_b P_o_b x_b is linear in the state with real entries: one operation closed under differentiation.
+# The cotangent of the state is the same node with ``transpose`` toggled (for layout 'drop' that is the expansion
+# 2^(n-k) -> 2^n); the cotangent of the real scale is Re <A x_b, gy_b> with A the map at scale 1 -- the node again and the
+# differentiable inner product -- which is Re <y_b, gy_b> / s_b without the division that an outcome of probability 0
+# (s = 0) would trip over.  Outcomes and masks are integers: constants.
+def _no_transform(what: str, transform: str):
+    raise RuntimeError(f'deepquantum_amd: {what} under {transform} is not supported yet: the samples of a batch collapse onto '
+                       'their own outcomes inside one launch; call it on the whole batch and differentiate in reverse mode')
+
+
+class _Collapse(torch.autograd.Function):
+    """y = s A x (A = X^x Z^z P_o per sample, or its transpose): gx = the transposed node on gy, gs = Re <A x, gy>."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, scale: torch.Tensor, outcome: torch.Tensor, xmask, zmask, bits: tuple, layout: str,
+                transpose: bool) -> torch.Tensor:
+        rec = backend.collapse_rec(outcome, _plain(scale).detach().to(torch.float64), xmask, zmask)
+        return backend.collapse(_kernel_arg(state), bits, rec, layout, transpose)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, scale, outcome, xmask, zmask, ctx.bits, ctx.layout, ctx.transpose = inputs
+        ctx.masks = (xmask, zmask)
+        ctx.save_for_backward(state, scale, outcome)
+
+    @staticmethod
+    def jvp(ctx, *_):
+        _no_transform('collapse', 'forward-mode differentiation (torch.func.jvp / jacfwd, forward_ad)')
+
+    @staticmethod
+    def vmap(info, in_dims, *_):
+        _no_transform('collapse', 'torch.vmap')
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, scale, outcome = ctx.saved_tensors
+        xmask, zmask = ctx.masks
+        gy = _flat_arg(gy)
+        gstate = gscale = None
+        if ctx.needs_input_grad[0]:
+            gstate = _Collapse.apply(gy, scale, outcome, xmask, zmask, ctx.bits, ctx.layout, not ctx.transpose)
+        if ctx.needs_input_grad[1]:
+            unit = _Collapse.apply(state, torch.ones_like(scale), outcome, xmask, zmask, ctx.bits, ctx.layout, ctx.transpose)
+            gscale = pauli_cross(unit, gy, 0, 0).real.to(scale.dtype)
+        return gstate, gscale, None, None, None, None, None, None
+
+
+def collapse(state: torch.Tensor, bits: Sequence[int], outcome: torch.Tensor, scale: torch.Tensor, xmask: torch.Tensor | None = None,
+             zmask: torch.Tensor | None = None, layout: str = 'full', transpose: bool = False) -> torch.Tensor:
+    """Differentiable (to any order, in the state and in the real per-sample ``scale``) collapse of a (B, 2**n) state:
+    sample b is projected on the value ``outcome[b]`` of the index bits ``bits`` (``bits[0]`` = its most significant
+    bit), multiplied by ``scale[b]`` and corrected by ``X^xmask[b] Z^zmask[b]`` (Z first, no phase; int64 masks over the
+    index bits).  ``layout='drop'`` squeezes the measured bits out; ``transpose`` applies the transposed map
+    (``backend.collapse`` has the formulas).  One write of the output and 1 / 2^k of a read.  Not under vmap or
+    forward-mode transforms.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    _no_legacy(state, scale)
+    for t in (state, scale):
+        if _is_batched(t):
+            _no_transform('collapse', 'torch.vmap')
+    if not isinstance(scale, torch.Tensor) or scale.is_complex() or scale.shape != outcome.shape:
+        raise ValueError('collapse: scale must be a real (B,) tensor, one value per sample')
+    bits, _ = _bit_args(bits, ())
+    return _Collapse.apply(_flat_arg(state), scale, outcome, xmask, zmask, bits, str(layout), bool(transpose))

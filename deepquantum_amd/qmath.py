@@ -878,3 +878,124 @@ def density_matrix_rdm(rho: torch.Tensor, nqubit: int, wires: list[int]) -> torc
         red = red.reshape([b] + [2] * (2 * k)).permute([0] + [1 + p for p in perm] + [1 + k + p for p in perm])
         red = red.reshape(b, 1 << k, 1 << k)
     return red.squeeze(0) if single else red
+
+
+# ---- mid-circuit measurement (csrc/dq_collapse.hip) ---------------------------------------------------------------------
+def _outcome_key(key: Any, k: int, what: str) -> int:
+    """An outcome given as an int or as a bit string over the measured wires in ascending wire order."""
+    if isinstance(key, str):
+        if len(key) != k or set(key) - set('01'):
+            raise ValueError(f'{what}: the outcome {key!r} is not a string of {k} bits')
+        return int(key, 2)
+    if isinstance(key, bool) or not isinstance(key, int) or key < 0 or key >= (1 << k):
+        raise ValueError(f'{what}: the outcome {key!r} is not an int in [0, {1 << k}) nor a bit string')
+    return key
+
+
+def collapse_tables(nqubit: int, wires: list[int], correct: Any = None, reset: bool = False,
+                    what: str = 'collapse_tables') -> tuple[list[int] | None, list[int] | None]:
+    """The feed-forward of a measurement of ``wires`` (ascending) compiled on the host: ``(fx, fz)``, each a list of 2^k
+    masks over the index bits by outcome, or ``None`` where every mask is 0.  ``correct`` is a dict from outcome (int or
+    bit string over the wires) to a Pauli string in ``PauliSum``'s spelling (``'x2z3'``), or a callable from the outcome
+    (an int) to such a string (or ``None`` / ``''``: nothing).  The operator applied is exactly ``X^x Z^z`` -- Z first, no
+    phase; a ``'y'`` sets both bits, i.e. acts as ``X Z = -i Y``.  ``reset`` ors the measured pattern into ``fx`` so that
+    the measured wires leave in |0..0>."""
+    import re
+
+    n, k = int(nqubit), len(wires)
+    if k > backend.COLLAPSE_MAX_BITS:
+        raise ValueError(f'{what}: {k} measured wires: at most {backend.COLLAPSE_MAX_BITS} (all wires of a large register are '
+                         'measured with sample())')
+    fx, fz = [0] * (1 << k), [0] * (1 << k)
+    if isinstance(correct, dict):
+        strings = {_outcome_key(key, k, what): s for key, s in correct.items()}
+    elif callable(correct):
+        strings = {o: correct(o) for o in range(1 << k)}
+    elif correct is None:
+        strings = {}
+    else:
+        raise ValueError(f'{what}: correct must be a dict or a callable from outcome to a Pauli string, got {type(correct).__name__}')
+    for o, s in strings.items():
+        if s is None:
+            continue
+        if not isinstance(s, str) or re.sub(r'[xyzXYZ]\d+', '', s).strip():
+            raise ValueError(f'{what}: the correction {s!r} of outcome {o} is not a Pauli string such as "x2z3"')
+        for p, w in re.findall(r'([xyzXYZ])(\d+)', s):
+            if int(w) >= n:
+                raise ValueError(f'{what}: the correction {s!r} has a wire outside [0, {n})')
+            bit = 1 << (n - 1 - int(w))
+            fx[o] ^= bit if p.lower() in 'xy' else 0
+            fz[o] ^= bit if p.lower() in 'yz' else 0
+    if reset:
+        for o in range(1 << k):
+            for j, w in enumerate(wires):
+                if (o >> (k - 1 - j)) & 1:
+                    fx[o] |= 1 << (n - 1 - w)
+    return (fx if any(fx) else None), (fz if any(fz) else None)
+
+
+def _collapse_flat(flat: torch.Tensor, n: int, wires: list[int], forced: torch.Tensor | None, generator, drop: bool,
+                   fx: torch.Tensor | None, fz: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """marginal -> draw -> collapse on a contiguous (B, 2**n) state; ``forced``: int64 (B,) or None; ``fx`` / ``fz``: device
+    tables.  Nothing is synchronised with the host."""
+    bits = [n - 1 - w for w in wires]
+    graph = torch.is_grad_enabled() and flat.requires_grad
+    if graph:
+        probs = ops.marginal(flat, bits)
+        table = probs.detach().to(torch.float64)
+    else:
+        table = backend.marginal(flat.detach(), bits)                   # (what ops.marginal runs, kept in float64)
+    u = None
+    if forced is None:
+        u = torch.rand(flat.shape[0], 1, dtype=torch.float64, device=flat.device, generator=generator)[:, 0]
+    rec = backend.measure_draw(table, u, forced, fx, fz)
+    layout = 'drop' if drop else 'full'
+    if not graph:
+        return backend.collapse(flat, bits, rec, layout), rec.outcome, rec.prob
+    # differentiated: the scale comes from the differentiable marginal, so the normalisation is differentiated too
+    po = torch.gather(probs, 1, rec.outcome[:, None])[:, 0]
+    live = rec.scale > 0
+    scale = torch.where(live, torch.where(live, po, torch.ones_like(po)) ** -0.5, torch.zeros_like(po))
+    out = ops.collapse(flat, bits, rec.outcome, scale, rec.xmask if fx is not None else None, rec.zmask if fz is not None else None,
+                       layout=layout)
+    return out, rec.outcome, rec.prob
+
+
+def collapse_state(state: torch.Tensor, nqubit: int, wires: int | list[int], outcome: Any = None,
+                   generator: torch.Generator | None = None, drop: bool = False, correct: Any = None,
+                   reset: bool = False) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Measure ``wires`` of a state vector in the computational basis and collapse it: ``(state, outcome, prob)``.
+
+    Every sample of a batch draws its own outcome from its marginal distribution (``ops.marginal``, then the draw kernel on
+    uniforms ``torch.rand(B, 1, dtype=float64, device=state.device, generator=generator)``, then one collapse pass:
+    ``backend.measure_draw`` / ``backend.collapse``), is projected on it and renormalised.  ``outcome`` -- an int, a bit
+    string over the wires in ascending wire order, or an int64 (B,) tensor -- post-selects; an outcome of probability 0
+    gives a zero state and ``prob = 0``, not an error.  ``drop=True`` returns the (B, 2**(n-k)) state of the other
+    wires; otherwise ``correct`` (see :func:`collapse_tables`) applies a Pauli correction chosen by the outcome and
+    ``reset=True`` leaves the measured wires in |0..0>.  ``outcome`` is int64 and ``prob`` float64, (B,) device tensors
+    (0-d for a single state): nothing is copied to the host.  With gradients enabled the result is differentiable in the
+    state, normalisation included."""
+    what = 'collapse_state'
+    flat, single = _state_batch(state, int(nqubit), what)
+    n = int(nqubit)
+    wires = sorted(_wire_list(wires, n, what))
+    k = len(wires)
+    if drop and k == n:
+        raise ValueError(f'{what}: drop=True with every wire measured leaves no state')
+    if drop and (correct is not None or reset):
+        raise ValueError(f'{what}: drop=True removes the measured wires: correct / reset act on a kept register (drop=False)')
+    if not flat.is_contiguous():
+        flat = flat.contiguous()
+    fx, fz = collapse_tables(n, wires, correct, reset, what)
+    dev = flat.device
+    fx = None if fx is None else torch.tensor(fx, dtype=torch.int64, device=dev)
+    fz = None if fz is None else torch.tensor(fz, dtype=torch.int64, device=dev)
+    forced = None
+    if isinstance(outcome, torch.Tensor):
+        if outcome.shape != (flat.shape[0],) or outcome.dtype != torch.int64:
+            raise ValueError(f'{what}: a tensor of outcomes must be int64 ({flat.shape[0]},), got {outcome.dtype} {tuple(outcome.shape)}')
+        forced = outcome.to(dev)
+    elif outcome is not None:
+        forced = torch.full((flat.shape[0],), _outcome_key(outcome, k, what), dtype=torch.int64, device=dev)
+    out, o, p = _collapse_flat(flat, n, wires, forced, generator, bool(drop), fx, fz)
+    return (out[0], o[0], p[0]) if single else (out, o, p)

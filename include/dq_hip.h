@@ -963,6 +963,51 @@ int dq_pauli_terms_cross_c128(const void* bra, const void* ket, const uint64_t* 
                               const double* weights, int ngroups, int nterms, int n, int64_t batch, double* out, void* ws,
                               int64_t ws_bytes, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 18. Mid-circuit measurement with Pauli feed-forward (csrc/dq_collapse.hip; added within ABI 30, presence is checked by
+ *     symbol).  bits[0..k) are distinct index-bit positions, bits[0] the most significant bit of the outcome, as in
+ *     dq_marginal_*:  sub(i) = sum_j bit_{bits[j]}(i) << (k - 1 - j);  scatter(o) = the index with o's bits at `bits`
+ *     and 0 elsewhere;  M = scatter(2^k - 1);  ext(i) = i with the measured bits squeezed out (n - k bits);
+ *     sigma(i) = (-1)^popcount(i & z).  1 <= k <= min(n, 20): a full-register measurement is dq_sample_*'s.
+ * ------------------------------------------------------------------------------------------ */
+/* What dq_measure_draw leaves per sample and dq_apply_collapse_* reads on the device. */
+typedef struct {
+    int64_t outcome;  /* in [0, 2^k) */
+    uint64_t xmask;   /* X^x and Z^z over the n index bits, Z first, no phase: a Y sets its bit in both */
+    uint64_t zmask;
+    double scale;     /* probs[outcome]^(-1/2); 0 for an outcome of probability 0 */
+    double prob;      /* probs[outcome] / sum(probs) */
+} DqCollapseRec;
+/* sizeof(DqCollapseRec), then the offsets of outcome, xmask, zmask, scale, prob -- at most `max` values written to
+ * `out`; returns how many there are (dq_struct_layout's service for this struct; that function's own list is pinned). */
+int dq_collapse_rec_layout(int* out, int max);
+/* rec[b] from the marginal table of sample b.  probs = DEVICE double [batch][2^k] as dq_marginal_* writes it (it need
+ * not be normalised), u = DEVICE double [batch] in [0, 1), forced = DEVICE int64 [batch] or NULL (an entry < 0: draw),
+ * fx / fz = DEVICE uint64 [2^k] or NULL (masks of the correction by outcome; NULL: 0).  With T = sum_o probs[b, o] and
+ * C the running sum in double, outcome = the smallest o with C(o) > u[b] * T; an outcome with probs == 0 is never drawn
+ * and the result is in [0, 2^k) whatever the rounding; every sum in a fixed order, bitwise reproducible.  A forced
+ * outcome is cut to its k low bits; one of probability 0 (or beyond 2^k) gives scale = 0 and prob = 0 -- a zero state, no
+ * error -- and so does a table of zeros.  u may be NULL where forced is given: an entry < 0 then draws with u = 0.
+ * One workgroup per sample, no host synchronisation (capturable).  1 <= batch <= 65535, pointers 8-byte aligned. */
+int dq_measure_draw(const double* probs, const double* u, const int64_t* forced, const uint64_t* fx, const uint64_t* fz, int k,
+                    int64_t batch, void* rec, dq_stream_t stream);
+typedef enum { DQ_COLLAPSE_FULL = 0, DQ_COLLAPSE_DROP = 1 } DqCollapseLayout;
+/* X^x Z^z P_o, scaled, every sample by its own rec[b] = (o, x, z, s):
+ *   FULL  (in, out: 2^n per sample)    out[b, j] = s sigma(j ^ x) in[b, j ^ x]  where sub(j ^ x) == o, else 0
+ *   DROP  (out: 2^(n-k) per sample)    out[b, t] = s sigma(i) in[b, i], i the kept index with ext(i ^ (x & ~M)) == t
+ *                                      (x & M is ignored); k < n
+ *   transpose != 0: the transpose of the same real-entried map (what a backward pass runs):
+ *   FULL                               out[b, i] = s sigma(i) in[b, i ^ x]  where sub(i) == o, else 0
+ *   DROP  (in: 2^(n-k), out: 2^n)      out[b, i] = s sigma(i) in[b, ext(i ^ x)]  where sub(i) == o, else 0
+ * Signs are flipped bit for bit and the scale is one multiplication by s rounded to the state's real precision; what is
+ * outside the kept slice is +0.  One write of the output and 1 / 2^k of a read.  may_flip == 0: the caller promises
+ * x == 0 and xmask is not read; only then, and only for FULL, in == out is allowed -- any other overlap of in, out and
+ * rec is DQ_ERR_ARG.  1 <= n <= 40, 1 <= batch <= 65535, in and out 16-byte aligned. */
+int dq_apply_collapse_c64(const void* in, void* out, const void* rec, int n, const int* bits, int k, int layout, int transpose,
+                          int may_flip, int64_t batch, dq_stream_t stream);
+int dq_apply_collapse_c128(const void* in, void* out, const void* rec, int n, const int* bits, int k, int layout, int transpose,
+                           int may_flip, int64_t batch, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
