@@ -3,20 +3,23 @@
 Every function takes PyTorch tensors (device memory owned by the caller), checks shapes on the host the
 way the reference asserts them (operation.py:91-107, 285-288), and enqueues the matching libdqhip call
 on ``torch.cuda.current_stream()``.  CUDA (= HIP on ROCm) tensors are required: a CPU tensor raises
-``RuntimeError`` -- there is no CPU fallback in the product.  The unit tests that exercise host logic
-without a GPU install an explicit test double with :func:`set_test_backend` (it lives under ``tests/``
-and is built on the oracle); the package itself never imports ``oracle/``.
+``RuntimeError`` -- the package has no CPU fallback.  The unit tests that exercise host logic without a
+GPU install an explicit test double with :func:`set_test_backend`.  Only then does a CPU tensor get through:
+the gate, fused-pass and reduction entry points call the double itself (it lives under ``tests/`` and is
+built on the oracle; the package never imports ``oracle/``), the streaming primitives from ``apply_diag``
+onward their contract as ``_standin.py`` writes it down in plain complex128 torch (:func:`_stand`).
 """
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Any, NamedTuple, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, _standin
 
 _test_backend: Any = None
 
@@ -39,13 +42,8 @@ class _NoGraph:
             for a in list(args) + list(kwargs.values()):      # (what `_ptr` refuses, the double refuses)
                 if isinstance(a, torch.Tensor) and (a.is_conj() or a.is_neg()):
                     raise ValueError('tensor with a pending conjugation / negation: resolve_conj() / resolve_neg() it first')
-            was = torch._C._is_fwd_grad_enabled()
-            torch._C._set_fwd_grad_enabled(False)
-            try:
-                with torch.no_grad():
-                    return attr(*args, **kwargs)
-            finally:
-                torch._C._set_fwd_grad_enabled(was)
+            with _standin.no_graph():
+                return attr(*args, **kwargs)
 
         return call
 
@@ -77,6 +75,12 @@ def _use_hip(t: torch.Tensor) -> bool:
         'deepquantum_amd: statevector kernels run on MI355X only; got a tensor on '
         f'{t.device}. Move the circuit/state to "cuda" (there is no CPU fallback).'
     )
+
+
+def _stand(name: str, *args):
+    """The stand-in of entry point ``name``, looked up when called, where ``_use_hip`` has said no: no graph, no tangent."""
+    with _standin.no_graph():
+        return getattr(_standin, name)(*args)
 
 
 def _stream(t: torch.Tensor) -> C.c_void_p:
@@ -417,8 +421,7 @@ def scale_z_signs(state: torch.Tensor, zmasks: Sequence[int], coef: torch.Tensor
     """(sum_k coef[b, k] Z-string_k) |psi_b>: (B, 2**n) in the state's dtype; coef real (B, K)."""
     n = _nqubit(state)
     if not _use_hip(state):
-        with torch.no_grad():
-            return _scale_z_signs_double(state, zmasks, coef, n)
+        return _stand('scale_z_signs', state, zmasks, coef, n)
     if state.dtype == torch.complex64 and len(zmasks) > 32:
         return _scale_z_signs_wide(state, zmasks, coef, n)      # (several launches: their sum is formed in double)
     fn = getattr(_lib.load(), f'dq_scale_zsigns_{_suffix(state)}')
@@ -431,19 +434,6 @@ def scale_z_signs(state: torch.Tensor, zmasks: Sequence[int], coef: torch.Tensor
         _lib.check(rc, 'dq_scale_zsigns')
         out = part if out is None else out.add_(part)
     return out
-
-
-def _scale_z_signs_double(state, zmasks, coef, n):
-    """``scale_z_signs`` for the CPU test double (tests only)."""
-    i = torch.arange(1 << n)
-    w = torch.zeros(state.shape[0], 1 << n, dtype=torch.float64)
-    for k, z in enumerate(zmasks):
-        par = torch.zeros_like(i)
-        for p in range(n):
-            if (z >> p) & 1:
-                par ^= (i >> p) & 1
-        w += coef[:, k : k + 1].to(torch.float64) * (1 - 2 * par).to(torch.float64)
-    return (state * w.to(state.real.dtype)).contiguous()
 
 
 def inner(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
@@ -807,8 +797,7 @@ def sample_indices(state: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
                          f'{u.dtype} {tuple(u.shape)} on {u.device}')
     if not _use_hip(state):
         _suffix(state)
-        with torch.no_grad():
-            return _sample_indices_double(state, u)
+        return _stand('sample_indices', state, u)
     u = u.contiguous()
     out = torch.empty(u.shape, dtype=torch.int64, device=state.device)
     for lo, hi in _slices(state.shape[0], 65535):            # (dq_sample_*'s limit on the batch)
@@ -819,21 +808,6 @@ def sample_indices(state: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
         pin_if_capturing(ws)
         _call('dq_sample', state, _ptr(state, lo), n, hi - lo, _ptr(u, lo), u.shape[1], _ptr(out, lo), _ptr(ws), nbytes)
     return out
-
-
-def _sample_indices_double(probs_or_state: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
-    """The contract of ``sample_indices`` in torch, for the CPU test double and for the (small) diagonal of a density
-    matrix: float64 ``cumsum`` + ``searchsorted(right=True)``, then the clamp onto the last entry of non-zero
-    probability.  A real input is taken as the probabilities, a complex one as amplitudes."""
-    if probs_or_state.is_complex():
-        p = probs_or_state.real.to(torch.float64) ** 2 + probs_or_state.imag.to(torch.float64) ** 2
-    else:
-        p = probs_or_state.to(torch.float64)
-    c = torch.cumsum(p, dim=-1)
-    idx = torch.searchsorted(c, (u * c[:, -1:]).contiguous(), right=True)
-    # the last index of non-zero probability == the number of entries below the total: nothing beyond it is returned
-    last = (c < c[:, -1:]).sum(-1, keepdim=True)
-    return torch.minimum(idx, last)
 
 
 _WIDE_BYTES = 256 << 20
@@ -853,10 +827,8 @@ def _scale_z_signs_wide(state: torch.Tensor, zmasks: Sequence[int], coef: torch.
     coef = coef.to(torch.float64).reshape(state.shape[0], k)
     if m < n:
         h = torch.arange(1 << (n - m), device=state.device)
-        par = torch.stack([h & (int(z) >> m) for z in zmasks], dim=1)
-        for sh in (32, 16, 8, 4, 2, 1):
-            par = par ^ (par >> sh)
-        coef = (coef[:, None, :] * (1 - 2 * (par & 1)).to(torch.float64)[None]).reshape(-1, k)
+        par = _standin.parity(torch.stack([h & (int(z) >> m) for z in zmasks], dim=1))
+        coef = (coef[:, None, :] * (1 - 2 * par).to(torch.float64)[None]).reshape(-1, k)
         zmasks = [int(z) & ((1 << m) - 1) for z in zmasks]
     out = torch.empty_like(state)
     src, dst = state.reshape(-1, 1 << m), out.view(-1, 1 << m)
@@ -907,17 +879,6 @@ def _diag_table(table: torch.Tensor, like: torch.Tensor, dtype: torch.dtype, k: 
     return _finish_table(table, like, dtype, what)
 
 
-def _sub_index(n: int, bits: Sequence[int], controls: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor]:
-    """sub(i) and the control test for every i (CPU test double only)."""
-    i = torch.arange(1 << n)
-    k = len(bits)
-    sub = torch.zeros_like(i)
-    for j, p in enumerate(bits):
-        sub |= ((i >> p) & 1) << (k - 1 - j)
-    cmask = sum(1 << c for c in controls)
-    return sub, (i & cmask) == cmask
-
-
 def apply_diag(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = (),
                out: torch.Tensor | None = None) -> torch.Tensor:
     """out[b, i] = diag[b, sub(i)] * state[b, i] on the amplitudes whose ``controls`` are all 1 (the others pass through):
@@ -928,31 +889,11 @@ def apply_diag(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], con
     diag = _diag_table(diag, state, state.dtype, k, 'apply_diag', True)
     out = _check_out(state, out, 'apply_diag')
     if not _use_hip(state):
-        return _diag_double(lambda: _apply_diag_double(state, diag, n, bits, controls, out))
+        return _stand('apply_diag', state, diag, n, bits, controls, out)
     stride = (1 << k) if (diag.ndim == 2 and diag.shape[0] > 1) else 0
     for lo, hi in _slices(state.shape[0]):
         _call('dq_apply_diag', state, _ptr(state, lo), _ptr(out, lo), _ptr(diag, lo if stride else 0), stride, n,
               _lib.int_array(bits), k, _lib.int_array(controls), len(controls), hi - lo)
-    return out
-
-
-def _diag_double(fn):
-    """The plain-torch complex128 stand-ins below, for the CPU test double (tests only): like the double itself
-    (``_NoGraph``) they build no graph and carry no forward-mode tangent."""
-    was = torch._C._is_fwd_grad_enabled()
-    torch._C._set_fwd_grad_enabled(False)
-    try:
-        with torch.no_grad():
-            return fn()
-    finally:
-        torch._C._set_fwd_grad_enabled(was)
-
-
-def _apply_diag_double(state, diag, n, bits, controls, out):
-    k = len(bits)
-    sub, ok = _sub_index(n, bits, controls)
-    f = diag.reshape(-1, 1 << k).to(torch.complex128)[:, sub]
-    out.copy_(torch.where(ok, f * state.to(torch.complex128), state.to(torch.complex128)).to(state.dtype))
     return out
 
 
@@ -982,18 +923,7 @@ def apply_cost(state: torch.Tensor, cost: torch.Tensor, par: torch.Tensor, bits:
         raise ValueError('apply_cost: the phase parameter is real')
     out = _check_out(state, out, 'apply_cost')
     if not _use_hip(state):
-        def double():
-            sub, ok = _sub_index(n, bits, controls)
-            c = cost.to(torch.float64)[sub]
-            x = state.to(torch.complex128)
-            if op == 'phase':
-                y = torch.where(ok, torch.exp(-1j * par.to(torch.float64).reshape(-1, 1) * c) * x, x)
-            else:
-                y = torch.where(ok, par.to(torch.complex128).reshape(-1, 1) * c * x, torch.zeros_like(x))
-            out.copy_(y.to(state.dtype))
-            return out
-
-        return _diag_double(double)
+        return _stand('apply_cost', state, cost, par, n, bits, controls, op, out)
     if op == 'phase':
         p = par.to(device=state.device, dtype=torch.float64).contiguous()
     else:
@@ -1027,12 +957,7 @@ def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: S
     _check_bra(bra, ket, 'cost_cross')
     cost = _diag_table(cost, ket, ket.real.dtype, k, 'cost_cross', False)
     if not _use_hip(ket):
-        def double():
-            sub, ok = _sub_index(n, bits, controls)
-            w = cost.to(torch.float64)[sub] * ok
-            return (w * bra.to(torch.complex128).conj() * ket.to(torch.complex128)).sum(dim=-1)
-
-        return _diag_double(double)
+        return _stand('cost_cross', bra, ket, cost, n, bits, controls)
     mid = (_ptr(cost), n, _lib.int_array(bits), k, _lib.int_array(controls), len(controls))
     return _cross_reduce('dq_cost_cross', 'dq_cost_cross_ws_bytes', bra, ket, mid)
 
@@ -1089,18 +1014,6 @@ def _real_angles(theta: torch.Tensor, state: torch.Tensor, what: str) -> torch.T
     return theta.to(device=state.device, dtype=torch.float64)
 
 
-def _pauli_gather(n: int, xmask: int, zmask: int, controls: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Source index i ^ x, factor i^ny (-1)^popc((i ^ x) & z) and the control test for every i (CPU test double only)."""
-    i = torch.arange(1 << n)
-    j = i ^ xmask
-    par = j & zmask
-    for sh in (32, 16, 8, 4, 2, 1):
-        par = par ^ (par >> sh)
-    factor = (1j ** (bin(xmask & zmask).count('1') % 4)) * (1 - 2 * (par & 1)).to(torch.complex128)
-    cmask = sum(1 << c for c in controls)
-    return j, factor, (i & cmask) == cmask
-
-
 def apply_pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, controls: Sequence[int] = (), mode: str = 'gate',
                       out: torch.Tensor | None = None) -> torch.Tensor:
     """out[b] = a[b] state[b] + c[b] P state[b] for the Pauli string P = (xmask, zmask) -- a Y sets its bit in both -- on
@@ -1117,14 +1030,7 @@ def apply_pauli_axpby(state: torch.Tensor, xmask: int, zmask: int, a, c, control
     a, c = _pauli_coef(a, state, 'apply_pauli_axpby'), _pauli_coef(c, state, 'apply_pauli_axpby')
     out = _check_out(state, out, 'apply_pauli_axpby')
     if not _use_hip(state):
-        def double():
-            j, factor, ok = _pauli_gather(n, xmask, zmask, controls)
-            x = state.to(torch.complex128)
-            y = a.reshape(-1, 1) * x + c.reshape(-1, 1) * factor * x[:, j]
-            out.copy_(torch.where(ok, y, x if mode == 'gate' else torch.zeros_like(x)).to(state.dtype))
-            return out
-
-        return _diag_double(double)
+        return _stand('apply_pauli_axpby', state, xmask, zmask, a, c, n, controls, mode, out)
     return _pauli_launch(state, out, xmask, zmask, _axpby_coef(a, c), _lib.PAULI_GATE if mode == 'gate' else _lib.PAULI_MAP, n, controls)
 
 
@@ -1157,11 +1063,7 @@ def pauli_cross(bra: torch.Tensor, ket: torch.Tensor, xmask: int, zmask: int, co
     n, xmask, zmask, controls = _pauli_args(ket, xmask, zmask, controls, 'pauli_cross')
     _check_bra(bra, ket, 'pauli_cross')
     if not _use_hip(ket):
-        def double():
-            j, factor, ok = _pauli_gather(n, xmask, zmask, controls)
-            return (ok * bra.to(torch.complex128).conj() * factor * ket.to(torch.complex128)[:, j]).sum(dim=-1)
-
-        return _diag_double(double)
+        return _stand('pauli_cross', bra, ket, xmask, zmask, n, controls)
     mid = (xmask, zmask, n, _lib.int_array(controls), len(controls))
     return _cross_reduce('dq_pauli_cross', 'dq_pauli_cross_ws_bytes', bra, ket, mid)
 
@@ -1209,22 +1111,10 @@ def apply_permutation(state: torch.Tensor, src: torch.Tensor, bits: Sequence[int
         raise ValueError(f"apply_permutation: path='local' needs every table bit below "
                          f'{permutation_local_bits(state.dtype)}, got {bits}')
     if not _use_hip(state):
-        return _diag_double(lambda: _apply_permutation_double(state, src, n, bits, controls, out))
+        return _stand('apply_permutation', state, src, n, bits, controls, out)
     for lo, hi in _slices(state.shape[0]):
         _call('dq_apply_permutation', state, _ptr(state, lo), _ptr(out, lo), _ptr(src), n, _lib.int_array(bits), k,
               _lib.int_array(controls), len(controls), hi - lo, PERM_PATHS[path])
-    return out
-
-
-def _apply_permutation_double(state, src, n, bits, controls, out):
-    k = len(bits)
-    sub, ok = _sub_index(n, bits, controls)
-    v = src.to(torch.int64)[sub] & ((1 << k) - 1)
-    i = torch.arange(1 << n)
-    index = i & ~sum(1 << p for p in bits)
-    for j, p in enumerate(bits):
-        index = index | (((v >> (k - 1 - j)) & 1) << p)
-    out.copy_(state[:, torch.where(ok, index, i)])
     return out
 
 
@@ -1312,25 +1202,10 @@ def apply_select_pauli(state: torch.Tensor, table_words: torch.Tensor, bits: Seq
     words = _select_words(table_words, state, k, what)
     out = _check_out(state, out, what, in_place=False)
     if not _use_hip(state):
-        return _diag_double(lambda: _apply_select_pauli_double(state, words, n, bits, controls, out))
+        return _stand('apply_select_pauli', state, words, n, bits, controls, out)
     for lo, hi in _slices(state.shape[0]):
         _call('dq_apply_select_pauli', state, _ptr(state, lo), _ptr(out, lo), _ptr(words), n, _lib.int_array(bits), k,
               _lib.int_array(controls), len(controls), hi - lo)
-    return out
-
-
-def _apply_select_pauli_double(state, words, n, bits, controls, out):
-    sub, ok = _sub_index(n, bits, controls)
-    i = torch.arange(1 << n)
-    free = ((1 << n) - 1) & ~sum(1 << p for p in [*bits, *controls])
-    w0, z = words[sub, 0], words[sub, 1]
-    j = i ^ (w0 & free)
-    par = torch.zeros_like(i)
-    for p in range(n):
-        par ^= ((j & z) >> p) & 1
-    q = torch.where(ok, ((w0 >> 62) + 2 * par) & 3, 0)
-    factor = torch.tensor([1, 1j, -1, -1j], dtype=state.dtype)[q]
-    out.copy_(state[:, torch.where(ok, j, i)] * factor)
     return out
 
 
@@ -1374,7 +1249,7 @@ def apply_qft(state: torch.Tensor, bits: Sequence[int], inverse: bool = False, s
     _suffix(state)
     out = _check_out(state, out, what)
     if not _use_hip(state):
-        return _diag_double(lambda: _apply_qft_double(state, n, bits, inverse, swaps, out))
+        return _stand('apply_qft', state, n, bits, inverse, swaps, out)
     c128 = int(state.dtype == torch.complex128)
     outside = bool(swaps) and _lib.load().dq_qft_passes(n, _lib.int_array(bits), m, c128) > 1
     flags = int(bool(inverse)) | (2 if swaps and not outside else 0)
@@ -1386,29 +1261,6 @@ def apply_qft(state: torch.Tensor, bits: Sequence[int], inverse: bool = False, s
         _call('dq_apply_qft', state, _ptr(src, lo), _ptr(dst, lo), n, _lib.int_array(bits), m, flags, hi - lo)
     if outside and not inverse:
         permute_bits(dst, _qft_reversal(n, bits), out=out)
-    return out
-
-
-def _apply_qft_double(state, n, bits, inverse, swaps, out):
-    m = len(bits)
-    rest = [p for p in range(n - 1, -1, -1) if p not in bits]
-    axis = lambda p: 1 + (n - 1 - p)                    # index bit p as an axis of the (B, 2, .., 2) view
-    x = state.to(torch.complex128).reshape(-1, *([2] * n))
-    order = [0] + [axis(p) for p in rest] + [axis(p) for p in bits]
-    x = x.permute(order).reshape(state.shape[0], 1 << (n - m), *([2] * m))
-    flip = lambda t: t.permute([0, 1] + list(range(m + 1, 1, -1)))
-    if not swaps and inverse:
-        x = flip(x)
-    x = x.reshape(state.shape[0], 1 << (n - m), 1 << m)
-    x = torch.fft.fft(x, dim=-1, norm='ortho') if inverse else torch.fft.ifft(x, dim=-1, norm='ortho')
-    x = x.reshape(state.shape[0], 1 << (n - m), *([2] * m))
-    if not swaps and not inverse:
-        x = flip(x)
-    x = x.reshape(state.shape[0], *([2] * n))
-    back = [0] * (n + 1)
-    for at, ax in enumerate(order):
-        back[ax] = at
-    out.copy_(x.permute(back).reshape(state.shape).to(state.dtype))
     return out
 
 
@@ -1457,29 +1309,10 @@ def apply_mux(state: torch.Tensor, table: torch.Tensor, kind: str, target: int, 
     table = _mux_table(table, state, kind, k, what)
     out = _check_out(state, out, what)
     if not _use_hip(state):
-        return _diag_double(lambda: _apply_mux_double(state, table, kind, n, target, bits, controls, bool(dagger), out))
+        return _stand('apply_mux', state, table, kind, n, target, bits, controls, bool(dagger), out)
     for lo, hi in _slices(state.shape[0]):
         _call('dq_apply_mux', state, _ptr(state, lo), _ptr(out, lo), _ptr(table), MUX_KINDS[kind], int(bool(dagger)), n,
               target, _lib.int_array(bits), k, _lib.int_array(controls), len(controls), hi - lo)
-    return out
-
-
-def _apply_mux_double(state, table, kind, n, target, bits, controls, dagger, out):
-    sub, ok = _sub_index(n, bits, controls)
-    if kind == 'ry':
-        c, s = table[:, 0].to(torch.complex128), table[:, 1].to(torch.complex128)
-        m = torch.stack([torch.stack([c, -s], -1), torch.stack([s, c], -1)], -2)
-    else:
-        m = table.to(torch.complex128)
-    if dagger:
-        m = m.mH.resolve_conj()
-    m = m[sub]                                          # (2^n, 2, 2)
-    i = torch.arange(1 << n)
-    x = state.to(torch.complex128)
-    x0, x1 = x[:, i & ~(1 << target)], x[:, i | (1 << target)]
-    t = (i >> target) & 1
-    row = m[i, t]                                       # (2^n, 2): the row of M that makes amplitude i
-    out.copy_(torch.where(ok, row[:, 0] * x0 + row[:, 1] * x1, x).to(state.dtype))
     return out
 
 
@@ -1501,7 +1334,7 @@ def mux_cross(bra: torch.Tensor, ket: torch.Tensor, axis: str, target: int, bits
     _suffix(ket)
     _check_bra(bra, ket, what)
     if not _use_hip(ket):
-        return _diag_double(lambda: _mux_cross_double(bra, ket, axis, n, target, bits, controls))
+        return _stand('mux_cross', bra, ket, axis, n, target, bits, controls)
     mid = (_lib.MUX_AXES[axis], n, target, _lib.int_array(bits), k, _lib.int_array(controls), len(controls))
     return _cross_reduce('dq_mux_cross', 'dq_mux_cross_ws_bytes', bra, ket, mid, (1 << k,), sizer_args=(k,))
 
@@ -1583,22 +1416,6 @@ def apply_mux_rot(state: torch.Tensor, theta, axis: str, target: int, bits: Sequ
     return _mux_launch(state, torch.stack([torch.cos(half), torch.sin(half)], dim=-1), 'ry', int(target), bits, controls)
 
 
-def _mux_cross_double(bra, ket, axis, n, target, bits, controls):
-    sub, ok = _sub_index(n, bits, controls)
-    i = torch.arange(1 << n)
-    v = ket.to(torch.complex128)
-    t = (i >> target) & 1
-    if axis in 'xy':
-        v = v[:, i ^ (1 << target)]
-    if axis == 'y':
-        v = v * (1j * (2 * t - 1)).to(torch.complex128)             # (Y v)_0 = -i v_1, (Y v)_1 = i v_0
-    elif axis == 'z':
-        v = v * (1 - 2 * t).to(torch.complex128)
-    terms = torch.where(ok, bra.to(torch.complex128).conj() * v, torch.zeros((), dtype=torch.complex128))
-    out = torch.zeros(ket.shape[0], 1 << len(bits), dtype=torch.complex128)
-    return out.index_add_(1, sub, terms)
-
-
 # ---------------------------------------------------------------------------------------------------
 # Excitation gates that touch only their subspace (csrc/dq_excite.hip).  A spec is (xmask, amask, zmask, negate) or
 # (xmask, amask, zmask, negate, controls) over index bits: for every i0 with i0 & xmask == amask inside the controls,
@@ -1619,18 +1436,6 @@ def _excite_args(state: torch.Tensor, spec, what: str) -> tuple[int, int, int, i
     if negate not in (0, 1):
         raise ValueError(f'{what}: negate must be 0 or 1, got {negate}')
     return n, xmask, amask, zmask, negate, controls
-
-
-def _excite_pairs(n: int, xmask: int, amask: int, zmask: int, negate: int, controls: Sequence[int]):
-    """i0, i1 and sigma of every pair (CPU test double only)."""
-    i = torch.arange(1 << n)
-    cmask = sum(1 << c for c in controls)
-    i0 = i[(i & (xmask | cmask)) == (amask | cmask)]
-    par = i0 & zmask
-    for sh in (32, 16, 8, 4, 2, 1):
-        par = par ^ (par >> sh)
-    sigma = (1 - 2 * ((par & 1) ^ negate)).to(torch.complex128)
-    return i0, i0 ^ xmask, sigma
 
 
 def apply_excite_axpby(state: torch.Tensor, spec, a, c, mode: str = 'gate', out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1661,14 +1466,7 @@ def apply_excite_axpby(state: torch.Tensor, spec, a, c, mode: str = 'gate', out:
     else:
         out.zero_()
     if not _use_hip(state):
-        def double():
-            i0, i1, sigma = _excite_pairs(n, xmask, amask, zmask, negate, controls)
-            x0, x1 = state[:, i0].to(torch.complex128), state[:, i1].to(torch.complex128)
-            out[:, i0] = (a.reshape(-1, 1) * x0 - c.reshape(-1, 1) * sigma * x1).to(state.dtype)
-            out[:, i1] = (a.reshape(-1, 1) * x1 + c.reshape(-1, 1) * sigma * x0).to(state.dtype)
-            return out
-
-        return _diag_double(double)
+        return _stand('apply_excite_axpby', state, out, a, c, n, xmask, amask, zmask, negate, controls)
     return _excite_launch(state, out, _axpby_coef(a, c), _lib.EXCITE_GATE if mode == 'gate' else _lib.EXCITE_MAP,
                           (xmask, amask, zmask, negate), n, controls)
 
@@ -1695,12 +1493,7 @@ def excite_cross(bra: torch.Tensor, ket: torch.Tensor, spec) -> torch.Tensor:
     n, xmask, amask, zmask, negate, controls = _excite_args(ket, spec, 'excite_cross')
     _check_bra(bra, ket, 'excite_cross')
     if not _use_hip(ket):
-        def double():
-            i0, i1, sigma = _excite_pairs(n, xmask, amask, zmask, negate, controls)
-            u, v = bra.to(torch.complex128).conj(), ket.to(torch.complex128)
-            return (sigma * (u[:, i1] * v[:, i0] - u[:, i0] * v[:, i1])).sum(dim=-1)
-
-        return _diag_double(double)
+        return _stand('excite_cross', bra, ket, n, xmask, amask, zmask, negate, controls)
     mid = (xmask, amask, zmask, negate, n, _lib.int_array(controls), len(controls))
     return _cross_reduce('dq_excite_cross', 'dq_excite_cross_ws_bytes', bra, ket, mid)
 
@@ -1781,22 +1574,6 @@ def _psum_args(state: torch.Tensor, table: PsumTable, what: str) -> int:
     return n
 
 
-def _psum_apply_double(x: torch.Tensor, table: PsumTable) -> torch.Tensor:
-    """H x in complex128, group by group (CPU test double only)."""
-    xmasks, bounds, zmasks, weights = (t.tolist() for t in table.on('cpu'))
-    j = torch.arange(x.shape[-1])
-    y = torch.zeros_like(x)
-    for g, xmask in enumerate(xmasks):
-        w = torch.zeros(x.shape[-1], dtype=torch.complex128)
-        for t in range(bounds[2 * g], bounds[2 * g + 2]):
-            par = j & zmasks[t]
-            for sh in (32, 16, 8, 4, 2, 1):
-                par = par ^ (par >> sh)
-            w += (weights[t] if t < bounds[2 * g + 1] else 1j * weights[t]) * (1 - 2 * (par & 1)).to(torch.complex128)
-        y += (w * x)[:, j ^ xmask]
-    return y
-
-
 def apply_psum_axpby(state: torch.Tensor, table: PsumTable, a, c, mode: str = 'gate', out: torch.Tensor | None = None) -> torch.Tensor:
     """out[b] = a[b] state[b] + c[b] H state[b] for the sum of Pauli strings H of ``table``, in one launch: G + 1 reads and
     one write of the state for G groups, whatever the number of strings (``dq_apply_psum_axpby_*``).  ``a``, ``c``:
@@ -1809,11 +1586,7 @@ def apply_psum_axpby(state: torch.Tensor, table: PsumTable, a, c, mode: str = 'g
     a, c = _pauli_coef(a, state, what), _pauli_coef(c, state, what)
     out = _check_out(state, out, what, in_place=False)
     if not _use_hip(state):
-        def double():
-            x = state.to(torch.complex128)
-            return out.copy_((a.reshape(-1, 1) * x + c.reshape(-1, 1) * _psum_apply_double(x, table)).to(state.dtype))
-
-        return _diag_double(double)
+        return _stand('apply_psum_axpby', state, table, a, c, out)
     coef = _axpby_coef(a, c)
     tail = table.tail(state.device)
     for lo, hi in _slices(state.shape[0]):
@@ -1829,7 +1602,7 @@ def psum_cross(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.
     _psum_args(ket, table, 'psum_cross')
     _check_bra(bra, ket, 'psum_cross')
     if not _use_hip(ket):
-        return _diag_double(lambda: (bra.to(torch.complex128).conj() * _psum_apply_double(ket.to(torch.complex128), table)).sum(dim=-1))
+        return _stand('psum_cross', bra, ket, table)
     return _cross_reduce('dq_psum_cross', 'dq_psum_cross_ws_bytes', bra, ket, table.tail(ket.device))
 
 
@@ -1866,23 +1639,6 @@ def _terms_pieces(table: PsumTable, cap: int) -> list[tuple[PsumTable, torch.Ten
     return cache[cap]
 
 
-def _terms_double(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.Tensor:
-    """What ``dq_pauli_terms_cross_*`` leaves for ``table``, in complex128 (CPU test double only)."""
-    xmasks, bounds, zmasks, weights = (t.tolist() for t in table.on('cpu'))
-    u, v = bra.to(torch.complex128).conj(), ket.to(torch.complex128)
-    i = torch.arange(v.shape[-1])
-    out = torch.empty(v.shape[0], table.nterms, dtype=torch.complex128)
-    for g, x in enumerate(xmasks):
-        p = u * v[:, i ^ x]
-        for t in range(bounds[2 * g], bounds[2 * g + 2]):
-            par = (i ^ x) & zmasks[t]
-            for sh in (32, 16, 8, 4, 2, 1):
-                par = par ^ (par >> sh)
-            c = math.copysign(1.0, weights[t]) * (1j if t >= bounds[2 * g + 1] else 1.0)
-            out[:, t] = c * (p * (1 - 2 * (par & 1)).to(torch.complex128)).sum(dim=-1)
-    return out
-
-
 def pauli_terms_cross(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) -> torch.Tensor:
     """out[b, t] = <bra[b]| P_t |ket[b]> for every string of ``table``, in table order (the order of ``PauliSum.terms``):
     complex128 (B, T), bitwise reproducible, one launch per ``pauli_terms_max()`` terms (``dq_pauli_terms_cross_*``) where
@@ -1895,13 +1651,12 @@ def pauli_terms_cross(bra: torch.Tensor, ket: torch.Tensor, table: PsumTable) ->
     parts = []
     for piece, sign in _terms_pieces(table, pauli_terms_max()):
         if not _use_hip(ket):
-            val = _diag_double(lambda: _terms_double(bra, ket, piece))
+            val = _stand('pauli_terms_cross', bra, ket, piece)
         else:
             val = _cross_reduce('dq_pauli_terms_cross', 'dq_pauli_terms_ws_bytes', bra, ket, piece.tail(ket.device),
                                 shape=(piece.nterms,), sizer_args=(piece.nterms,))
         parts.append(val * sign.to(val.device))
     return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
-
 
 
 # ---- exp(-i t H) for a Pauli sum: a Chebyshev expansion, one launch per order --------------------------------------------
@@ -2040,17 +1795,7 @@ def apply_psum_evolve(state: torch.Tensor, table: PsumTable, t, tol: float, out:
         c0 = torch.tensor([r[0] for r in coefs], dtype=torch.complex128).to(device=state.device, dtype=state.dtype)
         torch.mul(state, c0.reshape(-1, 1), out=out)
     elif not hip:
-        def double():
-            x = state.to(torch.complex128)
-            c = torch.tensor(coefs, dtype=torch.complex128)             # (B, K + 1)
-            prev, cur = x, (_psum_apply_double(x, table) - b * x) / a
-            acc = c[:, 0:1] * prev + c[:, 1:2] * cur
-            for k in range(2, order + 1):
-                prev, cur = cur, (2.0 / a) * _psum_apply_double(cur, table) - (2.0 * b / a) * cur - prev
-                acc = acc + c[:, k:k + 1] * cur
-            return out.copy_(acc.to(state.dtype))
-
-        _diag_double(double)
+        _stand('psum_evolve', state, table, coefs, order, a, b, out)
     else:
         # ONE host tensor, one copy: [B][4] for phi_1 = -b/a psi + 1/a H psi, [B][2] c_0, [B][2] c_1, then [K - 1][B][5]
         # rows (alpha, beta, gamma, Re c_k, Im c_k) = (2/a, -2b/a, -1, c_k) for the orders 2 .. K
@@ -2157,50 +1902,6 @@ class _LanczosHip:
         self.update(torch.zeros_like(self.start) if self.prev is self.start else self.prev, rows, self.acc, read=False)
 
 
-class _LanczosDouble:
-    """The same recurrence in complex128 on the host, sample by sample (CPU test double only): every sum is taken over one
-    sample's own 1-D tensors, so that a sample's record does not depend on its batch."""
-
-    def __init__(self, table: PsumTable, start: torch.Tensor, n: int, acc: torch.Tensor | None):
-        self.table, self.acc, self.batch = table, acc, start.shape[0]
-        self.cur = [start[b].to(torch.complex128) for b in range(self.batch)]
-        self.prev = [torch.zeros_like(x) for x in self.cur]
-        self.norm2 = [float((x.real * x.real + x.imag * x.imag).sum()) for x in self.cur]
-
-    @staticmethod
-    def sums(x, y):
-        return float((x.real * y.real + x.imag * y.imag).sum()), float((y.real * y.real + y.imag * y.imag).sum())
-
-    def step(self, rows, read=True):
-        if isinstance(rows, torch.Tensor):
-            rows = rows.tolist()
-        self.w, out = [], []
-        for b, (alpha, beta, gamma) in enumerate(rows):
-            hx = _psum_apply_double(self.cur[b].reshape(1, -1), self.table)[0] if alpha != 0.0 else torch.zeros_like(self.cur[b])
-            u = alpha * hx + beta * self.cur[b] + gamma * self.prev[b]
-            self.w.append(u)
-            out.append(list(self.sums(self.cur[b], u)))
-        return out
-
-    def finish(self, rows, read=True):
-        if isinstance(rows, torch.Tensor):
-            rows = rows.tolist()
-        out = []
-        for b, (e, d) in enumerate(rows):
-            self.w[b] = self.w[b] + e * self.cur[b]
-            if self.acc is not None:
-                self.acc[b] += d * self.cur[b]
-            out.append(list(self.sums(self.cur[b], self.w[b]))[::-1])
-        self.cur, self.prev = self.w, self.cur
-        return out
-
-    def last(self, rows):
-        if isinstance(rows, torch.Tensor):
-            rows = rows.tolist()
-        for b, (_e, d) in enumerate(rows):
-            self.acc[b] += d * self.cur[b]
-
-
 def _ritz_pair(alphas: list[float], betas: list[float], highest: bool):
     """The wanted eigenpair of T_m (alpha_1 .. alpha_m on the diagonal, beta_2 .. beta_m beside it), y_1 >= 0."""
     m = len(alphas)
@@ -2255,7 +1956,8 @@ def psum_lanczos(table: PsumTable, start: torch.Tensor, which: str = 'lowest', t
     batch, highest = start.shape[0], which == 'highest'
     nb = table.norm_bound
     eps = float(torch.finfo(torch.float32 if start.dtype == torch.complex64 else torch.float64).eps)
-    engine = _LanczosHip if _use_hip(start) else _LanczosDouble
+    hip = _use_hip(start)
+    engine = _LanczosHip if hip else _standin.Lanczos
 
     def run():
         first = engine(table, start, n, None)
@@ -2304,8 +2006,7 @@ def psum_lanczos(table: PsumTable, start: torch.Tensor, which: str = 'lowest', t
         steps = [len(a) for a in alphas]
         vec = None
         if vector:
-            vec = torch.zeros_like(start) if engine is _LanczosHip else [torch.zeros(start.shape[-1], dtype=torch.complex128)
-                                                                         for _ in range(batch)]
+            vec = torch.zeros_like(start) if hip else [torch.zeros(start.shape[-1], dtype=torch.complex128) for _ in range(batch)]
             again, top = engine(table, start, n, vec), max(steps)
             weight = lambda b, k: float(done[b][1][k - 1]) / scales[b][k - 1] if k <= steps[b] else 0.0  # noqa: E731
             # ONE host tensor, one copy: [top - 1][B][3] rows of the first kernel, then [top][B][2] rows of the second
@@ -2319,13 +2020,14 @@ def psum_lanczos(table: PsumTable, start: torch.Tensor, which: str = 'lowest', t
                 again.step(arows[k - 1], read=False)
                 again.finish(erows[k - 1], read=False)
             again.last(erows[top - 1])
-            if engine is _LanczosDouble:
+            if not hip:
                 vec = torch.stack(vec).to(start.dtype)
         return LanczosResult(torch.tensor([d[0] for d in done], dtype=torch.float64), vec,
                              torch.tensor([d[2] for d in done], dtype=torch.float64), torch.tensor(steps, dtype=torch.int64),
                              torch.tensor([bool(d[3]) for d in done], dtype=torch.bool), alphas, betas)
 
-    return run() if engine is _LanczosHip else _diag_double(run)
+    with contextlib.nullcontext() if hip else _standin.no_graph():
+        return run()
 
 
 # ---- every sample against every sample (csrc/dq_gram.hip) ----------------------------------------------------------------
@@ -2384,14 +2086,7 @@ def gram(bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
                              f'{bra.dtype} and {tuple(ket.shape)} {ket.dtype}')
         _gram_rows(bra, 'bra', what)
     if not _use_hip(ket):
-        def double():
-            g = bra.to(torch.complex128).conj() @ ket.to(torch.complex128).T
-            if bra.data_ptr() == ket.data_ptr() and bra.shape == ket.shape:      # the self-Gram, as the kernel leaves it
-                up = torch.triu(g, 1)
-                g = up + up.mH + torch.diag(g.diagonal().real).to(torch.complex128)
-            return g.resolve_conj()
-
-        return _diag_double(double)
+        return _stand('gram', bra, ket)
     M, N = bra.shape[0], ket.shape[0]
     out = torch.empty(M, N, 2, dtype=torch.float64, device=ket.device)
     whole = M <= GRAM_MAX_ROWS and N <= GRAM_MAX_ROWS
@@ -2423,7 +2118,7 @@ def combine(states: torch.Tensor, coef: torch.Tensor, out: torch.Tensor | None =
     M = coef.shape[0]
     out = _check_out(states, out, what, in_place=False, shape=(M, states.shape[1]))
     if not _use_hip(states):
-        return _diag_double(lambda: out.copy_((coef @ states.to(torch.complex128)).to(states.dtype)))
+        return _stand('combine', states, coef, out)
     for lo, hi in _slices(M, GRAM_MAX_ROWS):
         _call('dq_combine', states, _ptr(states), _ptr(coef, lo), _ptr(out, lo), n, hi - lo, N)
     return out
@@ -2506,29 +2201,11 @@ def measure_draw(probs: torch.Tensor, u: torch.Tensor | None, forced: torch.Tens
     forced = None if forced is None else forced.contiguous()
     rec = CollapseRec(torch.zeros(b, 5, dtype=torch.int64, device=probs.device), fx is not None)
     if not _use_hip(probs):
-        return _diag_double(lambda: _measure_draw_double(probs, u, forced, fx, fz, rec))
+        return _stand('measure_draw', probs, u, forced, fx, fz, rec)
     for lo, hi in _slices(b, 65535):                         # (one workgroup per sample)
         rc = _lib.load().dq_measure_draw(_ptr(probs, lo), _ptr(u, lo), _ptr(forced, lo), _ptr(fx), _ptr(fz), k, hi - lo,
                                          _ptr(rec.data, lo), _stream(probs))
         _lib.check(rc, 'dq_measure_draw')
-    return rec
-
-
-def _measure_draw_double(probs, u, forced, fx, fz, rec):
-    draw = _sample_indices_double(probs, (torch.zeros_like(probs[:, 0]) if u is None else u)[:, None])[:, 0]
-    want = torch.full_like(draw, -1) if forced is None else forced
-    o = torch.where(want >= 0, want & (probs.shape[1] - 1), draw)
-    po = torch.gather(probs, 1, o[:, None])[:, 0]
-    total = probs.sum(-1)
-    live = (po > 0) & (total > 0) & (want < probs.shape[1])
-    one = torch.ones_like(po)
-    rec.data[:, 0] = o
-    if fx is not None:
-        rec.data[:, 1] = fx[o]
-    if fz is not None:
-        rec.data[:, 2] = fz[o]
-    rec.scale.copy_(torch.where(live, torch.where(live, po, one) ** -0.5, 0 * one))
-    rec.prob.copy_(torch.where(live, po / torch.where(total > 0, total, one), 0 * one))
     return rec
 
 
@@ -2569,49 +2246,9 @@ def collapse(state: torch.Tensor, bits: Sequence[int], rec: CollapseRec, layout:
     out = _check_out(state, out, what, in_place=layout == 'full' and not rec.has_x, shape=(batch, 1 << nout))
     if not _use_hip(state):
         _suffix(state)
-        return _diag_double(lambda: _collapse_double(state, n, bits, rec, layout, bool(transpose), out))
+        return _stand('collapse', state, n, bits, rec, layout, bool(transpose), out)
     code = _lib.COLLAPSE_FULL if layout == 'full' else _lib.COLLAPSE_DROP
     for lo, hi in _slices(batch):
         _call('dq_apply_collapse', state, _ptr(state, lo), _ptr(out, lo), _ptr(rec.data, lo), n, _lib.int_array(bits), k, code,
               int(bool(transpose)), int(rec.has_x), hi - lo)
-    return out
-
-
-def _bit_parity(v: torch.Tensor) -> torch.Tensor:
-    for sh in (32, 16, 8, 4, 2, 1):
-        v = v ^ (v >> sh)
-    return v & 1
-
-
-def _collapse_double(state, n, bits, rec, layout, transpose, out):
-    """The four maps of ``collapse`` as they are defined, in complex128 torch (CPU test double only)."""
-    k = len(bits)
-    kept = [p for p in range(n - 1, -1, -1) if p not in bits]           # ext(): the kept positions, high to low
-    full = (1 << n) - 1
-    meas = sum(1 << p for p in bits)
-    o, s = rec.outcome[:, None], rec.scale[:, None]
-    x = (rec.xmask[:, None] & full) if rec.has_x else torch.zeros_like(o)
-    z = rec.zmask[:, None] & full
-    idx = torch.arange(1 << n, device=state.device)[None]
-
-    def sub(i, positions):
-        r = torch.zeros_like(i)
-        for j, p in enumerate(positions):
-            r |= ((i >> p) & 1) << (len(positions) - 1 - j)
-        return r
-
-    wide = state.to(torch.complex128)
-    if layout == 'full':
-        src = idx ^ x
-        at = idx if transpose else src                                  # the index of the input basis that P and Z see
-        val = torch.where(sub(at, bits) == o, (1 - 2 * _bit_parity(at & z)) * s * torch.gather(wide, 1, src), 0)
-    elif transpose:
-        val = torch.where(sub(idx, bits) == o, (1 - 2 * _bit_parity(idx & z)) * s * torch.gather(wide, 1, sub(idx ^ x, kept)), 0)
-    else:
-        keep = sub(idx, bits) == o                                      # (B, 2^n): 2^(n-k) kept indices per sample, ascending
-        i = idx.expand(state.shape[0], -1)[keep].reshape(state.shape[0], -1)
-        t = sub(i ^ (x & ~meas), kept)
-        val = torch.zeros(state.shape[0], 1 << (n - k), dtype=torch.complex128, device=state.device)
-        val.scatter_(1, t, (1 - 2 * _bit_parity(i & z)) * s * torch.gather(wide, 1, i))
-    out.copy_(val.to(state.dtype))
     return out

@@ -6,28 +6,41 @@ here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="${here}/../libdqhip.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 srcs=(dq_capi.hip dq_gate.hip dq_dense.hip dq_pass.hip dq_wave.hip dq_reduce.hip dq_dist.hip dq_plan.hip dq_entangle.hip dq_rdm.hip dq_sample.hip dq_diag.hip dq_pauli.hip dq_perm.hip dq_mux.hip dq_muxgrad.hip dq_excite.hip dq_psum.hip dq_select.hip dq_gram.hip dq_qft.hip dq_terms.hip dq_collapse.hip)
+flags=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -Wno-unused-value -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-uniform-regions)
+# "object:what it holds" of the kernels that keep their working set in registers: nothing of it may land in scratch memory.
+no_scratch=(
+  "dq_select:a select_pauli_kernel"                    # a unit's entries and vectors
+  "dq_gram:a gram_kernel / combine_kernel"             # the tiles' accumulators and a step's vectors
+  "dq_qft:a qft_stage_kernel"                          # a window's 16 amplitudes and its twiddles
+  "dq_terms:a terms_cross_kernel"                      # a unit's eight products through eleven butterfly stages
+  "dq_collapse:a collapse_kernel / measure_draw_kernel"  # a unit's source vectors and the lane's part of the index map
+)
+# the objects compiled with resource-usage remarks, which go to build/<name>.usage: what a guard below reads
+usage=(dq_wave "${no_scratch[@]%%:*}")
+usage_files=("${usage[@]/#/${here}/build/}")
+# compile $1 into $2 with the further flags $3..
+compile() { "$HIPCC" "${flags[@]}" "${@:3}" ${DQ_HIPCC_EXTRA:-} -c "$1" -o "$2"; }
 objs=()
 mkdir -p "${here}/build"
 # any header of this directory newer than object $1?
 newer_hpp() { local h; for h in "${here}"/*.hpp; do [[ "$h" -nt "$1" ]] && return 0; done; return 1; }
 pids=()
 for s in "${srcs[@]}"; do
-  o="${here}/build/${s%.hip}.o"
+  name="${s%.hip}"
+  o="${here}/build/${name}.o"
   objs+=("$o")
   if newer_hpp "$o" || [[ ! -f "$o" || "${here}/$s" -nt "$o" || "${here}/../../include/dq_hip.h" -nt "$o" || ( "$s" == dq_wave.hip && ( "${here}/dq_wave_asm.inc" -nt "$o" || "${here}/dq_wave_asm64.inc" -nt "$o" || "${here}/dq_wave_valu.inc" -nt "$o" || "${here}/dq_wave_valu64.inc" -nt "$o" ) ) ]]; then
-    if [[ "$s" == dq_wave.hip ]]; then
-      "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -Wno-unused-value -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-uniform-regions -Rpass-analysis=kernel-resource-usage ${DQ_HIPCC_EXTRA:-} -c "${here}/$s" -o "$o" 2> "${here}/build/dq_wave.usage" &
-    elif [[ "$s" == dq_select.hip || "$s" == dq_gram.hip || "$s" == dq_qft.hip || "$s" == dq_terms.hip || "$s" == dq_collapse.hip ]]; then
-      "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -Wno-unused-value -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-uniform-regions -Rpass-analysis=kernel-resource-usage ${DQ_HIPCC_EXTRA:-} -c "${here}/$s" -o "$o" 2> "${here}/build/${s%.hip}.usage" &
+    if [[ " ${usage[*]} " == *" ${name} "* ]]; then
+      compile "${here}/$s" "$o" -Rpass-analysis=kernel-resource-usage 2> "${here}/build/${name}.usage" &
     else
-    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -Wno-unused-value -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-uniform-regions ${DQ_HIPCC_EXTRA:-} -c "${here}/$s" -o "$o" &
+      compile "${here}/$s" "$o" &
     fi
     pids+=($!)
   fi
 done
 for p in "${pids[@]:-}"; do
   if [[ -n "$p" ]] && ! wait "$p"; then
-    grep -h -B2 -A3 "error" "${here}/build/dq_wave.usage" "${here}/build/dq_select.usage" "${here}/build/dq_gram.usage" "${here}/build/dq_qft.usage" "${here}/build/dq_terms.usage" "${here}/build/dq_collapse.usage" 2>/dev/null | head -40 >&2
+    grep -h -B2 -A3 "error" "${usage_files[@]/%/.usage}" 2>/dev/null | head -40 >&2
     echo "build failed" >&2
     exit 1
   fi
@@ -41,40 +54,14 @@ if [[ -f "${here}/build/dq_wave.usage" ]]; then
     exit 1
   fi
 fi
-# The SELECT kernels hold a unit's entries and vectors in registers: nothing of that may land in scratch memory.
-if [[ -f "${here}/build/dq_select.usage" ]]; then
-  if grep -E "ScratchSize \[bytes/lane\]: [1-9]|Spill: [1-9]" "${here}/build/dq_select.usage" > /dev/null; then
-    echo "dq_select.hip: a select_pauli_kernel instantiation spills or uses scratch memory (see build/dq_select.usage)" >&2
-    exit 1
+for g in "${no_scratch[@]}"; do
+  name="${g%%:*}"
+  if [[ -f "${here}/build/${name}.usage" ]]; then
+    if grep -E "ScratchSize \[bytes/lane\]: [1-9]|Spill: [1-9]" "${here}/build/${name}.usage" > /dev/null; then
+      echo "${name}.hip: ${g#*:} instantiation spills or uses scratch memory (see build/${name}.usage)" >&2
+      exit 1
+    fi
   fi
-fi
-# The Gram and combine kernels hold their tiles' accumulators and a step's vectors in registers: the same guard.
-if [[ -f "${here}/build/dq_gram.usage" ]]; then
-  if grep -E "ScratchSize \[bytes/lane\]: [1-9]|Spill: [1-9]" "${here}/build/dq_gram.usage" > /dev/null; then
-    echo "dq_gram.hip: a gram_kernel / combine_kernel instantiation spills or uses scratch memory (see build/dq_gram.usage)" >&2
-    exit 1
-  fi
-fi
-# The QFT stage kernels hold a window's 16 amplitudes and its twiddles in registers: the same guard.
-if [[ -f "${here}/build/dq_qft.usage" ]]; then
-  if grep -E "ScratchSize \[bytes/lane\]: [1-9]|Spill: [1-9]" "${here}/build/dq_qft.usage" > /dev/null; then
-    echo "dq_qft.hip: a qft_stage_kernel instantiation spills or uses scratch memory (see build/dq_qft.usage)" >&2
-    exit 1
-  fi
-fi
-# The per-string kernels hold a unit's eight products through eleven butterfly stages in registers: the same guard.
-if [[ -f "${here}/build/dq_terms.usage" ]]; then
-  if grep -E "ScratchSize \[bytes/lane\]: [1-9]|Spill: [1-9]" "${here}/build/dq_terms.usage" > /dev/null; then
-    echo "dq_terms.hip: a terms_cross_kernel instantiation spills or uses scratch memory (see build/dq_terms.usage)" >&2
-    exit 1
-  fi
-fi
-# The collapse kernels hold a unit's source vectors and the lane's part of the index map in registers: the same guard.
-if [[ -f "${here}/build/dq_collapse.usage" ]]; then
-  if grep -E "ScratchSize \[bytes/lane\]: [1-9]|Spill: [1-9]" "${here}/build/dq_collapse.usage" > /dev/null; then
-    echo "dq_collapse.hip: a collapse_kernel / measure_draw_kernel instantiation spills or uses scratch memory (see build/dq_collapse.usage)" >&2
-    exit 1
-  fi
-fi
+done
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$out"
 echo "built $out"

@@ -11,7 +11,7 @@ from typing import TYPE_CHECKING, Any, NamedTuple
 import torch
 from torch import nn
 
-from . import backend, ops
+from . import _standin, backend, ops
 
 if TYPE_CHECKING:
     from .layer import Observable
@@ -179,12 +179,6 @@ def evolve_den_mat(state: torch.Tensor, matrix: torch.Tensor, nqudit: int, wires
     return out.reshape(shape)
 
 
-def _parity(x: torch.Tensor) -> torch.Tensor:
-    for shift in (32, 16, 8, 4, 2, 1):
-        x = x ^ (x >> shift)
-    return x & 1
-
-
 def measure(
     state: torch.Tensor,
     shots: int = 1024,
@@ -290,7 +284,7 @@ def sample(
         wires = sorted(_wire_list(wires, n, 'sample')) if wires is not None else None
         u = torch.rand(flat.shape[0], shots, dtype=torch.float64, device=flat.device, generator=generator)
         if den_mat:       # the diagonal already holds the probabilities: the contract in torch, no kernel
-            idx = backend._sample_indices_double(flat.clamp_min(0), u)
+            idx = _standin.sample_indices(flat.clamp_min(0), u)
         else:
             idx = backend.sample_indices(flat, u)
         if wires is not None and len(wires) != n:
@@ -364,7 +358,7 @@ def expectation(state: torch.Tensor, observable: 'Observable', den_mat: bool = F
         dim = int(round(rho.shape[-1] ** 0.5))
         j = torch.arange(dim, device=rho.device)
         entries = rho[:, j * dim + (j ^ xmask)]
-        sign = (1 - 2 * _parity(j & zmask)).to(rho.real.dtype)
+        sign = (1 - 2 * _standin.parity(j & zmask)).to(rho.real.dtype)
         val = (entries * sign).sum(-1) * (1j) ** bin(xmask & zmask).count('1')
         out = val.real
         return out.squeeze(0) if single else out

@@ -5,7 +5,7 @@
     (U psi)[put(i, perm[sub(i)])] = psi[i]   where all control bits of i are 1,   (U psi)[i] = psi[i] elsewhere
 
 in scatter form and with ``np.arange`` index arithmetic: independent of the package's gather form and of its
-``_sub_index``."""
+``_standin.sub_index``."""
 
 import numpy as np
 

@@ -1,6 +1,6 @@
 """Mid-circuit measurement without a GPU: the new symbols, the host refusals of ``dq_apply_collapse_*`` /
 ``dq_measure_draw`` before any HIP call, and the host logic of ``Measure`` / ``cir.mid_measure`` under the CPU test double
-(whose collapse is ``backend._collapse_double``)."""
+(whose collapse is ``_standin.collapse``)."""
 
 import ctypes
 import re

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import deepquantum_amd as dq
-from deepquantum_amd import _lib, backend, ops, qmath
+from deepquantum_amd import _lib, _standin, backend, ops, qmath
 from _evolve_ref import bessel_integral, evolve_ref, smallest_order
 from _psum_ref import dense_psum
 
@@ -185,7 +185,7 @@ def test_backend_refusals_and_out(cpu_backend, monkeypatch):
     assert torch.allclose(backend.apply_psum_evolve(x, C.table, 0.4, 1e-12), np.exp(-0.6j) * x, atol=1e-15)
     # under capture the call is refused by name before anything runs
     calls = []
-    monkeypatch.setattr(backend, '_psum_apply_double', lambda *a: calls.append(1))
+    monkeypatch.setattr(_standin, 'psum_apply', lambda *a: calls.append(1))
     monkeypatch.setattr(torch.cuda, 'is_current_stream_capturing', lambda: True)
     with pytest.raises(RuntimeError, match='apply_psum_evolve under stream capture'):
         backend.apply_psum_evolve(x, H.table, 0.3, 1e-9)

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import deepquantum_amd as dq
-from deepquantum_amd import _lib, backend, qmath
+from deepquantum_amd import _lib, _standin, backend, qmath
 from _psum_ref import dense_psum
 from test_evolve_cpu import HAMS, rand_state
 
@@ -316,7 +316,7 @@ def test_refused_under_capture(cpu_backend, monkeypatch):
     H = dq.PauliSum(chain(4), 4)
     x = rand_state(1, 4, 1)
     calls = []
-    monkeypatch.setattr(backend, '_psum_apply_double', lambda *a: calls.append(1))
+    monkeypatch.setattr(_standin, 'psum_apply', lambda *a: calls.append(1))
     monkeypatch.setattr(torch.cuda, 'is_current_stream_capturing', lambda: True)
     with pytest.raises(RuntimeError, match='psum_lanczos under stream capture'):
         backend.psum_lanczos(H.table, x)

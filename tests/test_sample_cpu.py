@@ -1,5 +1,5 @@
 """The inverse-CDF shot sampler without a GPU: the C ABI's host-side checks (dq_sample_*), ``qmath.sample`` and
-``measure(sampler='inverse_cdf')`` on the CPU test double, whose ``backend._sample_indices_double`` states the kernel's
+``measure(sampler='inverse_cdf')`` on the CPU test double, whose ``_standin.sample_indices`` states the kernel's
 contract in torch."""
 
 import ctypes
@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import deepquantum_amd as dq
-from deepquantum_amd import _lib, backend, qmath
+from deepquantum_amd import _lib, _standin, backend, qmath
 
 
 def rand_state(n, batch=None, dtype=torch.complex64, seed=0):
@@ -78,7 +78,7 @@ def test_double_matches_a_longdouble_search():
     psi = rand_state(9, 2, torch.complex128, seed=3) * 1.7
     u = torch.rand(2, 500, dtype=torch.float64, generator=gen(1))
     u[0, 0], u[0, 1] = 0.0, float(np.nextafter(1.0, 0.0))
-    got = backend._sample_indices_double(psi, u).numpy()
+    got = _standin.sample_indices(psi, u).numpy()
     for b in range(2):
         a = psi[b].numpy()
         p = a.real.astype(np.longdouble) ** 2 + a.imag.astype(np.longdouble) ** 2
@@ -91,7 +91,7 @@ def test_double_never_returns_an_index_of_probability_zero():
     psi = torch.zeros(1, 64, dtype=torch.complex128)
     psi[0, 5], psi[0, 40] = 0.6, 0.8
     u = torch.tensor([[0.0, 0.3, 0.36, 0.999, 1.0 - 2.0**-53, 1.0]], dtype=torch.float64)     # (1.0: past the contract, clamped)
-    got = backend._sample_indices_double(psi, u)
+    got = _standin.sample_indices(psi, u)
     assert got.tolist() == [[5, 5, 40, 40, 40, 40]]
 
 
@@ -100,7 +100,7 @@ def test_sample_indices_dispatches_to_the_double_and_checks_u(cpu_backend):
     u = torch.rand(2, 9, dtype=torch.float64, generator=gen(0))
     got = backend.sample_indices(psi, u)
     assert got.dtype == torch.int64 and got.shape == (2, 9)
-    assert torch.equal(got, backend._sample_indices_double(psi, u))
+    assert torch.equal(got, _standin.sample_indices(psi, u))
     with pytest.raises(ValueError):
         backend.sample_indices(psi, u.float())
     with pytest.raises(ValueError):
@@ -139,7 +139,7 @@ def test_same_seed_same_tensor_and_all_forms_agree(cpu_backend):
     assert not torch.equal(a, qmath.sample(batch, n, shots=300, generator=gen(12)))
     # the uniforms are the documented draw
     u = torch.rand(2, 300, dtype=torch.float64, generator=gen(11))
-    assert torch.equal(a, backend._sample_indices_double(batch, u))
+    assert torch.equal(a, _standin.sample_indices(batch, u))
 
 
 def test_wires_pick_bits_in_ascending_wire_order(cpu_backend):

@@ -1,6 +1,6 @@
 """SELECT over Pauli strings and the block encoding built on it, without a GPU: the reference against the dense definition,
 both table constructors, every refusal by name, the library's host-side checks, and the block-encoding identities through
-the plain-torch stand-in of the kernel (``backend._apply_select_pauli_double``)."""
+the plain-torch stand-in of the kernel (``_standin.apply_select_pauli``)."""
 
 import os
 import pickle
