@@ -36,8 +36,8 @@ from .layer import (
 from .operation import Channel, Gate, Layer, Operation
 from .pauli_sum import PauliSum, PauliSumEvolution, SelectPauli
 from .qmath import (
-    amplitude_encoding, apply_pauli_sum, evolve_pauli_sum, expectation, expectation_cost, expectation_pauli_sum, fidelity_kernel,
-    gram_matrix, ising_cost, linear_combination, measure, meyer_wallach_measure, multi_kron, orthonormalize, partial_trace,
+    amplitude_encoding, apply_pauli_sum, cost_bins, cost_distribution, cvar_cost, evolve_pauli_sum, expectation, expectation_cost,
+    expectation_pauli_sum, fidelity_kernel, gibbs_cost, gram_matrix, ising_cost, linear_combination, measure, meyer_wallach_measure, multi_kron, orthonormalize, partial_trace,
     pauli_pool_gradients, pauli_sum_extremal, pauli_term_expectations, pauli_term_overlaps,
 )
 from .state import DistributedQubitState, QubitState

@@ -203,6 +203,10 @@ _SIGNATURES = {
     'dq_collapse_rec_layout': (_i, [_ip, _i]),
     'dq_measure_draw': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'dq_apply_collapse_{s}': (_i, [_vp, _vp, _vp, _i, _ip, _i, _i, _i, _i, _i64, _vp]),
+    'dq_cost_hist_max_bins': (_i, []),
+    'dq_cost_hist_ws_bytes': (_i64, [_i, _i64, _i, _i, _i]),
+    'dq_cost_hist_{s}': (_i, [_vp, _vp, _vp, _i, _i, _ip, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),
+    'dq_apply_binned_{s}': (_i, [_vp, _vp, _vp, _vp, _i, _i, _ip, _i, _ip, _i, _i64, _vp]),
 }
 
 

@@ -112,6 +112,21 @@ def cost_cross(bra, ket, cost, n, bits, controls):
     return (w * bra.to(torch.complex128).conj() * ket.to(torch.complex128)).sum(dim=-1)
 
 
+def cost_hist(bra, ket, bins, nbins, n, bits, controls):
+    sub, ok = sub_index(n, bits, controls)
+    terms = ok * bra.to(torch.complex128).conj() * ket.to(torch.complex128)
+    out = torch.zeros(ket.shape[0], nbins, dtype=torch.complex128)
+    return out.index_add_(1, bins.to(torch.int64)[sub], terms)
+
+
+def apply_binned(state, g, bins, n, bits, controls, out):
+    sub, ok = sub_index(n, bits, controls)
+    x = state.to(torch.complex128)
+    f = g.to(torch.complex128)[:, bins.to(torch.int64)[sub]]
+    out.copy_(torch.where(ok, f * x, torch.zeros_like(x)).to(state.dtype))
+    return out
+
+
 def apply_pauli_axpby(state, xmask, zmask, a, c, n, controls, mode, out):
     j, factor, ok = pauli_gather(n, xmask, zmask, controls)
     x = state.to(torch.complex128)

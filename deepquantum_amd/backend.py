@@ -963,6 +963,75 @@ def cost_cross(bra: torch.Tensor, ket: torch.Tensor, cost: torch.Tensor, bits: S
 
 
 # ---------------------------------------------------------------------------------------------------
+# The distribution of a tabulated cost (csrc/dq_hist.hip): a bin per table entry, sub(i) as above
+def cost_hist_max_bins() -> int:
+    """The most bins of one :func:`cost_hist` / :func:`apply_binned` (``dq_cost_hist_max_bins``)."""
+    return int(_lib.load().dq_cost_hist_max_bins())
+
+
+def _bin_table(bins: torch.Tensor, like: torch.Tensor, k: int, nbins: int, what: str) -> torch.Tensor:
+    """The bin of every table entry as the kernels read it: int16 (the bits of the library's uint16; a bin is below
+    2^15), (2^k,), on the state's device, 16-byte aligned.  A table of another integer dtype is checked here, once,
+    against ``nbins`` -- build it once and pass the result of :func:`bin_table` on; an int16 table on the state's device
+    is taken as checked (the kernels clamp a bin >= nbins, they never index out of range)."""
+    if not 1 <= nbins <= cost_hist_max_bins():
+        raise ValueError(f'{what}: {nbins} bins, between 1 and {cost_hist_max_bins()} (cost_hist_max_bins) are supported')
+    if bins.is_floating_point() or bins.is_complex() or bins.dtype == torch.bool or bins.shape != (1 << k,):
+        raise ValueError(f'{what}: the bins are an integer table of {1 << k} entries over {k} bits; got {bins.dtype} '
+                         f'{tuple(bins.shape)}')
+    if bins.dtype != torch.int16 or bins.device != like.device:
+        if int(bins.min()) < 0 or int(bins.max()) >= nbins:
+            raise ValueError(f'{what}: every bin must lie in [0, {nbins})')
+    return _finish_table(bins, like, torch.int16, what)
+
+
+def bin_table(bins: torch.Tensor, like: torch.Tensor, nbins: int) -> torch.Tensor:
+    """``bins`` (an integer table of 2^k entries, every entry in [0, nbins)) checked and laid out for :func:`cost_hist`
+    and :func:`apply_binned` on the device of ``like``: do this once per table."""
+    k = max(bins.numel(), 1).bit_length() - 1
+    return _bin_table(bins, like, k, int(nbins), 'bin_table')
+
+
+def cost_hist(bra: torch.Tensor, ket: torch.Tensor, bins: torch.Tensor, nbins: int, bits: Sequence[int],
+              controls: Sequence[int] = ()) -> torch.Tensor:
+    """out[b, v] = sum over the amplitudes whose ``controls`` are all 1 and whose table entry ``bins[sub(i)]`` is v of
+    conj(bra[b, i]) ket[b, i]: complex128 (B, nbins), accumulated in double, bitwise reproducible bin by bin, one read of
+    each state whatever nbins and k are (``dq_cost_hist_*``).  ``bra`` and ``ket`` the same buffer: one read of the
+    state, the distribution of the cost, imaginary parts exactly 0.  The workspace comes from PyTorch's allocator (legal
+    under capture)."""
+    n, bits, controls = _diag_args(ket, bits, controls, 'cost_hist')
+    k, nbins = len(bits), int(nbins)
+    _suffix(ket)
+    _check_bra(bra, ket, 'cost_hist')
+    bins = _bin_table(bins, ket, k, nbins, 'cost_hist')
+    if not _use_hip(ket):
+        return _stand('cost_hist', bra, ket, bins, nbins, n, bits, controls)
+    mid = (_ptr(bins), nbins, n, _lib.int_array(bits), k, _lib.int_array(controls), len(controls))
+    return _cross_reduce('dq_cost_hist', 'dq_cost_hist_ws_bytes', bra, ket, mid, (nbins,), sizer_args=(nbins,))
+
+
+def apply_binned(state: torch.Tensor, g: torch.Tensor, bins: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = (),
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[b, i] = g[b, bins[sub(i)]] state[b, i] on the amplitudes whose ``controls`` are all 1, 0 on the others (the
+    cotangent of :func:`cost_hist`, which leaves them out): ``g`` complex (B, nbins), one read and one write of the state
+    (``dq_apply_binned_*``).  ``out`` may be ``state``."""
+    n, bits, controls = _diag_args(state, bits, controls, 'apply_binned')
+    k = len(bits)
+    _suffix(state)
+    if g.ndim != 2 or g.shape[0] != state.shape[0] or not g.is_complex():
+        raise ValueError(f'apply_binned: g must be complex ({state.shape[0]}, nbins), got {g.dtype} {tuple(g.shape)}')
+    bins = _bin_table(bins, state, k, g.shape[1], 'apply_binned')
+    out = _check_out(state, out, 'apply_binned')
+    if not _use_hip(state):
+        return _stand('apply_binned', state, g, bins, n, bits, controls, out)
+    gr = torch.view_as_real(g.to(device=state.device, dtype=torch.complex128).resolve_conj().resolve_neg().contiguous())
+    for lo, hi in _slices(state.shape[0]):
+        _call('dq_apply_binned', state, _ptr(state, lo), _ptr(out, lo), _ptr(bins), _ptr(gr, lo), g.shape[1], n,
+              _lib.int_array(bits), k, _lib.int_array(controls), len(controls), hi - lo)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # Pauli strings on any number of wires (csrc/dq_pauli.hip): (P psi)[i] = i^ny (-1)^popc((i ^ x) & z) psi[i ^ x]
 def _support_args(state: torch.Tensor, controls: Sequence[int], support: int, named: str, what: str) -> tuple[int, list[int]]:
     """What the Pauli and the excitation entry points ask alike, before their own mask checks: a contiguous state and

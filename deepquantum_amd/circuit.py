@@ -401,6 +401,24 @@ class QubitCircuit(Operation):
             raise NotImplementedError('expectation_cost: den_mat=True (density matrices) is not supported')
         return qmath.expectation_cost(self.state, self.nqubit, cost, wires)
 
+    def cost_distribution(self, cost, wires: int | list[int] | None = None, bins=None) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(values, probs)``: the distribution ``P(C = v)`` of a classical cost table over ``wires`` (all by default) in
+        the final state of the last forward; see :func:`qmath.cost_distribution`."""
+        if self.state is None:
+            raise RuntimeError('cost_distribution: run the circuit first')
+        if self.den_mat:
+            raise NotImplementedError('cost_distribution: den_mat=True (density matrices) is not supported')
+        return qmath.cost_distribution(self.state, self.nqubit, cost, wires, bins)
+
+    def cvar_cost(self, cost, alpha: float, wires: int | list[int] | None = None, tail: str = 'lower') -> torch.Tensor:
+        """CVaR_alpha of a classical cost table over ``wires`` (all by default) in the final state of the last forward:
+        (B,) real, or 0-d for a single state; see :func:`qmath.cvar_cost`."""
+        if self.state is None:
+            raise RuntimeError('cvar_cost: run the circuit first')
+        if self.den_mat:
+            raise NotImplementedError('cvar_cost: den_mat=True (density matrices) is not supported')
+        return qmath.cvar_cost(self.state, self.nqubit, cost, alpha, wires, tail)
+
     def expectation_pauli_sum(self, H) -> torch.Tensor:
         """``Re <psi|H|psi>`` of the final state of the last forward for a sum of Pauli strings ``H`` -- a ``PauliSum`` or
         the list form ``[[0.5, 'x0y1'], [-1, 'z3y1'], [0.25, '']]``: (B,) real, or 0-d for a single state, the whole sum
@@ -1190,6 +1208,12 @@ class DistributedQubitCircuit(QubitCircuit):
 
     def entanglement_entropy(self, wires: int | list[int], alpha: float = 1.0, base: float | None = None) -> torch.Tensor:
         raise NotImplementedError('entanglement_entropy: sharded states are not supported')
+
+    def cost_distribution(self, cost, wires: int | list[int] | None = None, bins=None):
+        raise NotImplementedError('cost_distribution: sharded states are not supported')
+
+    def cvar_cost(self, cost, alpha: float, wires: int | list[int] | None = None, tail: str = 'lower') -> torch.Tensor:
+        raise NotImplementedError('cvar_cost: sharded states are not supported')
 
     def expectation_pauli_sum(self, H) -> torch.Tensor:
         raise NotImplementedError('expectation_pauli_sum: sharded states are not supported')

@@ -842,6 +842,79 @@ class _DiagMul(torch.autograd.Function):
         return _vmap_states(_DiagMul, 'diag_mul', info, in_dims, (state, diag, bits, controls), tables=(1,))
 
 
+class _CostHist(torch.autograd.Function):
+    """h[v] = sum over i with bins[sub(i)] = v of conj(a_i) b_i, complex128 (B, V): anti-linear in a, linear in b;
+    cotangents g_b = binned(a, gh) and g_a = binned(b, conj(gh)) (csrc/dq_hist.hip)."""
+
+    @staticmethod
+    def forward(bra: torch.Tensor, ket: torch.Tensor, bins: torch.Tensor, nbins: int, bits: tuple, controls: tuple) -> torch.Tensor:
+        pk = _kernel_arg(ket)
+        return backend.cost_hist(pk if bra is ket else _kernel_arg(bra), pk, bins, nbins, bits, controls)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        bra, ket, bins, ctx.nbins, ctx.bits, ctx.controls = inputs
+        ctx.save_for_backward(bra, ket, bins)
+        ctx.save_for_forward(bra, ket, bins)
+
+    @staticmethod
+    def jvp(ctx, bra_t, ket_t, _bins_t, _nbins_t, _bits_t, _controls_t):
+        _single_forward_level()
+        bra, ket, bins = ctx.saved_tensors
+        return _jvp_two_slots(lambda u, v: cost_hist(u, v, bins, ctx.nbins, ctx.bits, ctx.controls), bra, ket, bra_t, ket_t)
+
+    @staticmethod
+    def backward(ctx, gh: torch.Tensor):
+        bra, ket, bins = ctx.saved_tensors
+        gh = gh.to(torch.complex128)
+        gbra = apply_binned(ket, gh.conj(), bins, ctx.bits, ctx.controls) if ctx.needs_input_grad[0] else None
+        gket = apply_binned(bra, gh, bins, ctx.bits, ctx.controls) if ctx.needs_input_grad[1] else None
+        return gbra, gket, None, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, bra, ket, bins, nbins, bits, controls):
+        _unmapped_table(in_dims[2], 'cost_hist')
+        v = info.batch_size
+        kf = _fold(ket, in_dims[1], v)
+        bf = kf if bra is ket and in_dims[0] == in_dims[1] else _fold(bra, in_dims[0], v)
+        return _CostHist.apply(bf, kf, bins, nbins, bits, controls).reshape(v, -1, nbins), 0
+
+
+class _ApplyBinned(torch.autograd.Function):
+    """y_i = g[bins[sub(i)]] x_i with g complex128 (B, V), 0 outside the controls: cotangents gx = binned(gy, conj(g))
+    and gg = hist(x, gy)."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, g: torch.Tensor, bins: torch.Tensor, bits: tuple, controls: tuple) -> torch.Tensor:
+        return backend.apply_binned(_kernel_arg(state), _plain(g), bins, bits, controls)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, g, bins, ctx.bits, ctx.controls = inputs
+        ctx.save_for_backward(state, g, bins)
+        ctx.save_for_forward(state, g, bins)
+
+    @staticmethod
+    def jvp(ctx, state_t, g_t, _bins_t, _bits_t, _controls_t):
+        _single_forward_level()
+        state, g, bins = ctx.saved_tensors
+        return _jvp_two_slots(lambda x, v: apply_binned(x, v, bins, ctx.bits, ctx.controls), state, g, state_t, g_t)
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, g, bins = ctx.saved_tensors
+        gstate = gg = None
+        if ctx.needs_input_grad[0]:
+            gstate = apply_binned(gy, g.conj(), bins, ctx.bits, ctx.controls)
+        if ctx.needs_input_grad[1]:
+            gg = cost_hist(state, gy, bins, g.shape[-1], ctx.bits, ctx.controls).to(g.dtype)
+        return gstate, gg, None, None, None
+
+    @staticmethod
+    def vmap(info, in_dims, state, g, bins, bits, controls):
+        return _vmap_states(_ApplyBinned, 'apply_binned', info, in_dims, (state, g, bins, bits, controls), folded=(1,), tables=(2,))
+
+
 def _bit_args(bits: Sequence[int], controls: Sequence[int]) -> tuple[tuple, tuple]:
     return tuple(int(b) for b in bits), tuple(int(c) for c in controls)
 
@@ -880,6 +953,33 @@ def cost_scale(state: torch.Tensor, cost: torch.Tensor, s: torch.Tensor, bits: S
     bits, controls = _bit_args(bits, controls)
     s = _per_sample(s, state.shape[-2], torch.complex128, 'cost_scale')
     return _CostScale.apply(_flat_arg(state), cost, s, bits, controls)
+
+
+def cost_hist(bra: torch.Tensor, ket: torch.Tensor, bins: torch.Tensor, nbins: int, bits: Sequence[int],
+              controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable ``h[v] = sum over i with bins[sub(i)] = v of conj(bra_i) ket_i`` of two (B, 2**n) states: complex128
+    (B, nbins); ``bins`` a constant integer table (2^k,) over the index bits ``bits`` with entries in [0, nbins) --
+    ``backend.bin_table`` checks and lays it out once.  Pass the same tensor twice for the distribution of the cost (one
+    read of the state; the imaginary parts are exactly 0).  Closed under differentiation with :func:`apply_binned`.
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    bra, ket = _cross_pair(bra, ket, 'cost_hist')
+    bins = _const_table(bins, 'cost_hist')
+    bits, controls = _bit_args(bits, controls)
+    return _CostHist.apply(bra, ket, bins, int(nbins), bits, controls)
+
+
+def apply_binned(state: torch.Tensor, g: torch.Tensor, bins: torch.Tensor, bits: Sequence[int],
+                 controls: Sequence[int] = ()) -> torch.Tensor:
+    """Differentiable ``y_i = g[b, bins[sub(i)]] x_i`` on a (B, 2**n) state, ``g`` complex (B, nbins) or (nbins,);
+    amplitudes outside the controls come out as 0 (the cotangent of :func:`cost_hist`).
+    A state that is not 16-byte aligned (a view at an odd complex64 offset) is copied, not refused (:func:`_kernel_arg`)."""
+    _no_legacy(state, g)
+    bins = _const_table(bins, 'apply_binned')
+    bits, controls = _bit_args(bits, controls)
+    g = g.to(torch.complex128)
+    if g.ndim == 1:
+        g = g.unsqueeze(0).expand(state.shape[-2], -1)
+    return _ApplyBinned.apply(_flat_arg(state), g, bins, bits, controls)
 
 
 def diag_mul(state: torch.Tensor, diag: torch.Tensor, bits: Sequence[int], controls: Sequence[int] = ()) -> torch.Tensor:

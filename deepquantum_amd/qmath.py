@@ -535,6 +535,100 @@ def expectation_cost(state: torch.Tensor, nqubit: int, cost: torch.Tensor, wires
     return val.squeeze(0) if single else val
 
 
+class CostBins(NamedTuple):
+    """A cost table prepared for :func:`cost_distribution`: ``values`` (V,) ascending -- the distinct entries, or the bin
+    centres -- and ``table`` (2^k,) int16, the bin of every entry."""
+
+    values: torch.Tensor
+    table: torch.Tensor
+
+
+def cost_bins(cost: torch.Tensor, bins: Any = None, what: str = 'cost_bins') -> CostBins:
+    """Bin a real cost table of 2^k entries, once (a sort of the table): by its distinct values
+    (``torch.unique(..., return_inverse=True)``), or with ``bins=`` ascending edges by ``torch.bucketize`` into the
+    ``len(bins) - 1`` intervals [e_j, e_j+1) (the last one closed), whose centres become the values.  At most
+    ``backend.cost_hist_max_bins()`` bins.  Pass the result wherever a cost table is taken by :func:`cost_distribution`,
+    :func:`cvar_cost` and :func:`gibbs_cost` to pay for this once per table instead of once per call."""
+    if not isinstance(cost, torch.Tensor):
+        cost = torch.tensor(cost, dtype=torch.float)
+    cost = _cost_table(cost, max(cost.numel(), 1).bit_length() - 1, what).detach()
+    cap = backend.cost_hist_max_bins()
+    if bins is None:
+        values, index = torch.unique(cost, return_inverse=True)
+        if values.numel() > cap:
+            raise ValueError(f'{what}: the table has {values.numel()} distinct values, more than max_bins = {cap}; '
+                             'pass bins= (ascending bin edges) to bin them')
+    else:
+        edges = torch.as_tensor(bins, dtype=cost.dtype, device=cost.device)
+        if edges.ndim != 1 or not 2 <= edges.numel() <= cap + 1 or not bool((edges[1:] > edges[:-1]).all()):
+            raise ValueError(f'{what}: bins must be 2 to max_bins + 1 = {cap + 1} ascending edges')
+        if bool(cost.min() < edges[0]) or bool(cost.max() > edges[-1]):
+            raise ValueError(f'{what}: the table has entries outside the edges [{float(edges[0])}, {float(edges[-1])}]')
+        index = (torch.bucketize(cost, edges, right=True) - 1).clamp_(max=edges.numel() - 2)
+        values = (edges[:-1] + edges[1:]) / 2
+    return CostBins(values, index.to(torch.int16))
+
+
+def cost_distribution(state: torch.Tensor, nqubit: int, cost: Any, wires: int | list[int] | None = None,
+                      bins: Any = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(values, probs)`` with ``probs[v] = sum over i with cost[sub(i)] == values[v] of |psi_i|^2``: the distribution of a
+    classical cost given as a real table of 2^k entries over ``wires`` (``wires[0]`` the most significant bit of the
+    entry index; all n wires by default).  ``values`` are the V ascending distinct entries of the table -- or, with
+    ``bins=`` edges, the centres of the bins (:func:`cost_bins`; a prepared :class:`CostBins` may be passed as ``cost``) --
+    and ``probs`` is real (B, V) in the state's precision, (V,) for a single state.  ``state`` in the forms of
+    :func:`reduced_density_matrix`.  One read of the state and no 2^n temporary, accumulated in double, bitwise
+    reproducible (``dq_cost_hist_*``); differentiable to any order in the state (the table is a constant).  Not
+    normalised: a state of norm r gives r^2 P.  More distinct values than ``backend.cost_hist_max_bins()`` need ``bins=``."""
+    what = 'cost_distribution'
+    flat, single = _state_batch(state, nqubit, what)
+    n = int(nqubit)
+    wires = list(range(n)) if wires is None else _wire_list(wires, n, what)
+    cb = cost if isinstance(cost, CostBins) else cost_bins(_cost_table(cost, len(wires), what), bins, what)
+    if cb.table.shape != (1 << len(wires),):
+        raise ValueError(f'{what}: a cost over {len(wires)} wires has {1 << len(wires)} entries, got {tuple(cb.table.shape)}')
+    nbins = int(cb.values.numel())
+    table = backend.bin_table(cb.table, flat, nbins)
+    probs = ops.cost_hist(flat, flat, table, nbins, [n - 1 - w for w in wires]).real.to(flat.real.dtype)
+    return cb.values.to(flat.device), (probs.squeeze(0) if single else probs)
+
+
+def cvar_cost(state: torch.Tensor, nqubit: int, cost: Any, alpha: float, wires: int | list[int] | None = None,
+              tail: str = 'lower', bins: Any = None) -> torch.Tensor:
+    """CVaR_alpha of a classical cost table: the mean of the cost over the best ``alpha``-fraction of the outcomes, the
+    lowest for ``tail='lower'`` (minimisation) and the highest for ``tail='upper'``: (B,) real in the state's precision,
+    0-d for a single state.  Taken on ``p = probs / probs.sum(-1)`` of :func:`cost_distribution`: with tau the smallest
+    value whose cumulative probability reaches alpha, ``(1 / alpha) [sum_{v < tau} v p_v + tau (alpha - P(< tau))]``.  The
+    threshold is found without a graph; the value is formed from ``probs``, so the gradient flows through the histogram
+    node.  ``alpha = 1`` is :func:`expectation_cost` of the normalised state."""
+    alpha = float(alpha)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError(f'cvar_cost: alpha must lie in (0, 1], got {alpha}')
+    if tail not in ('lower', 'upper'):
+        raise ValueError(f"cvar_cost: tail must be 'lower' or 'upper', got {tail!r}")
+    values, probs = cost_distribution(state, nqubit, cost, wires, bins)
+    single = probs.ndim == 1
+    p = probs.reshape(-1, probs.shape[-1]).to(torch.float64)
+    p = p / p.sum(-1, keepdim=True)
+    v = values.to(torch.float64)
+    if tail == 'upper':
+        v, p = v.flip(0), p.flip(-1)
+    with torch.no_grad():
+        t = (p.cumsum(-1) < alpha).sum(-1, keepdim=True).clamp_(max=v.numel() - 1)      # the threshold bin
+        below = torch.arange(v.numel(), device=p.device) < t
+    head = p * below
+    val = ((head * v).sum(-1) + v[t.squeeze(-1)] * (alpha - head.sum(-1))) / alpha
+    val = val.to(probs.dtype)
+    return val.squeeze(0) if single else val
+
+
+def gibbs_cost(state: torch.Tensor, nqubit: int, cost: Any, eta: float, wires: int | list[int] | None = None,
+               bins: Any = None) -> torch.Tensor:
+    """The Gibbs objective ``-log(sum_v exp(-eta v) p_v) / eta`` of a classical cost table, ``p`` the (unnormalised)
+    :func:`cost_distribution`: (B,) real, 0-d for a single state."""
+    values, probs = cost_distribution(state, nqubit, cost, wires, bins)
+    return -torch.log((torch.exp(-float(eta) * values.to(probs.dtype)) * probs).sum(-1)) / float(eta)
+
+
 def _pauli_sum(H: Any, nqubit: int, what: str):
     from .pauli_sum import PauliSum
 

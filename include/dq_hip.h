@@ -1008,6 +1008,40 @@ int dq_apply_collapse_c64(const void* in, void* out, const void* rec, int n, con
 int dq_apply_collapse_c128(const void* in, void* out, const void* rec, int n, const int* bits, int k, int layout, int transpose,
                            int may_flip, int64_t batch, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 19. The distribution of a tabulated cost (csrc/dq_hist.hip; added within ABI 30, presence is checked by symbol): a
+ *     reduction binned through a table lookup and the streaming pass that is its cotangent.  sub(i), `bits`, `controls`,
+ *     `nc` and the limits 1 <= k, k + nc <= n <= 40, 1 <= batch <= 65535 as in section 8; bits = n-1 .. 0 without
+ *     controls streams the table beside the state.  `bin`: DEVICE uint16 table of 2^k entries shared by the batch, every
+ *     entry < V, 16-byte aligned (two bytes per amplitude beside a streamed state; V fits with room to spare).  An entry
+ *     >= V is the caller's error: the kernels clamp it to V - 1 and never index out of range.
+ *     1 <= V <= dq_cost_hist_max_bins().
+ * ------------------------------------------------------------------------------------------ */
+/* The most bins of a launch: 1024 -- a private copy of the bins per wave of a workgroup, in double, is 64 KiB of LDS. */
+int dq_cost_hist_max_bins(void);
+/* Bytes of device workspace dq_cost_hist_* needs (one partial sum per workgroup, bin and sample: at most 8 MiB per
+ * sample; `cross` != 0: bra != ket, the same amount); -1 on a bad argument. */
+int64_t dq_cost_hist_ws_bytes(int n, int64_t batch, int is_c128, int cross, int V);
+/* out[b][v] = sum over i with controls = 1 and bin[sub(i)] = v of conj(bra[b, i]) * ket[b, i]: DEVICE double
+ * [batch][V][2] (re, im), fully overwritten, accumulated in double, one read of each state whatever V and k are.
+ * bra == ket reads the state once: the distribution of the cost, imaginary parts exactly 0.  Bins are kept in LDS and
+ * added in an order fixed by the data and the geometry; workgroups write partial sums into `ws` (at least
+ * dq_cost_hist_ws_bytes bytes, 16-byte aligned) and a second kernel adds them in a fixed order: no atomics, results are
+ * bitwise reproducible. */
+int dq_cost_hist_c64(const void* bra, const void* ket, const void* bin, int V, int n, const int* bits, int k,
+                     const int* controls, int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+int dq_cost_hist_c128(const void* bra, const void* ket, const void* bin, int V, int n, const int* bits, int k,
+                      const int* controls, int nc, int64_t batch, double* out, void* ws, int64_t ws_bytes, dq_stream_t stream);
+/* out[b, i] = g[b][bin[sub(i)]] * in[b, i] where the controls are 1 and 0 elsewhere (the DQ_COST_SCALE convention: this
+ * is the cotangent of dq_cost_hist_* in ket, and with conj(g) in bra); g = DEVICE double [batch][V][2] (re, im), 16-byte
+ * aligned, staged in LDS once per workgroup; the product is formed in double and rounded once.  One read and one write
+ * of the state.  in == out is allowed (a lane owns the vectors it reads and writes); any other overlap is refused
+ * (DQ_ERR_ARG, "overlap"). */
+int dq_apply_binned_c64(const void* in, void* out, const void* bin, const double* g, int V, int n, const int* bits, int k,
+                        const int* controls, int nc, int64_t batch, dq_stream_t stream);
+int dq_apply_binned_c128(const void* in, void* out, const void* bin, const double* g, int V, int n, const int* bits, int k,
+                         const int* controls, int nc, int64_t batch, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
