@@ -25,7 +25,7 @@ from .channel import (
 )
 from .gate import (
     CNOT, ArbitraryGate, Barrier, CombinedSingleGate, CostPhase, DiagonalGate, DoubleControlGate, DoubleGate, ExcitationGate, Fredkin, Hadamard,
-    HamiltonianGate, Identity, ImaginarySwap, LatentGate, Measure, MultiplexedGate, MultiplexedRotation, ParametricDoubleGate, ParametricSingleGate, PauliEvolution, PauliRot, PauliX, PauliY,
+    HamiltonianGate, Identity, ImaginarySwap, LatentGate, Measure, MultiplexedGate, MultiplexedRotation, NoiseLayer, ParametricDoubleGate, ParametricSingleGate, PauliEvolution, PauliRot, PauliX, PauliY,
     PauliZ, PermutationGate, PhaseShift, ProjectionJ, QFTGate, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate,
     SingleGate, Swap, TDaggerGate, TGate, Toffoli, TripleGate, U3Gate, UAnyGate,
 )

@@ -41,6 +41,7 @@ MUX_AXES = {'i': 0, 'x': 1, 'y': 2, 'z': 3}        # axis of dq_mux_cross_*
 EXCITE_GATE, EXCITE_MAP = range(2)     # mode of dq_apply_excite_axpby_*
 COLLAPSE_FULL, COLLAPSE_DROP = range(2)        # layout of dq_apply_collapse_*
 COLLAPSE_MAX_BITS = 20                 # measured wires of one dq_measure_draw / dq_apply_collapse_*
+JUMP_MAX_QUBITS = 34                   # n of dq_apply_jump_* / dq_jump_cross_*
 
 
 class DqFusedGate(C.Structure):
@@ -207,6 +208,9 @@ _SIGNATURES = {
     'dq_cost_hist_ws_bytes': (_i64, [_i, _i64, _i, _i, _i]),
     'dq_cost_hist_{s}': (_i, [_vp, _vp, _vp, _i, _i, _ip, _i, _ip, _i, _i64, _vp, _vp, _i64, _vp]),
     'dq_apply_binned_{s}': (_i, [_vp, _vp, _vp, _vp, _i, _i, _ip, _i, _ip, _i, _i64, _vp]),
+    'dq_apply_jump_{s}': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
+    'dq_jump_cross_ws_bytes': (_i64, [_i, _i64, _i, _i]),
+    'dq_jump_cross_{s}': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

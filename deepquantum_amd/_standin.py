@@ -392,3 +392,29 @@ def collapse(state, n, bits, rec, layout, transpose, out):
         val.scatter_(1, t, (1 - 2 * parity(i & z)) * s * torch.gather(wide, 1, i))
     out.copy_(val.to(state.dtype))
     return out
+
+
+def jump_product(table, n):
+    """prod_p table[b, p, bit_p(i)] for every i: float64 (B, 2^n)."""
+    i = torch.arange(1 << n, device=table.device)
+    w = torch.ones(table.shape[0], 1 << n, dtype=torch.float64, device=table.device)
+    for p in range(n):
+        w = w * table[:, p, :].to(torch.float64)[:, (i >> p) & 1]
+    return w
+
+
+def jump_apply(state, n, factors, xmask, phase, scale, transpose, out):
+    """The two maps of ``backend.jump_apply`` as they are defined: seen from the output index q, the source is q ^ x and the
+    factors belong to the source (or, transposed, to q itself)."""
+    q = torch.arange(1 << n, device=state.device)[None]
+    src = q ^ (xmask[:, None] & ((1 << n) - 1))
+    f = jump_product(factors, n)
+    f = f if transpose else torch.gather(f, 1, src)
+    turn = torch.tensor([1, 1j, -1, -1j], dtype=torch.complex128, device=state.device)[(-phase if transpose else phase) & 3]
+    val = (turn * scale)[:, None] * f * torch.gather(state.to(torch.complex128), 1, src)
+    out.copy_(val.to(state.dtype))
+    return out
+
+
+def jump_cross(bra, ket, n, weights):
+    return (jump_product(weights, n) * bra.to(torch.complex128).conj() * ket.to(torch.complex128)).sum(-1)

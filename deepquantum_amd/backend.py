@@ -2321,3 +2321,71 @@ def collapse(state: torch.Tensor, bits: Sequence[int], rec: CollapseRec, layout:
         _call('dq_apply_collapse', state, _ptr(state, lo), _ptr(out, lo), _ptr(rec.data, lo), n, _lib.int_array(bits), k, code,
               int(bool(transpose)), int(rec.has_x), hi - lo)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Quantum jumps (csrc/dq_jump.hip): a layer of one-wire monomial operators K = i^m X^x diag(f0, f1), every sample with its
+# own, as one generalized permutation -- and its weight in one read.
+JUMP_MAX_QUBITS = _lib.JUMP_MAX_QUBITS
+
+
+def _jump_factors(factors: torch.Tensor, state: torch.Tensor, n: int, what: str, name: str) -> torch.Tensor:
+    if n > JUMP_MAX_QUBITS:
+        raise ValueError(f'{what}: {n} qubits: at most {JUMP_MAX_QUBITS} are supported')
+    if factors.shape != (state.shape[0], n, 2) or factors.is_complex():
+        raise ValueError(f'{what}: {name} must be real ({state.shape[0]}, {n}, 2) -- per sample and index-bit position, by the '
+                         f'value of that bit; got {factors.dtype} {tuple(factors.shape)}')
+    return _finish_table(factors, state, torch.float64, what)
+
+
+def jump_apply(state: torch.Tensor, factors: torch.Tensor, xmask: torch.Tensor, phase: torch.Tensor, scale: torch.Tensor,
+               transpose: bool = False, may_flip: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``out[b, i ^ x] = i^m s prod_p factors[b, p, bit_p(i)] state[b, i]`` with ``x = xmask[b]``, ``m = phase[b]`` (mod 4)
+    and ``s = scale[b]``: a tensor product of one-wire operators ``i^m X^x diag(f0, f1)``, every sample with its own, in one
+    write and at most one read (``dq_apply_jump_*``).  ``factors``: real (B, n, 2) by index-bit position (0 = the least
+    significant) and bit value, (1, 1) for a wire left alone; ``xmask`` / ``phase``: int64 (B,); ``scale``: real (B,).
+    ``transpose``: the adjoint map ``out[b, i] = (-i)^m s prod_p factors[b, p, bit_p(i)] state[b, i ^ x]``.  The product is
+    formed in the state's real precision; signs and the power of i are exact.  ``may_flip=False`` promises ``xmask == 0``
+    (it is not read); only then ``out`` may be ``state``."""
+    what = 'jump_apply'
+    n = _nqubit(state)
+    if not state.is_contiguous():
+        raise ValueError(f'{what}: state must be contiguous')
+    factors = _jump_factors(factors, state, n, what, 'factors')
+    b = state.shape[0]
+    for name, t, ok in (('xmask', xmask, xmask.dtype == torch.int64), ('phase', phase, phase.dtype == torch.int64),
+                        ('scale', scale, scale.is_floating_point())):
+        if t.shape != (b,) or not ok or t.device != state.device:
+            raise ValueError(f'{what}: {name} must be {"real" if name == "scale" else "int64"} ({b},) on the device of the '
+                             f'state, got {t.dtype} {tuple(t.shape)} on {t.device}')
+    xmask, phase = xmask.contiguous(), phase.contiguous()
+    scale = scale.detach().to(torch.float64).contiguous()
+    out = _check_out(state, out, what, in_place=not may_flip)
+    if not _use_hip(state):
+        _suffix(state)
+        return _stand('jump_apply', state, n, factors, xmask if may_flip else torch.zeros_like(xmask), phase, scale,
+                      bool(transpose), out)
+    for lo, hi in _slices(b):
+        _call('dq_apply_jump', state, _ptr(state, lo), _ptr(out, lo), _ptr(factors, lo), _ptr(xmask, lo), _ptr(phase, lo),
+              _ptr(scale, lo), n, int(bool(transpose)), int(bool(may_flip)), hi - lo)
+    return out
+
+
+def jump_cross(bra: torch.Tensor, ket: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """``out[b] = sum_i prod_p weights[b, p, bit_p(i)] conj(bra[b, i]) ket[b, i]``: complex128 (B,), tables and accumulation
+    in double, bitwise reproducible (``dq_jump_cross_*``).  ``weights``: real (B, n, 2), laid out as the factors of
+    :func:`jump_apply`.  ``bra`` and ``ket`` the same buffer: one read of the state -- with ``weights = factors ** 2`` the
+    probability of the layer's joint outcome."""
+    what = 'jump_cross'
+    n = _nqubit(ket)
+    if not ket.is_contiguous():
+        raise ValueError(f'{what}: ket must be contiguous')
+    _check_bra(bra, ket, what)
+    weights = _jump_factors(weights, ket, n, what, 'weights')
+    if not _use_hip(ket):
+        _suffix(ket)
+        return _stand('jump_cross', bra, ket, n, weights)
+    # (the weights are per sample: a slice of the batch at a time, each with its own rows of them)
+    parts = [_cross_reduce('dq_jump_cross', 'dq_jump_cross_ws_bytes', bra[lo:hi], ket[lo:hi], (_ptr(weights, lo), n))
+             for lo, hi in _slices(ket.shape[0])]
+    return parts[0] if len(parts) == 1 else torch.cat(parts)

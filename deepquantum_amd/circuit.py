@@ -27,7 +27,7 @@ from torch import nn
 
 from . import _functorch, executor, ops, qmath
 from .gate import (
-    CNOT, Barrier, CostPhase, DiagonalGate, ExcitationGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, Measure, MultiplexedGate, MultiplexedRotation, PauliEvolution,
+    CNOT, Barrier, CostPhase, DiagonalGate, ExcitationGate, Fredkin, Hadamard, HamiltonianGate, ImaginarySwap, LatentGate, Measure, MultiplexedGate, MultiplexedRotation, NoiseLayer, PauliEvolution,
     PauliRot, PauliX, PauliY, PauliZ, PermutationGate, PhaseShift, ProjectionJ, ReconfigurableBeamSplitter, Reset, Rx, Rxx, Rxy, Ry, Ryy, Rz, Rzz, SDaggerGate, SGate, Swap,
     TDaggerGate, TGate, Toffoli, U3Gate, UAnyGate,
 )
@@ -1080,6 +1080,26 @@ class QubitCircuit(Operation):
         self.add(Measure(nqubit=self.nqubit, wires=wires, postselect=postselect, reset=reset, correct=correct,
                          generator=generator))
 
+    def noise_layer(self, channel, inputs=None, wires=None, generator=None, encode=False):
+        """Add a noise channel on each of ``wires`` (all wires by default) of a state-vector circuit as one
+        quantum-trajectory step (:class:`NoiseLayer`): ``channel`` is ``'bit_flip'``, ``'phase_flip'``, ``'depolarizing'``,
+        ``'pauli'``, ``'amp_damp'``, ``'phase_damp'`` or ``'gen_amp_damp'``, ``inputs`` as that channel takes them
+        (probabilities are sin^2 theta), one value for all wires or one per wire.  The batch is the set of trajectories::
+
+            cir(state=cir.init_state.state.expand(T, -1, -1))
+            mean = cir.expectation().mean(0)
+
+        is, up to the sampling error of T trajectories, what the same circuit gives with ``den_mat=True`` and the channel
+        methods.  Returns the layer: after a forward its ``outcome`` and ``outcome_prob`` are device tensors."""
+        if self.den_mat or self.mps:
+            NoiseLayer._refuse('den_mat=True (density matrices: use the channel itself there)' if self.den_mat
+                               else 'MPS (matrix product states)')
+        if encode:
+            NoiseLayer._refuse('encode=True (the strengths are constants)')
+        layer = NoiseLayer(channel, inputs=inputs, nqubit=self.nqubit, wires=wires, generator=generator)
+        self.add(layer)
+        return layer
+
     @property
     def outcomes(self) -> list:
         """Per :class:`Measure` of the circuit, in circuit order: the int64 (B,) device tensor of the outcomes of the last
@@ -1102,7 +1122,7 @@ class QubitCircuit(Operation):
         from .qasm3 import cir_to_qasm2
 
         for op in self.operators:
-            if getattr(op, '_runs_flat', False):
+            if getattr(op, '_runs_flat', False) or isinstance(op, NoiseLayer):
                 op.qasm_refusal()
         return cir_to_qasm2(self)
 

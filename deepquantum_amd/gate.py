@@ -1672,6 +1672,104 @@ class Measure(Gate):
         return f'wires={self.wires}, postselect={self.postselect}, reset={self.reset}'
 
 
+class NoiseLayer(Gate):
+    r"""One noise channel on each of ``wires`` of a state vector, as a quantum-trajectory step of the whole layer.
+
+    ``channel`` names a class of ``channel.py`` -- ``'bit_flip'``, ``'phase_flip'``, ``'depolarizing'``, ``'pauli'``,
+    ``'amp_damp'``, ``'phase_damp'``, ``'gen_amp_damp'`` -- and ``inputs`` follows that class (probabilities are
+    :math:`\sin^2\theta`): one value (four for ``'pauli'``, two for ``'gen_amp_damp'``) for all wires or one per wire.
+    Every sample of the batch draws its own joint Kraus operator :math:`K_j=\bigotimes_q K_{q,j_q}` with probability
+    :math:`|K_j\psi|^2` and becomes :math:`K_j\psi/|K_j\psi|`, in one weight reduction and one pass over the state for the
+    whole layer (``qmath.apply_noise_layer``), all on the device.  The batch is the set of trajectories: their average of
+    :math:`|\psi\rangle\langle\psi|` -- and of any expectation value -- is what the channels do to a density matrix.
+    After a forward, ``outcome`` (int64 (B, W), Kraus indices in the order of ``wires``) and ``outcome_prob`` (float64 (B,))
+    are device tensors.  The gate depends on the state, so a circuit runs it between two fused stretches, as it runs
+    ``Measure``.  The strengths are constants.  The uniforms come from ``torch.rand`` on the state's device
+    (``generator``)."""
+
+    _state_dependent = True
+    CHANNELS = {'bit_flip': ('BitFlip', 1), 'phase_flip': ('PhaseFlip', 1), 'depolarizing': ('Depolarizing', 1),
+                'pauli': ('Pauli', 4), 'amp_damp': ('AmplitudeDamping', 1), 'phase_damp': ('PhaseDamping', 1),
+                'gen_amp_damp': ('GeneralizedAmplitudeDamping', 2)}
+
+    def __init__(self, channel, inputs=None, nqubit=1, wires=None, generator=None, den_mat=False, tsr_mode=False):
+        from . import channel as channels, qmath
+
+        if den_mat:
+            self._refuse('den_mat=True (density matrices: use the channel itself there)')
+        if channel not in self.CHANNELS:
+            raise ValueError(f'NoiseLayer: channel must be one of {sorted(self.CHANNELS)}, got {channel!r}')
+        if inputs is None or (isinstance(inputs, torch.Tensor) and inputs.requires_grad):
+            self._refuse('a trainable strength (inputs=None, or a tensor that requires grad): the strengths are constants,')
+        if wires is None:
+            wires = list(range(nqubit))
+        wires = qmath._wire_list(wires, nqubit, 'NoiseLayer')
+        super().__init__(name='NoiseLayer', nqubit=nqubit, wires=wires, tsr_mode=tsr_mode)
+        cls, npara = self.CHANNELS[channel]
+        theta = torch.as_tensor(inputs).detach().to('cpu', torch.float64).reshape(-1, npara)
+        if theta.shape[0] not in (1, len(wires)):
+            raise ValueError(f'NoiseLayer: inputs must hold {npara} value(s) for all wires or per wire ({len(wires)}), got '
+                             f'{theta.numel()} values')
+        proto = getattr(channels, cls)(inputs=theta[0], nqubit=1, wires=0)
+        self.channel, self.generator = channel, generator
+        self.kraus = [proto.get_matrix(theta[q % theta.shape[0]]).reshape(-1, 2, 2) for q in range(len(wires))]
+        self._host = qmath.noise_tables(nqubit, list(zip(wires, self.kraus)), 'cpu', 'NoiseLayer')
+        self.outcome = self.outcome_prob = None
+        self._tables: dict = {}
+
+    @staticmethod
+    def _refuse(what: str):
+        raise NotImplementedError(f'NoiseLayer: {what} is not supported (a trajectory step acts on a state vector on one '
+                                  'device, sample by sample)')
+
+    def apply_flat(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, 2**n) -> (B, 2**n)."""
+        from . import qmath
+
+        if not x.is_contiguous():
+            x = x.contiguous()
+        if x.device not in self._tables:
+            self._tables[x.device] = qmath.NoiseTables(*(t.to(x.device) for t in self._host[:4]), self._host.count)
+        out, self.outcome, self.outcome_prob = qmath._noise_flat(x, self.nqubit, self._tables[x.device], None, self.generator)
+        return out
+
+    def op_state(self, x: torch.Tensor) -> torch.Tensor:
+        shape = x.shape
+        return self.apply_flat(x.reshape(shape[0], -1)).reshape(shape)
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d['_tables'], d['outcome'], d['outcome_prob'] = {}, None, None
+        return d
+
+    def prims(self, decompose: bool = True) -> list[Prim]:
+        self._refuse('a matrix primitive -- get_unitary(), fused passes, DistributedQubitCircuit (sharded states) --')
+
+    def dm_prims(self, decompose: bool = True) -> list[Prim]:
+        self._refuse('den_mat=True (density matrices: use the channel itself there)')
+
+    def op_den_mat(self, x: torch.Tensor) -> torch.Tensor:
+        self._refuse('den_mat=True (density matrices: use the channel itself there)')
+
+    def op_dist_state(self, x):
+        self._refuse('DistributedQubitCircuit (a sharded state)')
+
+    def op_mps(self, x):
+        self._refuse('MPS (matrix product states)')
+
+    def inverse(self):
+        self._refuse('inverse() (a noise channel is not invertible)')
+
+    def get_unitary(self) -> torch.Tensor:
+        self._refuse('get_unitary() (a noise channel is not unitary)')
+
+    def qasm_refusal(self):
+        self._refuse('qasm()')
+
+    def extra_repr(self) -> str:
+        return f'channel={self.channel}, wires={self.wires}'
+
+
 class Barrier(Gate):
     """No-op separator (reference: gate.py:3097-3126)."""
 

@@ -1962,3 +1962,111 @@ def collapse(state: torch.Tensor, bits: Sequence[int], outcome: torch.Tensor, sc
         raise ValueError('collapse: scale must be a real (B,) tensor, one value per sample')
     bits, _ = _bit_args(bits, ())
     return _Collapse.apply(_flat_arg(state), scale, outcome, xmask, zmask, bits, str(layout), bool(transpose))
+
+
+# ---- quantum jumps: a layer of one-wire monomial operators per sample (csrc/dq_jump.hip) -----------------------------------
+# y_b = s_b A_b x_b with A_b = i^m X^x prod_p diag(F[b, p, :]) a generalized permutation: linear in the state, so the pair
+# below is closed under differentiation as the collapse is.  The cotangent of the state is the node with ``transpose``
+# toggled (A^H), that of the real scale Re <A x_b, gy_b>; the cotangents of z_b = sum_i W conj(a_i) b_i are W a_b and W b_b
+# times the real and imaginary parts of gz_b -- the node again with x = 0, the weights as factors and a power of i.
+# Factors, masks and phases are constants.
+class _Jump(torch.autograd.Function):
+    """y = s A x (A = i^m X^x diag per sample, or its adjoint): gx = the transposed node on gy, gs = Re <A x, gy>."""
+
+    @staticmethod
+    def forward(state: torch.Tensor, scale: torch.Tensor, factors: torch.Tensor, xmask: torch.Tensor, phase: torch.Tensor,
+                transpose: bool) -> torch.Tensor:
+        return backend.jump_apply(_kernel_arg(state), factors, xmask, phase, _plain(scale).detach(), transpose)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        state, scale, factors, xmask, phase, ctx.transpose = inputs
+        ctx.save_for_backward(state, scale, factors, xmask, phase)
+
+    @staticmethod
+    def jvp(ctx, *_):
+        _no_transform('jump_apply', 'forward-mode differentiation (torch.func.jvp / jacfwd, forward_ad)')
+
+    @staticmethod
+    def vmap(info, in_dims, *_):
+        _no_transform('jump_apply', 'torch.vmap')
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        state, scale, factors, xmask, phase = ctx.saved_tensors
+        gy = _flat_arg(gy)
+        gstate = gscale = None
+        if ctx.needs_input_grad[0]:
+            gstate = _Jump.apply(gy, scale, factors, xmask, phase, not ctx.transpose)
+        if ctx.needs_input_grad[1]:
+            unit = _Jump.apply(state, torch.ones_like(scale), factors, xmask, phase, ctx.transpose)
+            gscale = pauli_cross(unit, gy, 0, 0).real.to(scale.dtype)
+        return gstate, gscale, None, None, None, None
+
+
+class _JumpCross(torch.autograd.Function):
+    """z = sum_i W conj(a_i) b_i, complex128 (B,): anti-linear in a, linear in b; cotangents g_b = gz W a and
+    g_a = conj(gz) W b."""
+
+    @staticmethod
+    def forward(bra: torch.Tensor, ket: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+        pk = _kernel_arg(ket)
+        return backend.jump_cross(pk if bra is ket else _kernel_arg(bra), pk, weights)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.save_for_backward(*inputs)
+
+    @staticmethod
+    def jvp(ctx, *_):
+        _no_transform('jump_cross', 'forward-mode differentiation (torch.func.jvp / jacfwd, forward_ad)')
+
+    @staticmethod
+    def vmap(info, in_dims, *_):
+        _no_transform('jump_cross', 'torch.vmap')
+
+    @staticmethod
+    def backward(ctx, gz: torch.Tensor):
+        bra, ket, weights = ctx.saved_tensors
+        gz = gz.to(torch.complex128)
+        gr, gi = gz.real, gz.imag
+        zero = torch.zeros(gz.shape[0], dtype=torch.int64, device=gz.device)
+
+        def times(x, sign):                                 # (gr + sign i gi) W x
+            return _Jump.apply(x, gr, weights, zero, zero, False) + _Jump.apply(x, gi, weights, zero, zero + (sign & 3), False)
+
+        gbra = times(ket, -1) if ctx.needs_input_grad[0] else None
+        gket = times(bra, 1) if ctx.needs_input_grad[1] else None
+        return gbra, gket, None
+
+
+def _jump_table(t: torch.Tensor, what: str) -> torch.Tensor:
+    if _is_batched(t):
+        _no_transform(what, 'torch.vmap')
+    return _const_table(t, what)
+
+
+def jump_apply(state: torch.Tensor, scale: torch.Tensor, factors: torch.Tensor, xmask: torch.Tensor, phase: torch.Tensor,
+               transpose: bool = False) -> torch.Tensor:
+    """Differentiable (to any order, in the state and in the real per-sample ``scale``) jump of a (B, 2**n) state:
+    ``y[b, i ^ xmask[b]] = i^phase[b] scale[b] prod_p factors[b, p, bit_p(i)] state[b, i]`` -- a tensor product of one-wire
+    operators ``i^m X^x diag(f0, f1)``, every sample with its own; ``transpose`` applies the adjoint map
+    (``backend.jump_apply`` has the formulas).  ``factors`` real (B, n, 2), ``xmask`` / ``phase`` int64 (B,): constants.
+    One write and at most one read of the state.  Not under vmap or forward-mode transforms."""
+    _no_legacy(state, scale)
+    for t in (state, scale):
+        if _is_batched(t):
+            _no_transform('jump_apply', 'torch.vmap')
+    if not isinstance(scale, torch.Tensor) or scale.is_complex() or scale.ndim != 1:
+        raise ValueError('jump_apply: scale must be a real (B,) tensor, one value per sample')
+    return _Jump.apply(_flat_arg(state), scale, _jump_table(factors, 'jump_apply'), xmask, phase, bool(transpose))
+
+
+def jump_cross(bra: torch.Tensor, ket: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """Differentiable (to any order, in both states) ``sum_i prod_p weights[b, p, bit_p(i)] conj(bra[b, i]) ket[b, i]``:
+    complex128 (B,).  ``weights`` real (B, n, 2): constants.  Pass the same tensor twice for one read of the state -- with
+    the squared factors of a jump, the probability of that jump.  Not under vmap or forward-mode transforms."""
+    for t in (bra, ket):
+        if _is_batched(t):
+            _no_transform('jump_cross', 'torch.vmap')
+    return _JumpCross.apply(*_cross_pair(bra, ket, 'jump_cross'), _jump_table(weights, 'jump_cross'))

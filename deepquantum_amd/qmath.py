@@ -1087,3 +1087,142 @@ def collapse_state(state: torch.Tensor, nqubit: int, wires: int | list[int], out
         forced = torch.full((flat.shape[0],), _outcome_key(outcome, k, what), dtype=torch.int64, device=dev)
     out, o, p = _collapse_flat(flat, n, wires, forced, generator, bool(drop), fx, fz)
     return (out[0], o[0], p[0]) if single else (out, o, p)
+
+
+# ---- quantum trajectories: a layer of noise channels as one jump (csrc/dq_jump.hip) ---------------------------------------
+# Every Kraus operator of the channels of channel.py is monomial, K = i^m X^x diag(f0, f1) with f0, f1 real, so the joint
+# operator of a layer on distinct wires, K_j = (x)_q K_{q, j_q}, is a generalized permutation and its probability is
+# p(j) = sum_i |psi_i|^2 prod_q f_{q, j_q}(bit_q(i))^2.  Trace preservation gives sum_j f_{q, j}(c)^2 = 1 for either bit
+# value c, so j is drawn exactly by drawing one basis state i ~ |psi_i|^2 and then, per wire and independently, j_q with
+# probability f_{q, j}(bit_q(i))^2: summed over i that is p(j).
+def kraus_factors(kraus: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A (J, 2, 2) stack of Kraus operators as ``K_j = i^m[j] X^x[j] diag(f[j, 0], f[j, 1])``: ``(f, x, m)`` -- float64
+    (J, 2), int64 (J,), int64 (J,), on the host.  An operator that is neither diagonal nor anti-diagonal, or whose two
+    entries are not a common power of i times real numbers, to 1e-6, is refused."""
+    what, tol = 'kraus_factors', 1e-6
+    k = torch.as_tensor(kraus).detach().to('cpu', torch.complex128)
+    if k.ndim != 3 or k.shape[1:] != (2, 2) or k.shape[0] < 1:
+        raise ValueError(f'{what}: a (J, 2, 2) stack of Kraus operators is needed, got {tuple(k.shape)}')
+    f = torch.zeros(k.shape[0], 2, dtype=torch.float64)
+    x = torch.zeros(k.shape[0], dtype=torch.int64)
+    m = torch.zeros(k.shape[0], dtype=torch.int64)
+    for j, a in enumerate(k):
+        if max(abs(a[0, 1]), abs(a[1, 0])) <= tol:
+            e = torch.stack([a[0, 0], a[1, 1]])
+        elif max(abs(a[0, 0]), abs(a[1, 1])) <= tol:
+            e, x[j] = torch.stack([a[1, 0], a[0, 1]]), 1                 # X diag(f0, f1) = [[0, f1], [f0, 0]]
+        else:
+            raise ValueError(f'{what}: Kraus operator {j} is not monomial (neither diagonal nor anti-diagonal to {tol:g}): '
+                             'such a channel has no jump of this form')
+        if e.imag.abs().max() <= tol:
+            f[j] = e.real
+        elif e.real.abs().max() <= tol:
+            f[j], m[j] = e.imag, 1
+        else:
+            raise ValueError(f'{what}: Kraus operator {j} is not monomial: its entries are not a power of i times real '
+                             f'numbers to {tol:g}')
+    return f, x, m
+
+
+class NoiseTables(NamedTuple):
+    """The channels of a layer as the device reads them: ``pos`` int64 (W,) index-bit positions; ``f`` float64 (W, J, 2),
+    ``x`` int64 (W, J) masks over the index bits and ``m`` int64 (W, J) powers of i by Kraus index (a wire with fewer
+    than J operators is padded with factors 0: probability 0); ``count``: the wires' numbers of operators."""
+    pos: torch.Tensor
+    f: torch.Tensor
+    x: torch.Tensor
+    m: torch.Tensor
+    count: tuple
+
+
+def noise_tables(nqubit: int, channels: Any, device: Any = 'cpu', what: str = 'noise_tables') -> NoiseTables:
+    """The tables of a noise layer: ``channels`` is a list of ``(wire, kraus_stack)`` on distinct wires, each stack
+    (J, 2, 2) and monomial (:func:`kraus_factors`; host tensors -- a stack on a device is copied to the host)."""
+    n = int(nqubit)
+    channels = list(channels)
+    if not channels:
+        raise ValueError(f'{what}: at least one (wire, kraus_stack) is needed')
+    wires = _wire_list([w for w, _ in channels], n, what)                # (distinct, in range)
+    parts = [kraus_factors(k) for _, k in channels]
+    jmax = max(f.shape[0] for f, _, _ in parts)
+    f = torch.zeros(len(parts), jmax, 2, dtype=torch.float64)
+    x = torch.zeros(len(parts), jmax, dtype=torch.int64)
+    m = torch.zeros(len(parts), jmax, dtype=torch.int64)
+    for q, (fq, xq, mq) in enumerate(parts):
+        f[q, : fq.shape[0]], x[q, : fq.shape[0]], m[q, : fq.shape[0]] = fq, xq << (n - 1 - wires[q]), mq
+    pos = torch.tensor([n - 1 - w for w in wires], dtype=torch.int64)
+    return NoiseTables(pos.to(device), f.to(device), x.to(device), m.to(device), tuple(p[0].shape[0] for p in parts))
+
+
+def _noise_draw(flat: torch.Tensor, t: NoiseTables, u: torch.Tensor) -> torch.Tensor:
+    """The joint Kraus index of every sample for explicit uniforms ``u`` float64 (B, 1 + W): one basis state
+    ``i ~ |psi_i|^2`` from ``u[:, 0]``, then per wire the smallest j whose running sum of ``f[q, j, bit_q(i)]^2`` exceeds
+    ``u[:, 1 + q]`` -- never one of probability 0.  int64 (B, W); all on the device."""
+    i = backend.sample_indices(flat.detach(), u[:, :1].contiguous())                   # (B, 1)
+    c = (i >> t.pos[None, :]) & 1                                                     # (B, W)
+    w = torch.arange(t.pos.shape[0], device=flat.device)
+    pj = (t.f * t.f)[w[None, :], :, c]                                                # (B, W, J)
+    j = (pj.cumsum(-1) <= u[:, 1:, None]).sum(-1)
+    last = ((pj > 0) * torch.arange(pj.shape[-1], device=flat.device)).amax(-1)       # (rounding carried u beyond the sum)
+    return torch.minimum(j, last)
+
+
+def _noise_flat(flat: torch.Tensor, n: int, t: NoiseTables, forced: torch.Tensor | None,
+                generator) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """draw -> weight -> jump on a contiguous (B, 2**n) state; ``forced``: int64 (B, W) or None.  Nothing is synchronised
+    with the host."""
+    b, nw = flat.shape[0], t.pos.shape[0]
+    if forced is None:
+        u = torch.rand(b, 1 + nw, dtype=torch.float64, device=flat.device, generator=generator)
+        j = _noise_draw(flat, t, u)
+    else:
+        j = forced
+    w = torch.arange(nw, device=flat.device)[None, :]
+    factors = torch.ones(b, n, 2, dtype=torch.float64, device=flat.device)
+    factors[:, t.pos] = t.f[w, j]                                                      # (B, W, 2) at the wires' positions
+    xmask = t.x[w, j].sum(-1)                                                          # (distinct bits: the sum is the or)
+    phase = t.m[w, j].sum(-1) & 3
+    graph = torch.is_grad_enabled() and flat.requires_grad
+    cross, jump = (ops.jump_cross, ops.jump_apply) if graph else (backend.jump_cross, None)
+    prob = cross(flat, flat, factors * factors).real
+    live = prob.detach() > 0
+    scale = torch.where(live, torch.where(live, prob, torch.ones_like(prob)) ** -0.5, torch.zeros_like(prob))
+    if graph:
+        out = jump(flat, scale, factors, xmask, phase)
+    else:
+        out = backend.jump_apply(flat, factors, xmask, phase, scale)
+    return out, j, prob.detach()
+
+
+def apply_noise_layer(state: torch.Tensor, nqubit: int, channels: Any, outcome: Any = None,
+                      generator: torch.Generator | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One quantum-trajectory step of a layer of noise channels on a state vector: ``(state, outcome, prob)``.
+
+    ``channels`` is a list of ``(wire, kraus_stack)`` on distinct wires, every stack (J, 2, 2) with monomial operators
+    (:func:`kraus_factors`: all channels of ``channel.py`` are).  Every sample of a batch draws its own joint Kraus index j
+    with probability ``|K_j psi|^2`` -- one basis state from the inverse-CDF sampler, then one independent draw per wire,
+    on uniforms ``torch.rand(B, 1 + W, dtype=float64, device=state.device, generator=generator)`` -- and becomes
+    ``K_j psi / |K_j psi|`` in one weight reduction and one jump pass over the state, whatever the number of wires
+    (``backend.jump_cross`` / ``backend.jump_apply``); nothing is synchronised with the host.  ``outcome`` -- a list of W
+    Kraus indices or an int64 (B, W) tensor, in the order of ``channels`` -- forces j; one of weight 0 gives a zero state
+    and ``prob = 0``, not an error.  ``outcome`` is int64 (B, W) and ``prob`` float64 (B,) (``|K_j psi|^2``), device tensors
+    ((W,) and 0-d for a single state).  With gradients enabled the result is differentiable in the state, normalisation
+    included.  Averaged over samples, ``|psi><psi|`` is the channel's output density matrix."""
+    what = 'apply_noise_layer'
+    flat, single = _state_batch(state, int(nqubit), what)
+    n = int(nqubit)
+    if not flat.is_contiguous():
+        flat = flat.contiguous()
+    t = noise_tables(n, channels, flat.device, what)
+    forced = None
+    if outcome is not None:
+        forced = torch.as_tensor(outcome, device=flat.device)
+        if forced.dtype != torch.int64 or forced.shape not in ((len(t.count),), (flat.shape[0], len(t.count))):
+            raise ValueError(f'{what}: outcome must hold int64 Kraus indices, ({len(t.count)},) or ({flat.shape[0]}, '
+                             f'{len(t.count)}); got {forced.dtype} {tuple(forced.shape)}')
+        if not isinstance(outcome, torch.Tensor) and forced.ndim == 1 and any(
+                not 0 <= int(o) < c for o, c in zip(outcome, t.count)):
+            raise ValueError(f'{what}: outcome {list(outcome)} outside the wires\' numbers of Kraus operators {list(t.count)}')
+        forced = forced.expand(flat.shape[0], -1).clamp(0, t.f.shape[1] - 1)
+    out, j, p = _noise_flat(flat, n, t, forced, generator)
+    return (out[0], j[0], p[0]) if single else (out, j, p)

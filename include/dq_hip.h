@@ -1042,6 +1042,38 @@ int dq_apply_binned_c64(const void* in, void* out, const void* bin, const double
 int dq_apply_binned_c128(const void* in, void* out, const void* bin, const double* g, int V, int n, const int* bits, int k,
                          const int* controls, int nc, int64_t batch, dq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 20. Quantum jumps: a layer of one-wire monomial operators, per sample, in one pass (csrc/dq_jump.hip; added within
+ *     ABI 30, presence is checked by symbol).  A diagonal or anti-diagonal 2x2 operator is K = i^m X^x diag(f0, f1) with
+ *     f0, f1 real; a tensor product of such operators over any wires is a generalized permutation.  Per sample b, all
+ *     DEVICE memory, 8-byte aligned: factors = double [batch][n][2], indexed by the index-bit position p (0 = the least
+ *     significant) and the value of that bit, (1, 1) for a wire outside the layer; xmask = int64 [batch] over the n index
+ *     bits; phase = int64 [batch], the power of i, used modulo 4; scale = double [batch].  1 <= n <= 34 (three product
+ *     tables of 8 index bits above a unit of 1024 vectors, built in LDS per workgroup), 1 <= batch <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+/* out[b, i ^ x] = i^m s prod_p factors[b, p, bit_p(i)] in[b, i], and with transpose != 0 the adjoint map
+ * out[b, i] = (-i)^m s prod_p factors[b, p, bit_p(i)] in[b, i ^ x].  The product is formed in the state's real precision
+ * from per-lane registers and the LDS tables, never read from memory per amplitude; i^m swaps and flips signs bit for
+ * bit: with every factor +-1 and s == 1 the pass is bit-exact.  A unit of 1024 vectors whose high-bit factor is exactly
+ * 0 is zero-filled without a load.  One write and at most one read.  may_flip == 0: the caller promises x == 0 and xmask
+ * is not read (it may be NULL); only then in == out is allowed -- any other overlap is DQ_ERR_ARG.  in and out 16-byte
+ * aligned. */
+int dq_apply_jump_c64(const void* in, void* out, const double* factors, const int64_t* xmask, const int64_t* phase,
+                      const double* scale, int n, int transpose, int may_flip, int64_t batch, dq_stream_t stream);
+int dq_apply_jump_c128(const void* in, void* out, const double* factors, const int64_t* xmask, const int64_t* phase,
+                       const double* scale, int n, int transpose, int may_flip, int64_t batch, dq_stream_t stream);
+/* Bytes of device workspace dq_jump_cross_* needs (one partial sum per workgroup; `cross` != 0: bra != ket, the same
+ * amount); -1 on a bad argument. */
+int64_t dq_jump_cross_ws_bytes(int n, int64_t batch, int is_c128, int cross);
+/* out[b] = sum_i prod_p weights[b, p, bit_p(i)] conj(bra[b, i]) ket[b, i]: DEVICE double [batch][2] (re, im); weights laid
+ * out as `factors` above; tables and accumulation in double, partial sums in `ws` (16-byte aligned) added in a fixed
+ * order: no atomics, bitwise reproducible.  Units whose high-bit weight is exactly 0 are not loaded; bra == ket reads the
+ * state once (with weights = factors^2: the probability of the layer's joint outcome). */
+int dq_jump_cross_c64(const void* bra, const void* ket, const double* weights, int n, int64_t batch, double* out, void* ws,
+                      int64_t ws_bytes, dq_stream_t stream);
+int dq_jump_cross_c128(const void* bra, const void* ket, const double* weights, int n, int64_t batch, double* out, void* ws,
+                       int64_t ws_bytes, dq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
